@@ -17,13 +17,23 @@ A "step" = one pass of -[TRMTubeModel synthesize] over one resident batch of syn
                       configs[4] (8192 time-varying voices).  `--gpus 1 --config 4` is the single-GPU run an N-rank line
                       compares with (its `scaling_baseline`).
 
-The default line (N = 1, configs[1]) also carries a `stream` record: 1 048 576 voices streamed in ten 100 ms chunks through
-trm_stream_push_device (the metric's "concurrent real-time voices" half: every chunk must beat its audio time); --no-stream
-leaves it out.
+A plain run sets up, warms up, times --steps steps, writes its outputs (--dump-outputs) and prints the line; the roofline
+figures in it come from the timed launches themselves.  Everything that takes work of its own runs only with --full:
+  `cpu_baseline`      the oracle timed on the host's usable cores (--no-cpu-baseline leaves it out);
+  `stream`            default line (N = 1, configs[1]) only: 1 048 576 voices streamed in ten 100 ms chunks through
+                      trm_stream_push_device (the metric's "concurrent real-time voices" half: every chunk must beat its audio
+                      time; --no-stream leaves it out);
+  `end_to_end`        configs[3] only (--no-end-to-end leaves it out, see below);
+  `solo_ms_per_step`  N-rank line only: rank 0 running the same shard ALONE (the other ranks idle at a barrier; outside the
+                      timed region).  Without --full it is null.
 
 The N-rank line is self-contained for weak scaling: besides the contract's MAX-over-ranks time it carries every rank's
-own elapsed and kernel time (`per_rank_ms`, `per_rank_kernel_ms`, gathered after the timed region), `per_gpu_value`, and
-`solo_ms_per_step` = rank 0 running the same shard ALONE (the other ranks idle at a barrier; outside the timed region).
+own elapsed and kernel time (`per_rank_ms`, `per_rank_kernel_ms`, gathered after the timed region) and `per_gpu_value`.
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0's shard) as .npy files, float32 / float64,
+under 64 MB in all: `number_samples` and `maximum_sample_value` of every voice, and `pcm` = the samples of a fixed, seeded
+sample of the voices (`pcm_voices`, ascending), back to back, each voice's output length long.  The inputs are seeded, so
+two builds run with the same arguments can be compared file for file.
 
 Prints ONE JSON line on rank 0 (DESIGN.md "Measurement" explains every field).
 """
@@ -227,17 +237,21 @@ def resolve_workload(a, world):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)       # (a step is ~2.5 ms: half a second of GPU work after the CPU baseline's 3 s)
+    ap.add_argument("--steps", type=int, default=200)       # (a step is ~1.8 ms: a third of a second of GPU work)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes work of its own: cpu_baseline, the stream record, end_to_end, solo_ms_per_step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB)")
     ap.add_argument("--config", type=int, default=None, choices=sorted(CONFIGS),
                     help="per-GPU workload = BASELINE.json configs[K] (4: one GPU's shard of it); default 1 at --gpus 1, 4 at --gpus N")
     ap.add_argument("--voices", type=int, default=None, help="voices per GPU (overrides --config's)")
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--workload", default=None, choices=["static", "timevarying", "ragged"],
                     help="overrides --config's: static (config-2 voices), timevarying (config-3 voices) or ragged (configs[3]'s utterances)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stream", action="store_true", help="leave the default line's `stream` record out")
-    ap.add_argument("--no-end-to-end", action="store_true", help="leave configs[3]'s `end_to_end` record out (profiling passes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave `cpu_baseline` out")
+    ap.add_argument("--no-stream", action="store_true", help="with --full: leave the default line's `stream` record out")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: leave configs[3]'s `end_to_end` record out (profiling passes)")
     ap.add_argument("--split", default="auto", help="time split (include/trm_c_api.h): auto | off | control periods per segment")
     ap.add_argument("--mode", default="batch", choices=["batch", "stream"],
                     help="stream: the metric's second half demonstrated -- --voices N (default 1048576) streamed in 100 ms chunks "
@@ -330,8 +344,39 @@ def end_to_end_record(g, pd, caller_order, reps=3):
     return out
 
 
+DUMP_PCM_BYTES = 60 << 20       # --dump-outputs: the sampled PCM; the per-voice arrays add 12 B a voice
+DUMP_SEED = 20250120
+
+
+def dump_outputs(d, st):
+    """--dump-outputs: what synthesize_device() left in the resident state `st` (prepare_device) -- per-voice numberSamples and
+    maximumSampleValue, and the PCM of the voices a seeded permutation puts first, as many as fit in DUMP_PCM_BYTES.  The pick
+    depends on the voices' output lengths as the host plans them (st["nout"]), not on what the run produced."""
+    import numpy as np
+    import torch
+    V = st["V"]
+    nout = np.asarray(st["nout"], dtype=np.int64)
+    pick, used = [], 0
+    for v in np.random.default_rng(DUMP_SEED).permutation(V):
+        if used + 4 * int(nout[v]) > DUMP_PCM_BYTES:
+            break
+        pick.append(int(v))
+        used += 4 * int(nout[v])
+    pick.sort()
+    offs = st["out_offset_host"]
+    pcm = (torch.cat([st["out"][int(offs[v]):int(offs[v]) + int(nout[v])] for v in pick]).cpu().numpy() if pick
+           else np.zeros(0, np.float32))
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "number_samples.npy"), st["number_samples"][:V].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(d, "maximum_sample_value.npy"), st["max_sample"][:V].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "pcm_voices.npy"), np.asarray(pick, dtype=np.float64))
+    np.save(os.path.join(d, "pcm.npy"), pcm.astype(np.float32))
+
+
 def main():
     a = parse_args()
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         # No ranks yet: start them as a child process (never re-exec a process that may have touched the GPU -- this one
@@ -381,7 +426,7 @@ def main():
 
     # the CPU leg first: before this process has a GPU context (rank 0 at N=1 only)
     cpu = None
-    if rank == 0 and not dist and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not dist and not a.no_cpu_baseline:
         cpu = cpu_baseline_ragged(pd, frames) if workload == "ragged" else cpu_baseline(pd, frames)
 
     import torch
@@ -409,7 +454,7 @@ def main():
         b.synthesize_device(st, stream)
     torch.cuda.synchronize()
     solo_ms = None
-    if dist:
+    if dist and a.full:
         # outside the timed region: rank 0 runs its shard ALONE while the others wait -- what a reader needs to turn the
         # timed region below into a weak-scaling efficiency without a second run
         td.barrier()
@@ -446,6 +491,8 @@ def main():
         td.all_gather(allr, mine)
         per_rank_ms = [float(x[0]) for x in allr]
         per_rank_kernel_ms = [float(x[1]) for x in allr]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, st)
 
     samples_per_step_rank = int(st["total_out"])
     total_samples = samples_per_step_rank * a.steps * world
@@ -486,9 +533,9 @@ def main():
                              "count x the class-mix issue cost / (launch time x 1024 SIMDs x 2.4 GHz)"},
         "cpu_baseline": cpu,
     }
-    if rank == 0 and not dist and workload == "ragged" and not a.no_end_to_end:
+    if a.full and rank == 0 and not dist and workload == "ragged" and not a.no_end_to_end:
         out["end_to_end"] = end_to_end_record(g, pd, caller_order)
-    if rank == 0 and not dist and config == 1 and a.voices is None and a.workload is None and not a.no_stream:
+    if a.full and rank == 0 and not dist and config == 1 and a.voices is None and a.workload is None and not a.no_stream:
         del st, b
         torch.cuda.empty_cache()
         out["stream"] = stream_record()
@@ -496,7 +543,7 @@ def main():
         out["per_rank_ms"] = per_rank_ms                   # ms per step, every rank's own clock (launches + device sync)
         out["per_rank_kernel_ms"] = per_rank_kernel_ms     # average tube-kernel launch per rank (hipEvents)
         out["per_gpu_value"] = [samples_per_step_rank / (t * 1e-3) for t in per_rank_ms]
-        out["solo_ms_per_step"] = solo_ms                  # rank 0 alone on the same shard, outside the timed region
+        out["solo_ms_per_step"] = solo_ms                  # rank 0 alone on the same shard, outside the timed region (--full)
         out["weak_scaling_efficiency_in_run"] = (solo_ms / (dt / a.steps * 1e3)) if solo_ms else None
         out["scaling_baseline"] = ("python bench.py --gpus 1 %s: the same per-GPU shard on one GPU (--gpus 1 WITHOUT that is "
                                    "configs[1], another workload)" % ("--config %d" % config if (a.voices is None and a.workload is None and a.seconds == 1.0)

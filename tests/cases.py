@@ -137,6 +137,27 @@ def golden_cases():
     return cases
 
 
+def random_track_cases(seeds=(1, 2, 3)):
+    """name -> (params dict, frames): random voices over random 40-frame windows of gnuspeech.input with audible frication
+    (tests/test_oracle_vs_ref.py; frozen as tests/golden/random_tracks_seed<N>.npz)."""
+    rows = load_gnuspeech_rows()
+    out = {}
+    for seed in seeds:
+        rng = np.random.default_rng(seed)
+        pd = monet_default_params(44100.0 if seed % 2 else 22050.0)
+        pd["length"] = float(rng.uniform(11.0, 19.0))
+        pd["temperature"] = float(rng.uniform(25.0, 38.0))
+        pd["breathiness"] = float(rng.uniform(0.0, 8.0))
+        pd["lossFactor"] = float(rng.uniform(0.1, 3.0))
+        s = int(rng.integers(0, 280))
+        fr = rows[s:s + 40].copy()
+        fr[:, 0] += rng.uniform(-6, 6)
+        fr[:, 3] += rng.uniform(0, 30, size=40)          # audible frication
+        fr[:, 4] = rng.uniform(0, 7, size=40)
+        out["random_tracks_seed%d" % seed] = (pd, fr)
+    return out
+
+
 def corner_cases():
     """name -> (params dict, frames): corners no reference fixture covers, checked against the (pinned) oracle.
     pulse_no_rise_*: tp ~ 0 makes tableDiv1 = 0 -- the glottal table has no rise entries and is the fall alone

@@ -5,6 +5,7 @@ Runs oracle/_ref/tube_ref (Applications/TRAcT/tube.c compiled in place from /roo
 by oracle/Makefile, driven by oracle/ref_driver.c) on every case of tests/cases.golden_cases()
 and freezes what the reference computed: tube-rate doubles, converter output (fp32, as tube.c's
 dataEmpty emits it), numberSamples, maximumSampleValue, FIR taps, derived constants.
+cases.random_track_cases() the same way (tests/test_oracle_vs_ref.py);
 cases.tract_mode_cases() run through the same binary in TRAcT's own loop order (ref_driver.c `tract`),
 cases.tract_slice_cases() in that order with the parameters changing on a grid of samples (`tract slice=N`).
 A list of case names on the command line regenerates only those.
@@ -29,7 +30,8 @@ def main():
     if not O.have_ref():
         sys.exit("oracle/_ref/tube_ref missing: run `make -C oracle` where /root/reference exists")
     h_saved = False
-    todo = [(n, c + (0,), False) for n, c in cases.golden_cases().items()] + [(n, c + (0,), True) for n, c in cases.tract_mode_cases().items()]
+    todo = [(n, c + (0,), False) for n, c in list(cases.golden_cases().items()) + list(cases.random_track_cases().items())]
+    todo += [(n, c + (0,), True) for n, c in cases.tract_mode_cases().items()]
     todo += [(n, c, True) for n, c in cases.tract_slice_cases().items()]       # (round 4: parameters on a grid of `slice` samples)
     only = sys.argv[1:]
     for name, (pd, frames, slc), tract in todo:

@@ -207,6 +207,40 @@ def test_bench_config_flag_names_the_per_gpu_workload():
     assert bench.resolve_workload(bench.parse_args(["--voices", "65536", "--kernel", "wide"]), 1) == (1, 65536, "static")
     assert bench.parse_args([]).steps == 200          # half a second of GPU work: the driver's sampler sees the run
     assert bench.parse_args([]).mode == "batch" and bench.parse_args(["--mode", "stream", "--voices", "2097152"]).mode == "stream"
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full          # the extra records are opt-in
+    assert bench.parse_args([]).dump_outputs is None and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_under_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: per-voice counts and maxima of every voice, the PCM of a seeded sample of voices back to back, float32 /
+    float64 only; the pick depends on the planned output lengths alone, so two runs of the same arguments dump the same voices."""
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_PCM_BYTES + 12 * 65536 + 4096 < 64 << 20           # the largest batch bench.py runs stays under 64 MB
+    monkeypatch.setattr(bench, "DUMP_PCM_BYTES", 1 << 20)
+    rng = np.random.default_rng(0)
+    V = 100
+    nout = rng.integers(3000, 6000, size=V)
+    pitch = (nout + 31) // 32 * 32
+    ooff = np.concatenate([[0], np.cumsum(pitch[:-1])])
+    st = {"V": V, "nout": nout, "out_offset_host": ooff, "out": torch.from_numpy(rng.standard_normal(int(pitch.sum())).astype(np.float32)),
+          "number_samples": torch.from_numpy(nout.astype(np.int32)), "max_sample": torch.from_numpy(rng.random(V).astype(np.float32))}
+    bench.dump_outputs(str(tmp_path / "a"), st)
+    bench.dump_outputs(str(tmp_path / "b"), st)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["maximum_sample_value.npy", "number_samples.npy", "pcm.npy", "pcm_voices.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    pick = np.load(tmp_path / "a" / "pcm_voices.npy").astype(np.int64)
+    pcm = np.load(tmp_path / "a" / "pcm.npy")
+    assert 0 < len(pick) < V and np.all(np.diff(pick) > 0) and pcm.nbytes <= 1 << 20
+    out = st["out"].numpy()
+    assert np.array_equal(pcm, np.concatenate([out[ooff[v]:ooff[v] + nout[v]] for v in pick]))
+    assert np.array_equal(np.load(tmp_path / "a" / "number_samples.npy"), nout.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "maximum_sample_value.npy"), st["max_sample"].numpy())
 
 
 def test_no_kernel_spills_or_outgrows_its_register_budget(tmp_path):

@@ -547,6 +547,39 @@ def test_device_path_and_int16(g, form):
     assert n >= 2 and t > 0.0
 
 
+def test_bench_plain_run_and_its_dumped_outputs(g, tmp_path):
+    """A plain bench.py run times exactly --steps steps, carries none of the --full records, and --dump-outputs holds what the
+    device path computes for the same seeded batch (same kernel, same bits)."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--voices", "96",
+                        "--seconds", "0.2", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["n_gpus"] == 1
+    assert line["unit"] == "samples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["cpu_baseline"] is None and "stream" not in line and "end_to_end" not in line
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) < 64 << 20
+    fr = cases.config2_frames(96, nframes=51, seed=20250117)
+    b = g.TRMBatch(g.TRMInputParameters.from_dict(cases.monet_default_params(44100.0)))
+    st = b.prepare_device(fr)
+    b.synthesize_device(st)
+    torch.cuda.synchronize()
+    out = st["out"].cpu().numpy()
+    ns = st["number_samples"].cpu().numpy()
+    pick = np.load(d / "pcm_voices.npy").astype(np.int64)
+    assert len(pick) == 96                                                    # a batch this small is dumped whole
+    assert np.array_equal(np.load(d / "number_samples.npy"), ns.astype(np.float64))
+    assert np.array_equal(np.load(d / "maximum_sample_value.npy"), st["max_sample"].cpu().numpy())
+    exp = np.concatenate([out[int(st["out_offset_host"][v]):int(st["out_offset_host"][v]) + int(st["nout"][v])] for v in pick])
+    assert np.array_equal(np.load(d / "pcm.npy"), exp)
+    assert line["value"] == pytest.approx(int(ns.sum()) / (line["ms_per_step"] * 1e-3), rel=1e-9)
+
+
 def test_host_entry_input_forms_and_kept_buffer(g, form):
     """TRMBatch.synthesize: a [V,N,16] array == the list of its voices; the kept output buffer (reuse_output)
     gives the same bits and is overwritten by the next call."""
