@@ -67,6 +67,8 @@ EXPORTS = [
     "trm_events_count_frames", "trm_drift_seed_after", "trm_batch_generate_frames_device", "trm_batch_generate_frames_host",
     "trm_batch_set_kernel", "trm_batch_last_kernel", "trm_batch_set_time_split", "trm_batch_last_time_split", "trm_batch_hint_frames",
     "trm_batch_kernel_time_ms", "trm_batch_set_timing", "trm_batch_noise_table", "trm_device_count", "trm_build_info", "trm_kernel_blocks_per_cu", "trm_kernel_blocks_per_cu_form",
+    "trm_mixed_create", "trm_mixed_destroy", "trm_mixed_derived", "trm_mixed_samples_for_frames", "trm_mixed_synthesize_device",
+    "trm_mixed_synthesize_host", "trm_mixed_synthesize_host_int16", "trm_mixed_set_kernel", "trm_mixed_last_kernel",
 ]
 
 _lib = None
@@ -167,6 +169,16 @@ def lib():
     L.trm_batch_last_time_split.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.trm_batch_hint_frames.argtypes = [vp, vp, C.c_size_t]
     L.trm_batch_noise_table.argtypes = [vp, vp, C.c_size_t]
+    L.trm_mixed_create.argtypes = [C.POINTER(TrmInputParams), C.c_size_t, C.c_int, C.POINTER(vp)]
+    L.trm_mixed_destroy.argtypes = [vp]
+    L.trm_mixed_derived.argtypes = [vp, C.c_size_t, C.POINTER(TrmDerived)]
+    L.trm_mixed_samples_for_frames.argtypes = [vp, C.c_size_t, C.c_size_t]
+    L.trm_mixed_samples_for_frames.restype = C.c_size_t
+    L.trm_mixed_synthesize_device.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.trm_mixed_synthesize_host.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.trm_mixed_synthesize_host_int16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
+    L.trm_mixed_set_kernel.argtypes = [vp, C.c_int]
+    L.trm_mixed_last_kernel.argtypes = [vp]
     for name in EXPORTS:
         getattr(L, name)
     _lib = L

@@ -1753,4 +1753,389 @@ int trm_data_list_write_file(const char *path, const trm_input_params *params, c
     return TRM_OK;
 }
 
+
+// ------------------------------------------------------------------ mixed-parameter batches
+// One trm_batch per parameter set carries that set's constants, derived values and down-sampling rows (the read-only device
+// tables are shared per process anyway); the first one also lends its noise sequence, stream and staging buffers.  The
+// launch itself is one grid: workgroup w runs voices map[w].y .. map[w].z - 1 of set map[w].x with that set's constants
+// (trm_kernels.h, TubeArgs::mix_map).  Whole utterances only: the time split's warm-up is chosen per batch, and a mixed launch
+// must give every voice exactly what its own set's batch gives it (the split's rule for that is not settled).
+struct trm_mixed {
+    std::vector<trm_batch *> b;              // per set
+    int kernel = TRM_KERNEL_AUTO;            // trm_mixed_set_kernel
+    int lastKernel = TRM_KERNEL_AUTO;
+    trm::Const *dConst = nullptr;            // the sets' constants, [nsets]
+    DevBuf<uint4> dMap;                      // {set, first voice, end voice, 0} per workgroup
+    DevBuf<uint64_t> dTubeOff;               // down-sampling sets' voices: their tube-rate rows in dTube
+    DevBuf<float> dTube;
+    // the shape the three arrays above were built for (rebuilt when it changes: the device entry is pure stream work otherwise)
+    std::vector<size_t> shapeBegin;
+    int shapeForm = -1;
+    uint32_t shapeMaxFrames = 0, mapEntries = 0;
+    bool haveShape = false;
+    std::vector<uint4> hMap;                 // host copies the uploads read from (they outlive the asynchronous copies)
+    std::vector<uint64_t> hTubeOff;
+    // completes after the last launch that read the arrays, on whichever stream: a shape change waits for it alone (not for
+    // the device), then uploads in stream order
+    hipEvent_t lastUse = nullptr;
+    bool lastUseRecorded = false;
+    // host-entry staging
+    DevBuf<float> dFrames, dOut, dMax;
+    DevBuf<int16_t> dOut16;
+    DevBuf<uint64_t> dFrameOff, dOutOff, dRelOff;
+    DevBuf<uint32_t> dNFrames, dNSamples;
+};
+
+void trm_mixed_destroy(trm_mixed *m)
+{
+    if (!m) return;
+    if (!m->b.empty()) (void)hipSetDevice(m->b[0]->device);
+    if (m->dConst) (void)hipFree(m->dConst);
+    if (m->lastUse) (void)hipEventDestroy(m->lastUse);
+    std::vector<trm_batch *> b;
+    b.swap(m->b);
+    delete m;                 // device buffers first (the batches own the stream they were used on)
+    for (trm_batch *x : b) trm_batch_destroy(x);
+}
+
+int trm_mixed_create(const trm_input_params *params, size_t nsets, int device, trm_mixed **out)
+{
+    if (!params || !out || nsets == 0) return fail(TRM_EINVAL, "null argument / no parameter sets");
+    *out = nullptr;
+    if (nsets > 0xFFFFFFFFull) return fail(TRM_EINVAL, "too many parameter sets");
+    // every set is checked before a device is looked for: a bad set is reported (by index) on any host
+    for (size_t s = 0; s < nsets; s++) {
+        trm::Const c;
+        trm_derived d;
+        int rc = trm::build_const(params[s], c, d);
+        if (rc != TRM_OK) return fail(rc, "parameter set %zu: %s", s, trm_strerror(rc));
+        if (c.controlPeriod < 4)
+            return fail(TRM_ERANGE, "parameter set %zu: control period of %d tube samples is below the kernel's pipeline step", s, c.controlPeriod);
+    }
+    trm_mixed *m = new (std::nothrow) trm_mixed();
+    if (!m) return fail(TRM_ENOMEM, "trm_mixed");
+    for (size_t s = 0; s < nsets; s++) {
+        trm_batch *b = nullptr;
+        int rc = trm_batch_create(&params[s], device, &b);
+        if (rc) {
+            std::string err = trm_last_error();
+            trm_mixed_destroy(m);
+            return fail(rc, "parameter set %zu: %s", s, err.c_str());
+        }
+        m->b.push_back(b);
+        device = b->device;
+    }
+    std::vector<trm::Const> cs(nsets);
+    for (size_t s = 0; s < nsets; s++) cs[s] = m->b[s]->c;
+    hipError_t e = hipMalloc((void **)&m->dConst, nsets * sizeof(trm::Const));
+    if (e == hipSuccess) e = hipMemcpy(m->dConst, cs.data(), nsets * sizeof(trm::Const), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&m->lastUse, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        trm_mixed_destroy(m);
+        return fail(TRM_EHIP, "constant table: %s", hipGetErrorString(e));
+    }
+    *out = m;
+    return TRM_OK;
+}
+
+int trm_mixed_derived(const trm_mixed *m, size_t set, trm_derived *out)
+{
+    if (!m || !out) return fail(TRM_EINVAL, "null argument");
+    if (set >= m->b.size()) return fail(TRM_EINVAL, "parameter set %zu of %zu", set, m->b.size());
+    *out = m->b[set]->d;
+    return TRM_OK;
+}
+
+size_t trm_mixed_samples_for_frames(const trm_mixed *m, size_t set, size_t nframes)
+{
+    if (!m || set >= m->b.size()) return 0;
+    return trm_batch_samples_for_frames(m->b[set], nframes);
+}
+
+int trm_mixed_set_kernel(trm_mixed *m, int kernel)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    if (kernel != TRM_KERNEL_AUTO && kernel != TRM_KERNEL_WIDE && kernel != TRM_KERNEL_QUAD && kernel != TRM_KERNEL_OCT) return fail(TRM_EINVAL, "unknown kernel form %d", kernel);
+    m->kernel = kernel;
+    return TRM_OK;
+}
+
+int trm_mixed_last_kernel(const trm_mixed *m) { return m ? m->lastKernel : TRM_KERNEL_AUTO; }
+
+static int mixed_check_sets(const trm_mixed *m, const size_t *set_begin)
+{
+    if (!set_begin) return fail(TRM_EINVAL, "null set_begin");
+    if (set_begin[0] != 0) return fail(TRM_EINVAL, "set_begin[0] = %zu, not 0", set_begin[0]);
+    for (size_t s = 0; s < m->b.size(); s++)
+        if (set_begin[s + 1] < set_begin[s]) return fail(TRM_EINVAL, "set_begin decreases at set %zu (%zu -> %zu)", s, set_begin[s], set_begin[s + 1]);
+    if (set_begin[m->b.size()] > 0xFFFFFFFFull - 64) return fail(TRM_EINVAL, "too many voices");
+    return TRM_OK;
+}
+
+// The kernel form of a mixed launch: what a trm_batch of the same voice count -- every set padded to the form's workgroup --
+// runs with the time split off (trm_batch_synthesize_device), and the one-voice-per-lane form when a non-empty set forbids
+// the smaller ones.
+static int mixed_form(const trm_mixed *m, const size_t *set_begin)
+{
+    const trm_batch *b0 = m->b[0];
+    uint64_t padded16 = 0, wgs8 = 0;
+    int32_t minCP = 0x7FFFFFFF;
+    bool ratioTooHigh = false;
+    for (size_t s = 0; s < m->b.size(); s++) {
+        const uint64_t n = set_begin[s + 1] - set_begin[s];
+        if (n == 0) continue;
+        padded16 += (n + 15) / 16 * 16;
+        wgs8 += (n + 7) / 8;
+        minCP = std::min(minCP, m->b[s]->c.controlPeriod);
+        ratioTooHigh = ratioTooHigh || quad_ratio_too_high(m->b[s]->c);
+    }
+    const bool octFits = minCP >= 16 && b0->cus > 0 && wgs8 <= 2 * (uint64_t)b0->cus;
+    int which = m->kernel;
+    if (which == TRM_KERNEL_AUTO) which = b0->envKernel;
+    if (which == TRM_KERNEL_AUTO) which = padded16 >= (uint64_t)b0->wideThreshold ? TRM_KERNEL_WIDE : octFits ? TRM_KERNEL_OCT : TRM_KERNEL_QUAD;
+    if (which == TRM_KERNEL_OCT && !octFits) which = TRM_KERNEL_QUAD;
+    if (which != TRM_KERNEL_WIDE && ratioTooHigh) which = TRM_KERNEL_WIDE;
+    if (which == TRM_KERNEL_QUAD && minCP < 24) which = TRM_KERNEL_WIDE;
+    return which;
+}
+
+int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const float *d_frames, const uint64_t *d_frame_offset,
+                                const uint32_t *d_nframes, uint32_t max_nframes, float *d_out, const uint64_t *d_out_offset,
+                                uint32_t *d_number_samples, float *d_max_sample, void *stream_)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    int rc = mixed_check_sets(m, set_begin);
+    if (rc) return rc;
+    const size_t S = m->b.size(), nvoices = set_begin[S];
+    if (nvoices == 0) return TRM_OK;
+    if (!d_frames || !d_frame_offset || !d_nframes || !d_out || !d_out_offset || !d_number_samples || !d_max_sample)
+        return fail(TRM_EINVAL, "null device pointer");
+    hipStream_t stream = (hipStream_t)stream_;
+    trm_batch *b0 = m->b[0];
+    HIP_TRY(hipSetDevice(b0->device));
+    // the noise sequence for the longest voice of any set
+    uint64_t need = 0;
+    const trm_batch *cb = nullptr;        // the set with the shortest control period: the launchers' checks see it
+    for (size_t s = 0; s < S; s++) {
+        if (set_begin[s + 1] == set_begin[s]) continue;
+        const trm_batch *b = m->b[s];
+        const uint64_t ntube = max_nframes > 0 ? (uint64_t)(max_nframes - 1) * (uint64_t)b->d.controlPeriod : 0;
+        if (ntube + 64 > 0x7FFFFFFFull) return fail(TRM_ERANGE, "utterance too long (parameter set %zu)", s);
+        need = std::max<uint64_t>(need, ntube + 2ull * (uint64_t)b->d.padSize + 256u);
+        if (!cb || b->c.controlPeriod < cb->c.controlPeriod) cb = b;
+    }
+    if ((rc = ensure_noise(b0, (uint32_t)need, stream))) return rc;
+    const int which = mixed_form(m, set_begin);
+    const uint32_t perWg = which == TRM_KERNEL_WIDE ? 64u : which == TRM_KERNEL_QUAD ? 16u : 8u;
+    // the block map and the down-sampling sets' row offsets: rebuilt when the shape changes
+    if (!m->haveShape || m->shapeForm != which || m->shapeMaxFrames != max_nframes || !std::equal(set_begin, set_begin + S + 1, m->shapeBegin.begin())) {
+        // (an earlier launch, on whichever stream, may still read the arrays and their host copies' uploads)
+        if (m->lastUseRecorded) HIP_TRY(hipEventSynchronize(m->lastUse));
+        m->haveShape = false;
+        std::vector<uint4> &map = m->hMap;
+        std::vector<uint64_t> &toff = m->hTubeOff;
+        map.clear();
+        toff.assign(nvoices, 0);
+        uint64_t rows = 0;
+        for (size_t s = 0; s < S; s++) {
+            const size_t lo = set_begin[s], hi = set_begin[s + 1];
+            for (size_t f = lo; f < hi; f += perWg) map.push_back(make_uint4((uint32_t)s, (uint32_t)f, (uint32_t)std::min(f + perWg, hi), 0u));
+            const trm_batch *b = m->b[s];
+            if (!b->c.upsample && hi > lo) {
+                // fixed-pitch rows of (max_nframes-1)*controlPeriod + 2*pad floats per voice, 16-byte aligned (as a trm_batch lays them out)
+                const uint64_t ntube = max_nframes > 0 ? (uint64_t)(max_nframes - 1) * (uint64_t)b->d.controlPeriod : 0;
+                const uint64_t pitch = (ntube + 2ull * (uint64_t)b->d.padSize + 3ull) & ~3ull;
+                for (size_t v = lo; v < hi; v++) { toff[v] = rows; rows += pitch; }
+            }
+        }
+        if (map.size() > 0x7FFFFFFFull) return fail(TRM_ERANGE, "too many workgroups");
+        if ((rc = m->dMap.reserve(map.size())) || (rc = m->dTubeOff.reserve(nvoices)) || (rc = m->dTube.reserve(rows + 1))) return rc;
+        HIP_TRY(hipMemcpyAsync(m->dMap.p, map.data(), map.size() * sizeof(uint4), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(m->dTubeOff.p, toff.data(), nvoices * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        m->shapeBegin.assign(set_begin, set_begin + S + 1);
+        m->shapeForm = which;
+        m->shapeMaxFrames = max_nframes;
+        m->mapEntries = (uint32_t)map.size();
+        m->haveShape = true;
+    }
+    trm::TubeArgs a;
+    a.frames = d_frames;
+    a.frame_offset = d_frame_offset;
+    a.nframes = d_nframes;
+    a.out = d_out;
+    a.out_offset = d_out_offset;
+    a.number_samples = d_number_samples;
+    a.max_sample = d_max_sample;
+    a.lp_noise = b0->dNoise.p;
+    a.src_rows = b0->dRows;
+    a.sine = b0->dSine;
+    a.tube_out = m->dTube.p;
+    a.tube_offset = m->dTubeOff.p;
+    a.nvoices = (uint32_t)nvoices;
+    a.max_nframes = max_nframes;
+    a.stamps = nullptr;
+    a.stream_state = nullptr;
+    a.stream_flags = a.stream_n_base = a.stream_k_base = a.stream_k_end = 0;
+    a.mix_map = m->dMap.p;
+    a.set_const = (trm::ConstTable)m->dConst;
+    a.mix_grid = m->mapEntries;
+    m->lastKernel = which;
+    if (which == TRM_KERNEL_OCT)
+        HIP_TRY(trm::launch_tube_oct(cb->c, a, stream));
+    else if (which == TRM_KERNEL_QUAD)
+        HIP_TRY(trm::launch_tube_quad(cb->c, a, stream, b0->cus));
+    else
+        HIP_TRY(trm::launch_tube(cb->c, a, stream));
+    // the down-sampling sets: a voice range each, converted by the batch path's kernels with the set's own rows
+    for (size_t s = 0; s < S; s++) {
+        const size_t lo = set_begin[s], n = set_begin[s + 1] - lo;
+        const trm_batch *b = m->b[s];
+        if (b->c.upsample || n == 0) continue;
+        trm::DownArgs d;
+        d.tube = m->dTube.p;
+        d.tube_offset = m->dTubeOff.p + lo;
+        d.nframes = d_nframes + lo;
+        d.out = d_out;
+        d.out_offset = d_out_offset + lo;
+        d.number_samples = d_number_samples + lo;
+        d.max_sample = d_max_sample + lo;
+        d.fine = b->dFine;
+        d.nvoices = (uint32_t)n;
+        d.max_nframes = max_nframes;
+        d.rows = b->envDownGeneric ? nullptr : b->dDownRows;
+        d.lmax = b->downL; d.rmax = b->downR; d.pitch = b->downPitch;
+        d.stream = 0; d.n_origin = d.n_hi = 0; d.k_base = d.k_end = 0;
+        HIP_TRY(trm::launch_downsample(b->c, d, stream));
+    }
+    // (not while the stream is being captured into a graph: a shape change is not capturable anyway)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
+        HIP_TRY(hipEventRecord(m->lastUse, stream));
+        m->lastUseRecorded = true;
+    }
+    return TRM_OK;
+}
+
+// host-buffer entries: fp32 PCM (out) or int16 (out16, mono or interleaved stereo per set), not both.  On the device voice v's
+// PCM is packed in voice order (fp32: after the voices before it; int16: set by set, channels applied); the results go back to
+// the caller's offsets in one copy where those are the same packing, voice by voice otherwise.
+static int mixed_host_impl(trm_mixed *m, const size_t *set_begin, const float *frames, const uint64_t *frame_offset, const uint32_t *nframes,
+                           float *out, int16_t *out16, int for_wav_data, const uint64_t *out_offset, uint32_t *number_samples,
+                           float *max_sample)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    int rc = mixed_check_sets(m, set_begin);
+    if (rc) return rc;
+    const size_t S = m->b.size(), V = set_begin[S];
+    if (V == 0) return TRM_OK;
+    if (!frames || !frame_offset || !nframes || (!out && !out16) || !out_offset || !number_samples || !max_sample)
+        return fail(TRM_EINVAL, "null pointer");
+    trm_batch *b0 = m->b[0];
+    HIP_TRY(hipSetDevice(b0->device));
+    hipStream_t st = b0->stream;
+    std::vector<uint64_t> dev32(V), dev16(V), base32(S + 1), base16(S + 1);
+    std::vector<uint64_t> ns(V);
+    uint64_t frameRows = 1, o32 = 0, o16 = 0;
+    uint32_t maxFrames = 0;
+    for (size_t s = 0; s < S; s++) {
+        const uint64_t ch = m->b[s]->params.channels == 2 ? 2 : 1;
+        base32[s] = o32;
+        base16[s] = o16;
+        for (size_t v = set_begin[s]; v < set_begin[s + 1]; v++) {
+            ns[v] = trm_batch_samples_for_frames(m->b[s], nframes[v]);
+            dev32[v] = o32;
+            dev16[v] = o16;
+            o32 += ns[v];
+            o16 += ns[v] * ch;
+            frameRows = std::max<uint64_t>(frameRows, frame_offset[v] + nframes[v]);
+            maxFrames = std::max(maxFrames, nframes[v]);
+        }
+    }
+    base32[S] = o32;
+    base16[S] = o16;
+    const std::vector<uint64_t> &packed = out16 ? dev16 : dev32;
+    bool dense = true;
+    for (size_t v = 0; v < V && dense; v++) dense = out_offset[v] == out_offset[0] + packed[v];
+    // within a set, the kernels' voice index runs from the longest voice down (as trm_batch's host entry orders a ragged batch):
+    // a workgroup's voices end together
+    std::vector<uint32_t> perm(V);
+    for (size_t v = 0; v < V; v++) perm[v] = (uint32_t)v;
+    for (size_t s = 0; s < S; s++)
+        std::stable_sort(perm.begin() + set_begin[s], perm.begin() + set_begin[s + 1], [&](uint32_t x, uint32_t y) { return nframes[x] > nframes[y]; });
+    std::vector<uint64_t> pFrameOff(V), pOutOff(V), pRel(V);
+    std::vector<uint32_t> pNFrames(V), pNs(V);
+    std::vector<float> pMx(V);
+    for (size_t s = 0; s < S; s++)
+        for (size_t i = set_begin[s]; i < set_begin[s + 1]; i++) {
+            pFrameOff[i] = frame_offset[perm[i]];
+            pNFrames[i] = nframes[perm[i]];
+            pOutOff[i] = dev32[perm[i]];
+            pRel[i] = dev32[perm[i]] - base32[s];
+        }
+    if ((rc = m->dFrames.reserve(frameRows * 16)) || (rc = m->dOut.reserve(o32 + 1)) || (rc = m->dFrameOff.reserve(V)) ||
+        (rc = m->dOutOff.reserve(V)) || (rc = m->dNFrames.reserve(V)) || (rc = m->dNSamples.reserve(V)) || (rc = m->dMax.reserve(V)))
+        return rc;
+    if (out16 && ((rc = m->dOut16.reserve(o16 + 1)) || (rc = m->dRelOff.reserve(V)))) return rc;
+    HIP_TRY(hipMemcpyAsync(m->dFrames.p, frames, frameRows * 16 * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->dFrameOff.p, pFrameOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->dOutOff.p, pOutOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->dNFrames.p, pNFrames.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (out16) HIP_TRY(hipMemcpyAsync(m->dRelOff.p, pRel.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    rc = trm_mixed_synthesize_device(m, set_begin, m->dFrames.p, m->dFrameOff.p, m->dNFrames.p, maxFrames, m->dOut.p, m->dOutOff.p,
+                                     m->dNSamples.p, m->dMax.p, st);
+    if (rc) return rc;
+    if (out16) {
+        // each set scaled with its own volume, balance and channels (trm_batch_scale_to_int16_device per set)
+        for (size_t s = 0; s < S; s++) {
+            const size_t lo = set_begin[s], n = set_begin[s + 1] - lo;
+            if (n == 0) continue;
+            const trm_batch *b = m->b[s];
+            trm::ScaleArgs sc;
+            sc.pcm = m->dOut.p + base32[s];
+            sc.out_offset = m->dRelOff.p + lo;
+            sc.number_samples = m->dNSamples.p + lo;
+            sc.max_sample = m->dMax.p + lo;
+            sc.pcm16 = m->dOut16.p + base16[s];
+            sc.volumeAmp = trm::io_amplitude(b->params.volume);
+            sc.balance = b->params.balance;
+            sc.channels = b->params.channels;
+            sc.forWavData = for_wav_data != 0;
+            HIP_TRY(trm::launch_int16(sc, (uint32_t)n, st));
+        }
+        if (dense && o16 > 0) HIP_TRY(hipMemcpyAsync(out16 + out_offset[0], m->dOut16.p, o16 * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+        for (size_t s = 0; !dense && s < S; s++) {
+            const uint64_t ch = m->b[s]->params.channels == 2 ? 2 : 1;
+            for (size_t v = set_begin[s]; v < set_begin[s + 1]; v++)
+                if (ns[v]) HIP_TRY(hipMemcpyAsync(out16 + out_offset[v], m->dOut16.p + dev16[v], ns[v] * ch * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+        }
+    } else {
+        if (dense && o32 > 0) HIP_TRY(hipMemcpyAsync(out + out_offset[0], m->dOut.p, o32 * sizeof(float), hipMemcpyDeviceToHost, st));
+        for (size_t v = 0; !dense && v < V; v++)
+            if (ns[v]) HIP_TRY(hipMemcpyAsync(out + out_offset[v], m->dOut.p + dev32[v], ns[v] * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(pNs.data(), m->dNSamples.p, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pMx.data(), m->dMax.p, V * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t i = 0; i < V; i++) {
+        number_samples[perm[i]] = pNs[i];
+        max_sample[perm[i]] = pMx[i];
+    }
+    return TRM_OK;
+}
+
+int trm_mixed_synthesize_host(trm_mixed *m, const size_t *set_begin, const float *frames, const uint64_t *frame_offset,
+                              const uint32_t *nframes, float *out, const uint64_t *out_offset, uint32_t *number_samples, float *max_sample)
+{
+    if (!out) return fail(TRM_EINVAL, "null pointer");
+    return mixed_host_impl(m, set_begin, frames, frame_offset, nframes, out, nullptr, 0, out_offset, number_samples, max_sample);
+}
+
+int trm_mixed_synthesize_host_int16(trm_mixed *m, const size_t *set_begin, const float *frames, const uint64_t *frame_offset,
+                                    const uint32_t *nframes, int16_t *out16, const uint64_t *out_offset, uint32_t *number_samples,
+                                    float *max_sample, int for_wav_data)
+{
+    if (!out16) return fail(TRM_EINVAL, "null pointer");
+    return mixed_host_impl(m, set_begin, frames, frame_offset, nframes, nullptr, out16, for_wav_data, out_offset, number_samples, max_sample);
+}
+
 }  // extern "C"

@@ -9,6 +9,10 @@
 
 namespace trm {
 
+// The mixed launches' table of per-set constants, typed in the constant address space: the kernels' loads from it (at a
+// workgroup-uniform address) then stay scalar loads wherever they sit, as those from the Const kernel argument do.
+typedef const __attribute__((address_space(4))) Const *ConstTable;
+
 // Device pointers of one batch launch.  Layout in HBM:
 //   frames        fp32 [sum nframes][16], voice v owns rows frame_offset[v] .. +nframes[v]
 //   out           fp32 PCM at output rate, voice v's samples at out + out_offset[v]
@@ -66,6 +70,14 @@ struct TubeArgs {
     // Time-split launches: workgroup w of the grid runs segment seg_map[w].x of the block of voices seg_map[w].y, the pairs
     // that have work first (trm_seg_map_kernel).  Null: w / seg_wg_per_seg and w % seg_wg_per_seg.
     const uint2 *seg_map = nullptr;
+    // Mixed-parameter launches (trm_mix_kernel, trm_mix_kernel_q, trm_mix_kernel_o: the tube kernels in a mode of their own; null
+    // otherwise): workgroup w (the batch's, wg_base included) runs the voices mix_map[w].y <= v < mix_map[w].z -- at most
+    // one workgroup's worth, all of parameter set mix_map[w].x -- with set_const[mix_map[w].x] in place of the kernel's
+    // Const argument.  The set index is workgroup-uniform, so its constants stay scalar loads.  A set whose Const says
+    // upsample == 0 writes its tube-rate rows to tube_out (tube_offset per voice); the others convert inline.
+    const uint4 *mix_map = nullptr;       // {set, first voice, end voice, 0}
+    ConstTable set_const = nullptr;
+    uint32_t mix_grid = 0;                // workgroups of the launch = entries of mix_map
 };
 
 // trm_phase_*_kernel: the oscillator advances a time-split launch starts from, and the guard that decides whether the batch
@@ -102,6 +114,12 @@ struct ScaleArgs {
 int tube_kernel_blocks_per_cu();
 hipError_t launch_noise(float *lp, uint32_t from, uint32_t to, double *state, hipStream_t stream);
 hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream);
+// Mixed-parameter instances (TubeArgs::mix_map) of the three tube kernels: trm_mix.hip, trm_mix_q.hip and trm_mix_o.hip compile
+// each kernel's source once more with the mixed instance alone, under a name of its own (trm_mix_kernel, trm_mix_kernel_q,
+// trm_mix_kernel_o).  The launchers above call these for a launch with a mix_map.
+hipError_t launch_mix_wide(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);       // `grid` workgroups from a.wg_base
+hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int sub);
+hipError_t launch_mix_oct(const Const &c, const TubeArgs &a, hipStream_t stream);
 // small-batch form (trm_quad.hip): 16 voices per workgroup, four lanes per voice
 constexpr int kStreamFloats = 192;   // oscillator position, filter memories, 32 samples of FIR / converter history, 4 x 20 tube values
 // `cus` = the device's compute units: more workgroups than that run the instance that fits two per CU

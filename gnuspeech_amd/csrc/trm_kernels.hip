@@ -74,6 +74,10 @@ constexpr int kRoles = 7;            // waves per workgroup: osc, mix, coef x2, 
 constexpr int kTB = 2;               // tube samples per pipeline step (one barrier per step)
 constexpr int kKQuads = 5;           // coef -> tube: 20 floats per lane per sample
 
+// TRM_MIX_TU: trm_mix*.hip include this file again, for the tube kernel's mixed instance alone.  Outside these guards stays
+// ONLY what that kernel needs (constants, types, __device__ functions); every other __global__ kernel, __device__/__constant__
+// variable and host function goes inside them, or the second translation unit builds (and exports) another copy of it.
+#ifndef TRM_MIX_TU
 __global__ void trm_noise_kernel(float *lp, uint32_t from, uint32_t to, double *state)
 {
     // The generator is chaotic: the product must be rounded to double before the subtraction, exactly
@@ -92,6 +96,8 @@ __global__ void trm_noise_kernel(float *lp, uint32_t from, uint32_t to, double *
     state[0] = seed;
     state[1] = x1;
 }
+
+#endif  // TRM_MIX_TU
 
 // One workgroup = 64 voices x 7 waves.
 //   osc, mix, coef x2, tube: lane = voice.  At step i the osc wave produces block i (kTB tube samples), the
@@ -115,12 +121,14 @@ __global__ void trm_noise_kernel(float *lp, uint32_t from, uint32_t to, double *
 // kMode: kModeOneShot | kModeStream (above) | kModeSegments: a time-split launch (trm_kernels.h, TubeArgs::seg_*): the workgroup
 // runs ONE segment of its 64 voices from rest, a warm-up ahead of the segment's first control period; like a stream chunk
 // its tube samples and converter outputs keep their global indices (nBase, kBase -- here per workgroup), unlike one it
-// neither restores nor saves state: only the oscillator position is handed in.
-constexpr int kModeOneShot = 0, kModeStream = 1, kModeSegments = 2;
+// neither restores nor saves state: only the oscillator position is handed in.  kModeMixed: a one-shot launch whose
+// workgroups may belong to different parameter sets (TubeArgs::mix_map): the workgroup's constants come from set_const, its
+// voices are the map entry's range; otherwise it is the one-shot instance.
+constexpr int kModeOneShot = 0, kModeStream = 1, kModeSegments = 2, kModeMixed = 3;
 template <int kMode>
-__global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const C, const TubeArgs A)
+__global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const Carg, const TubeArgs A)
 {
-    constexpr bool kStream = kMode == kModeStream, kSeg = kMode == kModeSegments;
+    constexpr bool kStream = kMode == kModeStream, kSeg = kMode == kModeSegments, kMix = kMode == kModeMixed;
     // (two launches of one batch, one of which runs: TubeArgs::gate)
     if (A.gate && ((*A.gate != 0u) ? 1u : 0u) != A.gate_want) return;
     __shared__ __attribute__((aligned(16))) float4 sW[2 * kTB * kWave];          // osc -> mix: {wa, wb, ax, ah1}
@@ -156,9 +164,14 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
             vblock = wg - seg * A.seg_wg_per_seg;
         }
     }
-    const uint32_t vRaw = vblock * kWave + lane;
-    const bool laneValid = vRaw < A.nvoices;
-    const uint32_t v = laneValid ? vRaw : A.nvoices - 1;
+    // mixed launch: the workgroup's parameter set and voice range.  C is read in place (a reference into the table, not a
+    // copy: held live, its ~75 dwords would spill the scalar file); the set index depends on the workgroup only
+    const uint4 mix = kMix ? A.mix_map[wg] : make_uint4(0u, 0u, 0u, 0u);
+    const Const &C = kMix ? *(const Const *)(A.set_const + mix.x) : Carg;
+    const uint32_t vFirst = kMix ? mix.y : vblock * kWave, vEnd = kMix ? mix.z : A.nvoices;
+    const uint32_t vRaw = vFirst + lane;
+    const bool laneValid = vRaw < vEnd;
+    const uint32_t v = laneValid ? vRaw : vEnd - 1;
     const uint32_t CP = (uint32_t)C.controlPeriod;
     const uint32_t inc = C.timeRegisterIncrement;
     // converter outputs with a read position before tube sample `end`: k < outputs_before(end) (trm_capi.cc outputs_through)
@@ -424,7 +437,7 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
         }
         float *const ring = &sY[lane * kYStride];
         // down-sampling batches: tube-rate samples (and the zero flush) go to HBM for trm_downsample_kernel
-        float *const tubeOut = A.tube_out ? A.tube_out + A.tube_offset[v] : nullptr;
+        float *const tubeOut = (A.tube_out && (!kMix || !C.upsample)) ? A.tube_out + A.tube_offset[v] : nullptr;
         auto one = [&](const Waves &o, Waves &nw, int buf, int u, uint32_t n) {
             const float4 x = sX[(buf * kTB + u) * kWave + lane];
             const float4 *src = &sK[((buf * kTB + u) * kKQuads) * kWave + lane];
@@ -634,9 +647,9 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
             if (lane == 2 * r) myMax = lowHalf;
             if (lane == 2 * r + 1) myMax = highHalf;
         }
-        const uint32_t ov = vblock * kWave + 32 * cw + (lane & 31);
+        const uint32_t ov = vFirst + 32 * cw + (lane & 31);
         const uint32_t nov = __builtin_amdgcn_ds_bpermute(4 * (32 * cw + (lane & 31)), kSeg ? noutAll : noutLane);
-        if (lane < 32 && ov < A.nvoices && C.upsample) {
+        if (lane < 32 && ov < vEnd && C.upsample) {
             if (kSeg) {
                 // (non-negative floats order like their bit patterns; max_sample was zeroed by the launcher)
                 if (seg == 0) A.number_samples[ov] = nov;
@@ -649,6 +662,11 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
         return;
     }
 }
+
+// TRM_MIX_TU: trm_mix*.hip include this file again, for the tube kernel's mixed instance alone.  Outside these guards stays
+// ONLY what that kernel needs (constants, types, __device__ functions); every other __global__ kernel, __device__/__constant__
+// variable and host function goes inside them, or the second translation unit builds (and exports) another copy of it.
+#ifndef TRM_MIX_TU
 
 // Prefix pass of a time-split launch (TubeArgs::seg_*), two kernels.
 //   trm_phase_period_kernel   thread (v, p): the oscillator's advance over voice v's control period p, in units of 2^-30 table
@@ -1067,7 +1085,7 @@ hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream)
     if (a.nvoices == 0) return hipSuccess;
     // (time-split: one workgroup per segment and block of 64 voices; seg_wg_per_seg * segments, set by the caller in wg_base's
     // place holder `seg_grid`)
-    const uint32_t grid = a.seg_periods ? a.seg_grid : (a.nvoices + kWave - 1) / kWave;
+    const uint32_t grid = a.seg_periods ? a.seg_grid : a.mix_map ? a.mix_grid : (a.nvoices + kWave - 1) / kWave;
     // A grid of more than two rounds of resident workgroups (2 per CU) runs measurably slower per workgroup than its first
     // two rounds (MI355X, 256 CUs: 1024 workgroups 18.1 ms, 1536: 32.6, 2048: 40.6 -- profiles/ab_r03.txt): the
     // batch goes out in slices of `slice` workgroups, back to back on the stream.  TRM_WIDE_SLICE overrides (0 = one launch).
@@ -1080,6 +1098,10 @@ hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream)
         const uint32_t n = slice == 0 ? grid - base : (grid - base < slice ? grid - base : slice);
         s.wg_base = base;
         if (a.seg_periods) hipLaunchKernelGGL(trm_tube_kernel<kModeSegments>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s);
+        else if (a.mix_map) {
+            const hipError_t e = launch_mix_wide(c, s, n, stream);
+            if (e != hipSuccess) return e;
+        }
         else if (a.stream_state) hipLaunchKernelGGL(trm_tube_kernel<kModeStream>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s);
         else hipLaunchKernelGGL(trm_tube_kernel<kModeOneShot>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s);
         base += n;
@@ -1177,4 +1199,5 @@ hipError_t launch_int16(const ScaleArgs &s, uint32_t nvoices, hipStream_t stream
     return hipGetLastError();
 }
 
+#endif  // TRM_MIX_TU
 }  // namespace trm

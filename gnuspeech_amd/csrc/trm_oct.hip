@@ -96,7 +96,10 @@ __device__ __forceinline__ HalfPair across_halves(float x)
     return HalfPair{__builtin_bit_cast(float, r.lo), __builtin_bit_cast(float, r.hi)};
 }
 
-__global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Const C, const TubeArgs A)
+// kMix: a launch whose workgroups may belong to different parameter sets (trm_kernels.h, TubeArgs::mix_map): the
+// workgroup's constants come from set_const, its voices are the map entry's range.
+template <bool kMix = false>
+__global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Const Carg, const TubeArgs A)
 {
     typedef OctLds L;
     extern __shared__ __attribute__((aligned(16))) unsigned char sLds[];
@@ -136,9 +139,13 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     const int part = (lane >> 2) & 3;                                    // slot within the block
     const int slot = (upperHalf ? 4 : 0) + part;                         // slot within the step
     const int vq = role == 4 ? lane >> 3 : ((lane >> 4) & 1) * 4 + (lane & 3);      // voice within the workgroup
-    const uint32_t vRaw = blockIdx.x * kOV + vq;
-    const bool laneValid = vRaw < A.nvoices;
-    const uint32_t v = laneValid ? vRaw : A.nvoices - 1;
+    // mixed launch: the workgroup's parameter set (C read in place: a reference into the table) and voice range
+    const uint4 mix = kMix ? A.mix_map[blockIdx.x] : make_uint4(0u, 0u, 0u, 0u);
+    const Const &C = kMix ? *(const Const *)(A.set_const + mix.x) : Carg;
+    const uint32_t vFirst = kMix ? mix.y : blockIdx.x * kOV, vEnd = kMix ? mix.z : A.nvoices;
+    const uint32_t vRaw = vFirst + vq;
+    const bool laneValid = vRaw < vEnd;
+    const uint32_t v = laneValid ? vRaw : vEnd - 1;
 
     const uint32_t nfr = min(A.nframes[v], A.max_nframes);
     const uint32_t nfrMax = wave_max_u32(nfr);
@@ -166,7 +173,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     const float *stageSrc = nullptr;
     uint32_t stageNfr = 0;
     if (role == 2) {
-        const uint32_t sv = min(blockIdx.x * kOV + ((uint32_t)lane >> 2 & 7u), A.nvoices - 1);
+        const uint32_t sv = min(vFirst + ((uint32_t)lane >> 2 & 7u), vEnd - 1);
         stageNfr = min(A.nframes[sv], A.max_nframes);
         stageSrc = A.frames + (stageNfr > 0 ? A.frame_offset[sv] * 16 : 0) + (lane & 3) * 4;
     }
@@ -525,7 +532,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         OctState<float> S;
         oct_reset(S);
         float4 *const ring = reinterpret_cast<float4 *>(&sY[vq * kYStride]);
-        float *const tubeOut = A.tube_out ? A.tube_out + A.tube_offset[v] : nullptr;
+        float *const tubeOut = (A.tube_out && (!kMix || !C.upsample)) ? A.tube_out + A.tube_offset[v] : nullptr;
         // one sample's inputs: this part's record {k | injections} and the ONE per-voice value this part uses (part 0: the
         // glottal input, part 1: the three-way junction's alpha, part 4: the throat output)
         struct In { float4 r; float xs; };
@@ -720,8 +727,8 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
             if (lane == 2 * r) myMax = lowHalf;
             if (lane == 2 * r + 1) myMax = highHalf;
         }
-        const uint32_t ov = blockIdx.x * kOV + (uint32_t)lane;
-        if (lane < kOV && ov < A.nvoices && C.upsample) {
+        const uint32_t ov = vFirst + (uint32_t)lane;
+        if (lane < kOV && ov < vEnd && C.upsample) {
             const uint32_t nf = min(A.nframes[ov], A.max_nframes);
             uint32_t nov = 0;
             if (nf > 0) nov = (uint32_t)((((uint64_t)(nf - 1) * CP + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc);
@@ -732,22 +739,30 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     }
 }
 
+// TRM_MIX_TU: trm_mix*.hip include this file again, for the tube kernel's mixed instance alone.  Outside these guards stays
+// ONLY what that kernel needs (constants, types, __device__ functions); every other __global__ kernel, __device__/__constant__
+// variable and host function goes inside them, or the second translation unit builds (and exports) another copy of it.
+#ifndef TRM_MIX_TU
 hipError_t launch_tube_oct(const Const &c, const TubeArgs &a, hipStream_t stream)
 {
     if (a.nvoices == 0) return hipSuccess;
     if (a.stream_state || c.controlPeriod < 2 * kOB) return hipErrorInvalidValue;     // (the caller picks trm_quad.hip's kernel for these)
+    if (a.mix_map) {      // (a mixed launch: every set's control period; the host demotes the launch otherwise)
+        return a.mix_grid == 0 ? hipSuccess : launch_mix_oct(c, a, stream);
+    }
     static DynamicLdsAllowance lds;
-    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_tube_kernel_o), (int)OctLds::kBytes);
+    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_tube_kernel_o<false>), (int)OctLds::kBytes);
     if (e != hipSuccess) return e;
     const uint32_t grid = (a.nvoices + kOV - 1) / kOV;
-    hipLaunchKernelGGL(trm_tube_kernel_o, dim3(grid), dim3(kWave * kORoles), OctLds::kBytes, stream, c, a);
+    hipLaunchKernelGGL(trm_tube_kernel_o<false>, dim3(grid), dim3(kWave * kORoles), OctLds::kBytes, stream, c, a);
     return hipGetLastError();
 }
 
 int tube_oct_kernel_blocks_per_cu()
 {
     int n = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trm_tube_kernel_o, kWave * kORoles, OctLds::kBytes) == hipSuccess ? n : -1;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trm_tube_kernel_o<false>, kWave * kORoles, OctLds::kBytes) == hipSuccess ? n : -1;
 }
 
+#endif  // TRM_MIX_TU
 }  // namespace trm

@@ -95,10 +95,13 @@ struct QuadLds {
 // per workgroup -- workgroup w runs segment w / seg_wg_per_seg of 16 voices from rest, a warm-up ahead --, no state in or
 // out.  What the one-voice-per-lane kernel's segment instance is for batches that fill the chip, this one is for a handful of
 // voices: a single utterance becomes sixteen lanes' worth of segments on one CU.
-template <bool kStream, int kSub, bool kSeg = false>
-__global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Const C, const TubeArgs A)
+// kMix: a one-shot launch whose workgroups may belong to different parameter sets (trm_kernels.h, TubeArgs::mix_map): the
+// workgroup's constants come from set_const, its voices are the map entry's range.
+template <bool kStream, int kSub, bool kSeg = false, bool kMix = false>
+__global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Const Carg, const TubeArgs A)
 {
     static_assert(!kSeg || kStream, "the segment instance is built on the streaming instance");
+    static_assert(!kMix || !kStream, "mixed-parameter launches are one-shot");
     if (kSeg && A.gate && ((*A.gate != 0u) ? 1u : 0u) != A.gate_want) return;      // (two launches, the device runs one: TubeArgs::gate)
     constexpr int kStepN = kQB * kSub;       // tube samples per step
     typedef QuadLds<kSub> L;
@@ -148,9 +151,13 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
             vblock = blockIdx.x - seg * A.seg_wg_per_seg;
         }
     }
-    const uint32_t vRaw = vblock * kQV + vq;
-    const bool laneValid = vRaw < A.nvoices;
-    const uint32_t v = laneValid ? vRaw : A.nvoices - 1;
+    // mixed launch: the workgroup's parameter set (C read in place: a reference into the table) and voice range
+    const uint4 mix = kMix ? A.mix_map[blockIdx.x] : make_uint4(0u, 0u, 0u, 0u);
+    const Const &C = kMix ? *(const Const *)(A.set_const + mix.x) : Carg;
+    const uint32_t vFirst = kMix ? mix.y : vblock * kQV, vEnd = kMix ? mix.z : A.nvoices;
+    const uint32_t vRaw = vFirst + vq;
+    const bool laneValid = vRaw < vEnd;
+    const uint32_t v = laneValid ? vRaw : vEnd - 1;
     const uint32_t CP = (uint32_t)C.controlPeriod;
     const uint32_t inc = C.timeRegisterIncrement;
     auto outputs_before = [&](uint64_t end) { return end == 0 ? 0u : (uint32_t)(((end << 16) - 1) / inc + 1); };
@@ -210,7 +217,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     const float *stageSrc = nullptr;
     uint32_t stageNfr = 0;
     if (kLdsFrames && role == 2) {
-        const uint32_t sv = min(vblock * kQV + ((uint32_t)lane >> 2), A.nvoices - 1);
+        const uint32_t sv = min(vFirst + ((uint32_t)lane >> 2), vEnd - 1);
         stageNfr = min(A.nframes[sv], A.max_nframes);
         stageSrc = A.frames + (stageNfr > 0 ? A.frame_offset[sv] * 16 : 0) + (lane & 3) * 4;
     }
@@ -621,7 +628,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
             stTube[16] = S.radX.x; stTube[17] = S.radX.y; stTube[18] = S.radY.x; stTube[19] = S.radY.y;
         };
         float4 *const ring = reinterpret_cast<float4 *>(&sY[vq * kYStride]);
-        float *const tubeOut = A.tube_out ? A.tube_out + A.tube_offset[v] : nullptr;
+        float *const tubeOut = (A.tube_out && (!kMix || !C.upsample)) ? A.tube_out + A.tube_offset[v] : nullptr;
         // one sample's inputs: {gin, -, throat output}, end coefficients, this part's record {transmission | injection}
         struct In { float4 x, e4, k4, t4; };
         auto load_in = [&](uint32_t blk, int s) {
@@ -838,8 +845,8 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
             if (lane == 2 * r) myMax = lowHalf;
             if (lane == 2 * r + 1) myMax = highHalf;
         }
-        const uint32_t ov = vblock * kQV + (uint32_t)lane;
-        if (lane < kQV && ov < A.nvoices && C.upsample) {
+        const uint32_t ov = vFirst + (uint32_t)lane;
+        if (lane < kQV && ov < vEnd && C.upsample) {
             const uint32_t nf = min(A.nframes[ov], A.max_nframes);
             uint32_t nov = 0;
             if (streaming && !kSeg) nov = A.stream_k_end - kBase;
@@ -857,6 +864,11 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     }
 }
 
+// TRM_MIX_TU: trm_mix*.hip include this file again, for the tube kernel's mixed instance alone.  Outside these guards stays
+// ONLY what that kernel needs (constants, types, __device__ functions); every other __global__ kernel, __device__/__constant__
+// variable and host function goes inside them, or the second translation unit builds (and exports) another copy of it.
+#ifndef TRM_MIX_TU
+
 // `cus`: the device's compute units.  A batch of more workgroups than that runs the instance that fits two of them on
 // a CU (kSub = 1); up to one workgroup per CU the instance with two independent blocks per step (kSub = 2).
 template <bool kStream, int kSub, bool kSeg = false>
@@ -869,6 +881,7 @@ static hipError_t launch_instance(const Const &c, const TubeArgs &a, hipStream_t
     return hipGetLastError();
 }
 
+
 hipError_t launch_tube_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int cus)
 {
     if (a.nvoices == 0) return hipSuccess;
@@ -878,7 +891,12 @@ hipError_t launch_tube_quad(const Const &c, const TubeArgs &a, hipStream_t strea
     // one-shot instances stage the control frames in a ring of four: frame p+3 replaces frame p-1 one step into period p,
     // and the coefficient waves' last lanes read frame p-1 three steps into period p-1 -- a period must hold three steps
     // of up to 8 samples (the caller runs trm_kernels.hip's kernel otherwise)
+    // (a mixed launch: every set's control period; the host demotes the launch otherwise)
     if (c.controlPeriod < 24) return hipErrorInvalidValue;
+    if (a.mix_map) {
+        if (a.mix_grid == 0) return hipSuccess;
+        return launch_mix_quad(c, a, stream, cus > 0 && a.mix_grid > (uint32_t)cus ? 1 : 2);
+    }
     if (cus > 0 && grid > (uint32_t)cus) return launch_instance<false, 1>(c, a, stream, grid);
     return launch_instance<false, 2>(c, a, stream, grid);
 }
@@ -891,4 +909,5 @@ int tube_quad_kernel_blocks_per_cu(int sub)
     return e == hipSuccess ? n : -1;
 }
 
+#endif  // TRM_MIX_TU
 }  // namespace trm

@@ -436,6 +436,53 @@ int  trm_batch_set_timing(trm_batch *batch, int on);
  * (TRMUtility.m:71-85 + TRMFilters.m:81-86, generated on the GPU in fp64, stored fp32) to host. */
 int  trm_batch_noise_table(trm_batch *batch, float *host_out, size_t n);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mixed-parameter batches (no reference counterpart).  A trm_batch runs V tubes that share one trm_input_params; a server
+ * that batches the sentences of several voices (GnuSpeechServerProtocol.h:17 setVoiceType:, Monet's tube length,
+ * MMSynthesisParameters.m:293) would need one launch per parameter set, each too small to fill the chip.  A trm_mixed
+ * holds `nsets` parameter sets and runs all their voices in ONE launch: every workgroup holds voices of a single set and
+ * reads that set's constants from a small device table, so a voice's samples are bit for bit those a trm_batch of its own
+ * set computes in the same kernel form with the time split off.
+ *   - Voices are grouped by set: set s owns voices [set_begin[s], set_begin[s+1]) -- a host array of nsets+1 entries,
+ *     set_begin[0] == 0, non-decreasing, set_begin[nsets] == nvoices (TRM_EINVAL otherwise, before anything is enqueued).
+ *     Sets may be empty.  frame_offset, out_offset, nframes, number_samples and max_sample are indexed by voice as in the
+ *     trm_batch entries.
+ *   - Form under AUTO: the one a trm_batch of the same voice count (every set padded to the form's workgroup: 64, 16 or 8
+ *     voices) runs with the time split off; the launch runs the one-voice-per-lane form when any non-empty set forbids the
+ *     smaller ones (more than four outputs per tube sample; control period below 24 tube samples for TRM_KERNEL_QUAD, 16
+ *     for TRM_KERNEL_OCT).  A form set by name (trm_mixed_set_kernel, TRM_TUBE_KERNEL) is demoted the same way.
+ *   - Whole utterances always: time-split launches of mixed batches are not offered (TRM_TIME_SPLIT is not read).
+ *   - The block map and per-voice tube-row offsets are uploaded when the launch's shape (set_begin, form, max_nframes)
+ *     changes; a repeated call of one shape through the device entry is pure stream work.
+ * Not offered for mixed batches: streams (trm_stream_*), several devices (trm_multi_*), device-side sound-file images.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct trm_mixed trm_mixed;
+/* Validates every set (as trm_batch_create does: a bad set fails with its code and trm_last_error names its index) before it
+ * looks for a device.  Reads TRM_TUBE_KERNEL and TRM_QUAD_CUS once, like trm_batch_create. */
+int    trm_mixed_create(const trm_input_params *params, size_t nsets, int device, trm_mixed **out);
+void   trm_mixed_destroy(trm_mixed *m);
+int    trm_mixed_derived(const trm_mixed *m, size_t set, trm_derived *out);
+size_t trm_mixed_samples_for_frames(const trm_mixed *m, size_t set, size_t nframes);
+/* Device-buffer form (HIP device pointers on the object's device; asynchronous on `stream`, a hipStream_t or NULL);
+ * max_nframes = the largest d_nframes[v], as in trm_batch_synthesize_device. */
+int    trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin,
+                                   const float *d_frames, const uint64_t *d_frame_offset,
+                                   const uint32_t *d_nframes, uint32_t max_nframes,
+                                   float *d_out, const uint64_t *d_out_offset,
+                                   uint32_t *d_number_samples, float *d_max_sample, void *stream);
+/* Host-buffer form: as trm_batch_synthesize_host (caller sizes voice v's output with trm_mixed_samples_for_frames of its set). */
+int    trm_mixed_synthesize_host(trm_mixed *m, const size_t *set_begin, const float *frames,
+                                 const uint64_t *frame_offset, const uint32_t *nframes, float *out,
+                                 const uint64_t *out_offset, uint32_t *number_samples, float *max_sample);
+/* int16 as trm_batch_synthesize_host_int16, each voice with its own set's volume, balance and channels.
+ * out_offset counts int16 values (channels of the voice's set already applied): voice v starts at out16[out_offset[v]] */
+int    trm_mixed_synthesize_host_int16(trm_mixed *m, const size_t *set_begin, const float *frames,
+                                       const uint64_t *frame_offset, const uint32_t *nframes, int16_t *out16,
+                                       const uint64_t *out_offset, uint32_t *number_samples, float *max_sample,
+                                       int for_wav_data);
+int    trm_mixed_set_kernel(trm_mixed *m, int kernel);       /* TRM_KERNEL_AUTO (default) / _WIDE / _QUAD / _OCT */
+int    trm_mixed_last_kernel(const trm_mixed *m);
+
 /* Library / device identification. */
 int  trm_device_count(void);
 const char *trm_build_info(void);
