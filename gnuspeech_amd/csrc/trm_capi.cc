@@ -1862,15 +1862,16 @@ int trm_mixed_set_kernel(trm_mixed *m, int kernel)
 
 int trm_mixed_last_kernel(const trm_mixed *m) { return m ? m->lastKernel : TRM_KERNEL_AUTO; }
 
-static int mixed_check_sets(const trm_mixed *m, const size_t *set_begin)
+static int mixed_check_sets(size_t nsets, const size_t *set_begin)
 {
     if (!set_begin) return fail(TRM_EINVAL, "null set_begin");
     if (set_begin[0] != 0) return fail(TRM_EINVAL, "set_begin[0] = %zu, not 0", set_begin[0]);
-    for (size_t s = 0; s < m->b.size(); s++)
+    for (size_t s = 0; s < nsets; s++)
         if (set_begin[s + 1] < set_begin[s]) return fail(TRM_EINVAL, "set_begin decreases at set %zu (%zu -> %zu)", s, set_begin[s], set_begin[s + 1]);
-    if (set_begin[m->b.size()] > 0xFFFFFFFFull - 64) return fail(TRM_EINVAL, "too many voices");
+    if (set_begin[nsets] > 0xFFFFFFFFull - 64) return fail(TRM_EINVAL, "too many voices");
     return TRM_OK;
 }
+static int mixed_check_sets(const trm_mixed *m, const size_t *set_begin) { return mixed_check_sets(m->b.size(), set_begin); }
 
 // The kernel form of a mixed launch: what a trm_batch of the same voice count -- every set padded to the form's workgroup --
 // runs with the time split off (trm_batch_synthesize_device), and the one-voice-per-lane form when a non-empty set forbids
@@ -2136,6 +2137,471 @@ int trm_mixed_synthesize_host_int16(trm_mixed *m, const size_t *set_begin, const
 {
     if (!out16) return fail(TRM_EINVAL, "null pointer");
     return mixed_host_impl(m, set_begin, frames, frame_offset, nframes, nullptr, out16, for_wav_data, out_offset, number_samples, max_sample);
+}
+
+
+// ------------------------------------------------------------------ mixed-parameter streams
+// A trm_stream whose voices belong to several parameter sets: one trm_batch per set (constants, derived values, down-sampling
+// rows; the first lends its noise sequence and stream), one block map {set, first voice, end voice} built at create -- the
+// state is laid out for it, so the set layout is the stream's for life -- and one tube launch per chunk.  Every set has its own
+// control period and converter increment, so the chunk passes the count of control periods pushed so far (the same for every
+// set) and each workgroup derives its set's tube-sample base, output range and noise offset (trm_kernels.h, TubeArgs).
+struct trm_mixed_stream {
+    std::vector<trm_batch *> b;              // per set
+    std::vector<size_t> begin;               // set_begin: voices begin[s] .. begin[s + 1] - 1 are set s's
+    size_t nvoices = 0;
+    bool wide = false;                       // trm_mix_kernel's streaming instance instead of trm_mix_kernel_q's
+    int mode = TRM_STREAM_MODE_FRAMEWORK;
+    trm::Const *dConst = nullptr;            // the sets' constants, [nsets]
+    DevBuf<uint4> dMap;
+    uint32_t mapEntries = 0;
+    DevBuf<float> dState, dFrames, dOut, dMax, dLast, dPushed;
+    // down-sampling sets: [history | chunk] tube-rate rows per voice (set s's at tubeBase[s], pitch rowPitch[s]) and the history
+    // between chunks (set s's hist[s] floats per voice at histBase[s])
+    DevBuf<float> dTube, dHist;
+    DevBuf<uint64_t> dTubeOff, dTubeOff0;
+    std::vector<uint32_t> hist;
+    std::vector<uint64_t> histBase, tubeBase, rowPitch;
+    uint64_t tubeFloats = 0;
+    DevBuf<uint64_t> dFrameOff, dOutOff;
+    DevBuf<uint32_t> dNFrames, dNSamples;
+    std::vector<float> hostOut;
+    // host copies of the index arrays of the current chunk shape (the uploads read them until the chunk after them has run)
+    std::vector<uint64_t> hFrameOff, hOutOff, hTubeOff0, hTubeOff;
+    std::vector<uint32_t> hNFrames;
+    size_t shapeRows = 0, shapePitch = 0;
+    bool haveLast = false;                   // an utterance is open
+    bool first = true;                       // no chunk of it has been synthesized yet
+    uint64_t periods = 0;                    // control periods synthesized so far (every set)
+    // chunk ordering across HIP streams (as trm_stream's); chunkDone also marks the last use of the index arrays
+    hipEvent_t chunkDone = nullptr;
+    hipStream_t lastStream = nullptr;
+    bool haveChunk = false;
+};
+
+void trm_mixed_stream_destroy(trm_mixed_stream *s)
+{
+    if (!s) return;
+    if (!s->b.empty()) (void)hipSetDevice(s->b[0]->device);
+    if (s->dConst) (void)hipFree(s->dConst);
+    if (s->chunkDone) (void)hipEventDestroy(s->chunkDone);
+    std::vector<trm_batch *> b;
+    b.swap(s->b);
+    delete s;                 // device buffers first (the batches own the stream they were used on)
+    for (trm_batch *x : b) trm_batch_destroy(x);
+}
+
+int trm_mixed_stream_create(const trm_input_params *params, size_t nsets, const size_t *set_begin, int device, trm_mixed_stream **out)
+{
+    if (!params || !out || nsets == 0) return fail(TRM_EINVAL, "null argument / no parameter sets");
+    *out = nullptr;
+    if (nsets > 0xFFFFFFFFull) return fail(TRM_EINVAL, "too many parameter sets");
+    int rc = mixed_check_sets(nsets, set_begin);
+    if (rc) return rc;
+    const size_t V = set_begin[nsets];
+    if (V == 0) return fail(TRM_EINVAL, "no voices");
+    // every set is checked before a device is looked for: a bad set is reported (by index) on any host
+    for (size_t k = 0; k < nsets; k++) {
+        trm::Const c;
+        trm_derived d;
+        rc = trm::build_const(params[k], c, d);
+        if (rc != TRM_OK) return fail(rc, "parameter set %zu: %s", k, trm_strerror(rc));
+        if (c.controlPeriod < 4)
+            return fail(TRM_ERANGE, "parameter set %zu: control period of %d tube samples is below the kernel's pipeline step", k, c.controlPeriod);
+    }
+    trm_mixed_stream *s = new (std::nothrow) trm_mixed_stream();
+    if (!s) return fail(TRM_ENOMEM, "trm_mixed_stream");
+    for (size_t k = 0; k < nsets; k++) {
+        trm_batch *b = nullptr;
+        rc = trm_batch_create(&params[k], device, &b);
+        if (rc) {
+            std::string err = trm_last_error();
+            trm_mixed_stream_destroy(s);
+            return fail(rc, "parameter set %zu: %s", k, err.c_str());
+        }
+        s->b.push_back(b);
+        device = b->device;
+        if (!b->c.upsample && (!b->dDownRows || b->downR > (uint32_t)b->d.padSize || b->downL > (uint32_t)b->d.padSize + 1u ||
+                               !trm::downsample_tiled_fits(b->c, b->downL, b->downR))) {
+            // (as trm_stream_create: a chunk emits the outputs whose read position lies inside it)
+            const int rate = b->d.sampleRate;
+            trm_mixed_stream_destroy(s);
+            return fail(TRM_ERANGE, "parameter set %zu: streaming: output rate too far below the tube rate (%d Hz) for the tiled down-sampling kernel", k, rate);
+        }
+    }
+    s->begin.assign(set_begin, set_begin + nsets + 1);
+    s->nvoices = V;
+    trm_batch *b0 = s->b[0];
+    // the form, fixed for the stream's life: one voice per lane when the voices -- every set padded to a workgroup of 64 --
+    // fill the chip, or when a set with voices makes more than four outputs per tube sample; four lanes per voice otherwise.
+    // TRM_TUBE_KERNEL=wide|quad overrides, with the same demotion.
+    uint64_t padded64 = 0;
+    bool ratioTooHigh = false;
+    for (size_t k = 0; k < nsets; k++) {
+        const uint64_t n = set_begin[k + 1] - set_begin[k];
+        if (n == 0) continue;
+        padded64 += (n + 63) / 64 * 64;
+        ratioTooHigh = ratioTooHigh || quad_ratio_too_high(s->b[k]->c);
+    }
+    s->wide = padded64 >= (uint64_t)b0->wideThreshold || ratioTooHigh;
+    if (b0->envKernel == TRM_KERNEL_WIDE) s->wide = true;
+    if (b0->envKernel == TRM_KERNEL_QUAD && !ratioTooHigh) s->wide = false;
+    const size_t perWg = s->wide ? 64 : 16;
+    std::vector<uint4> map;
+    for (size_t k = 0; k < nsets; k++)
+        for (size_t f = set_begin[k]; f < set_begin[k + 1]; f += perWg)
+            map.push_back(make_uint4((uint32_t)k, (uint32_t)f, (uint32_t)std::min(f + perWg, set_begin[k + 1]), 0u));
+    s->mapEntries = (uint32_t)map.size();
+    // history rows of the down-sampling sets
+    s->hist.assign(nsets, 0);
+    s->histBase.assign(nsets, 0);
+    s->tubeBase.assign(nsets, 0);
+    s->rowPitch.assign(nsets, 0);
+    uint64_t histFloats = 0;
+    uint32_t noiseRate = 0;
+    for (size_t k = 0; k < nsets; k++) {
+        const trm_batch *b = s->b[k];
+        noiseRate = std::max(noiseRate, (uint32_t)b->d.sampleRate);
+        if (b->c.upsample) continue;
+        s->hist[k] = (2u * (uint32_t)b->d.padSize + 3u) & ~3u;
+        s->histBase[k] = histFloats;
+        histFloats += (uint64_t)(set_begin[k + 1] - set_begin[k]) * s->hist[k];
+    }
+    // state: the wide form keys it by map entry (64 lanes each), the four-lane form by voice
+    const size_t stateVoices = s->wide ? (size_t)s->mapEntries * 64 : (V + 63) / 64 * 64;
+    std::vector<trm::Const> cs(nsets);
+    for (size_t k = 0; k < nsets; k++) cs[k] = s->b[k]->c;
+    if ((rc = s->dState.reserve(stateVoices * trm::kStreamFloats)) || (rc = s->dLast.reserve(V * 16)) || (rc = s->dFrameOff.reserve(V)) ||
+        (rc = s->dOutOff.reserve(V)) || (rc = s->dNFrames.reserve(V)) || (rc = s->dNSamples.reserve(V)) || (rc = s->dMax.reserve(V)) ||
+        (rc = s->dMap.reserve(map.size())) || (rc = s->dTubeOff.reserve(V)) || (rc = s->dTubeOff0.reserve(V)) ||
+        (histFloats > 0 && (rc = s->dHist.reserve(histFloats)))) {
+        trm_mixed_stream_destroy(s);
+        return rc;
+    }
+    hipError_t e = hipMalloc((void **)&s->dConst, nsets * sizeof(trm::Const));
+    if (e == hipSuccess) e = hipMemcpy(s->dConst, cs.data(), nsets * sizeof(trm::Const), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s->dMap.p, map.data(), map.size() * sizeof(uint4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        trm_mixed_stream_destroy(s);
+        return fail(TRM_EHIP, "constant table / block map: %s", hipGetErrorString(e));
+    }
+    // the noise sequence of the first 16 s at the fastest tube rate, now rather than chunk by chunk (trm_stream_create)
+    if ((rc = ensure_noise(b0, 16u * noiseRate, b0->stream))) {
+        trm_mixed_stream_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return TRM_OK;
+}
+
+int trm_mixed_stream_set_mode(trm_mixed_stream *s, int mode)
+{
+    if (!s) return fail(TRM_EINVAL, "null stream");
+    if (mode != TRM_STREAM_MODE_FRAMEWORK && mode != TRM_STREAM_MODE_TRACT) return fail(TRM_EINVAL, "unknown stream mode %d", mode);
+    if (s->haveLast) return fail(TRM_EINVAL, "the stream's mode can only change between utterances (before the first push or after finish)");
+    if (mode == s->mode) return TRM_OK;
+    HIP_TRY(hipSetDevice(s->b[0]->device));
+    const size_t S = s->b.size();
+    std::vector<trm::Const> cs(S);
+    for (size_t k = 0; k < S; k++) {
+        s->b[k]->c.fricGain = mode == TRM_STREAM_MODE_TRACT ? 10.0f : 1.0f;      // Applications/TRAcT/tube.c:1371
+        cs[k] = s->b[k]->c;
+    }
+    // (between utterances: the last chunk, on whichever stream, may still read the table)
+    if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
+    HIP_TRY(hipMemcpy(s->dConst, cs.data(), S * sizeof(trm::Const), hipMemcpyHostToDevice));
+    s->mode = mode;
+    return TRM_OK;
+}
+
+int trm_mixed_stream_mode(const trm_mixed_stream *s) { return s ? s->mode : TRM_STREAM_MODE_FRAMEWORK; }
+int trm_mixed_stream_kernel(const trm_mixed_stream *s) { return s ? (s->wide ? TRM_KERNEL_WIDE : TRM_KERNEL_QUAD) : TRM_KERNEL_AUTO; }
+
+// set k's converter outputs of the next chunk: global indices k_base <= k < *kEnd (rows = frame rows per voice on the device)
+static uint64_t mixed_stream_range(const trm_mixed_stream *s, size_t k, uint64_t rows, bool flush, uint64_t *kEnd)
+{
+    const trm_batch *b = s->b[k];
+    const uint64_t CP = (uint64_t)b->d.controlPeriod, nBase = s->periods * CP;
+    const uint32_t inc = b->c.timeRegisterIncrement;
+    const uint64_t kBase = outputs_through(nBase, inc);
+    *kEnd = flush ? ((nBase + 2ull * (uint64_t)b->d.padSize) * 65536ull + inc - 1) / inc : outputs_through(nBase + (rows - 1) * CP, inc);
+    return kBase;
+}
+
+size_t trm_mixed_stream_samples_for_push(const trm_mixed_stream *s, size_t set, size_t nframes)
+{
+    if (!s || set >= s->b.size() || nframes == 0) return 0;
+    const bool leadRow = s->haveLast || s->mode == TRM_STREAM_MODE_TRACT;
+    uint64_t kEnd = 0;
+    const uint64_t kBase = mixed_stream_range(s, set, nframes + (leadRow ? 1 : 0), false, &kEnd);
+    return (size_t)(kEnd - kBase);
+}
+
+size_t trm_mixed_stream_samples_for_finish(const trm_mixed_stream *s, size_t set)
+{
+    if (!s || set >= s->b.size() || !s->haveLast) return 0;
+    uint64_t kEnd = 0;
+    const uint64_t kBase = mixed_stream_range(s, set, 1, true, &kEnd);
+    return (size_t)(kEnd - kBase);
+}
+
+// One chunk on the device, as stream_chunk_device: control periods from the stream's last frame through the pushed frames
+// (device, [nvoices][nframes][16]) or the converter's flush; set k's PCM (nout[k] samples per voice, nout optional) to d_out
+// (voice v at d_out + v * out_pitch).  Pure stream work on `st` unless the chunk's shape changes or the noise has to grow.
+static int mixed_stream_chunk_impl(trm_mixed_stream *s, const float *d_pushed, size_t nframes, bool flush, float *d_out, size_t out_pitch,
+                                   uint32_t *nout, hipStream_t st)
+{
+    trm_batch *b0 = s->b[0];
+    const size_t S = s->b.size(), V = s->nvoices;
+    const bool tract = s->mode == TRM_STREAM_MODE_TRACT;
+    const bool leadRow = s->haveLast || (tract && !flush);            // (trm_stream: TRAcT order's row 0 only has to exist)
+    const size_t rows = (flush ? 0 : nframes) + (leadRow ? 1 : 0);
+    if (rows == 0) { if (nout) memset(nout, 0, S * sizeof(uint32_t)); return TRM_OK; }
+    const uint64_t Q = rows - 1;                                     // control periods of this chunk
+    std::vector<uint64_t> kBase(S), kEnd(S);
+    uint64_t maxCount = 0, noiseNeed = 0;
+    bool anyDown = false;
+    for (size_t k = 0; k < S; k++) {
+        const trm_batch *b = s->b[k];
+        kBase[k] = mixed_stream_range(s, k, rows, flush, &kEnd[k]);
+        if (nout) nout[k] = (uint32_t)(kEnd[k] - kBase[k]);
+        if (s->begin[k + 1] == s->begin[k]) continue;
+        const uint64_t nHi = (s->periods + Q) * (uint64_t)b->d.controlPeriod + 2ull * (uint64_t)b->d.padSize;
+        if (nHi + 512 > 0x7FFFFFFFull || kEnd[k] > 0xFFFFFFFFull) return fail(TRM_ERANGE, "stream too long (parameter set %zu)", k);
+        maxCount = std::max(maxCount, kEnd[k] - kBase[k]);
+        noiseNeed = std::max(noiseNeed, nHi + 256u);
+        anyDown = anyDown || !b->c.upsample;
+    }
+    if (maxCount > 0 && (!d_out || out_pitch < maxCount))
+        return fail(TRM_EINVAL, "output pitch %zu < %llu samples (the largest set's count)", out_pitch, (unsigned long long)maxCount);
+    int rc;
+    if ((rc = s->dFrames.reserve(V * rows * 16))) return rc;
+    if (leadRow) {
+        const float *src = s->haveLast ? s->dLast.p : d_pushed;
+        const size_t spitch = s->haveLast ? 16 : nframes * 16;
+        HIP_TRY(hipMemcpy2DAsync(s->dFrames.p, rows * 16 * sizeof(float), src, spitch * sizeof(float), 16 * sizeof(float), V, hipMemcpyDeviceToDevice, st));
+    }
+    if (!flush)
+        HIP_TRY(hipMemcpy2DAsync(s->dFrames.p + (leadRow ? 16 : 0), rows * 16 * sizeof(float), d_pushed, nframes * 16 * sizeof(float),
+                                 nframes * 16 * sizeof(float), V, hipMemcpyDeviceToDevice, st));
+    // the index arrays depend on the chunk's shape only: rebuilt when it changes, behind the last chunk that read them
+    if (s->shapeRows != rows || s->shapePitch != out_pitch) {
+        if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
+        s->hFrameOff.resize(V); s->hOutOff.resize(V); s->hNFrames.assign(V, (uint32_t)rows);
+        for (size_t v = 0; v < V; v++) { s->hFrameOff[v] = v * rows; s->hOutOff[v] = v * out_pitch; }
+        HIP_TRY(hipMemcpyAsync(s->dFrameOff.p, s->hFrameOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s->dOutOff.p, s->hOutOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s->dNFrames.p, s->hNFrames.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (anyDown) {
+            // rows of [history | the chunk's tube samples (| the flush zeros)], 16-byte aligned, set after set
+            s->hTubeOff0.assign(V, 0); s->hTubeOff.assign(V, 0);
+            uint64_t at = 0;
+            for (size_t k = 0; k < S; k++) {
+                const trm_batch *b = s->b[k];
+                if (b->c.upsample) continue;
+                s->rowPitch[k] = ((uint64_t)s->hist[k] + Q * (uint64_t)b->d.controlPeriod + 2ull * (uint64_t)b->d.padSize + 3ull) & ~3ull;
+                s->tubeBase[k] = at;
+                for (size_t v = s->begin[k]; v < s->begin[k + 1]; v++) {
+                    s->hTubeOff0[v] = at;
+                    s->hTubeOff[v] = at + s->hist[k];
+                    at += s->rowPitch[k];
+                }
+            }
+            s->tubeFloats = at;
+            HIP_TRY(hipMemcpyAsync(s->dTubeOff0.p, s->hTubeOff0.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(s->dTubeOff.p, s->hTubeOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        }
+        s->shapeRows = rows; s->shapePitch = out_pitch;
+    }
+    if ((rc = ensure_noise(b0, (uint32_t)noiseNeed, st))) return rc;
+    if (Q > 0 || flush) {
+        if (anyDown) {
+            if ((rc = s->dTube.reserve(s->tubeFloats + 4))) return rc;
+            if (s->first) HIP_TRY(hipMemsetAsync(s->dHist.p, 0, s->dHist.cap * sizeof(float), st));
+            for (size_t k = 0; k < S; k++) {
+                const size_t n = s->begin[k + 1] - s->begin[k];
+                if (s->b[k]->c.upsample || n == 0) continue;
+                HIP_TRY(hipMemcpy2DAsync(s->dTube.p + s->tubeBase[k], s->rowPitch[k] * sizeof(float), s->dHist.p + s->histBase[k],
+                                         s->hist[k] * sizeof(float), s->hist[k] * sizeof(float), n, hipMemcpyDeviceToDevice, st));
+            }
+        }
+        trm::TubeArgs a;
+        a.frames = s->dFrames.p;
+        a.frame_offset = s->dFrameOff.p;
+        a.nframes = s->dNFrames.p;
+        a.out = d_out;
+        a.out_offset = s->dOutOff.p;
+        a.number_samples = s->dNSamples.p;
+        a.max_sample = s->dMax.p;
+        a.lp_noise = b0->dNoise.p;                  // (not advanced: every set's workgroups add their own base)
+        a.src_rows = b0->dRows;
+        a.sine = b0->dSine;
+        a.tube_out = anyDown ? s->dTube.p : nullptr;
+        a.tube_offset = anyDown ? s->dTubeOff.p : nullptr;
+        a.nvoices = (uint32_t)V;
+        a.max_nframes = 0xFFFFFFFFu;
+        a.stamps = nullptr;
+        a.stream_state = s->dState.p;
+        a.stream_flags = (s->first ? 1u : 0u) | (flush ? 2u : 0u) | (tract ? 4u : 0u);
+        a.stream_n_base = (uint32_t)s->periods;     // control periods, not tube samples (trm_kernels.h: a mixed stream)
+        a.stream_k_base = 0;
+        a.stream_k_end = (uint32_t)(s->periods + Q);
+        a.mix_map = s->dMap.p;
+        a.set_const = (trm::ConstTable)s->dConst;
+        a.mix_grid = s->mapEntries;
+        if (s->wide) HIP_TRY(trm::launch_tube(b0->c, a, st));
+        else HIP_TRY(trm::launch_tube_quad(b0->c, a, st, b0->cus));
+        s->first = false;
+        for (size_t k = 0; k < S; k++) {
+            const size_t lo = s->begin[k], n = s->begin[k + 1] - lo;
+            const trm_batch *b = s->b[k];
+            if (n == 0) continue;
+            const uint64_t count = kEnd[k] - kBase[k];
+            if (!b->c.upsample) {
+                const uint64_t nBase = s->periods * (uint64_t)b->d.controlPeriod, N = Q * (uint64_t)b->d.controlPeriod;
+                if (count > 0) {
+                    trm::DownArgs d;
+                    d.tube = s->dTube.p;
+                    d.tube_offset = s->dTubeOff0.p + lo;
+                    d.nframes = s->dNFrames.p + lo;
+                    d.out = d_out;
+                    d.out_offset = s->dOutOff.p + lo;
+                    d.number_samples = s->dNSamples.p + lo;
+                    d.max_sample = s->dMax.p + lo;
+                    d.fine = b->dFine;
+                    d.nvoices = (uint32_t)n;
+                    d.max_nframes = 0xFFFFFFFFu;
+                    d.rows = b->dDownRows;
+                    d.lmax = b->downL; d.rmax = b->downR; d.pitch = b->downPitch;
+                    d.stream = 1;
+                    d.n_origin = (long long)nBase - (long long)s->hist[k];
+                    d.n_hi = (long long)(nBase + N + (flush ? 2ull * (uint64_t)b->d.padSize : 0ull));
+                    d.k_base = (uint32_t)kBase[k];
+                    d.k_end = (uint32_t)kEnd[k];
+                    HIP_TRY(trm::launch_downsample(b->c, d, st));
+                } else {
+                    HIP_TRY(hipMemsetAsync(s->dMax.p + lo, 0, n * sizeof(float), st));
+                }
+                // the next chunk's history: the set's last hist tube samples so far (row positions N .. N + hist - 1)
+                HIP_TRY(hipMemcpy2DAsync(s->dHist.p + s->histBase[k], s->hist[k] * sizeof(float), s->dTube.p + s->tubeBase[k] + N,
+                                         s->rowPitch[k] * sizeof(float), s->hist[k] * sizeof(float), n, hipMemcpyDeviceToDevice, st));
+            }
+            // TRAcT order's x100 (trm_stream: applied to what the linear converter returns), per set over its voices and count
+            if (tract && count > 0)
+                HIP_TRY(trm::launch_gain(d_out + lo * out_pitch, out_pitch, (uint32_t)count, (uint32_t)n, s->dMax.p + lo, 100.0f, st));
+        }
+    } else {
+        HIP_TRY(hipMemsetAsync(s->dMax.p, 0, V * sizeof(float), st));
+    }
+    if (!flush)
+        HIP_TRY(hipMemcpy2DAsync(s->dLast.p, 16 * sizeof(float), d_pushed + (nframes - 1) * 16, nframes * 16 * sizeof(float), 16 * sizeof(float), V,
+                                 hipMemcpyDeviceToDevice, st));
+    s->periods += Q;
+    return TRM_OK;
+}
+
+// chunks ordered on the device whichever HIP stream each call names (stream_chunk_device)
+static int mixed_stream_chunk(trm_mixed_stream *s, const float *d_pushed, size_t nframes, bool flush, float *d_out, size_t out_pitch,
+                              uint32_t *nout, hipStream_t st)
+{
+    if (s->haveChunk && st != s->lastStream) HIP_TRY(hipStreamWaitEvent(st, s->chunkDone, 0));
+    int rc = mixed_stream_chunk_impl(s, d_pushed, nframes, flush, d_out, out_pitch, nout, st);
+    if (rc) return rc;
+    if (!s->chunkDone) HIP_TRY(hipEventCreateWithFlags(&s->chunkDone, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(s->chunkDone, st));
+    s->lastStream = st;
+    s->haveChunk = true;
+    return TRM_OK;
+}
+
+static void mixed_stream_after_finish(trm_mixed_stream *s)
+{
+    s->haveLast = false;          // the next push opens a new utterance: tube at rest, converter pre-roll
+    s->first = true;
+    s->periods = 0;
+}
+
+// host-buffer form: H2D of the frames, the chunk (PCM packed at the largest set's count), D2H, each voice's samples to `out`
+static int mixed_stream_host(trm_mixed_stream *s, const float *frames, size_t nframes, bool flush, float *out, size_t out_pitch,
+                             uint32_t *nout, float *max_out)
+{
+    trm_batch *b0 = s->b[0];
+    const size_t S = s->b.size(), V = s->nvoices;
+    HIP_TRY(hipSetDevice(b0->device));
+    hipStream_t st = b0->stream;
+    int rc;
+    std::vector<uint32_t> counts(S);
+    size_t maxCount = 0;
+    for (size_t k = 0; k < S; k++) {
+        counts[k] = (uint32_t)(flush ? trm_mixed_stream_samples_for_finish(s, k) : trm_mixed_stream_samples_for_push(s, k, nframes));
+        if (s->begin[k + 1] > s->begin[k]) maxCount = std::max<size_t>(maxCount, counts[k]);
+    }
+    if (maxCount > 0 && (!out || out_pitch < maxCount))
+        return fail(TRM_EINVAL, "output pitch %zu < %zu samples (the largest set's count)", out_pitch, maxCount);
+    if (!flush) {
+        if ((rc = s->dPushed.reserve(V * nframes * 16))) return rc;
+        HIP_TRY(hipMemcpyAsync(s->dPushed.p, frames, V * nframes * 16 * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    if ((rc = s->dOut.reserve(V * maxCount + 64))) return rc;
+    if ((rc = mixed_stream_chunk(s, flush ? nullptr : s->dPushed.p, nframes, flush, s->dOut.p, maxCount, counts.data(), st))) return rc;
+    if (nout) memcpy(nout, counts.data(), S * sizeof(uint32_t));
+    if (maxCount > 0) {
+        s->hostOut.resize(V * maxCount);
+        HIP_TRY(hipMemcpyAsync(s->hostOut.data(), s->dOut.p, V * maxCount * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    std::vector<float> mx(V, 0.0f);
+    HIP_TRY(hipMemcpyAsync(mx.data(), s->dMax.p, V * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t k = 0; k < S; k++)
+        for (size_t v = s->begin[k]; v < s->begin[k + 1] && counts[k] > 0; v++)
+            memcpy(out + v * out_pitch, &s->hostOut[v * maxCount], (size_t)counts[k] * sizeof(float));
+    if (max_out) memcpy(max_out, mx.data(), V * sizeof(float));
+    return TRM_OK;
+}
+
+int trm_mixed_stream_push(trm_mixed_stream *s, const float *frames, size_t nframes, float *out, size_t out_pitch, uint32_t *nout, float *max_out)
+{
+    if (!s || !frames || nframes == 0) return fail(TRM_EINVAL, "null argument / no frames");
+    int rc = mixed_stream_host(s, frames, nframes, false, out, out_pitch, nout, max_out);
+    if (rc) return rc;
+    s->haveLast = true;
+    return TRM_OK;
+}
+
+int trm_mixed_stream_finish(trm_mixed_stream *s, float *out, size_t out_pitch, uint32_t *nout, float *max_out)
+{
+    if (!s) return fail(TRM_EINVAL, "null stream");
+    if (!s->haveLast) { if (nout) memset(nout, 0, s->b.size() * sizeof(uint32_t)); return TRM_OK; }
+    int rc = mixed_stream_host(s, nullptr, 0, true, out, out_pitch, nout, max_out);
+    if (rc) return rc;
+    mixed_stream_after_finish(s);
+    return TRM_OK;
+}
+
+int trm_mixed_stream_push_device(trm_mixed_stream *s, const float *d_frames, size_t nframes, float *d_out, size_t out_pitch, uint32_t *nout,
+                                 float *d_max_out, void *stream)
+{
+    if (!s || !d_frames || nframes == 0) return fail(TRM_EINVAL, "null argument / no frames");
+    HIP_TRY(hipSetDevice(s->b[0]->device));
+    hipStream_t st = (hipStream_t)stream;
+    int rc = mixed_stream_chunk(s, d_frames, nframes, false, d_out, out_pitch, nout, st);
+    if (rc) return rc;
+    if (d_max_out) HIP_TRY(hipMemcpyAsync(d_max_out, s->dMax.p, s->nvoices * sizeof(float), hipMemcpyDeviceToDevice, st));
+    s->haveLast = true;
+    return TRM_OK;
+}
+
+int trm_mixed_stream_finish_device(trm_mixed_stream *s, float *d_out, size_t out_pitch, uint32_t *nout, float *d_max_out, void *stream)
+{
+    if (!s) return fail(TRM_EINVAL, "null stream");
+    if (!s->haveLast) { if (nout) memset(nout, 0, s->b.size() * sizeof(uint32_t)); return TRM_OK; }
+    HIP_TRY(hipSetDevice(s->b[0]->device));
+    hipStream_t st = (hipStream_t)stream;
+    int rc = mixed_stream_chunk(s, nullptr, 0, true, d_out, out_pitch, nout, st);
+    if (rc) return rc;
+    if (d_max_out) HIP_TRY(hipMemcpyAsync(d_max_out, s->dMax.p, s->nvoices * sizeof(float), hipMemcpyDeviceToDevice, st));
+    mixed_stream_after_finish(s);
+    return TRM_OK;
 }
 
 }  // extern "C"

@@ -40,12 +40,17 @@ struct TubeArgs {
     uint32_t max_nframes;         // the host sized the noise table (and the tube rows) for this many frames per voice:
                                   // a longer nframes[v] is cut to it (a caller's mistake must not run past them)
     unsigned long long *stamps;   // diagnostic builds only (TRM_STAMP); null in the product
-    // Streaming (trm_tube_kernel_q only): a chunk of a longer utterance.  Null for one-shot synthesis.
+    // Streaming: a chunk of a longer utterance.  Null for one-shot synthesis.
     //   stream_state   kStreamFloats floats per voice, carried from one chunk to the next
     //   stream_flags   bit 0: first chunk (state ignored: the tube starts at rest, the converter with its 25 zeros
     //                  of pre-roll); bit 1: last chunk (the converter's 2*pad zeros of flush are appended)
     //   stream_n_base  tube samples synthesized before this chunk; stream_k_base / stream_k_end: the chunk emits
     //                  converter outputs k_base <= k < k_end (global indices).  Same for every voice of the launch.
+    //   A mixed stream (mix_map and stream_state): the sets' control periods and converter increments differ, so the launch
+    //   passes what they share -- stream_n_base = control periods before the chunk, stream_k_end = control periods through
+    //   its end (stream_k_base unused) -- and each workgroup derives its set's bases: n_base = periods * controlPeriod,
+    //   k_base = the outputs whose read position lies before n_base, k_end likewise (the flush's formula on the last chunk).
+    //   lp_noise then arrives NOT advanced (the kernel adds its set's n_base).
     float *stream_state;
     uint32_t stream_flags, stream_n_base, stream_k_base, stream_k_end;
     // Time-split launches (trm_tube_kernel<kModeSegments> only; seg_periods == 0 otherwise).  An utterance is cut every
@@ -115,8 +120,9 @@ int tube_kernel_blocks_per_cu();
 hipError_t launch_noise(float *lp, uint32_t from, uint32_t to, double *state, hipStream_t stream);
 hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream);
 // Mixed-parameter instances (TubeArgs::mix_map) of the three tube kernels: trm_mix.hip, trm_mix_q.hip and trm_mix_o.hip compile
-// each kernel's source once more with the mixed instance alone, under a name of its own (trm_mix_kernel, trm_mix_kernel_q,
-// trm_mix_kernel_o).  The launchers above call these for a launch with a mix_map.
+// each kernel's source once more with the mixed instances alone, under a name of its own (trm_mix_kernel, trm_mix_kernel_q,
+// trm_mix_kernel_o).  The launchers above call these for a launch with a mix_map; with a stream_state too, the first two run
+// their mixed streaming instance.
 hipError_t launch_mix_wide(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);       // `grid` workgroups from a.wg_base
 hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int sub);
 hipError_t launch_mix_oct(const Const &c, const TubeArgs &a, hipStream_t stream);

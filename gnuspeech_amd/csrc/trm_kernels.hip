@@ -123,12 +123,15 @@ __global__ void trm_noise_kernel(float *lp, uint32_t from, uint32_t to, double *
 // its tube samples and converter outputs keep their global indices (nBase, kBase -- here per workgroup), unlike one it
 // neither restores nor saves state: only the oscillator position is handed in.  kModeMixed: a one-shot launch whose
 // workgroups may belong to different parameter sets (TubeArgs::mix_map): the workgroup's constants come from set_const, its
-// voices are the map entry's range; otherwise it is the one-shot instance.
-constexpr int kModeOneShot = 0, kModeStream = 1, kModeSegments = 2, kModeMixed = 3;
+// voices are the map entry's range; otherwise it is the one-shot instance.  kModeMixedStream: both, a chunk of a mixed stream
+// (trm_kernels.h: its time bases are the set's own, derived from a count of control periods); the state block of workgroup
+// wg is the map entry's.
+constexpr int kModeOneShot = 0, kModeStream = 1, kModeSegments = 2, kModeMixed = 3, kModeMixedStream = 4;
 template <int kMode>
 __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const Carg, const TubeArgs A)
 {
-    constexpr bool kStream = kMode == kModeStream, kSeg = kMode == kModeSegments, kMix = kMode == kModeMixed;
+    constexpr bool kStream = kMode == kModeStream || kMode == kModeMixedStream, kSeg = kMode == kModeSegments;
+    constexpr bool kMix = kMode == kModeMixed || kMode == kModeMixedStream, kMixStream = kMix && kStream;
     // (two launches of one batch, one of which runs: TubeArgs::gate)
     if (A.gate && ((*A.gate != 0u) ? 1u : 0u) != A.gate_want) return;
     __shared__ __attribute__((aligned(16))) float4 sW[2 * kTB * kWave];          // osc -> mix: {wa, wb, ax, ah1}
@@ -205,8 +208,12 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     const bool sHold = kStream && (A.stream_flags & 4u);       // TRAcT's loop order: a period runs on the frame that ends it, held
     // (segments: a workgroup's lanes either end inside the segment -- their flush follows -- or run to its end: nTotal
     // carries the flush's 2*pad samples either way, lanes that go on stop emitting at segOutEnd)
-    const uint32_t nBase = kStream ? A.stream_n_base : kSeg ? segFrame0 * CP : 0u;
-    const uint32_t kBase = kStream ? A.stream_k_base : kSeg ? outputs_before((uint64_t)seg_begin(seg) * CP) : 0u;
+    // (a mixed stream: stream_n_base / stream_k_end count control periods, the set's tube samples and outputs follow from them)
+    const uint32_t nBase = kMixStream ? A.stream_n_base * CP : kStream ? A.stream_n_base : kSeg ? segFrame0 * CP : 0u;
+    const uint32_t kBase = kMixStream ? outputs_before((uint64_t)nBase) : kStream ? A.stream_k_base : kSeg ? outputs_before((uint64_t)seg_begin(seg) * CP) : 0u;
+    const uint32_t kEnd = !kMixStream ? A.stream_k_end
+                        : sLast ? (uint32_t)((((uint64_t)nBase + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc)
+                                : outputs_before((uint64_t)A.stream_k_end * CP);
     // this voice's state record: per workgroup a block of [kStreamFloats fields][64 lanes] floats -- a wave's 64 lanes touch
     // 64 consecutive floats per field (voice-major records cost 64 cache lines per field and instruction) and a field is a
     // CONSTANT 256 bytes from the one before (one base address per lane: per-field 64-bit strides cost the streaming
@@ -308,7 +315,7 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     } else if (role == 1) {
         // ------------------------------------------------------------ mix: FIR + noise mixing, block i-1 at step i
         __builtin_amdgcn_s_setprio(TRM_PRIO_MIX);
-        const float *const lpNoise = A.lp_noise + (kSeg ? nBase : 0u);      // (a stream's pointer arrives advanced)
+        const float *const lpNoise = A.lp_noise + ((kSeg || kMixStream) ? nBase : 0u);      // (a uniform stream's pointer arrives advanced)
         auto fill_noise_half = [&](uint32_t nFirst, int half) {
             dma4(lpNoise + nFirst + lane, &sNoise[half * kNoiseHalf]);
         };
@@ -502,13 +509,13 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
         const int cw = role - 5;                    // this wave converts voices 32*cw .. 32*cw+31
         __builtin_amdgcn_s_setprio(kStream ? TRM_PRIO_CVT_S : TRM_PRIO_CVT);
         // outputs of this launch per voice: the utterance's (TRMSampleRateConverter.m:160-173); a chunk's: global indices
-        // kBase <= k < stream_k_end, the same for every voice
+        // kBase <= k < kEnd, the same for every voice of the workgroup
         uint32_t noutLane = 0;
         if (nfr > 0) {
             uint64_t total = (uint64_t)ntubeLane + 2ull * (uint32_t)C.padSize;
             noutLane = (uint32_t)((total * 65536ull + inc - 1) / inc);
         }
-        if (kStream) noutLane = A.stream_k_end - kBase;
+        if (kStream) noutLane = kEnd - kBase;
         uint32_t noutAll = 0;                   // (segments: the whole utterance's count)
         if (kSeg) {
             if (nfrAll > 0) noutAll = (uint32_t)((((uint64_t)(nfrAll - 1) * CP + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc);

@@ -95,13 +95,14 @@ struct QuadLds {
 // per workgroup -- workgroup w runs segment w / seg_wg_per_seg of 16 voices from rest, a warm-up ahead --, no state in or
 // out.  What the one-voice-per-lane kernel's segment instance is for batches that fill the chip, this one is for a handful of
 // voices: a single utterance becomes sixteen lanes' worth of segments on one CU.
-// kMix: a one-shot launch whose workgroups may belong to different parameter sets (trm_kernels.h, TubeArgs::mix_map): the
-// workgroup's constants come from set_const, its voices are the map entry's range.
+// kMix: a launch whose workgroups may belong to different parameter sets (trm_kernels.h, TubeArgs::mix_map): the
+// workgroup's constants come from set_const, its voices are the map entry's range.  With kStream: a chunk of a mixed stream,
+// whose time bases are the set's own (trm_kernels.h); the state records stay voice-major.
 template <bool kStream, int kSub, bool kSeg = false, bool kMix = false>
 __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Const Carg, const TubeArgs A)
 {
     static_assert(!kSeg || kStream, "the segment instance is built on the streaming instance");
-    static_assert(!kMix || !kStream, "mixed-parameter launches are one-shot");
+    static_assert(!kMix || !kSeg, "mixed-parameter launches run whole utterances or stream chunks");
     if (kSeg && A.gate && ((*A.gate != 0u) ? 1u : 0u) != A.gate_want) return;      // (two launches, the device runs one: TubeArgs::gate)
     constexpr int kStepN = kQB * kSub;       // tube samples per step
     typedef QuadLds<kSub> L;
@@ -188,8 +189,13 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     // TRAcT's loop (Applications/TRAcT/tube.c:1121-1136) reads the parameter set every sample and never interpolates: a
     // control period then runs on the frame that ENDS it, held (trm_stream_set_mode)
     const bool sHold = streaming && !kSeg && (A.stream_flags & 4u);
-    const uint32_t nBase = kSeg ? segFrame0 * CP : streaming ? A.stream_n_base : 0u;
-    const uint32_t kBase = kSeg ? outputs_before((uint64_t)seg_begin(seg) * CP) : streaming ? A.stream_k_base : 0u;
+    // (a mixed stream: stream_n_base / stream_k_end count control periods, the set's tube samples and outputs follow from them)
+    constexpr bool kMixStream = kMix && kStream;
+    const uint32_t nBase = kSeg ? segFrame0 * CP : kMixStream ? A.stream_n_base * CP : streaming ? A.stream_n_base : 0u;
+    const uint32_t kBase = kSeg ? outputs_before((uint64_t)seg_begin(seg) * CP) : kMixStream ? outputs_before((uint64_t)nBase) : streaming ? A.stream_k_base : 0u;
+    const uint32_t kEnd = !kMixStream ? A.stream_k_end
+                        : sLast ? (uint32_t)((((uint64_t)nBase + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc)
+                                : outputs_before((uint64_t)A.stream_k_end * CP);
     float *const st = saving ? A.stream_state + (size_t)v * kStreamFloats : nullptr;
     // outputs of this launch for this lane's voice (segments: its own stretch; the voice's last segment runs to the utterance's end)
     uint32_t noutSeg = 0, noutAll = 0;
@@ -238,7 +244,8 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         __syncthreads();
         for (int i = threadIdx.x; i < kQV * 32; i += kWave * kQRoles) {
             const int q = i >> 5, t = i & 31;
-            const uint32_t vv = vblock * kQV + q < A.nvoices ? vblock * kQV + q : A.nvoices - 1;
+            const uint32_t vv = kMix ? (vFirst + q < vEnd ? vFirst + q : vEnd - 1)
+                                     : (vblock * kQV + q < A.nvoices ? vblock * kQV + q : A.nvoices - 1);
             const float *h = A.stream_state + (size_t)vv * kStreamFloats;
             sO[q * kOStride + 32 + t] = make_float2(h[8 + 2 * t], h[9 + 2 * t]);            // slot (-32 + t) & 63
             const uint32_t slot = (uint32_t)(t - 32 + kQLead) & (kYRing - 1);
@@ -423,7 +430,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         __builtin_amdgcn_s_setprio(TRM_QPRIO_MIX);
 #endif
         // ------------------------------------------------------------ mix: block i-1 at step i, lane = (voice, slot)
-        const float *const lpNoise = A.lp_noise + (kSeg ? nBase : 0u);      // (a stream's pointer arrives advanced)
+        const float *const lpNoise = A.lp_noise + ((kSeg || kMixStream) ? nBase : 0u);      // (a uniform stream's pointer arrives advanced)
         auto fill_noise_half = [&](uint32_t nFirst, int half) {
             dma4(lpNoise + nFirst + lane, &sNoise[half * kNoiseHalf]);
         };
@@ -450,7 +457,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         uint32_t rowBlk = 0;
         bool rowsInFlight = false;
         float4 rq[4];
-        const uint32_t cvtOutputs = kSeg ? wave_max_u32(noutSeg) : streaming ? A.stream_k_end - kBase
+        const uint32_t cvtOutputs = kSeg ? wave_max_u32(noutSeg) : streaming ? kEnd - kBase
                                               : wave_max_u32(laneValid && nfr > 0 ? (uint32_t)((((uint64_t)ntubeLane + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc) : 0u);
         const uint32_t cvtBlocks = C.upsample ? (cvtOutputs + kCvtCols - 1) / kCvtCols : 0;
         STAMP_DECL
@@ -709,7 +716,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         if (kSeg) {
             noutLane = noutSeg;
         } else if (streaming) {
-            noutLane = A.stream_k_end - kBase;
+            noutLane = kEnd - kBase;
         } else if (nfr > 0) {
             uint64_t total = (uint64_t)ntubeLane + 2ull * (uint32_t)C.padSize;
             noutLane = (uint32_t)((total * 65536ull + inc - 1) / inc);
@@ -849,7 +856,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         if (lane < kQV && ov < vEnd && C.upsample) {
             const uint32_t nf = min(A.nframes[ov], A.max_nframes);
             uint32_t nov = 0;
-            if (streaming && !kSeg) nov = A.stream_k_end - kBase;
+            if (streaming && !kSeg) nov = kEnd - kBase;
             else if (nf > 0) nov = (uint32_t)((((uint64_t)(nf - 1) * CP + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc);
             if (kSeg) {
                 // (max_sample was zeroed by the launcher; non-negative floats order like their bit patterns)
@@ -887,6 +894,7 @@ hipError_t launch_tube_quad(const Const &c, const TubeArgs &a, hipStream_t strea
     if (a.nvoices == 0) return hipSuccess;
     uint32_t grid = (a.nvoices + kQV - 1) / kQV;
     if (a.seg_periods) return launch_instance<true, 2, true>(c, a, stream, a.seg_grid);      // time split: 16 voices x one segment per workgroup
+    if (a.stream_state && a.mix_map) return a.mix_grid ? launch_mix_quad(c, a, stream, 2) : hipSuccess;     // (streams: kSub = 2 only)
     if (a.stream_state) return launch_instance<true, 2>(c, a, stream, grid);
     // one-shot instances stage the control frames in a ring of four: frame p+3 replaces frame p-1 one step into period p,
     // and the coefficient waves' last lanes read frame p-1 three steps into period p-1 -- a period must hold three steps

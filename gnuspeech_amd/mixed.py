@@ -1,9 +1,11 @@
-"""Mixed-parameter batches: the voices of several TRMInputParameters sets in one launch (include/trm_c_api.h: trm_mixed_*).
+"""Mixed-parameter batches and streams: the voices of several TRMInputParameters sets in one launch (include/trm_c_api.h:
+trm_mixed_*, trm_mixed_stream_*).
 
 Every workgroup of the launch holds voices of one set and reads that set's constants from a device table, so a voice's
 samples are bit for bit what a TRMBatch of its own set computes in the same kernel form with the time split off.  Callers
 hand voices in any order with a set index per voice; the library wants them grouped by set, which group_voices() does
-(a stable sort), and the results come back in the caller's order.  Whole utterances only (no time split).
+(a stable sort), and the results come back in the caller's order.  Batches run whole utterances only (no time split);
+TRMMixedStream delivers utterances in chunks, like TRMStream.
 """
 import ctypes as C
 
@@ -178,3 +180,143 @@ class TRMMixedBatch:
     @property
     def last_kernel(self):
         return {0: "auto", 1: "wide", 2: "quad", 3: "oct"}[lib().trm_mixed_last_kernel(self._h)]
+
+
+class TRMMixedStream:
+    """A stream (TRMStream) whose voices belong to several parameter sets, advanced by one launch per chunk
+    (include/trm_c_api.h: trm_mixed_stream_*).  sets[i] = parameter set of voice i in the caller's order; the layout is fixed
+    for the stream's life.  Every voice's samples are bit for bit those of a TRMStream of its own set in the same kernel form.
+
+    The host entries take and return voices in the caller's order.  On the device voices stay in grouped order (the library's):
+    `order[j]` = the caller's voice at grouped position j, `inverse` the way back."""
+
+    def __init__(self, param_sets, sets, device=-1, mode="framework"):
+        from .stream import MODES
+        self._h = C.c_void_p()
+        self.param_sets = list(param_sets)
+        nsets = len(self.param_sets)
+        if nsets == 0:
+            raise ValueError("no parameter sets")
+        if mode not in MODES:
+            raise ValueError("unknown stream mode %r" % (mode,))
+        sets = np.asarray(sets, dtype=np.int64).reshape(-1)
+        if sets.size == 0:
+            raise ValueError("no voices")
+        self.order, self.set_begin, self.inverse = group_voices(sets, nsets)
+        self.sets = sets
+        self.nvoices = int(sets.size)
+        self._gsets = sets[self.order]
+        self._nonempty = np.diff(self.set_begin.astype(np.int64)) > 0
+        arr = (TrmInputParams * nsets)(*[p.c for p in self.param_sets])
+        sb = np.ascontiguousarray(self.set_begin, dtype=np.uint64)
+        assert sb.itemsize == C.sizeof(C.c_size_t)
+        check(lib().trm_mixed_stream_create(arr, nsets, sb.ctypes.data, device, C.byref(self._h)))
+        if mode != "framework":
+            self.set_mode(mode)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                lib().trm_mixed_stream_destroy(h)
+            except Exception:      # interpreter shutdown: the process is going away anyway
+                pass
+            self._h = None
+
+    @property
+    def nsets(self):
+        return len(self.param_sets)
+
+    @property
+    def kernel(self):
+        """"wide" (one voice per lane) or "quad" (four lanes per voice): fixed when the stream was created."""
+        return {1: "wide", 2: "quad"}[lib().trm_mixed_stream_kernel(self._h)]
+
+    def set_mode(self, mode):
+        """"framework" or "tract" (TRMStream.set_mode), for every set; between utterances only."""
+        from .stream import MODES
+        if mode not in MODES:
+            raise ValueError("unknown stream mode %r" % (mode,))
+        check(lib().trm_mixed_stream_set_mode(self._h, MODES[mode]))
+
+    @property
+    def mode(self):
+        return {0: "framework", 1: "tract"}[lib().trm_mixed_stream_mode(self._h)]
+
+    def samples_for_push(self, set, nframes):
+        return lib().trm_mixed_stream_samples_for_push(self._h, int(set), int(nframes))
+
+    def samples_for_finish(self, set):
+        return lib().trm_mixed_stream_samples_for_finish(self._h, int(set))
+
+    def _counts(self, nframes):
+        """samples per voice of every set for the next push of `nframes` frames (None: the finish)"""
+        if nframes is None:
+            return np.array([self.samples_for_finish(s) for s in range(self.nsets)], dtype=np.int64)
+        return np.array([self.samples_for_push(s, nframes) for s in range(self.nsets)], dtype=np.int64)
+
+    def _width(self, counts):
+        return int(counts[self._nonempty].max()) if np.any(self._nonempty) else 0
+
+    # -------------------------------------------------------------- host buffers (caller's voice order)
+    def push(self, frames):
+        """frames: [nvoices, n, 16] in the caller's order.  Returns (pcm [nvoices, max_m] float32, samples per voice uint32[nvoices],
+        max |sample| per voice float32[nvoices]); voice i's samples are pcm[i, :count[i]]."""
+        f = np.asarray(frames, dtype=np.float32)
+        if f.ndim != 3 or f.shape[0] != self.nvoices or f.shape[2] != 16 or f.shape[1] == 0:
+            raise ValueError("frames must be [%d voices, n >= 1, 16], got %s" % (self.nvoices, f.shape))
+        f = np.ascontiguousarray(f[self.order])
+        n = f.shape[1]
+        return self._run(lambda out, pitch, nout, mx: lib().trm_mixed_stream_push(self._h, f.ctypes.data, n, out, pitch, nout, mx),
+                         self._counts(n))
+
+    def finish(self):
+        """The converter's flush of every voice: as push()."""
+        return self._run(lambda out, pitch, nout, mx: lib().trm_mixed_stream_finish(self._h, out, pitch, nout, mx), self._counts(None))
+
+    def _run(self, call, counts):
+        m = self._width(counts)
+        out = np.zeros((self.nvoices, max(m, 1)), dtype=np.float32)
+        mx = np.zeros(self.nvoices, dtype=np.float32)
+        nout = np.zeros(self.nsets, dtype=np.uint32)
+        check(call(out.ctypes.data, max(m, 1), nout.ctypes.data, mx.ctypes.data))
+        assert np.array_equal(nout.astype(np.int64), counts)
+        per_voice = nout[self._gsets]
+        return out[self.inverse, :m], per_voice[self.inverse], mx[self.inverse]
+
+    # -------------------------------------------------------------- device buffers (torch tensors, grouped order)
+    def push_device(self, frames, out=None, max_out=None):
+        """frames: float32 CUDA tensor [nvoices, n, 16] in GROUPED order (frames[order] of the caller's).  Asynchronous on torch's
+        current stream; nothing crosses PCIe.  Returns (pcm [nvoices, max_m] view of `out`, samples per voice uint32[nvoices]),
+        both in grouped order.  `out` (optional): float32 CUDA tensor [nvoices, pitch >= max_m]; `max_out` (optional): float32
+        CUDA tensor [nvoices]."""
+        import torch
+        if not (frames.is_cuda and frames.dtype == torch.float32 and frames.is_contiguous() and frames.dim() == 3
+                and frames.shape[0] == self.nvoices and frames.shape[2] == 16 and frames.shape[1] > 0):
+            raise ValueError("frames must be a contiguous float32 CUDA tensor [%d, n >= 1, 16]" % self.nvoices)
+        n = frames.shape[1]
+        return self._run_device(lambda o, pitch, nout, mx, st: lib().trm_mixed_stream_push_device(self._h, frames.data_ptr(), n, o, pitch,
+                                                                                               nout, mx, st),
+                                self._counts(n), frames.device, out, max_out)
+
+    def finish_device(self, device=None, out=None, max_out=None):
+        import torch
+        dev = out.device if out is not None else (device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+        return self._run_device(lambda o, pitch, nout, mx, st: lib().trm_mixed_stream_finish_device(self._h, o, pitch, nout, mx, st),
+                                self._counts(None), dev, out, max_out)
+
+    def _run_device(self, call, counts, device, out, max_out):
+        import torch
+        m = self._width(counts)
+        if out is None:
+            out = torch.empty((self.nvoices, max(m, 1)), dtype=torch.float32, device=device)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == self.nvoices and out.stride(1) == 1
+                and out.shape[1] >= m):
+            raise ValueError("out must be a float32 CUDA tensor [%d, >= %d] with unit column stride" % (self.nvoices, m))
+        if max_out is not None and not (max_out.is_cuda and max_out.dtype == torch.float32 and max_out.numel() >= self.nvoices):
+            raise ValueError("max_out must be a float32 CUDA tensor of %d values" % self.nvoices)
+        nout = np.zeros(self.nsets, dtype=np.uint32)
+        st = torch.cuda.current_stream(device).cuda_stream
+        check(call(out.data_ptr(), out.stride(0), nout.ctypes.data, max_out.data_ptr() if max_out is not None else None, st))
+        assert np.array_equal(nout.astype(np.int64), counts)
+        return out[:, :m], nout[self._gsets]

@@ -454,7 +454,8 @@ int  trm_batch_noise_table(trm_batch *batch, float *host_out, size_t n);
  *   - Whole utterances always: time-split launches of mixed batches are not offered (TRM_TIME_SPLIT is not read).
  *   - The block map and per-voice tube-row offsets are uploaded when the launch's shape (set_begin, form, max_nframes)
  *     changes; a repeated call of one shape through the device entry is pure stream work.
- * Not offered for mixed batches: streams (trm_stream_*), several devices (trm_multi_*), device-side sound-file images.
+ * Not offered for mixed batches: several devices (trm_multi_*), device-side sound-file images.  Streams: trm_mixed_stream,
+ * below.
  * --------------------------------------------------------------------------------------------- */
 typedef struct trm_mixed trm_mixed;
 /* Validates every set (as trm_batch_create does: a bad set fails with its code and trm_last_error names its index) before it
@@ -482,6 +483,41 @@ int    trm_mixed_synthesize_host_int16(trm_mixed *m, const size_t *set_begin, co
                                        int for_wav_data);
 int    trm_mixed_set_kernel(trm_mixed *m, int kernel);       /* TRM_KERNEL_AUTO (default) / _WIDE / _QUAD / _OCT */
 int    trm_mixed_last_kernel(const trm_mixed *m);
+
+/* Mixed-parameter streams: a trm_stream like the above whose voices belong to several parameter sets, all of them advanced by ONE
+ * launch per chunk.  Every voice's samples, counts and maxima are bit for bit what a trm_stream of its own set returns in the
+ * same kernel form for the same chunks.
+ *   - Voices are grouped by set as for trm_mixed: set_begin, checked the same way; sets may be empty.  The layout is fixed
+ *     at create: the carried state is laid out for it.  Every set is checked as trm_stream_create checks its parameters
+ *     (a down-sampling ratio the tiled kernel cannot stream: TRM_ERANGE) and trm_last_error names the set's index.
+ *   - All voices advance together (same number of frames per push), so every set has run the same number of control
+ *     periods; the sets' tube samples and converter outputs per chunk differ (control period, output rate).  Set s's voices
+ *     return trm_mixed_stream_samples_for_push(s, ..) samples, nout[s] (optional, nsets entries) on return.
+ *   - Form, fixed at create (trm_mixed_stream_kernel): one voice per lane when the voices, every set padded to 64, fill the
+ *     chip, or when a non-empty set makes more than four outputs per tube sample; four lanes per voice otherwise.
+ *     TRM_TUBE_KERNEL=wide|quad overrides, with the same demotion.
+ *   - trm_mixed_stream_set_mode applies to every set, between utterances only.  Slices (trm_stream_set_slice) are not offered.
+ *   - As for trm_stream: chunks are ordered across HIP streams by an event, and the device entries make the host wait only
+ *     when the chunk's shape (frames per push, out_pitch) changes or the noise sequence has to grow.
+ * frames: fp32 [nvoices][nframes][16]; out: fp32 [nvoices][out_pitch], out_pitch >= the largest count of a set with voices
+ * (TRM_EINVAL otherwise); voice v's samples at out + v * out_pitch; max_out[v] (optional) = max |sample| of voice v in the chunk.
+ * The device entries take HIP device pointers on the stream's device and run asynchronously on `hip_stream`. */
+typedef struct trm_mixed_stream trm_mixed_stream;
+int    trm_mixed_stream_create(const trm_input_params *params, size_t nsets, const size_t *set_begin, int device,
+                               trm_mixed_stream **out);
+void   trm_mixed_stream_destroy(trm_mixed_stream *s);
+int    trm_mixed_stream_set_mode(trm_mixed_stream *s, int mode);      /* TRM_STREAM_MODE_*, every set; between utterances only */
+int    trm_mixed_stream_mode(const trm_mixed_stream *s);
+int    trm_mixed_stream_kernel(const trm_mixed_stream *s);            /* TRM_KERNEL_WIDE or TRM_KERNEL_QUAD, fixed at create */
+size_t trm_mixed_stream_samples_for_push(const trm_mixed_stream *s, size_t set, size_t nframes);
+size_t trm_mixed_stream_samples_for_finish(const trm_mixed_stream *s, size_t set);
+int    trm_mixed_stream_push(trm_mixed_stream *s, const float *frames, size_t nframes, float *out, size_t out_pitch,
+                             uint32_t *nout, float *max_out);
+int    trm_mixed_stream_finish(trm_mixed_stream *s, float *out, size_t out_pitch, uint32_t *nout, float *max_out);
+int    trm_mixed_stream_push_device(trm_mixed_stream *s, const float *d_frames, size_t nframes, float *d_out, size_t out_pitch,
+                                    uint32_t *nout, float *d_max_out, void *hip_stream);
+int    trm_mixed_stream_finish_device(trm_mixed_stream *s, float *d_out, size_t out_pitch, uint32_t *nout, float *d_max_out,
+                                      void *hip_stream);
 
 /* Library / device identification. */
 int  trm_device_count(void);
