@@ -1784,6 +1784,21 @@ struct trm_mixed {
     DevBuf<int16_t> dOut16;
     DevBuf<uint64_t> dFrameOff, dOutOff, dRelOff;
     DevBuf<uint32_t> dNFrames, dNSamples;
+    // the output entries (trm_mixed_scale_to_int16_device, trm_mixed_sound_files_device): every set's scaling and header
+    // template (built at create), and the device copy of set_begin their workgroups look their set up in -- uploaded when
+    // set_begin changes, under the block map's rule (hSetBegin outlives the upload; a change waits for outLastUse alone)
+    trm::MixOutSet *dOutSets = nullptr;
+    DevBuf<uint64_t> dSetBegin;
+    std::vector<uint64_t> hSetBegin;
+    bool haveSetBegin = false;
+    hipEvent_t outLastUse = nullptr;
+    bool outLastUseRecorded = false;
+    // trm_mixed_events_to_files_host staging
+    DevBuf<uint32_t> evT, evN;
+    DevBuf<double> evV;
+    DevBuf<uint64_t> evOff, dFileOff;
+    DevBuf<trm_intonation> dSettings;
+    DevBuf<uint8_t> dFiles;
 };
 
 void trm_mixed_destroy(trm_mixed *m)
@@ -1792,6 +1807,8 @@ void trm_mixed_destroy(trm_mixed *m)
     if (!m->b.empty()) (void)hipSetDevice(m->b[0]->device);
     if (m->dConst) (void)hipFree(m->dConst);
     if (m->lastUse) (void)hipEventDestroy(m->lastUse);
+    if (m->dOutSets) (void)hipFree(m->dOutSets);
+    if (m->outLastUse) (void)hipEventDestroy(m->outLastUse);
     std::vector<trm_batch *> b;
     b.swap(m->b);
     delete m;                 // device buffers first (the batches own the stream they were used on)
@@ -1827,9 +1844,22 @@ int trm_mixed_create(const trm_input_params *params, size_t nsets, int device, t
     }
     std::vector<trm::Const> cs(nsets);
     for (size_t s = 0; s < nsets; s++) cs[s] = m->b[s]->c;
+    std::vector<trm::MixOutSet> os(nsets);
+    for (size_t s = 0; s < nsets; s++) {
+        const trm_input_params &p = m->b[s]->params;
+        trm::MixOutSet &o = os[s];
+        memset(&o, 0, sizeof o);
+        o.volumeAmp = trm::io_amplitude(p.volume);
+        o.balance = p.balance;
+        o.channels = p.channels;
+        o.format = trm::io_sound_file_header(p, 0, o.header) ? p.outputFileFormat : -1;
+    }
     hipError_t e = hipMalloc((void **)&m->dConst, nsets * sizeof(trm::Const));
     if (e == hipSuccess) e = hipMemcpy(m->dConst, cs.data(), nsets * sizeof(trm::Const), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&m->dOutSets, nsets * sizeof(trm::MixOutSet));
+    if (e == hipSuccess) e = hipMemcpy(m->dOutSets, os.data(), nsets * sizeof(trm::MixOutSet), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&m->lastUse, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&m->outLastUse, hipEventDisableTiming);
     if (e != hipSuccess) {
         trm_mixed_destroy(m);
         return fail(TRM_EHIP, "constant table: %s", hipGetErrorString(e));
@@ -2139,6 +2169,219 @@ int trm_mixed_synthesize_host_int16(trm_mixed *m, const size_t *set_begin, const
     return mixed_host_impl(m, set_begin, frames, frame_offset, nframes, nullptr, out16, for_wav_data, out_offset, number_samples, max_sample);
 }
 
+
+// ------------------------------------------------------------------ mixed-parameter batches: control tracks and output
+int trm_mixed_generate_frames_device(trm_mixed *m, size_t nvoices, const uint32_t *d_event_times, const double *d_event_values,
+                                     const uint64_t *d_event_offset, const uint32_t *d_nevents, const trm_intonation *d_settings,
+                                     float *d_frames, const uint64_t *d_frame_offset, uint32_t *d_nframes_out, void *stream_)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    if (nvoices == 0) return TRM_OK;
+    if (!d_event_times || !d_event_values || !d_event_offset || !d_nevents || !d_settings || !d_frames || !d_frame_offset || !d_nframes_out)
+        return fail(TRM_EINVAL, "null device pointer");
+    if (nvoices > 0x7FFFFFFFull) return fail(TRM_EINVAL, "too many voices");
+    HIP_TRY(hipSetDevice(m->b[0]->device));
+    trm::MixedTrackArgs a;
+    a.event_times = d_event_times;
+    a.event_values = d_event_values;
+    a.event_offset = d_event_offset;
+    a.nevents = d_nevents;
+    a.frames = d_frames;
+    a.frame_offset = d_frame_offset;
+    a.nframes_out = d_nframes_out;
+    a.settings_v = (trm::IntonationTable)d_settings;
+    a.nvoices = (uint32_t)nvoices;
+    HIP_TRY(trm::launch_tracks_mixed(a, (hipStream_t)stream_));
+    return TRM_OK;
+}
+
+size_t trm_mixed_sound_file_size(const trm_mixed *m, size_t set, size_t nsamples)
+{
+    if (!m || set >= m->b.size()) return 0;
+    return trm_sound_file_size(&m->b[set]->params, nsamples);
+}
+
+// every set with voices must name a container the writers know
+static int mixed_check_formats(const trm_mixed *m, const size_t *set_begin)
+{
+    for (size_t s = 0; s < m->b.size(); s++)
+        if (set_begin[s + 1] > set_begin[s]) {
+            uint8_t hdr[56];
+            if (trm::io_sound_file_header(m->b[s]->params, 0, hdr) == 0)
+                return fail(TRM_EINVAL, "parameter set %zu: unknown sound file format %d", s, (int)m->b[s]->params.outputFileFormat);
+        }
+    return TRM_OK;
+}
+
+// int16 (d_int16 set) or file images (d_files set) of a mixed batch: one launch, workgroup v with its own set's table entry
+static int mixed_output(trm_mixed *m, const size_t *set_begin, const float *d_pcm, const uint64_t *d_out_offset,
+                        const uint32_t *d_number_samples, const float *d_max_sample, int16_t *d_int16, const uint64_t *d_int16_offset,
+                        int for_wav_data, uint8_t *d_files, const uint64_t *d_file_offset, hipStream_t stream)
+{
+    const size_t S = m->b.size(), V = set_begin[S];
+    HIP_TRY(hipSetDevice(m->b[0]->device));
+    if (!m->haveSetBegin || !std::equal(set_begin, set_begin + S + 1, m->hSetBegin.begin())) {
+        // (an earlier launch, on whichever stream, may still read the copy and the host array its upload reads from)
+        if (m->outLastUseRecorded) HIP_TRY(hipEventSynchronize(m->outLastUse));
+        m->haveSetBegin = false;
+        int rc = m->dSetBegin.reserve(S + 1);
+        if (rc) return rc;
+        m->hSetBegin.assign(set_begin, set_begin + S + 1);
+        HIP_TRY(hipMemcpyAsync(m->dSetBegin.p, m->hSetBegin.data(), (S + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        m->haveSetBegin = true;
+    }
+    trm::MixOutArgs a;
+    a.pcm = d_pcm;
+    a.out_offset = d_out_offset;
+    a.number_samples = d_number_samples;
+    a.max_sample = d_max_sample;
+    a.pcm16 = d_int16;
+    a.int16_offset = d_int16_offset;
+    a.files = d_files;
+    a.file_offset = d_file_offset;
+    a.sets = (trm::MixOutTable)m->dOutSets;
+    a.set_begin = (trm::SetBeginTable)m->dSetBegin.p;
+    a.nsets = (uint32_t)S;
+    a.forWavData = for_wav_data != 0;
+    if (d_files) HIP_TRY(trm::launch_mixed_file_images(a, (uint32_t)V, stream));
+    else HIP_TRY(trm::launch_mixed_int16(a, (uint32_t)V, stream));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
+        HIP_TRY(hipEventRecord(m->outLastUse, stream));
+        m->outLastUseRecorded = true;
+    }
+    return TRM_OK;
+}
+
+int trm_mixed_scale_to_int16_device(trm_mixed *m, const size_t *set_begin, const float *d_pcm, const uint64_t *d_out_offset,
+                                    const uint32_t *d_number_samples, const float *d_max_sample, int16_t *d_int16,
+                                    const uint64_t *d_int16_offset, int for_wav_data, void *stream_)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    int rc = mixed_check_sets(m, set_begin);
+    if (rc) return rc;
+    const size_t V = set_begin[m->b.size()];
+    if (V == 0) return TRM_OK;
+    if (!d_pcm || !d_out_offset || !d_number_samples || !d_max_sample || !d_int16 || !d_int16_offset)
+        return fail(TRM_EINVAL, "null device pointer");
+    if (V > 0x7FFFFFFFull) return fail(TRM_EINVAL, "too many voices");
+    return mixed_output(m, set_begin, d_pcm, d_out_offset, d_number_samples, d_max_sample, d_int16, d_int16_offset, for_wav_data,
+                        nullptr, nullptr, (hipStream_t)stream_);
+}
+
+int trm_mixed_sound_files_device(trm_mixed *m, const size_t *set_begin, const float *d_pcm, const uint64_t *d_out_offset,
+                                 const uint32_t *d_number_samples, const float *d_max_sample, uint8_t *d_files,
+                                 const uint64_t *d_file_offset, void *stream_)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    int rc = mixed_check_sets(m, set_begin);
+    if (rc) return rc;
+    const size_t V = set_begin[m->b.size()];
+    if (V == 0) return TRM_OK;
+    if (!d_pcm || !d_out_offset || !d_number_samples || !d_max_sample || !d_files || !d_file_offset)
+        return fail(TRM_EINVAL, "null device pointer");
+    if (V > 0x7FFFFFFFull) return fail(TRM_EINVAL, "too many voices");
+    if ((rc = mixed_check_formats(m, set_begin))) return rc;
+    return mixed_output(m, set_begin, d_pcm, d_out_offset, d_number_samples, d_max_sample, nullptr, nullptr, 0, d_files, d_file_offset,
+                        (hipStream_t)stream_);
+}
+
+int trm_mixed_events_to_files_host(trm_mixed *m, const size_t *set_begin, const uint32_t *event_times, const double *event_values,
+                                   const uint64_t *event_offset, const uint32_t *nevents, const trm_intonation *settings,
+                                   uint8_t *files, const uint64_t *file_offset, uint32_t *number_samples, float *max_sample)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    int rc = mixed_check_sets(m, set_begin);
+    if (rc) return rc;
+    const size_t S = m->b.size(), V = set_begin[S];
+    if (V == 0) return TRM_OK;
+    if (!event_offset || !nevents || !settings || !files || !file_offset || !number_samples || !max_sample) return fail(TRM_EINVAL, "null pointer");
+    if (V > 0x7FFFFFFFull) return fail(TRM_EINVAL, "too many voices");
+    if ((rc = mixed_check_formats(m, set_begin))) return rc;
+    uint64_t E = 0;
+    for (size_t v = 0; v < V; v++) E = std::max<uint64_t>(E, event_offset[v] + nevents[v]);
+    if (E && (!event_times || !event_values)) return fail(TRM_EINVAL, "null pointer");
+    // every voice's frame count with its own settings, its sample count and file size with its own set's
+    std::vector<uint32_t> nfr(V);
+    std::vector<uint64_t> fsize(V), devFile(V);
+    uint64_t fileBytes = 0;
+    uint32_t maxFrames = 0;
+    for (size_t s = 0; s < S; s++)
+        for (size_t v = set_begin[s]; v < set_begin[s + 1]; v++) {
+            size_t n = 0;
+            if ((rc = trm_events_count_frames(event_times ? event_times + event_offset[v] : nullptr, nevents[v], &settings[v], &n))) return rc;
+            if (n > 0xFFFFFFFFull) return fail(TRM_ERANGE, "voice %zu: %zu frames", v, n);
+            nfr[v] = (uint32_t)n;
+            maxFrames = std::max(maxFrames, nfr[v]);
+            fsize[v] = trm_sound_file_size(&m->b[s]->params, trm_batch_samples_for_frames(m->b[s], n));
+            devFile[v] = fileBytes;
+            fileBytes += fsize[v];
+        }
+    bool dense = true;
+    for (size_t v = 0; v < V && dense; v++) dense = file_offset[v] == file_offset[0] + devFile[v];
+    // within a set, the longest voice first (as mixed_host_impl orders it): a workgroup's voices end together
+    std::vector<uint32_t> perm(V);
+    for (size_t v = 0; v < V; v++) perm[v] = (uint32_t)v;
+    for (size_t s = 0; s < S; s++)
+        std::stable_sort(perm.begin() + set_begin[s], perm.begin() + set_begin[s + 1], [&](uint32_t x, uint32_t y) { return nfr[x] > nfr[y]; });
+    std::vector<uint64_t> pEvOff(V), pFrameOff(V), pOutOff(V), pFileOff(V);
+    std::vector<uint32_t> pNev(V), pNs(V), pNf(V);
+    std::vector<trm_intonation> pSet(V);
+    std::vector<float> pMx(V);
+    uint64_t frameRows = 0, outs = 0;
+    for (size_t s = 0; s < S; s++)
+        for (size_t i = set_begin[s]; i < set_begin[s + 1]; i++) {
+            const uint32_t v = perm[i];
+            pEvOff[i] = event_offset[v];
+            pNev[i] = nevents[v];
+            pSet[i] = settings[v];
+            pFrameOff[i] = frameRows;
+            frameRows += nfr[v];
+            pOutOff[i] = outs;
+            outs += (trm_batch_samples_for_frames(m->b[s], nfr[v]) + 31) / 32 * 32;
+            pFileOff[i] = devFile[v];
+        }
+    trm_batch *b0 = m->b[0];
+    HIP_TRY(hipSetDevice(b0->device));
+    hipStream_t st = b0->stream;
+    if ((rc = m->evT.reserve(E + 1)) || (rc = m->evV.reserve((E + 1) * TRM_EVENT_VALUES)) || (rc = m->evOff.reserve(V)) || (rc = m->evN.reserve(V)) ||
+        (rc = m->dSettings.reserve(V)) || (rc = m->dFrames.reserve((frameRows + 1) * 16)) || (rc = m->dFrameOff.reserve(V)) ||
+        (rc = m->dNFrames.reserve(V)) || (rc = m->dOut.reserve(outs + 1)) || (rc = m->dOutOff.reserve(V)) || (rc = m->dNSamples.reserve(V)) ||
+        (rc = m->dMax.reserve(V)) || (rc = m->dFiles.reserve(fileBytes + 1)) || (rc = m->dFileOff.reserve(V)))
+        return rc;
+    if (E) {
+        HIP_TRY(hipMemcpyAsync(m->evT.p, event_times, E * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m->evV.p, event_values, E * TRM_EVENT_VALUES * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipMemcpyAsync(m->evOff.p, pEvOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->evN.p, pNev.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->dSettings.p, pSet.data(), V * sizeof(trm_intonation), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->dFrameOff.p, pFrameOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->dOutOff.p, pOutOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->dFileOff.p, pFileOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    // three launches; the generator writes the frame counts the tube kernel reads
+    if ((rc = trm_mixed_generate_frames_device(m, V, m->evT.p, m->evV.p, m->evOff.p, m->evN.p, m->dSettings.p, m->dFrames.p, m->dFrameOff.p,
+                                               m->dNFrames.p, st)))
+        return rc;
+    if ((rc = trm_mixed_synthesize_device(m, set_begin, m->dFrames.p, m->dFrameOff.p, m->dNFrames.p, maxFrames, m->dOut.p, m->dOutOff.p,
+                                          m->dNSamples.p, m->dMax.p, st)))
+        return rc;
+    if ((rc = trm_mixed_sound_files_device(m, set_begin, m->dOut.p, m->dOutOff.p, m->dNSamples.p, m->dMax.p, m->dFiles.p, m->dFileOff.p, st)))
+        return rc;
+    if (dense && fileBytes > 0) HIP_TRY(hipMemcpyAsync(files + file_offset[0], m->dFiles.p, fileBytes, hipMemcpyDeviceToHost, st));
+    for (size_t v = 0; !dense && v < V; v++)
+        if (fsize[v]) HIP_TRY(hipMemcpyAsync(files + file_offset[v], m->dFiles.p + devFile[v], fsize[v], hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pNf.data(), m->dNFrames.p, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pNs.data(), m->dNSamples.p, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(pMx.data(), m->dMax.p, V * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t i = 0; i < V; i++) {
+        if (pNf[i] != nfr[perm[i]]) return fail(TRM_EHIP, "generator wrote %u frames for voice %u, %u expected", pNf[i], perm[i], nfr[perm[i]]);
+        number_samples[perm[i]] = pNs[i];
+        max_sample[perm[i]] = pMx[i];
+    }
+    return TRM_OK;
+}
 
 // ------------------------------------------------------------------ mixed-parameter streams
 // A trm_stream whose voices belong to several parameter sets: one trm_batch per set (constants, derived values, down-sampling

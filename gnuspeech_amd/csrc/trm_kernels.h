@@ -187,5 +187,48 @@ struct TrackArgs {
     uint32_t nvoices;
 };
 hipError_t launch_tracks(const TrackArgs &a, hipStream_t stream);
+// The same for a mixed-parameter batch: utterance v with settings_v[v] (trm_tracks_mixed_kernel).  Typed in the constant address
+// space like ConstTable: the address depends on the workgroup alone, so the struct is read with scalar loads into SGPRs.
+typedef const __attribute__((address_space(4))) trm_intonation *IntonationTable;
+struct MixedTrackArgs {
+    const uint32_t *event_times;
+    const double *event_values;
+    const uint64_t *event_offset;
+    const uint32_t *nevents;
+    float *frames;
+    const uint64_t *frame_offset;
+    uint32_t *nframes_out;
+    IntonationTable settings_v;       // [nvoices]
+    uint32_t nvoices;
+};
+hipError_t launch_tracks_mixed(const MixedTrackArgs &a, hipStream_t stream);
+
+// Output of a mixed-parameter batch (trm_mixed_out.hip): int16 PCM or sound-file images, one workgroup per voice, each voice with
+// its own set's scaling and container.  The per-set table is built once at trm_mixed_create.
+struct MixOutSet {
+    double volumeAmp;             // amplitude(volume)
+    double balance;
+    int32_t channels;
+    int32_t format;               // TRM_SOUND_FILE_FORMAT_*, -1: unknown (the files entries refuse the set)
+    uint8_t header[56];           // as FileArgs::header
+};
+typedef const __attribute__((address_space(4))) MixOutSet *MixOutTable;
+typedef const __attribute__((address_space(4))) uint64_t *SetBeginTable;
+struct MixOutArgs {
+    const float *pcm;
+    const uint64_t *out_offset;
+    const uint32_t *number_samples;
+    const float *max_sample;
+    int16_t *pcm16;               // trm_mixed_int16_kernel: voice v at pcm16 + int16_offset[v]
+    const uint64_t *int16_offset;
+    uint8_t *files;               // trm_mixed_file_image_kernel: voice v's image at files + file_offset[v]
+    const uint64_t *file_offset;
+    MixOutTable sets;             // [nsets]
+    SetBeginTable set_begin;      // [nsets + 1]: workgroup v finds its set here
+    uint32_t nsets;
+    int32_t forWavData;
+};
+hipError_t launch_mixed_int16(const MixOutArgs &a, uint32_t nvoices, hipStream_t stream);
+hipError_t launch_mixed_file_images(const MixOutArgs &a, uint32_t nvoices, hipStream_t stream);
 
 }  // namespace trm

@@ -8,6 +8,11 @@
 // (time, event index, frame count) lives in SGPRs, the per-value part (current value, delta: fp64, repeated
 // addition exactly as the reference does it) in the lanes.  Frames are written where the tube kernels read
 // them, so a batch goes from event lists to PCM without the frames crossing PCIe.
+//
+// TRM_TRACKS_MIXED_TU: trm_tracks_mixed.hip includes this file again for the mixed-parameter instance alone,
+// trm_tracks_mixed_kernel, which reads utterance v's trm_intonation from a device array (MixedTrackArgs::settings_v) instead of
+// the kernel argument.  (A __device__ body shared by two kernels in one file changes trm_tracks_kernel's code; a second
+// translation unit of the same text does not.)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -17,7 +22,11 @@
 
 namespace trm {
 
+#ifdef TRM_TRACKS_MIXED_TU
+__global__ __launch_bounds__(kWave) void trm_tracks_mixed_kernel(const MixedTrackArgs A)
+#else
 __global__ __launch_bounds__(kWave) void trm_tracks_kernel(const TrackArgs A)
+#endif
 {
     // every float expression below rounds per operation, like the reference's (no fused multiply-add)
 #pragma clang fp contract(off)
@@ -27,7 +36,12 @@ __global__ __launch_bounds__(kWave) void trm_tracks_kernel(const TrackArgs A)
     const uint32_t *times = A.event_times + A.event_offset[v];
     const double *values = A.event_values + A.event_offset[v] * TRM_EVENT_VALUES;
     float *frames = A.frames + A.frame_offset[v] * 16;
+#ifdef TRM_TRACKS_MIXED_TU
+    // (settings_v lies in the constant address space and v is wave-uniform: scalar loads, the struct in SGPRs as below)
+    const trm_intonation s = *(const trm_intonation *)(A.settings_v + v);
+#else
     const trm_intonation s = A.settings;
+#endif
     if (n < 2) {                                            // the reference indexes event 1 (EventList.m:920)
         if (lane == 0) A.nframes_out[v] = 0;
         return;
@@ -141,11 +155,20 @@ __global__ __launch_bounds__(kWave) void trm_tracks_kernel(const TrackArgs A)
     if (lane == 0) A.nframes_out[v] = count;
 }
 
+#ifdef TRM_TRACKS_MIXED_TU
+hipError_t launch_tracks_mixed(const MixedTrackArgs &a, hipStream_t stream)
+{
+    if (a.nvoices == 0) return hipSuccess;
+    hipLaunchKernelGGL(trm_tracks_mixed_kernel, dim3(a.nvoices), dim3(kWave), 0, stream, a);
+    return hipGetLastError();
+}
+#else
 hipError_t launch_tracks(const TrackArgs &a, hipStream_t stream)
 {
     if (a.nvoices == 0) return hipSuccess;
     hipLaunchKernelGGL(trm_tracks_kernel, dim3(a.nvoices), dim3(kWave), 0, stream, a);
     return hipGetLastError();
 }
+#endif
 
 }  // namespace trm

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import TrmDerived, TrmInputParams, check, lib
+from ._capi import TrmDerived, TrmInputParams, TrmIntonation, check, lib
 
 _KERNELS = {"auto": 0, "wide": 1, "quad": 2, "oct": 3}
 
@@ -172,6 +172,170 @@ class TRMMixedBatch:
             o = int(st["out_offset_host"][j])
             pcm[i] = out[o:o + int(ns[j])]
         return pcm, ns[st["inverse"]], mx[st["inverse"]]
+
+    # -------------------------------------------------------------- event lists -> sound files on the device
+    def _voice_settings(self, settings, sets):
+        """settings: one TrmIntonation (every voice), a list of nsets (one per set) or of V (one per voice, the caller's order;
+        taken per voice when V == nsets).  Returns the V structs in the caller's order."""
+        V = len(sets)
+        if isinstance(settings, TrmIntonation):
+            return [settings] * V
+        settings = list(settings)
+        if len(settings) == V:
+            return settings
+        if len(settings) == self.nsets:
+            return [settings[int(s)] for s in sets]
+        raise ValueError("%d settings: give one, one per set (%d) or one per voice (%d)" % (len(settings), self.nsets, V))
+
+    def prepare_events_device(self, event_lists, sets, settings, device="cuda"):
+        """Upload a mixed batch of event lists (list of (times u32[n], values f64[n,36]) in any order; sets[i] = parameter set of
+        list i) with their trm_intonation settings (_voice_settings).  Every voice's frame count follows its own settings
+        (trm_events_count_frames); generate_frames_device() fills the frames on the device, and the state then serves
+        synthesize_device / results_device / scale_to_int16_device / sound_files_device, voices grouped by set as prepare_device
+        groups them."""
+        import torch
+        if len(event_lists) != len(sets):
+            raise ValueError("%d event lists, %d set indices" % (len(event_lists), len(sets)))
+        per_voice = self._voice_settings(settings, sets)
+        V = len(event_lists)
+        nfr = np.zeros(V, dtype=np.int64)
+        for v, (t, _) in enumerate(event_lists):
+            n = C.c_size_t()
+            t32 = np.ascontiguousarray(t, dtype=np.uint32)
+            check(lib().trm_events_count_frames(t32.ctypes.data, len(t32), C.byref(per_voice[v]), C.byref(n)))
+            nfr[v] = n.value
+        st = self.prepare_device([np.zeros((int(n), 16), np.float32) for n in nfr], sets, device=device)
+        order = st["order"]
+        lists = [event_lists[i] for i in order]
+        nev = np.array([len(t) for t, _ in lists], dtype=np.int64)
+        times = np.concatenate([np.asarray(t, dtype=np.uint32) for t, _ in lists]) if V else np.zeros(0, np.uint32)
+        values = (np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, 36) for _, v in lists]) if V else np.zeros((0, 36)))
+        eoff = np.zeros(max(1, V), dtype=np.int64)
+        if V > 1:
+            eoff[1:V] = np.cumsum(nev[:-1])
+        gset = (TrmIntonation * max(1, V))(*[per_voice[i] for i in order])
+        dev = torch.device(device)
+        st["settings"] = [per_voice[i] for i in order]
+        st["d_settings"] = torch.frombuffer(bytearray(bytes(gset)), dtype=torch.uint8).to(dev)
+        st["event_times"] = torch.from_numpy(times.astype(np.int32) if times.size else np.zeros(1, np.int32)).to(dev)
+        st["event_values"] = torch.from_numpy(values if values.size else np.zeros((1, 36))).to(dev)
+        st["event_offset"] = torch.from_numpy(eoff).to(dev)
+        st["nevents"] = torch.from_numpy(nev.astype(np.int32) if V else np.zeros(1, np.int32)).to(dev)
+        st["nframes_generated"] = torch.zeros(max(1, V), dtype=torch.int32, device=dev)
+        return st
+
+    def generate_frames_device(self, st, stream=None):
+        """trm_tracks_mixed_kernel over a resident mixed batch of event lists (one launch, every voice with its own settings):
+        fills st["frames"]."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        check(lib().trm_mixed_generate_frames_device(
+            self._h, st["V"], st["event_times"].data_ptr(), st["event_values"].data_ptr(), st["event_offset"].data_ptr(),
+            st["nevents"].data_ptr(), st["d_settings"].data_ptr(), st["frames"].data_ptr(), st["frame_offset"].data_ptr(),
+            st["nframes_generated"].data_ptr(), C.c_void_p(s.cuda_stream)))
+
+    def _int16_layout(self, st):
+        ch = np.array([self.channels(int(s)) for s in st["sets"]], dtype=np.int64)
+        width = st["nout"] * ch
+        off = np.zeros(max(1, st["V"]), dtype=np.int64)
+        if st["V"] > 1:
+            off[1:st["V"]] = np.cumsum(width[:-1])
+        return off, int(width.sum())
+
+    def scale_to_int16_device(self, st, for_wav_data=False, stream=None):
+        """int16 PCM of the last synthesize_device, every voice with its own set's volume, balance and channels, in one launch
+        (trm_mixed_scale_to_int16_device).  Returns (int16 CUDA tensor, int16 offsets per voice in grouped order): voice j's
+        values start at offsets[j], nout[j] * channels of its set of them, stereo interleaved."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        off, total = self._int16_layout(st)
+        dev = st["out"].device
+        pcm16 = torch.zeros(max(1, total), dtype=torch.int16, device=dev)
+        d_off = torch.from_numpy(off).to(dev)
+        check(lib().trm_mixed_scale_to_int16_device(
+            self._h, st["set_begin"].ctypes.data, st["out"].data_ptr(), st["out_offset"].data_ptr(), st["number_samples"].data_ptr(),
+            st["max_sample"].data_ptr(), pcm16.data_ptr(), d_off.data_ptr(), int(bool(for_wav_data)), C.c_void_p(s.cuda_stream)))
+        st["_keep_int16_offset"] = d_off         # (alive until the launch has read it)
+        return pcm16, off[:st["V"]]
+
+    def sound_file_size(self, set, nsamples):
+        return lib().trm_mixed_sound_file_size(self._h, int(set), int(nsamples))
+
+    def sound_files_device(self, st, stream=None):
+        """Every voice's sound file composed on the device in its own set's container (trm_mixed_sound_files_device, one
+        launch).  Returns (uint8 CUDA tensor, byte offsets, sizes), both per voice in grouped order."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        sizes = np.array([self.sound_file_size(int(k), int(n)) for k, n in zip(st["sets"], st["nout"])], dtype=np.int64)
+        pitch = (sizes + 63) // 64 * 64
+        foff = np.zeros(max(1, st["V"]), dtype=np.int64)
+        if st["V"] > 1:
+            foff[1:st["V"]] = np.cumsum(pitch[:-1])
+        dev = st["out"].device
+        files = torch.zeros(max(1, int(pitch.sum())), dtype=torch.uint8, device=dev)
+        d_foff = torch.from_numpy(foff).to(dev)
+        check(lib().trm_mixed_sound_files_device(
+            self._h, st["set_begin"].ctypes.data, st["out"].data_ptr(), st["out_offset"].data_ptr(), st["number_samples"].data_ptr(),
+            st["max_sample"].data_ptr(), files.data_ptr(), d_foff.data_ptr(), C.c_void_p(s.cuda_stream)))
+        st["_keep_file_offset"] = d_foff
+        return files, foff[:st["V"]], sizes
+
+    def sound_files(self, st, stream=None):
+        """sound_files_device, copied back: a list of bytes per voice in the caller's order (synchronises)."""
+        files, foff, sizes = self.sound_files_device(st, stream)
+        buf = files.cpu().numpy()
+        out = [None] * st["V"]
+        for j, i in enumerate(st["order"]):
+            out[i] = buf[int(foff[j]):int(foff[j]) + int(sizes[j])].tobytes()
+        return out
+
+    def synthesize_event_lists(self, event_lists, sets, time_ranges=None):
+        """Host convenience over trm_mixed_events_to_files_host: gnuspeech_amd.EventList objects (each with its own pitchMean,
+        intonation switches and drift seed) and sets[i] = parameter set of list i -> the file images (bytes) in the caller's
+        order.  time_ranges (optional): (start_ms, length_ms) per list, as generateOutputInTimeRange takes them.  Advances each
+        list's driftSeed exactly as EventList.generateOutputInTimeRange does."""
+        V = len(event_lists)
+        if len(sets) != V:
+            raise ValueError("%d event lists, %d set indices" % (V, len(sets)))
+        ranges = list(time_ranges) if time_ranges is not None else [(0, 0)] * V
+        if len(ranges) != V:
+            raise ValueError("%d event lists, %d time ranges" % (V, len(ranges)))
+        order, set_begin, inverse = group_voices(sets, self.nsets)
+        gsets = np.asarray(sets, dtype=np.int64)[order]
+        arrays = [event_lists[i].arrays() for i in order]
+        settings = [event_lists[i].settings(*ranges[i]) for i in order]
+        nev = np.array([len(t) for t, _ in arrays], dtype=np.uint32)
+        eoff = np.zeros(max(1, V), dtype=np.uint64)
+        if V > 1:
+            eoff[1:V] = np.cumsum(nev[:-1].astype(np.uint64))
+        times = np.ascontiguousarray(np.concatenate([t for t, _ in arrays]) if V else np.zeros(1, np.uint32), dtype=np.uint32)
+        values = np.ascontiguousarray(np.concatenate([v for _, v in arrays]) if V else np.zeros((1, 36)), dtype=np.float64)
+        sizes = np.zeros(V, dtype=np.int64)
+        for j in range(V):
+            n = C.c_size_t()
+            t = arrays[j][0]
+            check(lib().trm_events_count_frames(t.ctypes.data, len(t), C.byref(settings[j]), C.byref(n)))
+            sizes[j] = self.sound_file_size(int(gsets[j]), self.samples_for_frames(int(gsets[j]), n.value))
+        foff = np.zeros(max(1, V), dtype=np.uint64)
+        if V > 1:
+            foff[1:V] = np.cumsum(sizes[:-1]).astype(np.uint64)
+        files = np.zeros(max(1, int(sizes.sum())), dtype=np.uint8)
+        ns = np.zeros(max(1, V), dtype=np.uint32)
+        mx = np.zeros(max(1, V), dtype=np.float32)
+        sarr = (TrmIntonation * max(1, V))(*settings)
+        sb = np.ascontiguousarray(set_begin, dtype=np.uint64)
+        nev_c = np.ascontiguousarray(nev if V else np.zeros(1, np.uint32))
+        check(lib().trm_mixed_events_to_files_host(self._h, sb.ctypes.data, times.ctypes.data, values.ctypes.data, eoff.ctypes.data,
+                                                   nev_c.ctypes.data, C.addressof(sarr), files.ctypes.data, foff.ctypes.data,
+                                                   ns.ctypes.data, mx.ctypes.data))
+        out = [None] * V
+        for j, i in enumerate(order):
+            out[i] = files[int(foff[j]):int(foff[j]) + int(sizes[j])].tobytes()
+        for el in event_lists:
+            if el.intonation.shouldUseDrift:
+                # one -generateDrift per 4 ms step, whatever the time range (EventList.generateOutputInTimeRange)
+                el.driftSeed = float(lib().trm_drift_seed_after(el.driftSeed, el.count_frames()))
+        return out
 
     def set_kernel(self, kernel):
         """'auto' | 'wide' | 'quad' | 'oct' (include/trm_c_api.h: trm_mixed_set_kernel; demoted like a TRMBatch's)."""

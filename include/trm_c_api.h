@@ -454,8 +454,11 @@ int  trm_batch_noise_table(trm_batch *batch, float *host_out, size_t n);
  *   - Whole utterances always: time-split launches of mixed batches are not offered (TRM_TIME_SPLIT is not read).
  *   - The block map and per-voice tube-row offsets are uploaded when the launch's shape (set_begin, form, max_nframes)
  *     changes; a repeated call of one shape through the device entry is pure stream work.
- * Not offered for mixed batches: several devices (trm_multi_*), device-side sound-file images.  Streams: trm_mixed_stream,
- * below.
+ *   - The whole server chain runs on the device, as for a trm_batch: event lists -> trm_mixed_generate_frames_device (one
+ *     trm_intonation per voice) -> trm_mixed_synthesize_device -> trm_mixed_scale_to_int16_device / trm_mixed_sound_files_device
+ *     (each voice with its own set's volume, balance, channels and container), three launches; trm_mixed_events_to_files_host
+ *     is the same chain over host buffers.
+ * Not offered for mixed batches: several devices (trm_multi_*).  Streams: trm_mixed_stream, below.
  * --------------------------------------------------------------------------------------------- */
 typedef struct trm_mixed trm_mixed;
 /* Validates every set (as trm_batch_create does: a bad set fails with its code and trm_last_error names its index) before it
@@ -483,6 +486,40 @@ int    trm_mixed_synthesize_host_int16(trm_mixed *m, const size_t *set_begin, co
                                        int for_wav_data);
 int    trm_mixed_set_kernel(trm_mixed *m, int kernel);       /* TRM_KERNEL_AUTO (default) / _WIDE / _QUAD / _OCT */
 int    trm_mixed_last_kernel(const trm_mixed *m);
+/* Control tracks with one trm_intonation per voice (device array d_settings[nvoices]: pitch mean, switches, drift seed, time
+ * range); otherwise as trm_batch_generate_frames_device, and voice v's frames are those that entry writes with d_settings[v].
+ * Frames do not depend on the tube parameters, so no set_begin.  nvoices == 0 is a no-op. */
+int    trm_mixed_generate_frames_device(trm_mixed *m, size_t nvoices, const uint32_t *d_event_times,
+                                        const double *d_event_values, const uint64_t *d_event_offset, const uint32_t *d_nevents,
+                                        const trm_intonation *d_settings, float *d_frames, const uint64_t *d_frame_offset,
+                                        uint32_t *d_nframes_out, void *stream);
+/* Each voice scaled with its own set's volume, balance and channels, as trm_batch_scale_to_int16_device of that set.
+ * d_int16_offset counts int16 values with the set's channels applied (as trm_mixed_synthesize_host_int16's out_offset): the
+ * pcm offsets cannot be reused, because mono and stereo voices interleaved in one buffer would overlap at 2 * out_offset.
+ * One launch.  A device copy of set_begin is uploaded when set_begin differs from the last call of this entry or of
+ * trm_mixed_sound_files_device (waiting only for the last launch that read the copy); a repeated call is pure stream work. */
+int    trm_mixed_scale_to_int16_device(trm_mixed *m, const size_t *set_begin, const float *d_pcm,
+                                       const uint64_t *d_out_offset, const uint32_t *d_number_samples,
+                                       const float *d_max_sample, int16_t *d_int16, const uint64_t *d_int16_offset,
+                                       int for_wav_data, void *stream);
+/* Each voice's file in its own set's container (outputFileFormat), byte for byte trm_batch_sound_files_device of that set, at
+ * d_files + d_file_offset[v]; voice v's image is trm_mixed_sound_file_size(m, its set, numberSamples) bytes.  One launch, the
+ * set_begin copy as above.  A set with voices and an unknown outputFileFormat: TRM_EINVAL naming the set, nothing enqueued. */
+size_t trm_mixed_sound_file_size(const trm_mixed *m, size_t set, size_t nsamples);
+int    trm_mixed_sound_files_device(trm_mixed *m, const size_t *set_begin, const float *d_pcm,
+                                    const uint64_t *d_out_offset, const uint32_t *d_number_samples,
+                                    const float *d_max_sample, uint8_t *d_files, const uint64_t *d_file_offset,
+                                    void *stream);
+/* Host-buffer form of the whole chain for C callers (the shim / a server without HIP pointers): host event lists (voice v's
+ * events at event_offset[v] .. +nevents[v], as trm_batch_generate_frames_device lays them out) and host settings[nvoices] in,
+ * file images out at files + file_offset[v].  The caller sizes each image as
+ * trm_mixed_sound_file_size(m, set, trm_mixed_samples_for_frames(m, set, trm_events_count_frames(voice, settings[v]))).
+ * number_samples and max_sample receive each voice's values.  Staging buffers live in the object and only grow; the frames
+ * and the PCM never leave the device. */
+int    trm_mixed_events_to_files_host(trm_mixed *m, const size_t *set_begin, const uint32_t *event_times,
+                                      const double *event_values, const uint64_t *event_offset, const uint32_t *nevents,
+                                      const trm_intonation *settings, uint8_t *files, const uint64_t *file_offset,
+                                      uint32_t *number_samples, float *max_sample);
 
 /* Mixed-parameter streams: a trm_stream like the above whose voices belong to several parameter sets, all of them advanced by ONE
  * launch per chunk.  Every voice's samples, counts and maxima are bit for bit what a trm_stream of its own set returns in the
