@@ -562,6 +562,17 @@ static int plan_time_split(const trm_batch *b, size_t nvoices, uint32_t max_nfra
     return TRM_OK;
 }
 
+// A hint holds for the one launch that follows it, whether that launch runs or fails: an entry drops it on every return
+// (a hint left by a failed call would plan the next launch by lengths that are not its own)
+struct HintDrop {
+    trm_batch *b;
+    ~HintDrop()
+    {
+        b->hintTotalPeriods = 0;
+        b->hintFrames.clear();
+    }
+};
+
 int trm_batch_hint_frames(trm_batch *b, const uint32_t *nframes, size_t nvoices)
 {
     if (!b) return fail(TRM_EINVAL, "null batch");
@@ -592,6 +603,7 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
                                 void *stream_)
 {
     if (!b) return fail(TRM_EINVAL, "null batch");
+    const HintDrop hintDrop{b};
     if (nvoices == 0) return TRM_OK;
     if (!d_frames || !d_frame_offset || !d_nframes || !d_out || !d_out_offset || !d_number_samples || !d_max_sample)
         return fail(TRM_EINVAL, "null device pointer");
@@ -686,8 +698,6 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
     const bool formByName = b->kernel != TRM_KERNEL_AUTO || b->envKernel != TRM_KERNEL_AUTO;
     const int byName = b->kernel != TRM_KERNEL_AUTO ? b->kernel : b->envKernel;
     if (!(formByName && b->splitSetting <= 0) && (rc = plan_time_split(b, nvoices, max_nframes, which, byName, b->hintTotalPeriods, pl))) return rc;
-    b->hintTotalPeriods = 0;                          // (a hint holds for one launch)
-    b->hintFrames.clear();
     b->lastSplitPeriods = pl.periods;
     b->lastSplitWarm = pl.periods ? pl.warm : 0;
     if (pl.periods) {
@@ -1198,6 +1208,7 @@ static int synthesize_host_impl(trm_batch *b, size_t nvoices, const float *frame
                                 const uint64_t *out_offset, uint32_t *number_samples, float *max_sample)
 {
     if (!b) return fail(TRM_EINVAL, "null batch");
+    const HintDrop hintDrop{b};
     if (nvoices == 0) return TRM_OK;
     if (!frames || !frame_offset || !nframes || (!out && !out16) || !out_offset || !number_samples || !max_sample)
         return fail(TRM_EINVAL, "null pointer");

@@ -274,13 +274,12 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
         S.oscPos = (kStream && !sFirst) ? st_load_f64() : 0.0;
         if (kSeg) {
             // the oscillator's position at the warm-up start: the wrapped advances between the warm-up starts of the
-            // segments so far, summed in order (every term and sum a multiple of 2^-30 below 2^10: exact)
-            const double *ph = A.seg_phase + vRaw;
+            // segments so far, summed in order (every term and sum a multiple of 2^-30 below 2^10: exact) and wrapped both
+            // ways like the four-lane form's: two representatives in (-1, 0) sum to one in (-2, -1].  (seg_phase holds
+            // entries for the batch's voices only: a lane past the end reads those of the voice it stands in for, v.)
+            const double *ph = A.seg_phase + v;
             const size_t pitch = (size_t)A.seg_wg_per_seg * kWave;
-            for (uint32_t q = 1; q <= seg; q++) {
-                const double t = S.oscPos + ph[q * pitch];
-                S.oscPos = t > 511.0 ? t - 512.0 : t;
-            }
+            for (uint32_t q = 1; q <= seg; q++) S.oscPos = osc_wrap(S.oscPos + ph[q * pitch]);
         }
         // (both frames of a control period are fetched when it starts, once per ~80 samples: carrying the current frame
         // to the next boundary in registers costs a register-to-register copy of it per STEP, the loop's phi nodes)

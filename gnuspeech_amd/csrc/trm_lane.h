@@ -286,6 +286,10 @@ TRM_HD double osc_increment(double f0, const Const &C)
     return rint_d(((f0 * 0.5) * C.basicIncrement) * 1073741824.0) * (1.0 / 1073741824.0);
 }
 
+// The representative of x (> -1) in (-1, 511]: what repeated `pos > 511 ? pos - 512 : pos` arrives at
+// (TRMWavetable.m:28-34,165-168).  (Also right for x in (-2, -1], the sum of two representatives.)
+TRM_HD double osc_wrap(double x) { return x - 512.0 * __builtin_ceil((x - 511.0) * (1.0 / 512.0)); }
+
 template <class SineLookup>
 TRM_HD OscOut osc_sample(OscState &S, ExciteTrack &T, const Const &C, int j, SineLookup sineTab)
 {

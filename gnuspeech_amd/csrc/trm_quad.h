@@ -326,10 +326,6 @@ TRM_HD void osc_slot_setup(OscSlotTrack &T, const Const &C, const float *prev, c
     osc_slot_setup_pow2<2>(T, C, prev, cur, j);
 }
 
-// The representative of x (> -1) in (-1, 511]: what repeated `pos > 511 ? pos - 512 : pos` arrives at
-// (TRMWavetable.m:28-34,165-168).
-TRM_HD double osc_wrap(double x) { return x - 512.0 * __builtin_ceil((x - 511.0) * (1.0 / 512.0)); }
-
 // ================================================================ 49-tap FIR, direct form over a window
 // y[m] = sum_{k=0..24} c[2k] b[m-k] + sum_{k=0..23} c[2k+1] a[m-k] (TRMFIRFilter.m:116-146, decimating by 2:
 // a, b = the two oversampled oscillator reads of a tube sample).  The window holds 26 samples starting at

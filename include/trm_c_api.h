@@ -421,7 +421,8 @@ int  trm_batch_last_time_split(const trm_batch *batch, uint32_t *periods, uint32
  * nframes array (in the launch's voice order) for the NEXT trm_batch_synthesize_device call: AUTO then counts the workgroups
  * that have work (a block of 64 voices x the segments its longest voice reaches) and picks shorter segments for a batch whose
  * voices mostly end early -- the GnuTTSServer sentence batch 1.8 ms instead of 2.3.  The host-buffer entries do this themselves.
- * Results do not depend on the hint (any split agrees with whole utterances to 1e-5); nframes == NULL withdraws it. */
+ * Results do not depend on the hint (any split agrees with whole utterances to 1e-5); nframes == NULL withdraws it.  That call
+ * consumes the hint whether it succeeds or fails (a host-buffer entry drops any hint too). */
 int  trm_batch_hint_frames(trm_batch *batch, const uint32_t *nframes, size_t nvoices);
 
 /* Average device time (ms) of the tube kernel launches since the last call, measured

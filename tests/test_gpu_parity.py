@@ -3,6 +3,8 @@
 Tolerance (BASELINE.json north_star): RMS error <= 1e-5 on output normalised by the reference's
 maximumSampleValue; numberSamples must match exactly.  The HIP path computes the signal in fp32
 (fp64 only at the reference's discontinuities), so agreement is a tolerance, not bit-equality.
+The same tolerance holds in every control period of a voice as well (tests/parity.py): an error
+confined to a few periods -- a seam, a period edge, a converter tile -- cannot hide behind the average.
 """
 import os
 import re
@@ -13,6 +15,7 @@ import pytest
 import cases
 import golden_io
 import oracle_lib as O
+import parity
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +71,7 @@ def test_tube_model_matches_reference_fixture(g, form, name):
     tol = RMS_TOL
     err = nrms(out, gold["samples_f32"].astype(np.float64), mx)
     assert err <= tol, "normalised RMS %.3e > %.1e" % (err, tol)
+    parity.check_parity(out, gold["samples_f32"], mx, parity.window_length_of(gold["params_dict"]), what="%s (%s)" % (name, form))
     assert abs(tube.maximumSampleValue - mx) / mx < 2e-4
 
 
@@ -84,7 +88,8 @@ def _batch_vs_oracle(g, pd, voices, tol=RMS_TOL):
     b = g.TRMBatch(ip)
     pcm, ns, mx = b.synthesize(voices)
     op = O.InputParams.from_dict(pd)
-    worst = 0.0
+    win = parity.window_length_of(pd)
+    worst = worst_win = 0.0
     for v, fr in enumerate(voices):
         f32 = np.asarray(fr, dtype=np.float32)
         o = O.synthesize(op, f32.astype(np.float64))      # identical (fp32-representable) control inputs
@@ -98,7 +103,9 @@ def _batch_vs_oracle(g, pd, voices, tol=RMS_TOL):
         e = nrms(pcm[v], o["samples"], m)
         worst = max(worst, e)
         assert e <= tol, "voice %d normalised RMS %.3e" % (v, e)
+        worst_win = max(worst_win, parity.check_oracle(pcm[v], o, win, what="voice %d (%s)" % (v, b.last_kernel), tol=tol)["worst_window_nrms"])
         assert abs(float(mx[v]) - m) / m < 2e-4
+    print("%d voices (%s): worst normalised RMS %.2e, worst control period %.2e" % (len(voices), b.last_kernel, worst, worst_win))
     return worst
 
 
@@ -210,6 +217,7 @@ def test_very_high_rate_ratio_runs_the_lane_form(g, form):
     for v in range(2):
         o = O.synthesize(op, fr[v].astype(np.float64))
         assert got.shape[1] == o["numberSamples"] and nrms(got[v], o["samples"], o["maximumSampleValue"]) <= RMS_TOL
+        parity.check_oracle(got[v], o, parity.window_length_of(pd), what="stream voice %d" % v)
 
 
 def test_eight_lane_form_runs_where_it_applies(g, monkeypatch):
@@ -259,6 +267,7 @@ def test_eight_lane_form_runs_where_it_applies(g, monkeypatch):
                 assert not np.any(pcm[v])
                 continue
             assert nrms(pcm[v], o["samples"], o["maximumSampleValue"]) <= RMS_TOL, (form, v)
+            parity.check_oracle(pcm[v], o, parity.window_length_of(pd), what="%s voice %d" % (form, v))
     monkeypatch.setenv("TRM_QUAD_CUS", "1")             # (read at create: a "device" of one CU holds 16 voices in this form)
     b = g.TRMBatch(g.TRMInputParameters.from_dict(cases.monet_default_params(44100.0)))
     b.synthesize([rows[:30].copy()] * 16)
@@ -865,6 +874,7 @@ def test_full_size_properties(g, form):
     for v in (0, 777, 4094):
         o = O.synthesize(op, fr[v].astype(np.float32).astype(np.float64))
         assert nrms(out[v], o["samples"], o["maximumSampleValue"]) <= RMS_TOL
+        parity.check_oracle(out[v], o, parity.window_length_of(pd), what="voice %d" % v)
 
 
 
@@ -902,6 +912,7 @@ def test_more_than_two_rounds_of_workgroups_go_out_in_slices(g):
             assert not np.any(out[v])
             continue
         assert nrms(out[v], o["samples"], o["maximumSampleValue"]) <= RMS_TOL, v
+        parity.check_oracle(out[v], o, parity.window_length_of(pd), what="voice %d" % v)
         checked += 1
     assert checked >= 4
 
@@ -931,6 +942,7 @@ def test_full_size_ragged_batch_config3(g):
         o = O.synthesize(op, np.asarray(utt[v], dtype=np.float32).astype(np.float64))
         assert o["numberSamples"] == int(ns[v])
         assert nrms(pcm[v], o["samples"], o["maximumSampleValue"]) <= RMS_TOL, v
+        parity.check_oracle(pcm[v], o, parity.window_length_of(pd), what="voice %d" % v)
 
 
 def test_host_entry_leaves_gaps_between_voices_alone(g, form):
@@ -998,6 +1010,7 @@ def test_full_size_configs4_per_gpu_batch(g, split):
     for v in (0, 4097, 8190):
         o = O.synthesize(op, fr[v].astype(np.float32).astype(np.float64))
         assert nrms(out[v], o["samples"], o["maximumSampleValue"]) <= RMS_TOL
+        parity.check_oracle(out[v], o, parity.window_length_of(pd), what="%s voice %d" % (split, v))
 
 
 @pytest.mark.gpu

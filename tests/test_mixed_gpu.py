@@ -6,6 +6,7 @@ import pytest
 
 import cases
 import golden_io
+import parity
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +48,8 @@ def test_all_reference_fixtures_in_one_launch(g, form, monkeypatch):
         assert int(ns[j]) == gold["numberSamples"], (golden_io.CASE_NAMES[i], int(ns[j]))
         err, a = cases.parity_error(pcm[j], gold["samples_f32"], gold["maximumSampleValue"])
         assert err <= 1e-5 or a <= cases.ABS_FLOOR, (golden_io.CASE_NAMES[i], form, err)
+        parity.check_parity(pcm[j], gold["samples_f32"], gold["maximumSampleValue"], parity.window_length_of(gold["params_dict"]),
+                            what="%s (%s)" % (golden_io.CASE_NAMES[i], form), floor=True)
 
 
 def _sets(g):

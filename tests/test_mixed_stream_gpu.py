@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import cases
+import parity
 
 pytestmark = pytest.mark.gpu
 
@@ -145,7 +146,8 @@ def test_second_utterance_starts_from_rest(g):
 
 
 def test_against_the_oracle(g):
-    """A few voices per set against the oracle: exact sample count, normalised RMS <= 1e-5 (the project's parity bar)."""
+    """A few voices per set against the oracle: exact sample count, normalised RMS <= 1e-5 (the project's parity bar) over the
+    utterance and in every control period."""
     import oracle_lib as O
     plist = _sets(g)
     counts = [3, 3, 3, 3, 3, 0]
@@ -166,6 +168,7 @@ def test_against_the_oracle(g):
             continue
         e = nrms(got, o["samples"], o["maximumSampleValue"])
         assert e <= 1e-5, (v, int(sets[v]), e)
+        parity.check_oracle(got, o, parity.window_length_of(pds[int(sets[v])]), what="voice %d (set %d)" % (v, int(sets[v])))
         checked += 1
     assert checked >= 12
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import cases
+import parity
 
 pytestmark = pytest.mark.gpu
 
@@ -158,7 +159,8 @@ def test_random_parameters_and_chunkings(g, seed):
 @pytest.mark.parametrize("rate,seed", [(44100.0, 0), (22050.0, 1), (16000.0, 2), (8000.0, 3), (44100.0, 4), (11025.0, 5)])
 def test_stream_matches_oracle(g, rate, seed):
     """The streamed utterance against the ORACLE (not against another HIP path): random cuts, both converter branches,
-    exact sample counts, normalised RMS <= 1e-5 -- the same bar as the one-shot path (tests/test_gpu_parity.py)."""
+    exact sample counts, normalised RMS <= 1e-5 over the utterance and in every control period -- the same bar as the one-shot
+    path (tests/test_gpu_parity.py)."""
     import oracle_lib as O
     rng = np.random.default_rng(900 + seed)
     pd = cases.monet_default_params(rate)
@@ -173,6 +175,7 @@ def test_stream_matches_oracle(g, rate, seed):
         assert got.shape[1] == o["numberSamples"], (chunks, got.shape[1], o["numberSamples"])
         e = nrms(got[v], o["samples"], o["maximumSampleValue"])
         assert e <= 1e-5, "voice %d: normalised RMS %.3e, chunks %s" % (v, e, chunks)
+        parity.check_oracle(got[v], o, parity.window_length_of(pd), what="voice %d, chunks %s" % (v, chunks))
         assert abs(float(got_max[v]) - o["maximumSampleValue"]) / o["maximumSampleValue"] < 2e-4
 
 
@@ -199,6 +202,7 @@ def test_stream_against_the_reference_in_tract_order(g, name):
     assert nrms(got, want, mx) <= 1e-5
     per = 441
     assert max(nrms(got[i:i + per], want[i:i + per], mx) for i in range(0, got.size - per, per)) <= 1e-5
+    parity.check_parity(got, want, mx, parity.window_length_of(gold["params_dict"]), what=name)      # (the partial last period too)
     assert abs(max(peaks) - mx) / mx < 2e-4
 
 
@@ -228,6 +232,7 @@ def test_tract_mode_stream_matches_oracle(g, rate, seed):
         assert got.shape[1] == o["numberSamples"], (chunks, got.shape[1], o["numberSamples"])
         e = nrms(got[v], o["samples"], o["maximumSampleValue"])
         assert e <= 1e-5, "voice %d: normalised RMS %.3e, chunks %s" % (v, e, chunks)
+        parity.check_oracle(got[v], o, parity.window_length_of(pd), what="voice %d, chunks %s" % (v, chunks))
     # a mode change in the middle of an utterance is refused
     s2 = g.TRMStream(g.TRMInputParameters.from_dict(pd), nvoices=1)
     s2.push(fr[:1, :2])
@@ -373,6 +378,7 @@ def test_large_wide_stream_across_launch_slices(g, stream_form):
         if o["maximumSampleValue"] == 0.0:
             continue
         assert nrms(whole[v], o["samples"], o["maximumSampleValue"]) <= 1e-5, v
+        parity.check_oracle(whole[v], o, parity.window_length_of(pd), what="voice %d" % v)
         checked += 1
     assert checked >= 2
 
