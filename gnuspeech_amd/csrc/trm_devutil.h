@@ -76,6 +76,9 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
     return __builtin_amdgcn_readfirstlane(v);
 }
 
+// `p` in every lane of the wave (all of them active): a wave-uniform answer
+__device__ __forceinline__ bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(!p) == 0; }
+
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
 {
     for (int off = 32; off > 0; off >>= 1) {

@@ -381,6 +381,13 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
         auto frame_at = [&](uint32_t i) { return nfr > 0 ? (i < nfr ? i : nfr - 1) : 0u; };
         // position of this wave's next sample in its control period; the first sample starts period 1
         uint32_t j = CP + (uint32_t)u, f = 0;
+        // held: no lane's coefficient tracks move in this control period (coef_track_held), so every sample's Coefs are the
+        // same bits.  The period's first two steps (j < 2*kTB) still write them, to both of this wave's hand-off slots (the
+        // tube wave reads at step i + 1 what step i wrote); the rest of the period leaves the slots as they are.  Only where it
+        // was measured faster: not in the streaming instances, and only in a dispatch of at most one round of resident
+        // workgroups (A.coef_hold, launch_tube) -- a TRAcT-order stream of 65 536 voices took 2.97 ms per chunk against 2.41,
+        // a one-shot batch of 65 536 static voices 20.9 ms against 15.4 (profiles/ab_r05.txt).
+        bool held = false;
         STAMP_DECL
         for (uint32_t step = 0; step < nSteps; step++) {
             STAMP_BEGIN
@@ -394,17 +401,20 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
                     load_frame(frames, frame_at(sHold ? f : f - 1), prev, 4);
                     load_frame(frames, frame_at(f), cur, 4);
                     coef_track_setup(T, C, prev, cur);
+                    held = !kStream && A.coef_hold && wave_all(coef_track_held(T));
                 }
-                Coefs K = coef_sample<kStream>(T, CC, (int)j);
+                if (!held || j < 2 * kTB) {
+                    Coefs K = coef_sample<kStream>(T, CC, (int)j);
+                    // 20 floats per sample: C8, alphaLR and bpAlpha are re-derived by the tube wave (1 op each)
+                    float4 *dst = &sK[((buf * kTB + u) * kKQuads) * kWave + lane];
+                    // (the junction coefficients travel as (1 + k) * damping: tube_step's working form)
+                    dst[0 * kWave] = make_float4(K.td[0], K.td[1], K.td[2], K.td[3]);
+                    dst[1 * kWave] = make_float4(K.td[4], K.td[5], K.td[6], K.onePlusK8);
+                    dst[2 * kWave] = make_float4(K.alphaU, K.ntd1, K.bpBeta, K.bpGamma);
+                    dst[3 * kWave] = make_float4(K.tap[0], K.tap[1], K.tap[2], K.tap[3]);
+                    dst[4 * kWave] = make_float4(K.tap[4], K.tap[5], K.tap[6], K.tap[7]);
+                }
                 j += kTB;
-                // 20 floats per sample: C8, alphaLR and bpAlpha are re-derived by the tube wave (1 op each)
-                float4 *dst = &sK[((buf * kTB + u) * kKQuads) * kWave + lane];
-                // (the junction coefficients travel as (1 + k) * damping: tube_step's working form)
-                dst[0 * kWave] = make_float4(K.td[0], K.td[1], K.td[2], K.td[3]);
-                dst[1 * kWave] = make_float4(K.td[4], K.td[5], K.td[6], K.onePlusK8);
-                dst[2 * kWave] = make_float4(K.alphaU, K.ntd1, K.bpBeta, K.bpGamma);
-                dst[3 * kWave] = make_float4(K.tap[0], K.tap[1], K.tap[2], K.tap[3]);
-                dst[4 * kWave] = make_float4(K.tap[4], K.tap[5], K.tap[6], K.tap[7]);
             }
             STAMP_MID
             step_barrier();
@@ -1099,10 +1109,14 @@ hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream)
         const char *e = getenv("TRM_WIDE_SLICE");
         return e ? (uint32_t)strtoul(e, nullptr, 10) : 1024u;
     }();
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return hipGetLastError();
     TubeArgs s = a;
     for (uint32_t base = 0; base < grid;) {
         const uint32_t n = slice == 0 ? grid - base : (grid - base < slice ? grid - base : slice);
         s.wg_base = base;
+        s.coef_hold = n <= 2u * (uint32_t)cus;        // one round: two workgroups per CU
         if (a.seg_periods) hipLaunchKernelGGL(trm_tube_kernel<kModeSegments>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s);
         else if (a.mix_map) {
             const hipError_t e = launch_mix_wide(c, s, n, stream);

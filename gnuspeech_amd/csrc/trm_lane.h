@@ -393,6 +393,16 @@ TRM_HD void coef_track_setup(CoefTrack &T, const Const &C, const float *prev, co
     }
 }
 
+// A control period whose coefficient tracks hold: every delta is +0 or -0, so fma(j, delta, base) -- the only way j enters
+// coef_sample -- gives the same value for every j >= 0, and so does every field of Coefs.  A NaN or infinite column makes
+// its delta NaN, which compares unequal: such a period takes the per-sample path.
+TRM_HD bool coef_track_held(const CoefTrack &T)
+{
+    bool h = T.fricPosDelta == 0.0f;
+    for (int i = 0; i < 12; i++) h &= T.delta[i] == 0.0f;
+    return h;
+}
+
 // Stateless in the sample index: any wave may compute any sample j of the current control period.
 // Two halves that touch disjoint fields of Coefs (they may run in different waves):
 //   coef_sample_area   radii, velum -> scattering coefficients, three-way junction, NC1
