@@ -1,0 +1,159 @@
+// trm_host.h -- what the host translation units of libtrm_hip share (private; the public interface is include/trm_c_api.h).
+//   trm_capi.cc    errors and info, trm_batch (with the time-split planner and the host entries), trm_tube and the data list,
+//                  trm_multi, the uniform tracks, int16 and file entries; defines the launch set-up helpers declared here
+//   trm_stream.cc  trm_stream and trm_mixed_stream: one chunk engine over parameter sets
+//   trm_mixed.cc   trm_mixed with its tracks, output and events-to-files entries; SetBatches and the block map
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/trm_c_api.h"
+#include "trm_io.h"
+#include "trm_kernels.h"
+#include "trm_setup.h"
+
+#pragma GCC visibility push(hidden)
+
+// sets the calling thread's trm_last_error text and returns `code` (one definition, one thread_local text: trm_capi.cc)
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define HIP_TRY(expr)                                                                         \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess) return fail(TRM_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;   // elements
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int reserve(size_t n)
+    {
+        if (n <= cap) return TRM_OK;
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        size_t want = n + n / 4 + 64;
+        hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+        if (e != hipSuccess) return fail(TRM_EHIP, "hipMalloc(%zu bytes): %s", want * sizeof(T), hipGetErrorString(e));
+        cap = want;
+        return TRM_OK;
+    }
+};
+
+struct trm_batch {
+    trm_input_params params;
+    trm::Const c;
+    trm_derived d;
+    int device = 0;
+    hipStream_t stream = nullptr;        // used by the host-buffer entry points
+    trm::Const *dConst = nullptr;
+    // read-only tables shared per process and device (trm_batch_create): not owned
+    const float *dRows = nullptr, *dSine = nullptr;
+    const float *dFine = nullptr;        // down-sampling batches only
+    const float *dDownRows = nullptr;    // down-sampling batches only: per-phase coefficient rows
+    uint32_t downL = 0, downR = 0, downPitch = 0;
+    DevBuf<float> dTube;                 // down-sampling: tube-rate samples between the two kernels
+    DevBuf<uint64_t> dTubeOff;
+    DevBuf<float> dNoise;
+    double *dNoiseState = nullptr;
+    uint32_t noiseLen = 0;
+    // host-form staging
+    DevBuf<float> dFrames, dOut, dMax;
+    DevBuf<int16_t> dOut16;
+    // trm_batch_generate_frames_host staging
+    DevBuf<uint32_t> evT, evN;
+    DevBuf<double> evV;
+    DevBuf<uint64_t> evOff;
+    DevBuf<float> evF;
+    DevBuf<uint64_t> dFrameOff, dOutOff;
+    DevBuf<uint32_t> dNFrames, dNSamples;
+    // kernel timing (hipEvents on the launch stream)
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;      // launches not yet folded into the sums below
+    double timedMs = 0.0;
+    uint32_t timedLaunches = 0;
+    bool timing = true;
+    int kernel = TRM_KERNEL_AUTO;        // trm_batch_set_kernel
+    uint32_t wideThreshold = 4097;       // voices from which the one-voice-per-lane kernel is the faster form (set at create)
+    int lastKernel = TRM_KERNEL_AUTO;    // what the last launch ran
+    int cus = 0;                         // compute units of the device (set at create)
+    int envKernel = TRM_KERNEL_AUTO;     // TRM_TUBE_KERNEL, read once at create (steers launches left on AUTO; tests)
+    bool envDownGeneric = false;         // TRM_DOWNSAMPLE_GENERIC, read once at create (tests: the generic down-sampling kernel)
+    size_t tubeOffVoices = 0;            // dTubeOff holds pitch * v for v < tubeOffVoices ...
+    uint64_t tubeOffPitch = 0;           // ... at this row pitch (down-sampling batches: rebuilt only when either changes)
+    // time-split launches (trm_batch_set_time_split)
+    int splitSetting = TRM_TIME_SPLIT_AUTO;      // AUTO, OFF, or a segment length in control periods
+    uint32_t lastSplitPeriods = 0, lastSplitWarm = 0;      // what the last launch did (0: whole utterances)
+    int lastSplitForm = TRM_KERNEL_WIDE;
+    DevBuf<double> dSegPhase, dPeriodAdv;
+    DevBuf<uint2> dSegMap;               // a time-split grid's launch order (trm_seg_map_kernel)
+    DevBuf<uint32_t> dBlockFrames;
+    uint32_t *dGate = nullptr;
+    uint64_t hintTotalPeriods = 0;       // set by the host-buffer entries (they see every voice's length) for the launch that follows
+    std::vector<uint32_t> hintFrames;    // every voice's frame count in launch order (trm_batch_hint_frames / the host entries), for that launch
+};
+
+// ------------------------------------------------------------------ launch set-up, stated once (trm_capi.cc)
+// the process-wide noise sequence, at least `need` tube samples of it in b->dNoise
+int ensure_noise(trm_batch *b, uint32_t need, hipStream_t stream);
+
+// the forms with several lanes per voice convert at most four outputs per tube sample (choose_form)
+inline bool quad_ratio_too_high(const trm::Const &c) { return c.upsample && c.timeRegisterIncrement < 65536u / 4u; }
+
+// The kernel form of a launch.  byHandle / byEnv: the form asked for (trm_*_set_kernel, TRM_TUBE_KERNEL; AUTO = none);
+// voices: the count held against wideThreshold (the caller's own padding); wgs8: workgroups of 8 voices; minCP: the shortest
+// control period and ratioTooHigh: quad_ratio_too_high, both over the sets that have voices.  streaming: the streaming
+// instances exist as wide and quad only.
+int choose_form(int byHandle, int byEnv, uint64_t voices, uint64_t wgs8, int32_t minCP, bool ratioTooHigh, int cus,
+                uint32_t wideThreshold, bool streaming);
+
+// row pitch (floats, rows 16-byte aligned) of a down-sampling voice's `ntube` tube-rate samples + the 2 * pad of flush
+inline uint64_t tube_row_pitch(const trm_batch *b, uint64_t ntube) { return (ntube + 2ull * (uint64_t)b->d.padSize + 3ull) & ~3ull; }
+
+// A tube launch's arguments with what every launch shares set from b0 (noise, converter rows, sine; no stamps, not a stream
+// chunk, no tube-rate rows).  The caller adds what is its own: tube rows, gate, segments, mix map, stream state.
+trm::TubeArgs tube_args(const trm_batch *b0, const float *frames, const uint64_t *frame_offset, const uint32_t *nframes, float *out,
+                        const uint64_t *out_offset, uint32_t *number_samples, float *max_sample, size_t nvoices, uint32_t max_nframes);
+
+// The down-sampling launch behind tube launch `a` for its voices [lo, lo + n), all of b's parameter set, their tube-rate rows
+// at a.tube_out + tube_offset[v].  chunk: the bounds of a stream's chunk (DownArgs); null = one-shot.
+struct DownChunk { long long n_origin, n_hi; uint32_t k_base, k_end; };
+trm::DownArgs down_args(const trm_batch *b, const trm::TubeArgs &a, const uint64_t *tube_offset, size_t lo, size_t n, const DownChunk *chunk);
+
+// int16 scaling with b's volume, balance and channels
+trm::ScaleArgs scale_args(const trm_batch *b, const float *pcm, const uint64_t *out_offset, const uint32_t *number_samples,
+                          const float *max_sample, int16_t *pcm16, int for_wav_data);
+
+// ------------------------------------------------------------------ parameter sets (trm_mixed.cc)
+// One trm_batch per parameter set -- that set's constants, derived values and down-sampling rows (the read-only device tables
+// are shared per process anyway); the first one also lends its noise sequence, stream and staging buffers -- and the device
+// table of their constants (TubeArgs::set_const).  Declared FIRST in its owner: the owner's device buffers then go before the
+// batches, which own the stream they were used on.
+struct SetBatches {
+    std::vector<trm_batch *> b;              // per set
+    trm::Const *dConst = nullptr;            // [b.size()]
+    SetBatches() = default;
+    SetBatches(const SetBatches &) = delete;
+    ~SetBatches();
+    // Every set is checked before a device is looked for: a bad set is reported (by index) on any host.  Then the batches
+    // (all on the first one's device) and the table.
+    int create(const trm_input_params *params, size_t nsets, int device);
+    int upload();                            // the table from the batches' constants as they are now (synchronous)
+    size_t size() const { return b.size(); }
+    trm_batch *operator[](size_t s) const { return b[s]; }
+};
+
+int check_set_begin(size_t nsets, const size_t *set_begin);
+
+// {set, first voice, end voice, 0} per workgroup of perWg voices (TubeArgs::mix_map)
+void build_block_map(const size_t *set_begin, size_t nsets, size_t perWg, std::vector<uint4> &map);
+
+#pragma GCC visibility pop

@@ -20,7 +20,8 @@ esac
 mkdir -p build/var_$NAME
 hipcc --offload-arch=gfx950 $FLAGS "$@" -c $SRC.hip -o build/var_$NAME/$SRC.o
 OBJS=""
-for o in trm_kernels trm_quad trm_oct trm_tracks trm_capi trm_setup trm_io; do
+for f in $(make -s print-srcs); do      # the product's objects, the one source swapped
+  o=${f%.*}
   if [ $o = $SRC ]; then OBJS="$OBJS build/var_$NAME/$o.o"; else OBJS="$OBJS build/$o.o"; fi
 done
 hipcc --offload-arch=gfx950 -shared -o ../libtrm_var_$NAME.so $OBJS

@@ -15,9 +15,11 @@ if [ "$MODE" = build ]; then
   build_one() {
     n=$1; shift; cd gnuspeech_amd/csrc; mkdir -p build/var_$n
     hipcc $FLAGS "$@" -c trm_kernels.hip -o build/var_$n/trm_kernels.o 2>/dev/null
-    hipcc --offload-arch=gfx950 -shared -o ../libtrm_var_$n.so build/var_$n/trm_kernels.o build/trm_quad.o build/trm_oct.o build/trm_tracks.o build/trm_capi.o build/trm_setup.o build/trm_io.o
+    hipcc --offload-arch=gfx950 -shared -o ../libtrm_var_$n.so build/var_$n/trm_kernels.o $OTHERS
   }
-  export -f build_one; export FLAGS
+  # the product's other objects, from the Makefile's list
+  OTHERS=$(for f in $(make -s -C gnuspeech_amd/csrc print-srcs); do [ $f = trm_kernels.hip ] || echo -n "build/${f%.*}.o "; done)
+  export -f build_one; export FLAGS OTHERS
   xargs -P 6 -L 1 bash -c 'build_one "$@"' _ < "$LIST"
 else
   echo "product - $(one product 65536) $(one product 12288)"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # CPU-side AddressSanitizer + UBSan pass (GPU sanitizers are not available on the pool): the oracle (gcc) and the
-# library's host code (trm_capi.cc, trm_setup.cc, trm_io.cc; clang runtime of the ROCm toolchain) are rebuilt
+# library's host code (the .cc files of the Makefile's SRCS; clang runtime of the ROCm toolchain) are rebuilt
 # instrumented into /tmp and the CPU test suite runs against them.  Leaves the tree as it was.
 set -e
 cd "$(dirname "$0")/.."
@@ -15,11 +15,16 @@ ASAN_OPTIONS=detect_leaks=0 LD_PRELOAD="$(gcc -print-file-name=libasan.so) $(gcc
     python -m pytest tests -x -q -m "not gpu" -p no:cacheprovider
 cp $T/oracle_orig.so oracle/libtrm_oracle.so; touch oracle/libtrm_oracle.so
 cd gnuspeech_amd/csrc
-for f in trm_capi trm_setup trm_io; do
-    hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $f.cc -o $T/$f.o
+SRCS=$(make -s print-srcs)
+OBJS=""
+for f in $SRCS; do
+    case $f in
+    *.cc) hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=address,undefined -fno-sanitize-recover=undefined -c $f -o $T/${f%.cc}.o
+          OBJS="$OBJS $T/${f%.cc}.o" ;;
+    *)    OBJS="$OBJS build/${f%.*}.o" ;;      # the kernels as the product has them
+    esac
 done
-hipcc --offload-arch=gfx950 -shared -fsanitize=address,undefined -o $T/libtrm_hip_san.so $T/trm_capi.o $T/trm_setup.o $T/trm_io.o \
-    build/trm_kernels.o build/trm_quad.o build/trm_oct.o build/trm_tracks.o
+hipcc --offload-arch=gfx950 -shared -fsanitize=address,undefined -o $T/libtrm_hip_san.so $OBJS
 cd ../..
 echo "== library host code under clang ASan+UBSan"
 RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
