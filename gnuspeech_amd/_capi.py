@@ -69,6 +69,7 @@ EXPORTS = [
     "trm_batch_kernel_time_ms", "trm_batch_set_timing", "trm_batch_noise_table", "trm_device_count", "trm_build_info", "trm_kernel_blocks_per_cu", "trm_kernel_blocks_per_cu_form",
     "trm_mixed_create", "trm_mixed_destroy", "trm_mixed_derived", "trm_mixed_samples_for_frames", "trm_mixed_synthesize_device",
     "trm_mixed_synthesize_host", "trm_mixed_synthesize_host_int16", "trm_mixed_set_kernel", "trm_mixed_last_kernel",
+    "trm_mixed_set_time_split", "trm_mixed_last_time_split", "trm_mixed_hint_frames",
     "trm_mixed_generate_frames_device", "trm_mixed_scale_to_int16_device", "trm_mixed_sound_file_size", "trm_mixed_sound_files_device",
     "trm_mixed_events_to_files_host",
     "trm_mixed_stream_create", "trm_mixed_stream_destroy", "trm_mixed_stream_set_mode", "trm_mixed_stream_mode", "trm_mixed_stream_kernel",
@@ -184,6 +185,9 @@ def lib():
     L.trm_mixed_synthesize_host_int16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     L.trm_mixed_set_kernel.argtypes = [vp, C.c_int]
     L.trm_mixed_last_kernel.argtypes = [vp]
+    L.trm_mixed_set_time_split.argtypes = [vp, C.c_int]
+    L.trm_mixed_last_time_split.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t]
+    L.trm_mixed_hint_frames.argtypes = [vp, vp, C.c_size_t]
     L.trm_mixed_generate_frames_device.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.trm_mixed_scale_to_int16_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
     L.trm_mixed_sound_file_size.argtypes = [vp, C.c_size_t, C.c_size_t]

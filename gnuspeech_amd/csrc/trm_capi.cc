@@ -433,8 +433,11 @@ struct SplitPlan {
 constexpr double kSplitLogEps = -11.512925464970229;
 }  // namespace
 
+// (declared in trm_host.h: trm_mixed.cc plans its time split with the same functions)
+extern "C++" {
+
 // warm-up (tube samples) after which a tube started from rest has forgotten that it was; 0 = never (a pole on the unit circle)
-static uint32_t split_warm_samples(const trm::Const &c)
+uint32_t split_warm_samples(const trm::Const &c)
 {
     double pole = fabs((double)c.damping);
     const double others[] = {fabs((double)c.mCoeff), fabs((double)c.nCoeff), fabs((double)c.tb1)};
@@ -451,7 +454,7 @@ static uint32_t split_warm_samples(const trm::Const &c)
 // The one-voice-per-lane kernel: a CU holds two workgroups; one per CU runs at 6.7, two at 7.5, and more go in ROUNDS of two
 // per CU at 7.75 each -- a round is not cheaper for being partly filled (its workgroups last as long), except that a last
 // round of at most one workgroup per CU saves ~0.8 (measured at 2.5 .. 10 workgroups per CU).
-static double wide_cost(const trm_batch *b, uint64_t workgroups)
+double wide_cost(const trm_batch *b, uint64_t workgroups)
 {
     const double cus = b->cus > 0 ? b->cus : 256, x = (double)workgroups / cus;
     if (x <= 1.0) return 6.7;
@@ -459,7 +462,7 @@ static double wide_cost(const trm_batch *b, uint64_t workgroups)
     const double rounds = ceil(x / 2.0), last = x - 2.0 * (rounds - 1.0);
     return 7.75 * rounds - (last <= 1.0 ? 0.8 : 0.0);
 }
-static double unsplit_cost(const trm_batch *b, size_t nvoices, int which)
+double unsplit_cost(const trm_batch *b, size_t nvoices, int which)
 {
     const double cus = b->cus > 0 ? b->cus : 256, vpc = (double)nvoices / cus;
     if (which == TRM_KERNEL_OCT) return vpc <= 4 ? 2.06 : vpc <= 8 ? 2.24 : 2.37 * (vpc <= 16 ? 1.0 : vpc / 16.0);
@@ -469,7 +472,7 @@ static double unsplit_cost(const trm_batch *b, size_t nvoices, int which)
 
 // segments of an utterance of P control periods cut every `periods`: the first one is periods + warm long (it has no warm-up
 // of its own: with it that long every workgroup of the launch runs periods + warm control periods)
-static uint32_t split_segments(uint32_t P, uint32_t periods, uint32_t warm)
+uint32_t split_segments(uint32_t P, uint32_t periods, uint32_t warm)
 {
     const uint32_t first = periods + warm;
     return P <= first ? 1u : 1u + (P - first + periods - 1) / periods;
@@ -477,12 +480,24 @@ static uint32_t split_segments(uint32_t P, uint32_t periods, uint32_t warm)
 
 // workgroups of a time-split launch that have work: block by block (its longest voice, in control periods) the segments it
 // reaches -- what trm_seg_map_kernel counts on the device
-static uint64_t busy_workgroups(const std::vector<uint32_t> &longest, uint32_t periods, uint32_t warm)
+uint64_t busy_workgroups(const std::vector<uint32_t> &longest, uint32_t periods, uint32_t warm)
 {
     uint64_t n = 0;
     for (uint32_t per : longest) n += split_segments(per, periods, warm);
     return n;
 }
+
+// the frication band-pass (TRMFilters.m:9-29) has poles of radius sqrt(2 beta), 2 beta = (1 - t) / (1 + t),
+// t = tan(pi BW / SR): the bandwidth at which a warm-up of `warm` control periods leaves 1e-5 of its memory
+float split_bw_floor(const trm_batch *b, uint32_t warm)
+{
+    const uint32_t CP = (uint32_t)b->c.controlPeriod;
+    const double r2 = exp(2.0 * kSplitLogEps / (double)(warm * CP - 64u));
+    const double t = (1.0 - r2) / (1.0 + r2);
+    return (float)((double)b->d.sampleRate * atan(t) / 3.14159265358979323846);
+}
+
+}  // extern "C++"
 
 // `which` = the kernel form the launch would take unsplit.  `totalPeriods` = the control periods of all voices together where
 // the caller knows them (the host-buffer entries; 0: every voice is taken to be as long as the longest).
@@ -557,13 +572,7 @@ static int plan_time_split(const trm_batch *b, size_t nvoices, uint32_t max_nfra
     }
     pl.periods = periods;
     pl.warm = warm;
-    {
-        // the frication band-pass (TRMFilters.m:9-29) has poles of radius sqrt(2 beta), 2 beta = (1 - t) / (1 + t),
-        // t = tan(pi BW / SR): the bandwidth at which the warm-up leaves 1e-5 of its memory
-        const double r2 = exp(2.0 * kSplitLogEps / (double)(warm * CP - 64u));
-        const double t = (1.0 - r2) / (1.0 + r2);
-        pl.bwFloor = (float)((double)b->d.sampleRate * atan(t) / 3.14159265358979323846);
-    }
+    pl.bwFloor = split_bw_floor(b, warm);
     return TRM_OK;
 }
 

@@ -132,6 +132,20 @@ trm::DownArgs down_args(const trm_batch *b, const trm::TubeArgs &a, const uint64
 trm::ScaleArgs scale_args(const trm_batch *b, const float *pcm, const uint64_t *out_offset, const uint32_t *number_samples,
                           const float *max_sample, int16_t *pcm16, int for_wav_data);
 
+// ------------------------------------------------------------------ time-split planning, stated once (trm_capi.cc)
+// What trm_batch's planner and trm_mixed's share: each fact has one definition, so the two paths cut a set's voices alike.
+// warm-up (tube samples) after which a tube started from rest has forgotten that it was; 0 = never
+uint32_t split_warm_samples(const trm::Const &c);
+// segments of an utterance of P control periods cut every `periods` (the first one periods + warm long)
+uint32_t split_segments(uint32_t P, uint32_t periods, uint32_t warm);
+// workgroups with work: per block (its longest voice, in control periods) the segments it reaches
+uint64_t busy_workgroups(const std::vector<uint32_t> &longest, uint32_t periods, uint32_t warm);
+// predicted ms per second of speech (19 750 tube samples) of the one-voice-per-lane kernel / of a whole-utterance launch in form `which`
+double wide_cost(const trm_batch *b, uint64_t workgroups);
+double unsplit_cost(const trm_batch *b, size_t nvoices, int which);
+// frication bandwidth (Hz) below which a warm-up of `warm` control periods of b's set is too short: the guard's floor
+float split_bw_floor(const trm_batch *b, uint32_t warm);
+
 // ------------------------------------------------------------------ parameter sets (trm_mixed.cc)
 // One trm_batch per parameter set -- that set's constants, derived values and down-sampling rows (the read-only device tables
 // are shared per process anyway); the first one also lends its noise sequence, stream and staging buffers -- and the device

@@ -81,7 +81,11 @@ struct TubeArgs {
     // one workgroup's worth, all of parameter set mix_map[w].x -- with set_const[mix_map[w].x] in place of the kernel's
     // Const argument.  The set index is workgroup-uniform, so its constants stay scalar loads.  A set whose Const says
     // upsample == 0 writes its tube-rate rows to tube_out (tube_offset per voice); the others convert inline.
-    const uint4 *mix_map = nullptr;       // {set, first voice, end voice, 0}
+    // A mixed time-split launch (seg_periods and mix_map both set; trm_mixseg_kernel): workgroup w runs segment seg_map[w].x of
+    // map entry seg_map[w].y with the entry's own warm-up (its fourth component; seg_warm and seg_first are unused), so that
+    // every voice's segments are those of its set's own batch; seg_phase rows are indexed by map entry * 64 + lane (pitch
+    // 64 * seg_wg_per_seg, seg_wg_per_seg = the map's entries).
+    const uint4 *mix_map = nullptr;       // {set, first voice, end voice, the set's warm-up in control periods (time split; else 0)}
     ConstTable set_const = nullptr;
     uint32_t mix_grid = 0;                // workgroups of the launch = entries of mix_map
 };
@@ -125,6 +129,10 @@ hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream);
 // trm_mix_kernel_o).  The launchers above call these for a launch with a mix_map; with a stream_state too, the first two run
 // their mixed streaming instance.
 hipError_t launch_mix_wide(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);       // `grid` workgroups from a.wg_base
+// ... and of a mixed batch's time-split launch (trm_mix_seg.hip: trm_mixseg_kernel; a.seg_periods and a.mix_map both set)
+hipError_t launch_mix_seg(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);
+// max_sample[0 .. n) = 0 and, where gate is not null, *gate = 0, in one launch (trm_mix_seg.hip)
+hipError_t launch_split_clear(float *max_sample, uint32_t n, uint32_t *gate, hipStream_t stream);
 hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int sub);
 hipError_t launch_mix_oct(const Const &c, const TubeArgs &a, hipStream_t stream);
 // small-batch form (trm_quad.hip): 16 voices per workgroup, four lanes per voice

@@ -125,13 +125,16 @@ __global__ void trm_noise_kernel(float *lp, uint32_t from, uint32_t to, double *
 // workgroups may belong to different parameter sets (TubeArgs::mix_map): the workgroup's constants come from set_const, its
 // voices are the map entry's range; otherwise it is the one-shot instance.  kModeMixedStream: both, a chunk of a mixed stream
 // (trm_kernels.h: its time bases are the set's own, derived from a count of control periods); the state block of workgroup
-// wg is the map entry's.
-constexpr int kModeOneShot = 0, kModeStream = 1, kModeSegments = 2, kModeMixed = 3, kModeMixedStream = 4;
+// wg is the map entry's.  kModeMixedSegments: a time-split launch of a mixed batch: the workgroup runs one segment of one
+// map entry (seg_map lists the pairs), with the set's constants and the set's own warm-up (the map entry's fourth component):
+// its segment boundaries and time bases are those of a kModeSegments launch of that set alone.
+constexpr int kModeOneShot = 0, kModeStream = 1, kModeSegments = 2, kModeMixed = 3, kModeMixedStream = 4, kModeMixedSegments = 5;
 template <int kMode>
 __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const Carg, const TubeArgs A)
 {
-    constexpr bool kStream = kMode == kModeStream || kMode == kModeMixedStream, kSeg = kMode == kModeSegments;
-    constexpr bool kMix = kMode == kModeMixed || kMode == kModeMixedStream, kMixStream = kMix && kStream;
+    constexpr bool kStream = kMode == kModeStream || kMode == kModeMixedStream, kSeg = kMode == kModeSegments || kMode == kModeMixedSegments;
+    constexpr bool kMix = kMode == kModeMixed || kMode == kModeMixedStream || kMode == kModeMixedSegments, kMixStream = kMix && kStream;
+    constexpr bool kMixSeg = kMix && kSeg;
     // (two launches of one batch, one of which runs: TubeArgs::gate)
     if (A.gate && ((*A.gate != 0u) ? 1u : 0u) != A.gate_want) return;
     __shared__ __attribute__((aligned(16))) float4 sW[2 * kTB * kWave];          // osc -> mix: {wa, wb, ax, ah1}
@@ -155,7 +158,7 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     int role = 0;
     for (int i = 0; i < kRoles; i++) role = waveIdx == i ? rolePerm[i] : role;
     const uint32_t wg = A.wg_base + blockIdx.x;          // (a large batch is launched in slices: launch_tube)
-    // time-split: workgroup -> (segment, block of 64 voices)
+    // time-split: workgroup -> (segment, block of 64 voices; a mixed launch: map entry)
     uint32_t seg = 0, vblock = wg;
     if (kSeg) {
         if (A.seg_map) {                     // (the pairs with work first: trm_seg_map_kernel)
@@ -169,7 +172,7 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     }
     // mixed launch: the workgroup's parameter set and voice range.  C is read in place (a reference into the table, not a
     // copy: held live, its ~75 dwords would spill the scalar file); the set index depends on the workgroup only
-    const uint4 mix = kMix ? A.mix_map[wg] : make_uint4(0u, 0u, 0u, 0u);
+    const uint4 mix = kMix ? A.mix_map[kSeg ? vblock : wg] : make_uint4(0u, 0u, 0u, 0u);
     const Const &C = kMix ? *(const Const *)(A.set_const + mix.x) : Carg;
     const uint32_t vFirst = kMix ? mix.y : vblock * kWave, vEnd = kMix ? mix.z : A.nvoices;
     const uint32_t vRaw = vFirst + lane;
@@ -182,7 +185,11 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
 
     // segment s covers the control periods seg_begin(s) .. seg_begin(s + 1): the first segment is a warm-up longer than the
     // others (it has none of its own), so that every workgroup of the launch runs the same number of periods
-    auto seg_begin = [&](uint32_t sgm) { return sgm == 0 ? 0u : A.seg_first + (sgm - 1) * A.seg_periods; };
+    // (a mixed launch: the warm-up is the set's own, mix.w; the segment length is the launch's)
+    auto seg_begin = [&](uint32_t sgm) {
+        if constexpr (kMixSeg) return sgm == 0 ? 0u : mix.w + sgm * A.seg_periods;
+        else return sgm == 0 ? 0u : A.seg_first + (sgm - 1) * A.seg_periods;
+    };
     const uint32_t nfrAll = min(A.nframes[v], A.max_nframes);
     // the frames this launch runs for this lane: the utterance's, or those of the workgroup's segment with its warm-up
     uint32_t nfr = nfrAll, segFrame0 = 0, segOutEnd = 0;
@@ -190,7 +197,7 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     if (kSeg) {
         const uint32_t nper = nfrAll > 0 ? nfrAll - 1 : 0;
         const uint32_t pLo = seg_begin(seg), pEnd = seg_begin(seg + 1);
-        segFrame0 = pLo > A.seg_warm ? pLo - A.seg_warm : 0u;                      // (uniform)
+        segFrame0 = pLo > (kMixSeg ? mix.w : A.seg_warm) ? pLo - (kMixSeg ? mix.w : A.seg_warm) : 0u;     // (uniform)
         if (seg > 0 && pLo >= nper) nfr = 0;                                       // the voice ended before this segment
         else if (nfrAll > 0) {
             const uint32_t pHi = pEnd < nper ? pEnd : nper;
@@ -277,7 +284,8 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
             // segments so far, summed in order (every term and sum a multiple of 2^-30 below 2^10: exact) and wrapped both
             // ways like the four-lane form's: two representatives in (-1, 0) sum to one in (-2, -1].  (seg_phase holds
             // entries for the batch's voices only: a lane past the end reads those of the voice it stands in for, v.)
-            const double *ph = A.seg_phase + v;
+            // (a mixed launch: rows of 64 entries per map entry -- its voices are not block-aligned)
+            const double *ph = A.seg_phase + (kMixSeg ? vblock * kWave + (v - vFirst) : v);
             const size_t pitch = (size_t)A.seg_wg_per_seg * kWave;
             for (uint32_t q = 1; q <= seg; q++) S.oscPos = osc_wrap(S.oscPos + ph[q * pitch]);
         }
@@ -1117,7 +1125,11 @@ hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream)
         const uint32_t n = slice == 0 ? grid - base : (grid - base < slice ? grid - base : slice);
         s.wg_base = base;
         s.coef_hold = n <= 2u * (uint32_t)cus;        // one round: two workgroups per CU
-        if (a.seg_periods) hipLaunchKernelGGL(trm_tube_kernel<kModeSegments>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s);
+        if (a.seg_periods && a.mix_map) {
+            const hipError_t e = launch_mix_seg(c, s, n, stream);
+            if (e != hipSuccess) return e;
+        }
+        else if (a.seg_periods) hipLaunchKernelGGL(trm_tube_kernel<kModeSegments>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s);
         else if (a.mix_map) {
             const hipError_t e = launch_mix_wide(c, s, n, stream);
             if (e != hipSuccess) return e;
@@ -1183,7 +1195,8 @@ hipError_t launch_downsample(const Const &c, const DownArgs &a, hipStream_t stre
         // (a shorter voice may end on the reference's extra lap, src_count_outputs: cover it)
         uint64_t noutMax = (((uint64_t)ntubeMax + 2ull * (uint32_t)c.padSize + kSrcRing) * 65536ull + c.timeRegisterIncrement - 1) / c.timeRegisterIncrement;
         if (a.stream) noutMax = a.k_end - a.k_base;
-        hipError_t e = hipMemsetAsync(a.max_sample, 0, a.nvoices * sizeof(float), stream);
+        // (a kernel, not a memset: trm_mix_seg.hip)
+        hipError_t e = launch_split_clear(a.max_sample, a.nvoices, nullptr, stream);
         if (e != hipSuccess) return e;
         DownArgs t = a;
         t.ntiles = (uint32_t)((noutMax + kDownCols - 1) / kDownCols > 0 ? (noutMax + kDownCols - 1) / kDownCols : 1);

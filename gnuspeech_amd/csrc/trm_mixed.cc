@@ -67,13 +67,15 @@ extern "C" {
 
 // ------------------------------------------------------------------ mixed-parameter batches
 // One trm_batch per parameter set (SetBatches).  The launch itself is one grid: workgroup w runs voices map[w].y .. map[w].z - 1 of set map[w].x with that set's constants
-// (trm_kernels.h, TubeArgs::mix_map).  Whole utterances only: the time split's warm-up is chosen per batch, and a mixed launch
-// must give every voice exactly what its own set's batch gives it (the split's rule for that is not settled).
+// (trm_kernels.h, TubeArgs::mix_map).  Whole utterances unless trm_mixed_set_time_split asks for the time split: then a workgroup
+// is one segment of one map entry, cut with the launch's segment length S and the SET's own warm-up W (split_warm_samples),
+// so that every voice gets bit for bit what a trm_batch of its set computes with trm_batch_set_time_split(S) in the
+// one-voice-per-lane form -- the boundaries depend on S and W alone, a voice's lane neighbours do not enter its arithmetic.
 struct trm_mixed {
     SetBatches sets;                         // (first: destroyed after the device buffers below)
     int kernel = TRM_KERNEL_AUTO;            // trm_mixed_set_kernel
     int lastKernel = TRM_KERNEL_AUTO;
-    DevBuf<uint4> dMap;                      // {set, first voice, end voice, 0} per workgroup
+    DevBuf<uint4> dMap;                      // {set, first voice, end voice, the set's warm-up (split launches; else 0)} per workgroup
     DevBuf<uint64_t> dTubeOff;               // down-sampling sets' voices: their tube-rate rows in dTube
     DevBuf<float> dTube;
     // the shape the three arrays above were built for (rebuilt when it changes: the device entry is pure stream work otherwise)
@@ -81,6 +83,17 @@ struct trm_mixed {
     int shapeForm = -1;
     uint32_t shapeMaxFrames = 0, mapEntries = 0;
     bool haveShape = false;
+    // time split (trm_mixed_set_time_split): OFF unless asked for; TRM_TIME_SPLIT in the environment is not read here
+    int splitSetting = TRM_TIME_SPLIT_OFF;
+    uint32_t lastSplitPeriods = 0;           // what the last launch did (0: whole utterances)
+    std::vector<uint32_t> lastWarm;          // ... and every set's warm-up in control periods then
+    std::vector<uint32_t> hintFrames;        // trm_mixed_hint_frames / the host entries: every voice's length, for the launch that follows
+    // a split launch's part of the shape: the segment length, the lengths its launch order was built from, the order itself
+    uint32_t shapeSplit = 0, segGrid = 0, segRows = 0;
+    std::vector<uint32_t> shapeHint;
+    DevBuf<uint2> dSegMap;                   // (segment, map entry) per workgroup of the split grid, the pairs with work first
+    std::vector<uint2> hSegMap;
+    DevBuf<double> dSegPhase, dPeriodAdv;    // the pre-pass's rows (per set: its voice range / its map entries)
     std::vector<uint4> hMap;                 // host copies the uploads read from (they outlive the asynchronous copies)
     std::vector<uint64_t> hTubeOff;
     // completes after the last launch that read the arrays, on whichever stream: a shape change waits for it alone (not for
@@ -176,6 +189,31 @@ int trm_mixed_set_kernel(trm_mixed *m, int kernel)
 
 int trm_mixed_last_kernel(const trm_mixed *m) { return m ? m->lastKernel : TRM_KERNEL_AUTO; }
 
+int trm_mixed_set_time_split(trm_mixed *m, int periods)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    if (periods < TRM_TIME_SPLIT_AUTO) return fail(TRM_EINVAL, "time split: %d", periods);
+    m->splitSetting = periods;
+    return TRM_OK;
+}
+
+int trm_mixed_last_time_split(const trm_mixed *m, uint32_t *periods, uint32_t *warm_periods, size_t nsets)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    if (warm_periods && nsets > m->sets.size()) return fail(TRM_EINVAL, "%zu parameter sets asked for, the batch has %zu", nsets, m->sets.size());
+    if (periods) *periods = m->lastSplitPeriods;
+    for (size_t s = 0; warm_periods && s < nsets; s++) warm_periods[s] = s < m->lastWarm.size() ? m->lastWarm[s] : 0u;
+    return TRM_OK;
+}
+
+int trm_mixed_hint_frames(trm_mixed *m, const uint32_t *nframes, size_t nvoices)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    if (!nframes || nvoices == 0) { m->hintFrames.clear(); return TRM_OK; }
+    m->hintFrames.assign(nframes, nframes + nvoices);
+    return TRM_OK;
+}
+
 static int mixed_check_sets(const trm_mixed *m, const size_t *set_begin) { return check_set_begin(m->sets.size(), set_begin); }
 
 // The kernel form of a mixed launch: what a trm_batch of the same voice count -- every set padded to the form's workgroup --
@@ -198,11 +236,79 @@ static int mixed_form(const trm_mixed *m, const size_t *set_begin)
     return choose_form(m->kernel, b0->envKernel, padded16, wgs8, minCP, ratioTooHigh, b0->cus, b0->wideThreshold, false);
 }
 
+// The time split of a mixed launch: one segment length S (control periods) for all sets, every set's own warm-up.  Priced with
+// trm_batch's figures (trm_host.h): a split launch lasts as long as its longest workgroup, S + W_s periods of CP_s samples,
+// at the rate its busy workgroups fill the chip; whole utterances as long as the longest voice of the slowest set.
+// `longest`: per entry of the 64-voice block map its longest voice in control periods (the hint's, else the launch's).
+static int mixed_plan_split(const trm_mixed *m, const size_t *set_begin, uint32_t max_nframes, int which, const std::vector<uint4> &map64,
+                            const std::vector<uint32_t> &longest, uint32_t &periodsOut, std::vector<uint32_t> &warm)
+{
+    const size_t S = m->sets.size();
+    periodsOut = 0;
+    warm.assign(S, 0);
+    const int setting = m->splitSetting;
+    if (setting == TRM_TIME_SPLIT_OFF || max_nframes < 2) return TRM_OK;
+    const uint32_t P = max_nframes - 1;
+    const trm_batch *b0 = m->sets[0];
+    uint32_t warmMax = 0, minPeriods = 4;
+    double wholeSamples = 0.0;
+    for (size_t s = 0; s < S; s++) {
+        const trm_batch *b = m->sets[s];
+        const uint32_t CP = (uint32_t)b->c.controlPeriod, ws = split_warm_samples(b->c);
+        warm[s] = (ws + CP - 1) / CP;
+        if (set_begin[s + 1] == set_begin[s]) continue;
+        if (ws == 0) {
+            if (setting > 0) return fail(TRM_ERANGE, "time split: the tube of parameter set %zu never forgets (loss factor %g %%)", s, b->params.lossFactor);
+            return TRM_OK;
+        }
+        warmMax = std::max(warmMax, warm[s]);
+        minPeriods = std::max(minPeriods, (255u + CP) / CP);
+        wholeSamples = std::max(wholeSamples, (double)P * CP);
+    }
+    // the launch's longest workgroup, in tube samples, with segments of sp periods
+    auto seg_samples = [&](uint32_t sp) {
+        double x = 0.0;
+        for (size_t s = 0; s < S; s++)
+            if (set_begin[s + 1] > set_begin[s]) x = std::max(x, (double)(sp + warm[s]) * (double)m->sets[s]->c.controlPeriod);
+        return x;
+    };
+    auto busy = [&](uint32_t sp) {
+        uint64_t n = 0;
+        for (size_t e = 0; e < map64.size(); e++) n += split_segments(longest[e], sp, warm[map64[e].x]);
+        return n;
+    };
+    uint32_t periods = 0;
+    if (setting > 0) periods = (uint32_t)setting;
+    else {
+        // AUTO: trm_batch's search (plan_time_split) with the largest warm-up in its constraints
+        const double whole = (which == TRM_KERNEL_WIDE ? wide_cost(b0, map64.size()) : unsplit_cost(b0, set_begin[S], which)) * wholeSamples / 19750.0;
+        double best = whole * 0.9;
+        minPeriods = std::max(minPeriods, (warmMax + 1) / 2);
+        for (uint32_t nseg = 2; nseg <= 4096 && P > warmMax; nseg++) {
+            const uint32_t sp = (P - warmMax + nseg - 1) / nseg;
+            if (sp < minPeriods) break;
+            const double t = 0.03 + wide_cost(b0, busy(sp)) * seg_samples(sp) / 19750.0;
+            if (t < best) { best = t; periods = sp; }
+        }
+    }
+    if (periods == 0) return TRM_OK;
+    // (no voice reaches past its set's first segment: one segment is the whole utterance)
+    bool any = false;
+    for (size_t s = 0; s < S; s++) any = any || (set_begin[s + 1] > set_begin[s] && split_segments(P, periods, warm[s]) >= 2);
+    if (any) periodsOut = periods;
+    return TRM_OK;
+}
+
 int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const float *d_frames, const uint64_t *d_frame_offset,
                                 const uint32_t *d_nframes, uint32_t max_nframes, float *d_out, const uint64_t *d_out_offset,
                                 uint32_t *d_number_samples, float *d_max_sample, void *stream_)
 {
     if (!m) return fail(TRM_EINVAL, "null handle");
+    // a hint holds for the one launch that follows it, whether that launch runs or fails (as trm_batch_hint_frames')
+    struct HintDrop {
+        trm_mixed *m;
+        ~HintDrop() { m->hintFrames.clear(); }
+    } const hintDrop{m};
     int rc = mixed_check_sets(m, set_begin);
     if (rc) return rc;
     const size_t S = m->sets.size(), nvoices = set_begin[S];
@@ -224,16 +330,60 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
         if (!cb || b->c.controlPeriod < cb->c.controlPeriod) cb = b;
     }
     if ((rc = ensure_noise(b0, (uint32_t)need, stream))) return rc;
-    const int which = mixed_form(m, set_begin);
+    int which = mixed_form(m, set_begin);
+    // the time split: planned over the 64-voice block map (the split launch's, shared with its whole-utterance fallback)
+    uint32_t split = 0;
+    std::vector<uint32_t> warm(S, 0), longest;
+    const bool hinted = m->hintFrames.size() == nvoices;
+    if (m->splitSetting != TRM_TIME_SPLIT_OFF && max_nframes >= 2) {
+        std::vector<uint4> map64;
+        build_block_map(set_begin, S, 64, map64);
+        longest.assign(map64.size(), max_nframes - 1);
+        for (size_t e = 0; hinted && e < map64.size(); e++) {
+            uint32_t nfr = 0;
+            for (uint32_t v = map64[e].y; v < map64[e].z; v++) nfr = std::max(nfr, std::min(m->hintFrames[v], max_nframes));
+            longest[e] = nfr > 0 ? nfr - 1 : 0;
+        }
+        if ((rc = mixed_plan_split(m, set_begin, max_nframes, which, map64, longest, split, warm))) return rc;
+    }
+    m->lastSplitPeriods = split;
+    m->lastWarm.assign(S, 0);
+    if (split) {
+        m->lastWarm = warm;
+        which = TRM_KERNEL_WIDE;
+    }
     const uint32_t perWg = which == TRM_KERNEL_WIDE ? 64u : which == TRM_KERNEL_QUAD ? 16u : 8u;
-    // the block map and the down-sampling sets' row offsets: rebuilt when the shape changes
-    if (!m->haveShape || m->shapeForm != which || m->shapeMaxFrames != max_nframes || !std::equal(set_begin, set_begin + S + 1, m->shapeBegin.begin())) {
+    // the block map and the down-sampling sets' row offsets: rebuilt when the shape changes (a split launch's shape includes its
+    // segment length and the lengths its launch order was built from)
+    if (!m->haveShape || m->shapeForm != which || m->shapeMaxFrames != max_nframes || !std::equal(set_begin, set_begin + S + 1, m->shapeBegin.begin()) ||
+        m->shapeSplit != split || (split && (hinted ? m->shapeHint != m->hintFrames : !m->shapeHint.empty()))) {
         // (an earlier launch, on whichever stream, may still read the arrays and their host copies' uploads)
         if (m->lastUseRecorded) HIP_TRY(hipEventSynchronize(m->lastUse));
         m->haveShape = false;
         std::vector<uint4> &map = m->hMap;
         std::vector<uint64_t> &toff = m->hTubeOff;
         build_block_map(set_begin, S, perWg, map);
+        m->hSegMap.clear();
+        m->segRows = 0;
+        if (split) {
+            // The launch order: every (segment, map entry) pair up to the segments max_nframes allows -- a wrong hint changes
+            // the order, never the set of pairs -- those with work by the lengths we know first, in (segment, entry) order: a
+            // workgroup that exits at once does not free its place.
+            uint32_t nsegMax = 0;
+            for (size_t e = 0; e < map.size(); e++) {
+                map[e].w = warm[map[e].x];
+                nsegMax = std::max(nsegMax, split_segments(max_nframes - 1, split, map[e].w));
+            }
+            if ((uint64_t)nsegMax * map.size() > 0x7FFFFFFFull / 64) return fail(TRM_ERANGE, "time split: too many segments");
+            for (int pass = 0; pass < 2; pass++)
+                for (uint32_t sgm = 0; sgm < nsegMax; sgm++)
+                    for (size_t e = 0; e < map.size(); e++) {
+                        if (sgm >= split_segments(max_nframes - 1, split, map[e].w)) continue;
+                        const bool work = sgm < split_segments(longest[e], split, map[e].w);
+                        if (work == (pass == 0)) m->hSegMap.push_back(make_uint2(sgm, (uint32_t)e));
+                    }
+            m->segRows = nsegMax;
+        }
         toff.assign(nvoices, 0);
         uint64_t rows = 0;
         for (size_t s = 0; s < S; s++) {
@@ -250,6 +400,16 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
         if ((rc = m->dMap.reserve(map.size())) || (rc = m->dTubeOff.reserve(nvoices)) || (rc = m->dTube.reserve(rows + 1))) return rc;
         HIP_TRY(hipMemcpyAsync(m->dMap.p, map.data(), map.size() * sizeof(uint4), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemcpyAsync(m->dTubeOff.p, toff.data(), nvoices * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        if (split) {
+            if ((rc = m->dSegMap.reserve(m->hSegMap.size())) || (rc = m->dSegPhase.reserve((size_t)m->segRows * map.size() * 64)) ||
+                (rc = m->dPeriodAdv.reserve(nvoices * (size_t)max_nframes)))
+                return rc;
+            HIP_TRY(hipMemcpyAsync(m->dSegMap.p, m->hSegMap.data(), m->hSegMap.size() * sizeof(uint2), hipMemcpyHostToDevice, stream));
+        }
+        m->shapeSplit = split;
+        m->segGrid = (uint32_t)m->hSegMap.size();
+        if (split && hinted) m->shapeHint = m->hintFrames;
+        else m->shapeHint.clear();
         m->shapeBegin.assign(set_begin, set_begin + S + 1);
         m->shapeForm = which;
         m->shapeMaxFrames = max_nframes;
@@ -263,6 +423,36 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
     a.set_const = (trm::ConstTable)m->sets.dConst;
     a.mix_grid = m->mapEntries;
     m->lastKernel = which;
+    if (split) {
+        // The pre-pass, set by set over its voice range (the oscillator's advance per period and the guard's floor are the
+        // set's): its rows of seg_phase start at the set's first map entry, every set ORs into one gate word.  Then both
+        // launches, of which the device runs one (TubeArgs::gate): the segments, or -- a frame of any voice below its set's
+        // floor -- whole utterances over the same map.
+        uint32_t *gate = b0->dGate;
+        HIP_TRY(trm::launch_split_clear(d_max_sample, (uint32_t)nvoices, gate, stream));
+        size_t entry = 0;
+        for (size_t s = 0; s < S; s++) {
+            const size_t lo = set_begin[s], n = set_begin[s + 1] - lo;
+            if (n == 0) continue;
+            const trm_batch *b = m->sets[s];
+            trm::PhaseArgs ph;
+            ph.frames = d_frames; ph.frame_offset = d_frame_offset + lo; ph.nframes = d_nframes + lo;
+            ph.period_adv = m->dPeriodAdv.p + lo * (size_t)max_nframes; ph.seg_phase = m->dSegPhase.p + entry * 64; ph.gate = gate;
+            ph.bw_floor = split_bw_floor(b, warm[s]);
+            ph.nvoices = (uint32_t)n; ph.max_nframes = max_nframes; ph.nseg = split_segments(max_nframes - 1, split, warm[s]);
+            ph.seg_periods = split; ph.seg_warm = warm[s]; ph.seg_wg_per_seg = m->mapEntries; ph.seg_first = split + warm[s];
+            ph.voices_per_wg = 64;
+            HIP_TRY(trm::launch_phase(b->c, ph, stream));
+            entry += (n + 63) / 64;
+        }
+        trm::TubeArgs sa = a;
+        sa.seg_periods = split; sa.seg_wg_per_seg = m->mapEntries; sa.seg_grid = m->segGrid;
+        sa.seg_phase = m->dSegPhase.p;
+        sa.seg_map = m->dSegMap.p;
+        sa.gate = gate; sa.gate_want = 0;
+        HIP_TRY(trm::launch_tube(cb->c, sa, stream));
+        a.gate = gate; a.gate_want = 1;
+    }
     if (which == TRM_KERNEL_OCT)
         HIP_TRY(trm::launch_tube_oct(cb->c, a, stream));
     else if (which == TRM_KERNEL_QUAD)
@@ -350,6 +540,7 @@ static int mixed_host_impl(trm_mixed *m, const size_t *set_begin, const float *f
     HIP_TRY(hipMemcpyAsync(m->dOutOff.p, pOutOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(m->dNFrames.p, pNFrames.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if (out16) HIP_TRY(hipMemcpyAsync(m->dRelOff.p, pRel.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    m->hintFrames = pNFrames;       // (the lengths in launch order: the time split's plan and launch order)
     rc = trm_mixed_synthesize_device(m, set_begin, m->dFrames.p, m->dFrameOff.p, m->dNFrames.p, maxFrames, m->dOut.p, m->dOutOff.p,
                                      m->dNSamples.p, m->dMax.p, st);
     if (rc) return rc;
@@ -592,6 +783,8 @@ int trm_mixed_events_to_files_host(trm_mixed *m, const size_t *set_begin, const 
     if ((rc = trm_mixed_generate_frames_device(m, V, m->evT.p, m->evV.p, m->evOff.p, m->evN.p, m->dSettings.p, m->dFrames.p, m->dFrameOff.p,
                                                m->dNFrames.p, st)))
         return rc;
+    m->hintFrames.resize(V);
+    for (size_t i = 0; i < V; i++) m->hintFrames[i] = nfr[perm[i]];
     if ((rc = trm_mixed_synthesize_device(m, set_begin, m->dFrames.p, m->dFrameOff.p, m->dNFrames.p, maxFrames, m->dOut.p, m->dOutOff.p,
                                           m->dNSamples.p, m->dMax.p, st)))
         return rc;

@@ -2,10 +2,10 @@
 trm_mixed_*, trm_mixed_stream_*).
 
 Every workgroup of the launch holds voices of one set and reads that set's constants from a device table, so a voice's
-samples are bit for bit what a TRMBatch of its own set computes in the same kernel form with the time split off.  Callers
+samples are bit for bit what a TRMBatch of its own set computes in the same kernel form with the same time-split setting.  Callers
 hand voices in any order with a set index per voice; the library wants them grouped by set, which group_voices() does
-(a stable sort), and the results come back in the caller's order.  Batches run whole utterances only (no time split);
-TRMMixedStream delivers utterances in chunks, like TRMStream.
+(a stable sort), and the results come back in the caller's order.  Batches run whole utterances unless set_time_split() asks
+for the time split (opt-in: "off" is the default); TRMMixedStream delivers utterances in chunks, like TRMStream.
 """
 import ctypes as C
 
@@ -157,6 +157,11 @@ class TRMMixedBatch:
         """One launch over a resident mixed batch; asynchronous on `stream` (default: torch's current stream)."""
         import torch
         s = stream if stream is not None else torch.cuda.current_stream()
+        # the lengths as the host knows them, in grouped order: a time split's plan and launch order (trm_mixed_hint_frames)
+        nfh = st.get("nframes_host")
+        if nfh is not None and st["V"] > 0:
+            nfh = np.ascontiguousarray(nfh, dtype=np.uint32)
+            check(lib().trm_mixed_hint_frames(self._h, nfh.ctypes.data, st["V"]))
         check(lib().trm_mixed_synthesize_device(
             self._h, st["set_begin"].ctypes.data, st["frames"].data_ptr(), st["frame_offset"].data_ptr(), st["nframes"].data_ptr(),
             st["max_nframes"], st["out"].data_ptr(), st["out_offset"].data_ptr(), st["number_samples"].data_ptr(),
@@ -344,6 +349,19 @@ class TRMMixedBatch:
     @property
     def last_kernel(self):
         return {0: "auto", 1: "wide", 2: "quad", 3: "oct"}[lib().trm_mixed_last_kernel(self._h)]
+
+    def set_time_split(self, periods):
+        """'off' (default) | 'auto' | control periods per segment (include/trm_c_api.h: trm_mixed_set_time_split): every voice then
+        gets what a TRMBatch of its own set computes with set_kernel("wide") and the same set_time_split()."""
+        check(lib().trm_mixed_set_time_split(self._h, {"auto": -1, "off": 0}.get(periods, periods)))
+
+    @property
+    def last_time_split(self):
+        """(control periods per segment, [warm-up control periods of every set]) of the last launch; 0 = whole utterances."""
+        p = C.c_uint32()
+        w = (C.c_uint32 * max(1, self.nsets))()
+        check(lib().trm_mixed_last_time_split(self._h, C.byref(p), w, self.nsets))
+        return p.value, [int(x) for x in w[:self.nsets]]
 
 
 class TRMMixedStream:

@@ -443,7 +443,7 @@ int  trm_batch_noise_table(trm_batch *batch, float *host_out, size_t n);
  * MMSynthesisParameters.m:293) would need one launch per parameter set, each too small to fill the chip.  A trm_mixed
  * holds `nsets` parameter sets and runs all their voices in ONE launch: every workgroup holds voices of a single set and
  * reads that set's constants from a small device table, so a voice's samples are bit for bit those a trm_batch of its own
- * set computes in the same kernel form with the time split off.
+ * set computes in the same kernel form with the same time-split setting (off by default).
  *   - Voices are grouped by set: set s owns voices [set_begin[s], set_begin[s+1]) -- a host array of nsets+1 entries,
  *     set_begin[0] == 0, non-decreasing, set_begin[nsets] == nvoices (TRM_EINVAL otherwise, before anything is enqueued).
  *     Sets may be empty.  frame_offset, out_offset, nframes, number_samples and max_sample are indexed by voice as in the
@@ -452,9 +452,15 @@ int  trm_batch_noise_table(trm_batch *batch, float *host_out, size_t n);
  *     voices) runs with the time split off; the launch runs the one-voice-per-lane form when any non-empty set forbids the
  *     smaller ones (more than four outputs per tube sample; control period below 24 tube samples for TRM_KERNEL_QUAD, 16
  *     for TRM_KERNEL_OCT).  A form set by name (trm_mixed_set_kernel, TRM_TUBE_KERNEL) is demoted the same way.
- *   - Whole utterances always: time-split launches of mixed batches are not offered (TRM_TIME_SPLIT is not read).
- *   - The block map and per-voice tube-row offsets are uploaded when the launch's shape (set_begin, form, max_nframes)
- *     changes; a repeated call of one shape through the device entry is pure stream work.
+ *   - Whole utterances by default (TRM_TIME_SPLIT is not read).  The time split is opt-in, trm_mixed_set_time_split: a split
+ *     launch with segment length S gives every voice bit for bit what a trm_batch of its own set computes with
+ *     trm_batch_set_time_split(S) in the form TRM_KERNEL_WIDE -- the warm-up is the set's own, a function of its constants,
+ *     and the segment boundaries depend on S and that warm-up alone.  Should a frame of any voice fall below its set's
+ *     frication-bandwidth floor, the whole launch runs as whole utterances in the one-voice-per-lane form (chosen on the
+ *     device; the call stays asynchronous).
+ *   - The block map and per-voice tube-row offsets are uploaded when the launch's shape (set_begin, form, max_nframes; for a
+ *     split launch also its segment length and the hinted lengths) changes; a repeated call of one shape through the device
+ *     entry is pure stream work.
  *   - The whole server chain runs on the device, as for a trm_batch: event lists -> trm_mixed_generate_frames_device (one
  *     trm_intonation per voice) -> trm_mixed_synthesize_device -> trm_mixed_scale_to_int16_device / trm_mixed_sound_files_device
  *     (each voice with its own set's volume, balance, channels and container), three launches; trm_mixed_events_to_files_host
@@ -487,6 +493,19 @@ int    trm_mixed_synthesize_host_int16(trm_mixed *m, const size_t *set_begin, co
                                        int for_wav_data);
 int    trm_mixed_set_kernel(trm_mixed *m, int kernel);       /* TRM_KERNEL_AUTO (default) / _WIDE / _QUAD / _OCT */
 int    trm_mixed_last_kernel(const trm_mixed *m);
+/* Time split of a mixed batch (see trm_batch_set_time_split): TRM_TIME_SPLIT_OFF (the default), TRM_TIME_SPLIT_AUTO (one
+ * segment length for all sets, priced with trm_batch's launch-time model; whole utterances when that does not win by a tenth or
+ * a non-empty set never forgets) or a segment length in control periods (TRM_ERANGE, nothing enqueued, when a non-empty
+ * set never forgets: loss factor 0; whole utterances when no voice can reach past its set's first segment).  Split launches
+ * run the one-voice-per-lane form.  TRM_EINVAL below TRM_TIME_SPLIT_AUTO. */
+int    trm_mixed_set_time_split(trm_mixed *m, int periods);
+/* What the last launch was set up with: *periods (0 = whole utterances) and, where warm_periods is not NULL, every set's
+ * warm-up in control periods in warm_periods[0 .. nsets) (nsets at most the batch's; zeros after a whole-utterance launch). */
+int    trm_mixed_last_time_split(const trm_mixed *m, uint32_t *periods, uint32_t *warm_periods, size_t nsets);
+/* A host copy of every voice's length for the next trm_mixed_synthesize_device call, as trm_batch_hint_frames: the plan under
+ * AUTO and the launch order of a split use it, the samples never depend on it; consumed by that call whether it succeeds or
+ * fails.  The host-buffer entries pass it themselves. */
+int    trm_mixed_hint_frames(trm_mixed *m, const uint32_t *nframes, size_t nvoices);
 /* Control tracks with one trm_intonation per voice (device array d_settings[nvoices]: pitch mean, switches, drift seed, time
  * range); otherwise as trm_batch_generate_frames_device, and voice v's frames are those that entry writes with d_settings[v].
  * Frames do not depend on the tube parameters, so no set_begin.  nvoices == 0 is a no-op. */

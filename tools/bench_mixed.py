@@ -3,13 +3,17 @@
 Five parameter sets -- male 17.5 cm, female 15 cm and child 12.5 cm at 44.1 kHz, a 15 cm tube at 22.05 kHz (down-sampling: its
 tube rate is above the output rate) and a sine-wave / no-modulation voice -- share the voices of a workload round-robin.  Device
 time of (hipEvents via torch, after warm-up, median of the repeats):
-  (a) one mixed launch, AUTO (trm_mixed_synthesize_device);
+  (a) one mixed launch, AUTO form, whole utterances (trm_mixed_synthesize_device; the default);
   (b) one TRMBatch per set, back to back on one stream, time split off;
   (c) the same with every batch on AUTO (the time split allowed);
-  (d) one TRMBatch per set, time split off, on separate HIP streams (at most 4).
+  (d) one TRMBatch per set, time split off, on separate HIP streams (at most 4);
+  (e) one mixed launch with the time split on AUTO (trm_mixed_set_time_split).
+(a), (c) and (e) -- the comparison that matters -- are timed alternately, repeat by repeat, in one process; median, minimum and
+maximum of the repeats are written, with the plan (e) chose and the launches of its pre-pass.
 Workloads: 1024 ragged sentences (tests/cases.py config4_frames), 4096 x 1 s (config3_frames, 251 frames), 64 sentences.
 
-    python tools/bench_mixed.py [--repeats 15] [--warmup 3] [--out profiles/bench_mixed.txt]
+    python tools/bench_mixed.py [--repeats 15] [--warmup 3] [--out profiles/bench_mixed_split.txt]
+(profiles/bench_mixed.txt is the record of columns (a) to (d) from before the mixed time split existed.)
 """
 import argparse
 import json
@@ -57,11 +61,29 @@ def timed(torch, fn, warmup, repeats):
     return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
 
 
+def timed_alternately(torch, fns, warmup, repeats):
+    """{name: fn} timed in turn within every repeat: drift of the box over the run lands on all of them alike."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    return {k: (float(np.median(v)), float(np.min(v)), float(np.max(v))) for k, v in ms.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_mixed.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_mixed_split.txt"))
     a = ap.parse_args()
     import torch
     plist = params()
@@ -70,6 +92,9 @@ def main():
         sets = [i % len(plist) for i in range(len(voices))]
         mixed = g.TRMMixedBatch(plist, device=0)
         st = mixed.prepare_device(voices, sets)
+        split = g.TRMMixedBatch(plist, device=0)
+        split.set_time_split("auto")
+        st_e = split.prepare_device(voices, sets)
         per = []
         for s, p in enumerate(plist):
             b = g.TRMBatch(p, device=0)
@@ -79,6 +104,9 @@ def main():
 
         def run_a():
             mixed.synthesize_device(st)
+
+        def run_e():
+            split.synthesize_device(st_e)
 
         def run_b():
             for b, bst in per:
@@ -94,8 +122,6 @@ def main():
                 cur.wait_stream(s)
 
         res = {}
-        res["a"] = timed(torch, run_a, a.warmup, a.repeats)
-        form_a = mixed.last_kernel
         for b, _ in per:
             b.set_time_split("off")
         res["b"] = timed(torch, run_b, a.warmup, a.repeats)
@@ -103,20 +129,33 @@ def main():
         res["d"] = timed(torch, run_d, a.warmup, a.repeats)
         for b, _ in per:
             b.set_time_split("auto")
-        res["c"] = timed(torch, run_b, a.warmup, a.repeats)
-        forms_c = [b.last_kernel + ("/split" if b.last_time_split[0] else "") for b, _ in per]
-        rows.append({"workload": wname, "voices": len(voices), "form_a": form_a, "forms_b": forms_b, "forms_c": forms_c,
+        res.update(timed_alternately(torch, {"a": run_a, "c": run_b, "e": run_e}, a.warmup, a.repeats))
+        form_a = mixed.last_kernel
+        forms_c = [b.last_kernel + ("/split %d+%d" % b.last_time_split if b.last_time_split[0] else "") for b, _ in per]
+        periods, warm = split.last_time_split
+        nonempty = len(set(sets))
+        plan_e = {"form": split.last_kernel, "periods": periods, "warm": warm,
+                  # (trm_mixed.cc: per non-empty set trm_phase_period_kernel + trm_phase_segment_kernel; the launch order is built on the host)
+                  "prepass_launches": 2 * nonempty if periods else 0}
+        rows.append({"workload": wname, "voices": len(voices), "form_a": form_a, "forms_b": forms_b, "forms_c": forms_c, "plan_e": plan_e,
                      "ms": {k: {"median": v[0], "min": v[1], "max": v[2]} for k, v in sorted(res.items())}})
         print(wname, json.dumps(rows[-1]["ms"]), flush=True)
     lines = ["# tools/bench_mixed.py: device time (ms, median of %d after %d warm-up) on %s" % (a.repeats, a.warmup, torch.cuda.get_device_name(0)),
              "# sets (voices dealt round-robin): " + "; ".join(n for n, _ in SETS),
-             "# (a) one mixed launch, AUTO  (b) a batch per set, one stream, split off  (c) same, AUTO split  (d) a batch per set on 4 streams, split off",
-             "%-24s %6s %9s %9s %9s %9s  %-6s %s" % ("workload", "voices", "(a)", "(b)", "(c)", "(d)", "form a", "forms b / c")]
+             "# (a) one mixed launch, whole utterances  (b) a batch per set, one stream, split off  (c) same, AUTO split  (d) a batch per set on 4 streams, split off",
+             "# (e) one mixed launch, time split AUTO.  (a), (c), (e) timed alternately in one process: median [min .. max]",
+             "%-24s %6s %24s %9s %24s %9s %24s" % ("workload", "voices", "(a)", "(b)", "(c)", "(d)", "(e)")]
+    cell = lambda x: "%8.3f [%6.3f..%6.3f]" % (x["median"], x["min"], x["max"])
     for r in rows:
         m = r["ms"]
-        lines.append("%-24s %6d %9.3f %9.3f %9.3f %9.3f  %-6s %s / %s" % (r["workload"], r["voices"], m["a"]["median"], m["b"]["median"],
-                                                                        m["c"]["median"], m["d"]["median"], r["form_a"],
-                                                                        ",".join(r["forms_b"]), ",".join(r["forms_c"])))
+        lines.append("%-24s %6d %24s %9.3f %24s %9.3f %24s" % (r["workload"], r["voices"], cell(m["a"]), m["b"]["median"], cell(m["c"]),
+                                                             m["d"]["median"], cell(m["e"])))
+    for r in rows:
+        p = r["plan_e"]
+        lines.append("# %s: form a %s; forms b %s; forms c %s" % (r["workload"], r["form_a"], ",".join(r["forms_b"]), ",".join(r["forms_c"])))
+        lines.append("#   (e) plan: %s" % ("S = %d control periods, warm-up per set %s, form %s, %d pre-pass launches"
+                                          % (p["periods"], p["warm"], p["form"], p["prepass_launches"]) if p["periods"]
+                                          else "whole utterances (form %s): AUTO did not split" % p["form"]))
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

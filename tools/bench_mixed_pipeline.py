@@ -7,10 +7,13 @@ clipped to speech ranges), every voice with its own pitch mean and drift seed.  
 torch, after warm-up, median of the repeats) of:
   (a) the mixed chain: per-voice tracks + trm_mixed_synthesize_device + mixed files (three launches);
   (b) one TRMBatch chain per set (tracks + tube + files), back to back on one stream, time split off;
-  (c) the same with the split on AUTO.
+  (c) the same with the split on AUTO;
+  (e) the mixed chain with the mixed batch's time split on AUTO (trm_mixed_set_time_split).
+(a), (c) and (e) are timed alternately, repeat by repeat, in one process.
 Workloads: 1024 ragged sentences (0.6 to 6 s), 64 sentences, 4096 x 1 s.
 
-    python tools/bench_mixed_pipeline.py [--repeats 10] [--warmup 2] [--out profiles/bench_mixed_pipeline.txt]
+    python tools/bench_mixed_pipeline.py [--repeats 15] [--warmup 2] [--out profiles/bench_mixed_pipeline_split.txt]
+(profiles/bench_mixed_pipeline.txt is the record of (a) to (c) from before the mixed time split existed.)
 """
 import argparse
 import json
@@ -69,32 +72,34 @@ def settings_for(rng, nvoices):
     return out
 
 
-def timed(torch, stages, warmup, repeats):
-    """stages: list of (name, fn) run in order; returns {name: (median, min, max)} and the total"""
+def timed(torch, chains, warmup, repeats):
+    """chains: {chain: list of (stage, fn) run in order}, the chains taken in turn within every repeat (drift of the box over the
+    run lands on all of them alike); returns {chain: {stage: (median, min, max), "total": ...}}"""
     for _ in range(warmup):
-        for _, fn in stages:
-            fn()
+        for stages in chains.values():
+            for _, fn in stages:
+                fn()
     torch.cuda.synchronize()
-    ms = {name: [] for name, _ in stages}
-    ms["total"] = []
+    ms = {c: dict({name: [] for name, _ in stages}, total=[]) for c, stages in chains.items()}
     for _ in range(repeats):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(stages) + 1)]
-        ev[0].record()
-        for k, (_, fn) in enumerate(stages):
-            fn()
-            ev[k + 1].record()
-        ev[-1].synchronize()
-        for k, (name, _) in enumerate(stages):
-            ms[name].append(ev[k].elapsed_time(ev[k + 1]))
-        ms["total"].append(ev[0].elapsed_time(ev[-1]))
-    return {k: (float(np.median(v)), float(np.min(v)), float(np.max(v))) for k, v in ms.items()}
+        for c, stages in chains.items():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(stages) + 1)]
+            ev[0].record()
+            for k, (_, fn) in enumerate(stages):
+                fn()
+                ev[k + 1].record()
+            ev[-1].synchronize()
+            for k, (name, _) in enumerate(stages):
+                ms[c][name].append(ev[k].elapsed_time(ev[k + 1]))
+            ms[c]["total"].append(ev[0].elapsed_time(ev[-1]))
+    return {c: {k: (float(np.median(v)), float(np.min(v)), float(np.max(v))) for k, v in m.items()} for c, m in ms.items()}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_mixed_pipeline.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_mixed_pipeline_split.txt"))
     a = ap.parse_args()
     import torch
     plist = params()
@@ -105,6 +110,9 @@ def main():
         settings = settings_for(np.random.default_rng(V), V)
         mixed = g.TRMMixedBatch(plist, device=0)
         st = mixed.prepare_events_device(lists, sets, settings)
+        split = g.TRMMixedBatch(plist, device=0)
+        split.set_time_split("auto")
+        st_e = split.prepare_events_device(lists, sets, settings)
         per = []
         for s, p in enumerate(plist):
             idx = [i for i in range(V) if sets[i] == s]
@@ -124,6 +132,15 @@ def main():
         def a_files():
             files_a["x"] = mixed.sound_files_device(st)
 
+        def e_tracks():
+            split.generate_frames_device(st_e)
+
+        def e_tube():
+            split.synthesize_device(st_e)
+
+        def e_files():
+            files_a["e"] = split.sound_files_device(st_e)
+
         def b_tracks():
             for b, bst in per:
                 b.generate_frames_device(bst)
@@ -136,32 +153,42 @@ def main():
             for b, bst in per:
                 b.sound_files_device(bst)
 
-        res = {"a": timed(torch, [("tracks", a_tracks), ("tube", a_tube), ("files", a_files)], a.warmup, a.repeats)}
-        form_a = mixed.last_kernel
+        per_set = [("tracks", b_tracks), ("tube", b_tube), ("files", b_files)]
         for b, _ in per:
             b.set_time_split("off")
-        res["b"] = timed(torch, [("tracks", b_tracks), ("tube", b_tube), ("files", b_files)], a.warmup, a.repeats)
+        res = {"b": timed(torch, {"b": per_set}, a.warmup, a.repeats)["b"]}
         forms_b = [b.last_kernel for b, _ in per]
         for b, _ in per:
             b.set_time_split("auto")
-        res["c"] = timed(torch, [("tracks", b_tracks), ("tube", b_tube), ("files", b_files)], a.warmup, a.repeats)
-        forms_c = [b.last_kernel + ("/split" if b.last_time_split[0] else "") for b, _ in per]
+        res.update(timed(torch, {"a": [("tracks", a_tracks), ("tube", a_tube), ("files", a_files)], "c": per_set,
+                                 "e": [("tracks", e_tracks), ("tube", e_tube), ("files", e_files)]}, a.warmup, a.repeats))
+        form_a = mixed.last_kernel
+        forms_c = [b.last_kernel + ("/split %d+%d" % b.last_time_split if b.last_time_split[0] else "") for b, _ in per]
+        periods, warm = split.last_time_split
+        plan_e = {"form": split.last_kernel, "periods": periods, "warm": warm, "prepass_launches": 2 * len(set(sets)) if periods else 0}
         seconds = float(st["nframes_host"].sum()) * 0.004
-        rows.append({"workload": wname, "voices": V, "speech_s": seconds, "form_a": form_a, "forms_b": forms_b, "forms_c": forms_c,
+        rows.append({"workload": wname, "voices": V, "speech_s": seconds, "form_a": form_a, "forms_b": forms_b, "forms_c": forms_c, "plan_e": plan_e,
                      "ms": {k: {s: {"median": x[0], "min": x[1], "max": x[2]} for s, x in v.items()} for k, v in sorted(res.items())}})
         print(wname, json.dumps({k: {s: x["median"] for s, x in v.items()} for k, v in rows[-1]["ms"].items()}), flush=True)
     lines = ["# tools/bench_mixed_pipeline.py: device time (ms, median of %d after %d warm-up) on %s" % (a.repeats, a.warmup, torch.cuda.get_device_name(0)),
              "# sets (voices dealt round-robin): " + "; ".join(n for n, _ in SETS),
              "# (a) mixed chain: per-voice tracks + mixed tube + mixed files  (b) a TRMBatch chain per set, one stream, split off  (c) same, AUTO split",
-             "# columns: tracks / tube / files / total per chain; share = tracks and files of (a)'s total",
-             "%-22s %6s %8s  %-31s %-31s %-31s %11s  %-6s %s" % ("workload", "voices", "speech s", "(a) tracks/tube/files/total", "(b) tracks/tube/files/total",
-                                                                 "(c) tracks/tube/files/total", "share a", "form a", "forms b / c")]
+             "# (e) the mixed chain with the mixed batch's time split on AUTO.  (a), (c), (e) timed alternately in one process",
+             "# columns: tracks / tube / files / total per chain (medians), then every chain's total as median [min .. max]",
+             "%-22s %6s %8s  %-31s %-31s %-31s %-31s" % ("workload", "voices", "speech s", "(a) tracks/tube/files/total", "(b) tracks/tube/files/total",
+                                                         "(c) tracks/tube/files/total", "(e) tracks/tube/files/total")]
     for r in rows:
         m = r["ms"]
         cell = lambda k: "%6.2f/%7.2f/%6.2f/%7.2f" % tuple(m[k][s]["median"] for s in ("tracks", "tube", "files", "total"))
-        share = "%4.1f%%/%4.1f%%" % (100 * m["a"]["tracks"]["median"] / m["a"]["total"]["median"], 100 * m["a"]["files"]["median"] / m["a"]["total"]["median"])
-        lines.append("%-22s %6d %8.0f  %-31s %-31s %-31s %11s  %-6s %s / %s" % (r["workload"], r["voices"], r["speech_s"], cell("a"), cell("b"), cell("c"), share,
-                                                                            r["form_a"], ",".join(r["forms_b"]), ",".join(r["forms_c"])))
+        lines.append("%-22s %6d %8.0f  %-31s %-31s %-31s %-31s" % (r["workload"], r["voices"], r["speech_s"], cell("a"), cell("b"), cell("c"), cell("e")))
+    for r in rows:
+        m, p = r["ms"], r["plan_e"]
+        lines.append("# %s: totals %s" % (r["workload"], "  ".join("(%s) %.3f [%.3f..%.3f]" % (k, m[k]["total"]["median"], m[k]["total"]["min"], m[k]["total"]["max"])
+                                                                   for k in ("a", "b", "c", "e"))))
+        lines.append("#   form a %s; forms b %s; forms c %s" % (r["form_a"], ",".join(r["forms_b"]), ",".join(r["forms_c"])))
+        lines.append("#   (e) plan: %s" % ("S = %d control periods, warm-up per set %s, form %s, %d pre-pass launches"
+                                          % (p["periods"], p["warm"], p["form"], p["prepass_launches"]) if p["periods"]
+                                          else "whole utterances (form %s): AUTO did not split" % p["form"]))
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
