@@ -167,7 +167,8 @@ struct SetBatches {
 
 int check_set_begin(size_t nsets, const size_t *set_begin);
 
-// {set, first voice, end voice, 0} per workgroup of perWg voices (TubeArgs::mix_map)
+// {set, first voice, end voice, 0} per workgroup of perWg voices (TubeArgs::mix_map; a split launch's caller writes the set's
+// warm-up into the fourth component: the 64-voice map's entries, or the 16-voice map's for four-lane segments)
 void build_block_map(const size_t *set_begin, size_t nsets, size_t perWg, std::vector<uint4> &map);
 
 #pragma GCC visibility pop

@@ -84,7 +84,8 @@ struct TubeArgs {
     // A mixed time-split launch (seg_periods and mix_map both set; trm_mixseg_kernel): workgroup w runs segment seg_map[w].x of
     // map entry seg_map[w].y with the entry's own warm-up (its fourth component; seg_warm and seg_first are unused), so that
     // every voice's segments are those of its set's own batch; seg_phase rows are indexed by map entry * 64 + lane (pitch
-    // 64 * seg_wg_per_seg, seg_wg_per_seg = the map's entries).
+    // 64 * seg_wg_per_seg, seg_wg_per_seg = the map's entries).  The four-lane form's (trm_mixqseg_kernel) is the same over
+    // the 16-voice map: 16 in place of 64.
     const uint4 *mix_map = nullptr;       // {set, first voice, end voice, the set's warm-up in control periods (time split; else 0)}
     ConstTable set_const = nullptr;
     uint32_t mix_grid = 0;                // workgroups of the launch = entries of mix_map
@@ -134,6 +135,9 @@ hipError_t launch_mix_seg(const Const &c, const TubeArgs &a, uint32_t grid, hipS
 // max_sample[0 .. n) = 0 and, where gate is not null, *gate = 0, in one launch (trm_mix_seg.hip)
 hipError_t launch_split_clear(float *max_sample, uint32_t n, uint32_t *gate, hipStream_t stream);
 hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int sub);
+// ... and the four-lane form's (trm_mix_seg_q.hip: trm_mixqseg_kernel; mix_map is then the 16-voice map, seg_phase rows are
+// indexed by map entry * 16 + the voice within the entry)
+hipError_t launch_mix_seg_quad(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);
 hipError_t launch_mix_oct(const Const &c, const TubeArgs &a, hipStream_t stream);
 // small-batch form (trm_quad.hip): 16 voices per workgroup, four lanes per voice
 constexpr int kStreamFloats = 192;   // oscillator position, filter memories, 32 samples of FIR / converter history, 4 x 20 tube values

@@ -70,18 +70,21 @@ extern "C" {
 // (trm_kernels.h, TubeArgs::mix_map).  Whole utterances unless trm_mixed_set_time_split asks for the time split: then a workgroup
 // is one segment of one map entry, cut with the launch's segment length S and the SET's own warm-up W (split_warm_samples),
 // so that every voice gets bit for bit what a trm_batch of its set computes with trm_batch_set_time_split(S) in the
-// one-voice-per-lane form -- the boundaries depend on S and W alone, a voice's lane neighbours do not enter its arithmetic.
+// form of the plan (trm_mixed_last_kernel) -- the boundaries depend on S and W alone, a voice's lane neighbours do not enter
+// its arithmetic.  The form is the one-voice-per-lane one (64-voice map entries) unless the caller NAMED the four-lane form
+// and every set with voices admits its segment instance (mixed_split_quad_ok): then the entries are the 16-voice map's.
 struct trm_mixed {
     SetBatches sets;                         // (first: destroyed after the device buffers below)
     int kernel = TRM_KERNEL_AUTO;            // trm_mixed_set_kernel
     int lastKernel = TRM_KERNEL_AUTO;
     DevBuf<uint4> dMap;                      // {set, first voice, end voice, the set's warm-up (split launches; else 0)} per workgroup
+    DevBuf<uint4> dMap64;                    // a four-lane split launch: the 64-voice map of its whole-utterance fallback
     DevBuf<uint64_t> dTubeOff;               // down-sampling sets' voices: their tube-rate rows in dTube
     DevBuf<float> dTube;
     // the shape the three arrays above were built for (rebuilt when it changes: the device entry is pure stream work otherwise)
     std::vector<size_t> shapeBegin;
     int shapeForm = -1;
-    uint32_t shapeMaxFrames = 0, mapEntries = 0;
+    uint32_t shapeMaxFrames = 0, mapEntries = 0, map64Entries = 0;
     bool haveShape = false;
     // time split (trm_mixed_set_time_split): OFF unless asked for; TRM_TIME_SPLIT in the environment is not read here
     int splitSetting = TRM_TIME_SPLIT_OFF;
@@ -94,7 +97,7 @@ struct trm_mixed {
     DevBuf<uint2> dSegMap;                   // (segment, map entry) per workgroup of the split grid, the pairs with work first
     std::vector<uint2> hSegMap;
     DevBuf<double> dSegPhase, dPeriodAdv;    // the pre-pass's rows (per set: its voice range / its map entries)
-    std::vector<uint4> hMap;                 // host copies the uploads read from (they outlive the asynchronous copies)
+    std::vector<uint4> hMap, hMap64;         // host copies the uploads read from (they outlive the asynchronous copies)
     std::vector<uint64_t> hTubeOff;
     // completes after the last launch that read the arrays, on whichever stream: a shape change waits for it alone (not for
     // the device), then uploads in stream order
@@ -240,11 +243,16 @@ static int mixed_form(const trm_mixed *m, const size_t *set_begin)
 // trm_batch's figures (trm_host.h): a split launch lasts as long as its longest workgroup, S + W_s periods of CP_s samples,
 // at the rate its busy workgroups fill the chip; whole utterances as long as the longest voice of the slowest set.
 // `longest`: per entry of the 64-voice block map its longest voice in control periods (the hint's, else the launch's).
+// `map16`, `longest16`: the same over the 16-voice map where the four-lane segment form is admissible (mixed_split_quad_ok),
+// null otherwise.  `formOut`: the segments' form.  A split asked for by name then takes the four-lane form (the form was asked
+// for by name too: plan_time_split's rule); AUTO prices both forms for every candidate and takes the cheaper.
 static int mixed_plan_split(const trm_mixed *m, const size_t *set_begin, uint32_t max_nframes, int which, const std::vector<uint4> &map64,
-                            const std::vector<uint32_t> &longest, uint32_t &periodsOut, std::vector<uint32_t> &warm)
+                            const std::vector<uint32_t> &longest, const std::vector<uint4> *map16, const std::vector<uint32_t> *longest16,
+                            uint32_t &periodsOut, std::vector<uint32_t> &warm, int &formOut)
 {
     const size_t S = m->sets.size();
     periodsOut = 0;
+    formOut = TRM_KERNEL_WIDE;
     warm.assign(S, 0);
     const int setting = m->splitSetting;
     if (setting == TRM_TIME_SPLIT_OFF || max_nframes < 2) return TRM_OK;
@@ -272,14 +280,17 @@ static int mixed_plan_split(const trm_mixed *m, const size_t *set_begin, uint32_
             if (set_begin[s + 1] > set_begin[s]) x = std::max(x, (double)(sp + warm[s]) * (double)m->sets[s]->c.controlPeriod);
         return x;
     };
-    auto busy = [&](uint32_t sp) {
+    auto busy = [&](const std::vector<uint4> &map, const std::vector<uint32_t> &lng, uint32_t sp) {
         uint64_t n = 0;
-        for (size_t e = 0; e < map64.size(); e++) n += split_segments(longest[e], sp, warm[map64[e].x]);
+        for (size_t e = 0; e < map.size(); e++) n += split_segments(lng[e], sp, warm[map[e].x]);
         return n;
     };
     uint32_t periods = 0;
-    if (setting > 0) periods = (uint32_t)setting;
-    else {
+    int form = TRM_KERNEL_WIDE;
+    if (setting > 0) {
+        periods = (uint32_t)setting;
+        if (map16) form = TRM_KERNEL_QUAD;
+    } else {
         // AUTO: trm_batch's search (plan_time_split) with the largest warm-up in its constraints
         const double whole = (which == TRM_KERNEL_WIDE ? wide_cost(b0, map64.size()) : unsplit_cost(b0, set_begin[S], which)) * wholeSamples / 19750.0;
         double best = whole * 0.9;
@@ -287,16 +298,37 @@ static int mixed_plan_split(const trm_mixed *m, const size_t *set_begin, uint32_
         for (uint32_t nseg = 2; nseg <= 4096 && P > warmMax; nseg++) {
             const uint32_t sp = (P - warmMax + nseg - 1) / nseg;
             if (sp < minPeriods) break;
-            const double t = 0.03 + wide_cost(b0, busy(sp)) * seg_samples(sp) / 19750.0;
-            if (t < best) { best = t; periods = sp; }
+            const double t = 0.03 + wide_cost(b0, busy(map64, longest, sp)) * seg_samples(sp) / 19750.0;
+            if (t < best) { best = t; periods = sp; form = TRM_KERNEL_WIDE; }
+            // ... or in the four-lane form, one workgroup per CU: trm_batch's figure (plan_time_split), 3.1 ms per second of
+            // speech -- measured for uniform batches; nobody has measured it for a mixed launch
+            if (map16 && busy(*map16, *longest16, sp) <= (uint64_t)(b0->cus > 0 ? b0->cus : 256)) {
+                const double tq = 0.03 + 3.1 * seg_samples(sp) / 19750.0;
+                if (tq < best) { best = tq; periods = sp; form = TRM_KERNEL_QUAD; }
+            }
         }
     }
     if (periods == 0) return TRM_OK;
     // (no voice reaches past its set's first segment: one segment is the whole utterance)
     bool any = false;
     for (size_t s = 0; s < S; s++) any = any || (set_begin[s + 1] > set_begin[s] && split_segments(P, periods, warm[s]) >= 2);
-    if (any) periodsOut = periods;
+    if (any) {
+        periodsOut = periods;
+        formOut = form;
+    }
     return TRM_OK;
+}
+
+// Whether a split launch may run in the four-lane form: the caller named it (the environment alone does not: launches left on
+// AUTO keep the one-voice-per-lane segments and their bits), no set with voices demotes it (mixed_form: more than four outputs
+// per tube sample, a control period below 24 tube samples), and every set with voices up-samples -- plan_time_split's quadOk
+// for each of them.
+static bool mixed_split_quad_ok(const trm_mixed *m, const size_t *set_begin, int which)
+{
+    if (m->kernel != TRM_KERNEL_QUAD || which != TRM_KERNEL_QUAD) return false;
+    for (size_t s = 0; s < m->sets.size(); s++)
+        if (set_begin[s + 1] > set_begin[s] && !m->sets[s]->c.upsample) return false;
+    return true;
 }
 
 int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const float *d_frames, const uint64_t *d_frame_offset,
@@ -331,31 +363,50 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
     }
     if ((rc = ensure_noise(b0, (uint32_t)need, stream))) return rc;
     int which = mixed_form(m, set_begin);
-    // the time split: planned over the 64-voice block map (the split launch's, shared with its whole-utterance fallback)
+    // the time split: planned over the 64-voice block map (the one-voice-per-lane segments', and every split launch's
+    // whole-utterance fallback) and, where the four-lane segment form is admissible, the 16-voice map
     uint32_t split = 0;
+    int segForm = TRM_KERNEL_WIDE;
     std::vector<uint32_t> warm(S, 0), longest;
     const bool hinted = m->hintFrames.size() == nvoices;
     if (m->splitSetting != TRM_TIME_SPLIT_OFF && max_nframes >= 2) {
-        std::vector<uint4> map64;
+        // per entry of a block map its longest voice in control periods: the hint's, else the launch's
+        auto longest_of = [&](const std::vector<uint4> &map, std::vector<uint32_t> &lng) {
+            lng.assign(map.size(), max_nframes - 1);
+            for (size_t e = 0; hinted && e < map.size(); e++) {
+                uint32_t nfr = 0;
+                for (uint32_t v = map[e].y; v < map[e].z; v++) nfr = std::max(nfr, std::min(m->hintFrames[v], max_nframes));
+                lng[e] = nfr > 0 ? nfr - 1 : 0;
+            }
+        };
+        std::vector<uint4> map64, map16;
+        std::vector<uint32_t> longest16;
         build_block_map(set_begin, S, 64, map64);
-        longest.assign(map64.size(), max_nframes - 1);
-        for (size_t e = 0; hinted && e < map64.size(); e++) {
-            uint32_t nfr = 0;
-            for (uint32_t v = map64[e].y; v < map64[e].z; v++) nfr = std::max(nfr, std::min(m->hintFrames[v], max_nframes));
-            longest[e] = nfr > 0 ? nfr - 1 : 0;
+        longest_of(map64, longest);
+        const bool quadOk = mixed_split_quad_ok(m, set_begin, which);
+        if (quadOk) {
+            build_block_map(set_begin, S, 16, map16);
+            longest_of(map16, longest16);
         }
-        if ((rc = mixed_plan_split(m, set_begin, max_nframes, which, map64, longest, split, warm))) return rc;
+        if ((rc = mixed_plan_split(m, set_begin, max_nframes, which, map64, longest, quadOk ? &map16 : nullptr, quadOk ? &longest16 : nullptr,
+                                   split, warm, segForm)))
+            return rc;
+        if (split && segForm == TRM_KERNEL_QUAD) longest.swap(longest16);       // (the launch order below: per entry of the segments' map)
     }
     m->lastSplitPeriods = split;
     m->lastWarm.assign(S, 0);
+    // `form`: of the launch that is meant to run (a split launch: its segments); `which`: of the whole-utterance launch -- a
+    // split launch's fallback is the one-voice-per-lane kernel over the 64-voice map, whatever the segments' form (trm_batch's)
+    const int form = split ? segForm : which;
     if (split) {
         m->lastWarm = warm;
         which = TRM_KERNEL_WIDE;
     }
-    const uint32_t perWg = which == TRM_KERNEL_WIDE ? 64u : which == TRM_KERNEL_QUAD ? 16u : 8u;
+    const bool quadSplit = split && segForm == TRM_KERNEL_QUAD;
+    const uint32_t perWg = form == TRM_KERNEL_WIDE ? 64u : form == TRM_KERNEL_QUAD ? 16u : 8u;
     // the block map and the down-sampling sets' row offsets: rebuilt when the shape changes (a split launch's shape includes its
     // segment length and the lengths its launch order was built from)
-    if (!m->haveShape || m->shapeForm != which || m->shapeMaxFrames != max_nframes || !std::equal(set_begin, set_begin + S + 1, m->shapeBegin.begin()) ||
+    if (!m->haveShape || m->shapeForm != form || m->shapeMaxFrames != max_nframes || !std::equal(set_begin, set_begin + S + 1, m->shapeBegin.begin()) ||
         m->shapeSplit != split || (split && (hinted ? m->shapeHint != m->hintFrames : !m->shapeHint.empty()))) {
         // (an earlier launch, on whichever stream, may still read the arrays and their host copies' uploads)
         if (m->lastUseRecorded) HIP_TRY(hipEventSynchronize(m->lastUse));
@@ -397,11 +448,17 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
             }
         }
         if (map.size() > 0x7FFFFFFFull) return fail(TRM_ERANGE, "too many workgroups");
+        m->hMap64.clear();
+        if (quadSplit) {
+            build_block_map(set_begin, S, 64, m->hMap64);
+            if ((rc = m->dMap64.reserve(m->hMap64.size()))) return rc;
+            HIP_TRY(hipMemcpyAsync(m->dMap64.p, m->hMap64.data(), m->hMap64.size() * sizeof(uint4), hipMemcpyHostToDevice, stream));
+        }
         if ((rc = m->dMap.reserve(map.size())) || (rc = m->dTubeOff.reserve(nvoices)) || (rc = m->dTube.reserve(rows + 1))) return rc;
         HIP_TRY(hipMemcpyAsync(m->dMap.p, map.data(), map.size() * sizeof(uint4), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemcpyAsync(m->dTubeOff.p, toff.data(), nvoices * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
         if (split) {
-            if ((rc = m->dSegMap.reserve(m->hSegMap.size())) || (rc = m->dSegPhase.reserve((size_t)m->segRows * map.size() * 64)) ||
+            if ((rc = m->dSegMap.reserve(m->hSegMap.size())) || (rc = m->dSegPhase.reserve((size_t)m->segRows * map.size() * perWg)) ||
                 (rc = m->dPeriodAdv.reserve(nvoices * (size_t)max_nframes)))
                 return rc;
             HIP_TRY(hipMemcpyAsync(m->dSegMap.p, m->hSegMap.data(), m->hSegMap.size() * sizeof(uint2), hipMemcpyHostToDevice, stream));
@@ -411,9 +468,10 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
         if (split && hinted) m->shapeHint = m->hintFrames;
         else m->shapeHint.clear();
         m->shapeBegin.assign(set_begin, set_begin + S + 1);
-        m->shapeForm = which;
+        m->shapeForm = form;
         m->shapeMaxFrames = max_nframes;
         m->mapEntries = (uint32_t)map.size();
+        m->map64Entries = (uint32_t)m->hMap64.size();
         m->haveShape = true;
     }
     trm::TubeArgs a = tube_args(b0, d_frames, d_frame_offset, d_nframes, d_out, d_out_offset, d_number_samples, d_max_sample, nvoices, max_nframes);
@@ -422,12 +480,12 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
     a.mix_map = m->dMap.p;
     a.set_const = (trm::ConstTable)m->sets.dConst;
     a.mix_grid = m->mapEntries;
-    m->lastKernel = which;
+    m->lastKernel = form;
     if (split) {
         // The pre-pass, set by set over its voice range (the oscillator's advance per period and the guard's floor are the
         // set's): its rows of seg_phase start at the set's first map entry, every set ORs into one gate word.  Then both
         // launches, of which the device runs one (TubeArgs::gate): the segments, or -- a frame of any voice below its set's
-        // floor -- whole utterances over the same map.
+        // floor -- whole utterances, over the same map or (four-lane segments) over the 64-voice one.
         uint32_t *gate = b0->dGate;
         HIP_TRY(trm::launch_split_clear(d_max_sample, (uint32_t)nvoices, gate, stream));
         size_t entry = 0;
@@ -437,20 +495,25 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
             const trm_batch *b = m->sets[s];
             trm::PhaseArgs ph;
             ph.frames = d_frames; ph.frame_offset = d_frame_offset + lo; ph.nframes = d_nframes + lo;
-            ph.period_adv = m->dPeriodAdv.p + lo * (size_t)max_nframes; ph.seg_phase = m->dSegPhase.p + entry * 64; ph.gate = gate;
+            ph.period_adv = m->dPeriodAdv.p + lo * (size_t)max_nframes; ph.seg_phase = m->dSegPhase.p + entry * perWg; ph.gate = gate;
             ph.bw_floor = split_bw_floor(b, warm[s]);
             ph.nvoices = (uint32_t)n; ph.max_nframes = max_nframes; ph.nseg = split_segments(max_nframes - 1, split, warm[s]);
             ph.seg_periods = split; ph.seg_warm = warm[s]; ph.seg_wg_per_seg = m->mapEntries; ph.seg_first = split + warm[s];
-            ph.voices_per_wg = 64;
+            ph.voices_per_wg = perWg;
             HIP_TRY(trm::launch_phase(b->c, ph, stream));
-            entry += (n + 63) / 64;
+            entry += (n + perWg - 1) / perWg;
         }
         trm::TubeArgs sa = a;
         sa.seg_periods = split; sa.seg_wg_per_seg = m->mapEntries; sa.seg_grid = m->segGrid;
         sa.seg_phase = m->dSegPhase.p;
         sa.seg_map = m->dSegMap.p;
         sa.gate = gate; sa.gate_want = 0;
-        HIP_TRY(trm::launch_tube(cb->c, sa, stream));
+        if (quadSplit) {
+            HIP_TRY(trm::launch_tube_quad(cb->c, sa, stream, b0->cus));
+            a.mix_map = m->dMap64.p;
+            a.mix_grid = m->map64Entries;
+        } else
+            HIP_TRY(trm::launch_tube(cb->c, sa, stream));
         a.gate = gate; a.gate_want = 1;
     }
     if (which == TRM_KERNEL_OCT)

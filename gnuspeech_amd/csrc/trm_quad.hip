@@ -97,12 +97,15 @@ struct QuadLds {
 // voices: a single utterance becomes sixteen lanes' worth of segments on one CU.
 // kMix: a launch whose workgroups may belong to different parameter sets (trm_kernels.h, TubeArgs::mix_map): the
 // workgroup's constants come from set_const, its voices are the map entry's range.  With kStream: a chunk of a mixed stream,
-// whose time bases are the set's own (trm_kernels.h); the state records stay voice-major.
+// whose time bases are the set's own (trm_kernels.h); the state records stay voice-major.  With kSeg (trm_mix_seg_q.hip:
+// trm_mixqseg_kernel): a time-split launch of a mixed batch, one segment of one entry of the 16-voice block map per workgroup
+// (seg_map lists the pairs), with the set's constants and the set's own warm-up (the entry's fourth component): segment
+// boundaries and time bases are those of a kSeg launch of that set alone.
 template <bool kStream, int kSub, bool kSeg = false, bool kMix = false>
 __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Const Carg, const TubeArgs A)
 {
     static_assert(!kSeg || kStream, "the segment instance is built on the streaming instance");
-    static_assert(!kMix || !kSeg, "mixed-parameter launches run whole utterances or stream chunks");
+    constexpr bool kMixSeg = kMix && kSeg;
     if (kSeg && A.gate && ((*A.gate != 0u) ? 1u : 0u) != A.gate_want) return;      // (two launches, the device runs one: TubeArgs::gate)
     constexpr int kStepN = kQB * kSub;       // tube samples per step
     typedef QuadLds<kSub> L;
@@ -142,7 +145,11 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     const int vq = (lane >> 4) * 4 + (lane & 3);        // voice within the workgroup
     // time-split: workgroup -> (segment, block of 16 voices)
     uint32_t seg = 0, vblock = blockIdx.x;
-    if (kSeg) {
+    if constexpr (kMixSeg) {                 // (a mixed split always has the list: vblock = the map entry)
+        const uint2 m = A.seg_map[blockIdx.x];
+        seg = m.x;
+        vblock = m.y;
+    } else if (kSeg) {
         if (A.seg_map) {                     // (the pairs with work first: trm_kernels.hip, trm_seg_map_kernel)
             const uint2 m = A.seg_map[blockIdx.x];
             seg = m.x;
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         }
     }
     // mixed launch: the workgroup's parameter set (C read in place: a reference into the table) and voice range
-    const uint4 mix = kMix ? A.mix_map[blockIdx.x] : make_uint4(0u, 0u, 0u, 0u);
+    const uint4 mix = kMix ? A.mix_map[kMixSeg ? vblock : blockIdx.x] : make_uint4(0u, 0u, 0u, 0u);
     const Const &C = kMix ? *(const Const *)(A.set_const + mix.x) : Carg;
     const uint32_t vFirst = kMix ? mix.y : vblock * kQV, vEnd = kMix ? mix.z : A.nvoices;
     const uint32_t vRaw = vFirst + vq;
@@ -162,7 +169,12 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     const uint32_t CP = (uint32_t)C.controlPeriod;
     const uint32_t inc = C.timeRegisterIncrement;
     auto outputs_before = [&](uint64_t end) { return end == 0 ? 0u : (uint32_t)(((end << 16) - 1) / inc + 1); };
-    auto seg_begin = [&](uint32_t sgm) { return sgm == 0 ? 0u : A.seg_first + (sgm - 1) * A.seg_periods; };
+    // (a mixed launch: the warm-up is the set's own, mix.w; the segment length is the launch's -- the boundaries of
+    // trm_mixseg_kernel.  `if constexpr`: the other instances' lambda must not capture mix)
+    auto seg_begin = [&](uint32_t sgm) {
+        if constexpr (kMixSeg) return sgm == 0 ? 0u : mix.w + sgm * A.seg_periods;
+        else return sgm == 0 ? 0u : A.seg_first + (sgm - 1) * A.seg_periods;
+    };
 
     const uint32_t nfrAll = min(A.nframes[v], A.max_nframes);
     // the frames this launch runs for this lane: the utterance's (chunk's), or those of the workgroup's segment with its warm-up
@@ -171,7 +183,9 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     if (kSeg) {
         const uint32_t nper = nfrAll > 0 ? nfrAll - 1 : 0;
         const uint32_t pLo = seg_begin(seg), pEnd = seg_begin(seg + 1);
-        segFrame0 = pLo > A.seg_warm ? pLo - A.seg_warm : 0u;
+        uint32_t segWarm = A.seg_warm;
+        if constexpr (kMixSeg) segWarm = mix.w;
+        segFrame0 = pLo > segWarm ? pLo - segWarm : 0u;
         if (seg > 0 && pLo >= nper) nfr = 0;
         else if (nfrAll > 0) {
             const uint32_t pHi = pEnd < nper ? pEnd : nper;
@@ -190,7 +204,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     // control period then runs on the frame that ENDS it, held (trm_stream_set_mode)
     const bool sHold = streaming && !kSeg && (A.stream_flags & 4u);
     // (a mixed stream: stream_n_base / stream_k_end count control periods, the set's tube samples and outputs follow from them)
-    constexpr bool kMixStream = kMix && kStream;
+    constexpr bool kMixStream = kMix && kStream && !kSeg;
     const uint32_t nBase = kSeg ? segFrame0 * CP : kMixStream ? A.stream_n_base * CP : streaming ? A.stream_n_base : 0u;
     const uint32_t kBase = kSeg ? outputs_before((uint64_t)seg_begin(seg) * CP) : kMixStream ? outputs_before((uint64_t)nBase) : streaming ? A.stream_k_base : 0u;
     const uint32_t kEnd = !kMixStream ? A.stream_k_end
@@ -327,7 +341,15 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         OscSlotTrack T;
         double P = 0.0;                                 // oscillator position at the start of the block
         if (streaming && !sFirst) P = *reinterpret_cast<const double *>(st);
-        if (kSeg) {
+        if constexpr (kMixSeg) {
+            // (rows of 16 entries per map entry -- a set's voices are not block-aligned --, written for the entry's voices
+            // only: a lane past its end reads nothing, its samples go nowhere)
+            if (laneValid) {
+                const double *ph = A.seg_phase + (size_t)vblock * kQV + vq;
+                const size_t pitch = (size_t)A.seg_wg_per_seg * kQV;
+                for (uint32_t q = 1; q <= seg; q++) P = osc_wrap(P + ph[q * pitch]);
+            }
+        } else if (kSeg) {
             // the oscillator's position at the warm-up start: the advances between the warm-up starts of the segments so far
             // (trm_phase_segment_kernel), summed and wrapped in order -- exact
             const double *ph = A.seg_phase + vRaw;
@@ -893,6 +915,7 @@ hipError_t launch_tube_quad(const Const &c, const TubeArgs &a, hipStream_t strea
 {
     if (a.nvoices == 0) return hipSuccess;
     uint32_t grid = (a.nvoices + kQV - 1) / kQV;
+    if (a.seg_periods && a.mix_map) return a.seg_grid ? launch_mix_seg_quad(c, a, a.seg_grid, stream) : hipSuccess;     // ... of one map entry
     if (a.seg_periods) return launch_instance<true, 2, true>(c, a, stream, a.seg_grid);      // time split: 16 voices x one segment per workgroup
     if (a.stream_state && a.mix_map) return a.mix_grid ? launch_mix_quad(c, a, stream, 2) : hipSuccess;     // (streams: kSub = 2 only)
     if (a.stream_state) return launch_instance<true, 2>(c, a, stream, grid);

@@ -2,7 +2,8 @@
 trm_mixed_*, trm_mixed_stream_*).
 
 Every workgroup of the launch holds voices of one set and reads that set's constants from a device table, so a voice's
-samples are bit for bit what a TRMBatch of its own set computes in the same kernel form with the same time-split setting.  Callers
+samples are bit for bit what a TRMBatch of its own set computes in the same kernel form (last_kernel) with the same time-split
+setting.  Callers
 hand voices in any order with a set index per voice; the library wants them grouped by set, which group_voices() does
 (a stable sort), and the results come back in the caller's order.  Batches run whole utterances unless set_time_split() asks
 for the time split (opt-in: "off" is the default); TRMMixedStream delivers utterances in chunks, like TRMStream.
@@ -343,7 +344,11 @@ class TRMMixedBatch:
         return out
 
     def set_kernel(self, kernel):
-        """'auto' | 'wide' | 'quad' | 'oct' (include/trm_c_api.h: trm_mixed_set_kernel; demoted like a TRMBatch's)."""
+        """'auto' | 'wide' | 'quad' | 'oct' (include/trm_c_api.h: trm_mixed_set_kernel; demoted like a TRMBatch's).  With
+        set_time_split() on, 'quad' also asks for the segments in the four-lane form (16 voices of a set per workgroup: made for
+        launches of a few sentences per set); they run that way when every set with voices admits it -- up-sampling, at most four
+        outputs per tube sample, a control period of at least 24 tube samples -- and in the one-voice-per-lane form otherwise.
+        last_kernel tells which."""
         check(lib().trm_mixed_set_kernel(self._h, _KERNELS[kernel]))
 
     @property
@@ -352,7 +357,10 @@ class TRMMixedBatch:
 
     def set_time_split(self, periods):
         """'off' (default) | 'auto' | control periods per segment (include/trm_c_api.h: trm_mixed_set_time_split): every voice then
-        gets what a TRMBatch of its own set computes with set_kernel("wide") and the same set_time_split()."""
+        gets what a TRMBatch of its own set computes with set_kernel(last_kernel) and set_time_split(last_time_split[0]).  The
+        segments run in the "wide" form unless set_kernel("quad") named the four-lane one and every set with voices admits it;
+        under 'auto' with "quad" named both forms are priced and the cheaper one taken.  A frame below a set's frication-bandwidth
+        floor runs the whole launch as whole utterances in the "wide" form, whatever the segments' form."""
         check(lib().trm_mixed_set_time_split(self._h, {"auto": -1, "off": 0}.get(periods, periods)))
 
     @property

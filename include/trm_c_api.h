@@ -454,10 +454,19 @@ int  trm_batch_noise_table(trm_batch *batch, float *host_out, size_t n);
  *     for TRM_KERNEL_OCT).  A form set by name (trm_mixed_set_kernel, TRM_TUBE_KERNEL) is demoted the same way.
  *   - Whole utterances by default (TRM_TIME_SPLIT is not read).  The time split is opt-in, trm_mixed_set_time_split: a split
  *     launch with segment length S gives every voice bit for bit what a trm_batch of its own set computes with
- *     trm_batch_set_time_split(S) in the form TRM_KERNEL_WIDE -- the warm-up is the set's own, a function of its constants,
- *     and the segment boundaries depend on S and that warm-up alone.  Should a frame of any voice fall below its set's
- *     frication-bandwidth floor, the whole launch runs as whole utterances in the one-voice-per-lane form (chosen on the
- *     device; the call stays asynchronous).
+ *     trm_batch_set_time_split(S) in the form trm_mixed_last_kernel reports -- the warm-up is the set's own, a function of
+ *     its constants, and the segment boundaries depend on S and that warm-up alone.  That form is TRM_KERNEL_WIDE (a
+ *     workgroup is one segment of 64 voices of a set) unless the caller NAMED the four-lane form,
+ *     trm_mixed_set_kernel(TRM_KERNEL_QUAD): the segments then run with four lanes per voice (a workgroup is one segment of
+ *     16 voices of a set; made for launches of a few sentences per set, which leave the 64-voice workgroups mostly empty)
+ *     when every non-empty set admits that -- and in the one-voice-per-lane form, as if no form had been named, when a
+ *     non-empty set down-samples (tube rate above the output rate), makes more than four outputs per tube sample or has a
+ *     control period below 24 tube samples.  TRM_TUBE_KERNEL alone never selects the four-lane segments, and neither does
+ *     TRM_KERNEL_OCT: launches left on TRM_KERNEL_AUTO keep their bits.  Should a frame of any voice fall below its set's
+ *     frication-bandwidth floor, the whole launch runs as whole utterances in the one-voice-per-lane form, whatever the
+ *     segments' form (what a trm_batch's split falls back to: every voice then gets the bits of its set's trm_batch in
+ *     TRM_KERNEL_WIDE with the split off); that is chosen on the device, the call stays asynchronous, and
+ *     trm_mixed_last_kernel / trm_mixed_last_time_split report the plan.
  *   - The block map and per-voice tube-row offsets are uploaded when the launch's shape (set_begin, form, max_nframes; for a
  *     split launch also its segment length and the hinted lengths) changes; a repeated call of one shape through the device
  *     entry is pure stream work.
@@ -491,13 +500,23 @@ int    trm_mixed_synthesize_host_int16(trm_mixed *m, const size_t *set_begin, co
                                        const uint64_t *frame_offset, const uint32_t *nframes, int16_t *out16,
                                        const uint64_t *out_offset, uint32_t *number_samples, float *max_sample,
                                        int for_wav_data);
-int    trm_mixed_set_kernel(trm_mixed *m, int kernel);       /* TRM_KERNEL_AUTO (default) / _WIDE / _QUAD / _OCT */
+/* TRM_KERNEL_AUTO (default) / _WIDE / _QUAD / _OCT: the form of whole-utterance launches, demoted as described above.  With the
+ * time split on, TRM_KERNEL_QUAD also asks for four-lane segments (above); every other value leaves split launches in the
+ * one-voice-per-lane form. */
+int    trm_mixed_set_kernel(trm_mixed *m, int kernel);
+/* The form the last launch was set up in: of its segments when it was split (TRM_KERNEL_WIDE or TRM_KERNEL_QUAD), else of its
+ * whole utterances. */
 int    trm_mixed_last_kernel(const trm_mixed *m);
 /* Time split of a mixed batch (see trm_batch_set_time_split): TRM_TIME_SPLIT_OFF (the default), TRM_TIME_SPLIT_AUTO (one
  * segment length for all sets, priced with trm_batch's launch-time model; whole utterances when that does not win by a tenth or
  * a non-empty set never forgets) or a segment length in control periods (TRM_ERANGE, nothing enqueued, when a non-empty
  * set never forgets: loss factor 0; whole utterances when no voice can reach past its set's first segment).  Split launches
- * run the one-voice-per-lane form.  TRM_EINVAL below TRM_TIME_SPLIT_AUTO. */
+ * run the one-voice-per-lane form, or -- with TRM_KERNEL_QUAD named and admitted by every non-empty set -- the four-lane form:
+ * a segment length given here is then taken as it is (no size rule, as for a trm_batch with both named), and AUTO prices both
+ * forms for every candidate length (the four-lane one with trm_batch's figure, admissible while its busy workgroups are at
+ * most the compute units) and splits in the cheaper one when that beats whole four-lane utterances by a tenth.  Every voice
+ * gets what a trm_batch of its set computes in the form trm_mixed_last_kernel with trm_batch_set_time_split(S), S as
+ * trm_mixed_last_time_split reports it.  TRM_EINVAL below TRM_TIME_SPLIT_AUTO. */
 int    trm_mixed_set_time_split(trm_mixed *m, int periods);
 /* What the last launch was set up with: *periods (0 = whole utterances) and, where warm_periods is not NULL, every set's
  * warm-up in control periods in warm_periods[0 .. nsets) (nsets at most the batch's; zeros after a whole-utterance launch). */
