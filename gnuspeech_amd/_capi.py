@@ -9,7 +9,7 @@ LIB_PATH = os.environ.get("TRM_LIB") or os.path.join(_HERE, "libtrm_hip.so")
 
 TRM_OK = 0
 TRM_KERNEL_AUTO, TRM_KERNEL_WIDE, TRM_KERNEL_QUAD = 0, 1, 2
-TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_FINISH = 0, 1, 2      # what a group of a grouped stream does in a step
+TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_FINISH, TRM_GROUP_RUN = 0, 1, 2, 3      # what a group of a grouped stream does in a step
 (TRM_EINVAL, TRM_EINVAL_LENGTH, TRM_EFIR, TRM_ENOMEM, TRM_EHIP, TRM_ENODEVICE, TRM_EIO, TRM_EPARSE,
  TRM_ESILENT, TRM_ERANGE) = range(1, 11)
 
@@ -78,6 +78,7 @@ EXPORTS = [
     "trm_mixed_stream_push_device", "trm_mixed_stream_finish_device",
     "trm_mixed_stream_create_groups", "trm_mixed_stream_groups", "trm_mixed_stream_group_open", "trm_mixed_stream_group_samples_for",
     "trm_mixed_stream_step", "trm_mixed_stream_step_device",
+    "trm_mixed_stream_group_set_events", "trm_mixed_stream_group_frames_left", "trm_mixed_stream_last_frames",
 ]
 
 _lib = None
@@ -218,6 +219,10 @@ def lib():
     L.trm_mixed_stream_group_samples_for.restype = C.c_size_t
     L.trm_mixed_stream_step.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
     L.trm_mixed_stream_step_device.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
+    L.trm_mixed_stream_group_set_events.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.trm_mixed_stream_group_frames_left.argtypes = [vp, C.c_size_t]
+    L.trm_mixed_stream_group_frames_left.restype = C.c_size_t
+    L.trm_mixed_stream_last_frames.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     for name in EXPORTS:
         getattr(L, name)
     _lib = L

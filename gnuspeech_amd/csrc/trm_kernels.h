@@ -250,6 +250,35 @@ struct MixedTrackArgs {
 };
 hipError_t launch_tracks_mixed(const MixedTrackArgs &a, hipStream_t stream);
 
+// The resumable instance for grouped streams whose groups run from event lists (trm_tracks_run.hip: trm_tracks_run_kernel).  One
+// wave per entry of `run`, the voices that take frames from the generator in this step: {voice, frames of the step | bit 31:
+// the utterance opens}.  The wave writes the voice's rows of the step's tube launch -- frames[voice][0] = the lead row (the
+// frame the period before ended on; the first generated frame where the utterance opens), rows 1 .. the generated frames --
+// and the voice's last frame, as trm_grp_prep_kernel does for the groups that push.  The voice's record lives in lanes / head.
+constexpr uint32_t kTrackRunOpening = 0x80000000u;
+struct TrackRunHead {
+    uint32_t event, emitted;          // the event the time loop stands at; frames emitted so far
+    uint32_t time_lo, time_hi;        // the loop's current time (ms)
+    float seed, prev;                 // MMDriftGenerator's seed and its filter's last value
+    uint32_t pad[2];
+};
+struct TrackRunArgs {
+    const __attribute__((address_space(4))) uint32_t *event_times;      // the stream's lists: voice v's events at event_offset[v]
+    const double *event_values;
+    const __attribute__((address_space(4))) uint64_t *event_offset;     // [nvoices]
+    const __attribute__((address_space(4))) uint32_t *nevents;          // [nvoices]
+    IntonationTable settings_v;       // [nvoices]
+    const __attribute__((address_space(4))) uint32_t *run;              // [nrun][2]
+    double2 *lanes;                   // [nvoices][64]: {current value, delta} per lane
+    TrackRunHead *head;               // [nvoices]
+    float *frames;                    // [nvoices][rows][16]
+    float *last;                      // [nvoices][16]
+    uint32_t nvoices, rows, nrun;
+};
+// The host units do not name the launcher (they are also linked without the kernels: tests/_emul): trm_tracks_run.hip installs
+// it here when the library is loaded.  Null: the library holds no such kernel, and a step that needs it fails.
+extern hipError_t (*tracks_run_launcher)(const TrackRunArgs &a, hipStream_t stream);
+
 // Output of a mixed-parameter batch (trm_mixed_out.hip): int16 PCM or sound-file images, one workgroup per voice, each voice with
 // its own set's scaling and container.  The per-set table is built once at trm_mixed_create.
 struct MixOutSet {

@@ -13,7 +13,10 @@
 // A GROUPED trm_mixed_stream (trm_mixed_stream_create_groups) partitions the voices into groups that begin and end their
 // utterances independently: progress, the open flag and the first-chunk flag are kept per group, the block map is built over the
 // groups (an entry never straddles two), and a step (stream_step_impl) launches the entries of the groups that synthesize, each
-// with its group's clock (TubeArgs::grp_*).  What a chunk and a step share is stated once: the converter range of a run of
+// with its group's clock (TubeArgs::grp_*).  A group may also be given its event lists once (trm_mixed_stream_group_set_events)
+// and then RUN: the step plans it as a push of the frames it has left, at most the step's, which the resumable track kernel
+// (trm_tracks_run.hip) generates in place in front of the tube launch, and as the flush once they have run out.
+// What a chunk and a step share is stated once: the converter range of a run of
 // control periods (unit_range), the length limit (unit_too_long), the index arrays of a shape (stream_shape), the down-sampling
 // launches around the tube launch (down_history_in, down_convert) and the ordering of calls across HIP streams (stream_ordered).
 #include "trm_host.h"
@@ -68,6 +71,28 @@ struct trm_stream_engine {
     // host is that many steps ahead of the device -- another one is allocated.
     struct StepCopy { uint32_t *p = nullptr; hipEvent_t uploaded = nullptr; };
     std::vector<StepCopy> stepCopies;
+    // ---- groups that run from event lists (trm_mixed_stream_group_set_events, TRM_GROUP_RUN)
+    // A group's lists as they were given (times / values voice after voice, voice k's first event at off[k]) and where they lie
+    // in the device pool; the host copy is what the pool is rebuilt from when it has to grow.
+    struct GroupEvents {
+        int state = kEvNone;
+        std::vector<uint32_t> times, n;
+        std::vector<double> values;
+        std::vector<uint64_t> off;
+        std::vector<trm_intonation> settings;
+        uint64_t at = 0, cap = 0;            // the group's stretch of the pool (events)
+        uint64_t frames = 0, emitted = 0;    // F of the issue's text, and the frames generated so far
+    };
+    enum { kEvNone = 0, kEvPending = 1, kEvConsumed = 2 };      // no lists yet / lists that run or wait to / lists run to their end or dropped
+    std::vector<GroupEvents> gev;            // per group (grouped streams)
+    std::vector<uint32_t> glastq;            // frame rows every voice of the group consumed in the last step
+    DevBuf<uint32_t> dEvTimes, dEvN;         // the pool: [events]; per voice
+    DevBuf<double> dEvValues;                // [events][36]
+    DevBuf<uint64_t> dEvOff;                 // per voice: its first event in the pool
+    DevBuf<trm_intonation> dEvSettings;      // per voice
+    DevBuf<double2> dTrkLanes;               // the generator's record: [nvoices][64] {value, delta} ...
+    DevBuf<trm::TrackRunHead> dTrkHead;      // ... and [nvoices] heads (trm_kernels.h: TrackRunArgs)
+    uint64_t evUsed = 0;                     // events of the pool handed out
     ~trm_stream_engine()
     {
         for (StepCopy &c : stepCopies) {
@@ -76,6 +101,10 @@ struct trm_stream_engine {
         }
     }
 };
+
+namespace trm {
+hipError_t (*tracks_run_launcher)(const TrackRunArgs &a, hipStream_t stream) = nullptr;      // (trm_kernels.h; set by trm_tracks_run.hip)
+}
 
 struct trm_stream : trm_stream_engine {};
 struct trm_mixed_stream : trm_stream_engine {};
@@ -88,6 +117,9 @@ static void stream_destroy(Stream *s)
     if (s->chunkDone) (void)hipEventDestroy(s->chunkDone);
     delete s;
 }
+
+// words of a step's tables with `nrun` voices that run from event lists: [clock | active entries | group actions | those voices]
+static size_t step_words(const trm_stream_engine *s, size_t nrun) { return (size_t)s->mapEntries * 5 + (s->gbegin.size() - 1) + 2 * nrun; }
 
 // what create does once the batches exist (on failure the caller destroys the stream)
 static int stream_init(trm_stream_engine *s, const size_t *set_begin)
@@ -137,6 +169,8 @@ static int stream_init(trm_stream_engine *s, const size_t *set_begin)
         s->gperiods.assign(G, 0);
         s->gopen.assign(G, 0);
         s->gfirst.assign(G, 1);
+        s->gev.assign(G, trm_stream_engine::GroupEvents());
+        s->glastq.assign(G, 0);
     } else if (s->mixed) build_block_map(set_begin, S, s->wide ? 64 : 16, map);
     s->mapEntries = (uint32_t)map.size();
     // history rows of the down-sampling sets
@@ -166,7 +200,7 @@ static int stream_init(trm_stream_engine *s, const size_t *set_begin)
         std::vector<uint32_t> vg(V);
         for (size_t g = 0; g < G; g++)
             for (size_t v = s->gbegin[g]; v < s->gbegin[g + 1]; v++) vg[v] = (uint32_t)g;
-        if ((rc = s->dVoiceGroup.reserve(V)) || (rc = s->dStep.reserve((size_t)s->mapEntries * 5 + G))) return rc;
+        if ((rc = s->dVoiceGroup.reserve(V)) || (rc = s->dStep.reserve(step_words(s, V)))) return rc;
         hipError_t e = hipMemcpy(s->dVoiceGroup.p, vg.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail(TRM_EHIP, "group table: %s", hipGetErrorString(e));
     }
@@ -442,24 +476,58 @@ struct GroupPlan {
     bool push = false, flush = false;        // the group pushes frames / flushes its open utterance
     bool runs = false;                       // ... and synthesizes: its map entries are launched
     bool lead = false;                       // a pushing group: its rows begin with a lead row
+    bool gen = false;                        // a pushing group whose frames come from its event lists (TRM_GROUP_RUN)
+    bool drop = false;                       // the group's event lists end with this step: run to their end, or dropped by a finish
+    uint64_t frames = 0;                     // a pushing group: the frames it pushes (the step's; a running group's last stretch: fewer)
     uint64_t Q = 0, kBase = 0, kEnd = 0;     // control periods of the step; converter outputs kBase <= k < kEnd
 };
 
-static int step_plan(const trm_stream_engine *s, const uint8_t *action, size_t nframes, std::vector<GroupPlan> &plan)
+// what TRM_GROUP_RUN means for group g now: push `*frames` generated frames (> 0), flush (returns true with *frames = 0 on an
+// open group), or nothing
+static void run_means(const trm_stream_engine *s, size_t g, size_t nframes, bool *push, bool *flush, uint64_t *frames)
+{
+    const trm_stream_engine::GroupEvents &ev = s->gev[g];
+    const uint64_t left = ev.state == trm_stream_engine::kEvPending ? ev.frames - ev.emitted : 0;
+    *frames = std::min<uint64_t>(nframes, left);
+    *push = left > 0;
+    *flush = ev.state == trm_stream_engine::kEvPending && left == 0 && s->gopen[g];
+}
+
+// `frames`: the caller's frames, looked at for null alone
+static int step_plan(const trm_stream_engine *s, const uint8_t *action, const float *frames, size_t nframes, std::vector<GroupPlan> &plan)
 {
     const size_t G = s->gbegin.size() - 1;
     const bool tract = s->mode == TRM_STREAM_MODE_TRACT;
     plan.assign(G, GroupPlan());
+    bool anyRun = false, anyPushed = false;
     for (size_t g = 0; g < G; g++) {
         GroupPlan &p = plan[g];
-        if (action[g] > TRM_GROUP_FINISH) return fail(TRM_EINVAL, "group %zu: unknown action %u", g, (unsigned)action[g]);
+        if (action[g] > TRM_GROUP_RUN) return fail(TRM_EINVAL, "group %zu: unknown action %u", g, (unsigned)action[g]);
+        const int ev = s->gev[g].state;
         p.push = action[g] == TRM_GROUP_PUSH;
         p.flush = action[g] == TRM_GROUP_FINISH && s->gopen[g];
+        p.frames = nframes;
+        // (a finish aborts a group that runs, and drops lists that have not begun)
+        p.drop = action[g] == TRM_GROUP_FINISH && ev == trm_stream_engine::kEvPending;
+        if (p.push && ev == trm_stream_engine::kEvPending)
+            return fail(TRM_EINVAL, "group %zu pushes, but it has event lists that have not run to their end (TRM_GROUP_RUN, or TRM_GROUP_FINISH to drop them)", g);
+        if (action[g] == TRM_GROUP_RUN) {
+            if (ev == trm_stream_engine::kEvNone) return fail(TRM_EINVAL, "group %zu runs, but it never had event lists (trm_mixed_stream_group_set_events)", g);
+            if (ev == trm_stream_engine::kEvConsumed && s->gopen[g])
+                return fail(TRM_EINVAL, "group %zu runs, but its utterance was opened by pushed frames", g);
+            run_means(s, g, nframes, &p.push, &p.flush, &p.frames);
+            p.gen = p.push;
+            p.drop = p.flush;
+            anyRun = true;
+            if (p.gen && !trm::tracks_run_launcher)
+                return fail(TRM_EHIP, "group %zu runs, but this build of the library holds no resumable track kernel (trm_tracks_run.hip)", g);
+        }
         if (p.push && nframes == 0) return fail(TRM_EINVAL, "group %zu pushes, but the step has no frames", g);
+        anyPushed = anyPushed || (p.push && !p.gen);
         if (!p.push && !p.flush) continue;
         // (as stream_chunk_impl: TRAcT order's first period runs on row 1, so an opening push has a lead row too)
         p.lead = p.push && (s->gopen[g] || tract);
-        const uint64_t rows = p.push ? nframes + (p.lead ? 1 : 0) : 1;
+        const uint64_t rows = p.push ? p.frames + (p.lead ? 1 : 0) : 1;
         p.Q = rows - 1;
         p.runs = p.Q > 0 || p.flush;
         const trm_batch *b = s->sets[s->gset[g]];
@@ -467,6 +535,8 @@ static int step_plan(const trm_stream_engine *s, const uint8_t *action, size_t n
         if (s->gbegin[g + 1] > s->gbegin[g] && unit_too_long(b, s->gperiods[g] + p.Q, p.kEnd))
             return fail(TRM_ERANGE, "utterance too long (group %zu)", g);
     }
+    // (frames may stay away where every frame of the step is generated)
+    if (nframes > 0 && !frames && (anyPushed || !anyRun)) return fail(TRM_EINVAL, "null frames");
     return TRM_OK;
 }
 
@@ -476,6 +546,9 @@ static void step_after(trm_stream_engine *s, const std::vector<GroupPlan> &plan)
     for (size_t g = 0; g < plan.size(); g++) {
         const GroupPlan &p = plan[g];
         if (p.push) { s->gopen[g] = 1; s->gperiods[g] += p.Q; }
+        if (p.gen) s->gev[g].emitted += p.frames;
+        if (p.drop) s->gev[g].state = trm_stream_engine::kEvConsumed;
+        s->glastq[g] = p.push ? (uint32_t)p.frames : 0u;
         if (p.runs) s->gfirst[g] = 0;
         if (p.flush) { s->gopen[g] = 0; s->gfirst[g] = 1; s->gperiods[g] = 0; }      // the next push opens a new utterance
         anyOpen = anyOpen || s->gopen[g];
@@ -528,16 +601,25 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     if ((rc = s->dFrames.reserve(V * rows * 16))) return rc;
     if ((rc = stream_shape(s, rows, out_pitch, rows - 1, anyDown, st))) return rc;
     // the step's tables
-    const size_t words = E * 5 + G;
+    size_t nRun = 0;                         // voices whose frames are generated in this step
+    for (size_t g = 0; g < G; g++) nRun += plan[g].gen ? s->gbegin[g + 1] - s->gbegin[g] : 0;
+    const size_t words = step_words(s, nRun);
     uint32_t *h = nullptr;
-    if ((rc = step_copy(s, words, &h))) return rc;
-    uint32_t *clock = h, *active = h + E * 4, *what = active + E;
+    if ((rc = step_copy(s, step_words(s, V), &h))) return rc;
+    uint32_t *clock = h, *active = h + E * 4, *what = active + E, *run = what + G;
     memset(h, 0, words * sizeof(uint32_t));
     uint32_t nActive = 0;
+    nRun = 0;
     for (size_t g = 0; g < G; g++) {
         const GroupPlan &p = plan[g];
-        what[g] = (p.push ? trm::kGrpPush : 0u) | (p.flush ? trm::kGrpFinish : 0u) | (p.push && !s->gopen[g] ? trm::kGrpOpening : 0u) |
+        // (the rows of a group that generates its frames are the track kernel's: the prep kernel only clears its maxima)
+        const bool pushed = p.push && !p.gen;
+        what[g] = (pushed ? trm::kGrpPush : 0u) | (p.flush ? trm::kGrpFinish : 0u) | (pushed && !s->gopen[g] ? trm::kGrpOpening : 0u) |
                   (p.kEnd == p.kBase ? trm::kGrpClear : 0u);
+        for (size_t v = s->gbegin[g]; p.gen && v < s->gbegin[g + 1]; v++) {
+            run[2 * nRun] = (uint32_t)v;
+            run[2 * nRun++ + 1] = (uint32_t)p.frames | (s->gopen[g] ? 0u : trm::kTrackRunOpening);
+        }
         if (!p.runs) continue;
         for (uint32_t e = s->gentry[g]; e < s->gentry[g + 1]; e++) {
             clock[4 * e] = (uint32_t)s->gperiods[g];
@@ -550,6 +632,14 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     HIP_TRY(hipEventRecord(s->stepCopies.back().uploaded, st));
     trm::GrpPrepArgs prep{s->dFrames.p, s->dLast.p, d_pushed, s->dVoiceGroup.p, s->dStep.p + E * 5, s->dMax.p, (uint32_t)V, (uint32_t)rows};
     HIP_TRY(trm::launch_grp_prep(prep, st));
+    if (nRun > 0) {
+        // the frames of the groups that run: generated in place, with their lead rows and last frames
+        typedef const __attribute__((address_space(4))) uint32_t *Words;
+        trm::TrackRunArgs t{(Words)s->dEvTimes.p, s->dEvValues.p, (const __attribute__((address_space(4))) uint64_t *)s->dEvOff.p, (Words)s->dEvN.p,
+                            (trm::IntonationTable)s->dEvSettings.p, (Words)(s->dStep.p + E * 5 + G), s->dTrkLanes.p, s->dTrkHead.p,
+                            s->dFrames.p, s->dLast.p, (uint32_t)V, (uint32_t)rows, (uint32_t)nRun};
+        HIP_TRY(trm::tracks_run_launcher(t, st));
+    }
     if (nActive == 0) return TRM_OK;         // nothing synthesizes: no tube launch
     if ((rc = ensure_noise(b0, (uint32_t)noiseNeed, st))) return rc;
     trm::TubeArgs a = tube_args(b0, s->dFrames.p, s->dFrameOff.p, s->dNFrames.p, d_out, s->dOutOff.p, s->dNSamples.p, s->dMax.p, V, (uint32_t)rows);
@@ -583,11 +673,10 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     return TRM_OK;
 }
 
-static int step_check(const trm_stream_engine *s, const uint8_t *action, const float *frames, size_t nframes)
+static int step_check(const trm_stream_engine *s, const uint8_t *action, size_t nframes)
 {
     if (!s || !action) return fail(TRM_EINVAL, "null argument");
     if (!s->grouped) return fail(TRM_EINVAL, "not a grouped stream (trm_mixed_stream_create_groups): push / finish advance its voices together");
-    if (nframes > 0 && !frames) return fail(TRM_EINVAL, "null frames");
     if (nframes >= 0x7FFFFFFFull) return fail(TRM_EINVAL, "too many frames");
     return TRM_OK;
 }
@@ -595,10 +684,10 @@ static int step_check(const trm_stream_engine *s, const uint8_t *action, const f
 static int stream_step_device(trm_stream_engine *s, const uint8_t *action, const float *d_frames, size_t nframes, float *d_out, size_t out_pitch,
                               uint32_t *nout, float *d_max_out, void *stream)
 {
-    int rc = step_check(s, action, d_frames, nframes);
+    int rc = step_check(s, action, nframes);
     if (rc) return rc;
     std::vector<GroupPlan> plan;
-    if ((rc = step_plan(s, action, nframes, plan))) return rc;
+    if ((rc = step_plan(s, action, d_frames, nframes, plan))) return rc;
     HIP_TRY(hipSetDevice(s->sets[0]->device));
     hipStream_t st = (hipStream_t)stream;
     // (the maxima leave inside the ordered work: the next step, on whichever stream, clears and writes them again)
@@ -616,10 +705,10 @@ static int stream_step_device(trm_stream_engine *s, const uint8_t *action, const
 static int stream_step_host(trm_stream_engine *s, const uint8_t *action, const float *frames, size_t nframes, float *out, size_t out_pitch,
                             uint32_t *nout, float *max_out)
 {
-    int rc = step_check(s, action, frames, nframes);
+    int rc = step_check(s, action, nframes);
     if (rc) return rc;
     std::vector<GroupPlan> plan;
-    if ((rc = step_plan(s, action, nframes, plan))) return rc;
+    if ((rc = step_plan(s, action, frames, nframes, plan))) return rc;
     const size_t G = plan.size(), V = s->nvoices;
     trm_batch *b0 = s->sets[0];
     HIP_TRY(hipSetDevice(b0->device));
@@ -633,9 +722,9 @@ static int stream_step_host(trm_stream_engine *s, const uint8_t *action, const f
         if ((rc = s->dPushed.reserve(V * nframes * 16))) return rc;
         // (runs of neighbouring pushing groups; the rows of the others are not read)
         for (size_t g = 0; g < G;) {
-            if (!plan[g].push) { g++; continue; }
+            if (!plan[g].push || plan[g].gen) { g++; continue; }
             size_t e = g;
-            while (e < G && plan[e].push) e++;
+            while (e < G && plan[e].push && !plan[e].gen) e++;
             const size_t lo = s->gbegin[g] * nframes * 16, hi = s->gbegin[e] * nframes * 16;
             if (hi > lo) HIP_TRY(hipMemcpyAsync(s->dPushed.p + lo, frames + lo, (hi - lo) * sizeof(float), hipMemcpyHostToDevice, st));
             g = e;
@@ -919,12 +1008,126 @@ int trm_mixed_stream_group_open(const trm_mixed_stream *s, size_t group)
 size_t trm_mixed_stream_group_samples_for(const trm_mixed_stream *s, size_t group, int action, size_t nframes)
 {
     if (!s || !s->grouped || group + 1 >= s->gbegin.size()) return 0;
-    const bool push = action == TRM_GROUP_PUSH && nframes > 0, flush = action == TRM_GROUP_FINISH && s->gopen[group];
+    bool push = action == TRM_GROUP_PUSH && nframes > 0, flush = action == TRM_GROUP_FINISH && s->gopen[group];
+    uint64_t frames = nframes;
+    if (action == TRM_GROUP_RUN) {
+        run_means(s, group, nframes, &push, &flush, &frames);
+        push = push && frames > 0;
+    }
     if (!push && !flush) return 0;
     const bool lead = s->gopen[group] || s->mode == TRM_STREAM_MODE_TRACT;
     uint64_t kEnd = 0;
-    const uint64_t kBase = unit_range(s->sets[s->gset[group]], s->gperiods[group], push ? nframes + (lead ? 1 : 0) : 1, flush, &kEnd);
+    const uint64_t kBase = unit_range(s->sets[s->gset[group]], s->gperiods[group], push ? frames + (lead ? 1 : 0) : 1, flush, &kEnd);
     return (size_t)(kEnd - kBase);
+}
+
+// The device pool of event lists with room for `need` more events: what is there stays where it is while it fits; otherwise
+// the pool is allocated anew and the lists that have not run to their end are uploaded again from their host copies (the
+// caller has waited for the device; group `skip`'s lists are the ones about to be replaced).
+static int events_room(trm_stream_engine *s, size_t skip, uint64_t need)
+{
+    if (s->evUsed + need <= s->dEvTimes.cap && s->dEvTimes.p) return TRM_OK;
+    uint64_t live = 0;
+    for (size_t g = 0; g < s->gev.size(); g++)
+        if (g != skip && s->gev[g].state == trm_stream_engine::kEvPending) live += s->gev[g].times.size();
+    const uint64_t want = std::max<uint64_t>(2 * (live + need), 1024);
+    DevBuf<uint32_t> t;
+    DevBuf<double> v;
+    int rc;
+    if ((rc = t.reserve(want)) || (rc = v.reserve(want * TRM_EVENT_VALUES))) return rc;
+    std::swap(t.p, s->dEvTimes.p); std::swap(t.cap, s->dEvTimes.cap);
+    std::swap(v.p, s->dEvValues.p); std::swap(v.cap, s->dEvValues.cap);
+    s->evUsed = 0;
+    std::vector<uint64_t> off;
+    for (size_t g = 0; g < s->gev.size(); g++) {
+        trm_stream_engine::GroupEvents &ev = s->gev[g];
+        ev.at = ev.cap = 0;
+        if (g == skip || ev.state != trm_stream_engine::kEvPending) continue;
+        const size_t lo = s->gbegin[g], nv = s->gbegin[g + 1] - lo, n = ev.times.size();
+        ev.at = s->evUsed; ev.cap = n;
+        s->evUsed += n;
+        off.resize(nv);
+        for (size_t k = 0; k < nv; k++) off[k] = ev.at + ev.off[k];
+        HIP_TRY(hipMemcpy(s->dEvTimes.p + ev.at, ev.times.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->dEvValues.p + ev.at * TRM_EVENT_VALUES, ev.values.data(), n * TRM_EVENT_VALUES * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->dEvOff.p + lo, off.data(), nv * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    return TRM_OK;
+}
+
+int trm_mixed_stream_group_set_events(trm_mixed_stream *s, size_t group, const uint32_t *event_times, const double *event_values,
+                                      const uint64_t *event_offset, const uint32_t *nevents, const trm_intonation *settings)
+{
+    if (!s || !event_times || !event_values || !event_offset || !nevents || !settings) return fail(TRM_EINVAL, "null argument");
+    if (!s->grouped) return fail(TRM_EINVAL, "not a grouped stream (trm_mixed_stream_create_groups)");
+    if (group + 1 >= s->gbegin.size()) return fail(TRM_EINVAL, "group %zu of %zu", group, s->gbegin.size() - 1);
+    if (s->gopen[group]) return fail(TRM_EINVAL, "group %zu has an utterance open: event lists are given to a closed group", group);
+    const size_t lo = s->gbegin[group], nv = s->gbegin[group + 1] - lo, V = s->nvoices;
+    if (nv == 0) return fail(TRM_EINVAL, "group %zu has no voices", group);
+    trm_stream_engine::GroupEvents ev;
+    for (size_t k = 0; k < nv; k++) {
+        size_t f = 0;
+        if (int rc = trm_events_count_frames(event_times + event_offset[k], nevents[k], settings + k, &f)) return rc;
+        if (f == 0) return fail(TRM_EINVAL, "group %zu, voice %zu: the event list gives no frame", group, k);
+        if (k > 0 && f != ev.frames)
+            return fail(TRM_EINVAL, "group %zu: voice %zu's event list gives %zu frames, voice 0's %llu (the voices of a group share one clock)", group, k, f,
+                        (unsigned long long)ev.frames);
+        ev.frames = f;
+        ev.off.push_back(ev.times.size());
+        ev.n.push_back(nevents[k]);
+        ev.times.insert(ev.times.end(), event_times + event_offset[k], event_times + event_offset[k] + nevents[k]);
+        const double *val = event_values + event_offset[k] * TRM_EVENT_VALUES;
+        ev.values.insert(ev.values.end(), val, val + (size_t)nevents[k] * TRM_EVENT_VALUES);
+    }
+    ev.settings.assign(settings, settings + nv);
+    ev.state = trm_stream_engine::kEvPending;
+    HIP_TRY(hipSetDevice(s->sets[0]->device));
+    // the steps so far may still read the pool and the tables, on whichever HIP stream: the one wait of this entry
+    if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
+    int rc;
+    if ((rc = s->dEvOff.reserve(V)) || (rc = s->dEvN.reserve(V)) || (rc = s->dEvSettings.reserve(V)) || (rc = s->dTrkLanes.reserve(V * 64)) ||
+        (rc = s->dTrkHead.reserve(V)))
+        return rc;
+    const trm_stream_engine::GroupEvents &old = s->gev[group];      // (replaced below; its stretch of the pool serves again if it is large enough)
+    const uint64_t n = ev.times.size();
+    if (n <= old.cap) { ev.at = old.at; ev.cap = old.cap; }
+    else {
+        if ((rc = events_room(s, group, n))) return rc;
+        ev.at = s->evUsed; ev.cap = n;
+        s->evUsed += n;
+    }
+    std::vector<uint64_t> off(nv);
+    for (size_t k = 0; k < nv; k++) off[k] = ev.at + ev.off[k];
+    HIP_TRY(hipMemcpy(s->dEvTimes.p + ev.at, ev.times.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->dEvValues.p + ev.at * TRM_EVENT_VALUES, ev.values.data(), n * TRM_EVENT_VALUES * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->dEvOff.p + lo, off.data(), nv * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->dEvN.p + lo, ev.n.data(), nv * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->dEvSettings.p + lo, ev.settings.data(), nv * sizeof(trm_intonation), hipMemcpyHostToDevice));
+    s->gev[group] = std::move(ev);
+    return TRM_OK;
+}
+
+size_t trm_mixed_stream_group_frames_left(const trm_mixed_stream *s, size_t group)
+{
+    if (!s || !s->grouped || group + 1 >= s->gbegin.size() || s->gev[group].state != trm_stream_engine::kEvPending) return 0;
+    return (size_t)(s->gev[group].frames - s->gev[group].emitted);
+}
+
+int trm_mixed_stream_last_frames(trm_mixed_stream *s, size_t voice, float *rows, size_t cap_rows, size_t *nrows)
+{
+    if (!s || !nrows) return fail(TRM_EINVAL, "null argument");
+    if (!s->grouped) return fail(TRM_EINVAL, "not a grouped stream (trm_mixed_stream_create_groups)");
+    if (voice >= s->nvoices) return fail(TRM_EINVAL, "voice %zu of %zu", voice, s->nvoices);
+    const size_t g = (size_t)(std::upper_bound(s->gbegin.begin(), s->gbegin.end(), voice) - s->gbegin.begin()) - 1;
+    const size_t q = s->glastq[g];
+    if (cap_rows < q || (q > 0 && !rows)) return fail(TRM_EINVAL, "room for %zu rows, the last step gave voice %zu %zu", rows ? cap_rows : (size_t)0, voice, q);
+    *nrows = q;
+    if (q == 0) return TRM_OK;
+    HIP_TRY(hipSetDevice(s->sets[0]->device));
+    if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
+    // (the step's rows of the voice behind its lead row)
+    HIP_TRY(hipMemcpy(rows, s->dFrames.p + ((size_t)voice * s->shapeRows + 1) * 16, q * 16 * sizeof(float), hipMemcpyDeviceToHost));
+    return TRM_OK;
 }
 
 int trm_mixed_stream_step(trm_mixed_stream *s, const uint8_t *action, const float *frames, size_t nframes, float *out, size_t out_pitch,

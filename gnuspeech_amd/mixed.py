@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import TRM_GROUP_FINISH, TRM_GROUP_IDLE, TRM_GROUP_PUSH, TrmDerived, TrmInputParams, TrmIntonation, check, lib
+from ._capi import TRM_GROUP_FINISH, TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_RUN, TrmDerived, TrmInputParams, TrmIntonation, check, lib
 
 _KERNELS = {"auto": 0, "wide": 1, "quad": 2, "oct": 3}
 
@@ -556,11 +556,15 @@ class TRMGroupedStream:
     frames, finishes its utterance or sits idle, and all of it is one tube launch.  Every voice's samples are bit for bit those
     of a TRMStream of its set with the group's voices, fed the group's pushes and finishes alone.
 
+    A group can also be given its event lists once (set_events) and then "run": every step generates the step's frames on the
+    device, bit for bit the frames of the batch track generator for the whole list, and the group finishes by itself.
+
     The host entry takes and returns voices in the caller's order and groups by the caller's indices.  On the device voices stay
     in grouped order: `order[j]` = the caller's voice at grouped position j, `inverse` the way back."""
 
-    _ACTIONS = {"idle": TRM_GROUP_IDLE, "push": TRM_GROUP_PUSH, "finish": TRM_GROUP_FINISH, None: TRM_GROUP_IDLE,
-                TRM_GROUP_IDLE: TRM_GROUP_IDLE, TRM_GROUP_PUSH: TRM_GROUP_PUSH, TRM_GROUP_FINISH: TRM_GROUP_FINISH}
+    _ACTIONS = {"idle": TRM_GROUP_IDLE, "push": TRM_GROUP_PUSH, "finish": TRM_GROUP_FINISH, "run": TRM_GROUP_RUN, None: TRM_GROUP_IDLE,
+                TRM_GROUP_IDLE: TRM_GROUP_IDLE, TRM_GROUP_PUSH: TRM_GROUP_PUSH, TRM_GROUP_FINISH: TRM_GROUP_FINISH,
+                TRM_GROUP_RUN: TRM_GROUP_RUN}
 
     def __init__(self, param_sets, sets, groups, device=-1, mode="framework", ngroups=None):
         from .stream import MODES
@@ -622,8 +626,58 @@ class TRMGroupedStream:
         return bool(lib().trm_mixed_stream_group_open(self._h, int(self._gindex[int(group)])))
 
     def samples_for(self, group, action, nframes=0):
-        """Samples every voice of the caller's group receives from `action` ("push" of nframes frames, "finish", "idle") now."""
+        """Samples every voice of the caller's group receives from `action` ("push" or "run" of nframes frames, "finish", "idle") now."""
         return lib().trm_mixed_stream_group_samples_for(self._h, int(self._gindex[int(group)]), self._ACTIONS[action], int(nframes))
+
+    def set_events(self, group, event_lists, settings=None):
+        """Event lists for the caller's CLOSED group `group`, which then advances by the action "run": one EventList per voice of
+        the group (in the caller's voice order), or one list for all of them.  settings: one TrmIntonation per voice (or one for
+        all); default each list's own settings().  All voices must count the same number of frames (>= 1)."""
+        g = int(group)
+        if not 0 <= g < self.ngroups:
+            raise ValueError("group %r outside 0 .. %d" % (group, self.ngroups - 1))
+        voices = np.flatnonzero(self.groups == g)          # caller's order == the library's order inside a group (stable sort)
+        nv = int(voices.size)
+        if nv == 0:
+            raise ValueError("group %d has no voices" % g)
+        lists = [event_lists] * nv if hasattr(event_lists, "arrays") else list(event_lists)
+        if len(lists) == 1 and nv > 1:
+            lists = lists * nv
+        if len(lists) != nv:
+            raise ValueError("%d event lists for the %d voices of group %d" % (len(lists), nv, g))
+        if settings is None:
+            sts = [e.settings() for e in lists]
+        elif isinstance(settings, TrmIntonation):
+            sts = [settings] * nv
+        else:
+            sts = list(settings)
+            if len(sts) != nv:
+                raise ValueError("%d settings for the %d voices of group %d" % (len(sts), nv, g))
+        arrs = [e.arrays() for e in lists]
+        nev = np.array([len(t) for t, _ in arrs], dtype=np.uint32)
+        off = np.zeros(nv, dtype=np.uint64)
+        off[1:] = np.cumsum(nev[:-1], dtype=np.uint64)
+        times = np.ascontiguousarray(np.concatenate([t for t, _ in arrs]), dtype=np.uint32)
+        values = np.ascontiguousarray(np.concatenate([v.reshape(-1, 36) for _, v in arrs]), dtype=np.float64)
+        sarr = (TrmIntonation * nv)(*sts)
+        check(lib().trm_mixed_stream_group_set_events(self._h, int(self._gindex[g]), times.ctypes.data, values.ctypes.data, off.ctypes.data,
+                                                      nev.ctypes.data, sarr))
+
+    def frames_left(self, group):
+        """Frames the caller's group `group` still has to run from its event lists (0 without lists that have not run out)."""
+        return lib().trm_mixed_stream_group_frames_left(self._h, int(self._gindex[int(group)]))
+
+    def last_frames(self, voice):
+        """The frame rows [q, 16] the caller's voice `voice` consumed in the last step, pushed or generated (the reference's
+        parameterLogger:).  Synchronous."""
+        v = int(voice)
+        if not 0 <= v < self.nvoices:
+            raise ValueError("voice %r outside 0 .. %d" % (voice, self.nvoices - 1))
+        cap = max(int(getattr(self, "_max_n", 0)), 1)      # the longest step so far
+        rows = np.zeros((cap, 16), dtype=np.float32)
+        n = C.c_size_t()
+        check(lib().trm_mixed_stream_last_frames(self._h, int(self.inverse[v]), rows.ctypes.data, cap, C.byref(n)))
+        return rows[:n.value].copy()
 
     def _actions(self, actions):
         """the library's action array (its group order) from a sequence of ngroups actions or a dict {group: action}"""
@@ -639,7 +693,7 @@ class TRMGroupedStream:
             if not 0 <= int(g) < self.ngroups:
                 raise ValueError("group %r outside 0 .. %d" % (g, self.ngroups - 1))
             if act not in self._ACTIONS:
-                raise ValueError("unknown action %r (push, finish, idle)" % (act,))
+                raise ValueError("unknown action %r (push, finish, idle, run)" % (act,))
             a[self._gindex[int(g)]] = self._ACTIONS[act]
         return a
 
@@ -652,9 +706,10 @@ class TRMGroupedStream:
         return int(counts[nonempty].max()) if np.any(nonempty) else 0
 
     # -------------------------------------------------------------- host buffers (caller's voice order)
-    def step(self, actions, frames=None):
-        """actions: ngroups entries ("push" | "finish" | "idle" / None), or a dict {group: "push" | "finish"} (the others idle).
+    def step(self, actions, frames=None, nframes=None):
+        """actions: ngroups entries ("push" | "finish" | "idle" / None | "run"), or a dict {group: action} (the others idle).
         frames: [nvoices, n, 16] in the caller's order, needed when a group pushes; only the rows of pushing groups are read.
+        nframes: the frames of the step where no group pushes and groups "run" (with frames given it must be their count).
         Returns (pcm [nvoices, max_m] float32, samples per voice uint32[nvoices], max |sample| per voice float32[nvoices]);
         voice i's samples are pcm[i, :count[i]]."""
         a = self._actions(actions)
@@ -667,6 +722,13 @@ class TRMGroupedStream:
                 raise ValueError("frames must be [%d voices, n >= 1, 16], got %s" % (self.nvoices, f.shape))
             f = np.ascontiguousarray(f[self.order])
             n = f.shape[1]
+            if nframes is not None and int(nframes) != n:
+                raise ValueError("nframes = %r, but the pushed frames are %d" % (nframes, n))
+        elif np.any(a == TRM_GROUP_RUN):
+            if nframes is None:
+                raise ValueError("a group runs and none pushes: nframes needed")
+            n = int(nframes)
+        self._max_n = max(getattr(self, "_max_n", 0), n)      # (room for last_frames)
         counts = self._counts(a, n)
         m = self._width(counts)
         out = np.zeros((self.nvoices, max(m, 1)), dtype=np.float32)
@@ -679,20 +741,28 @@ class TRMGroupedStream:
         return out[self.inverse, :m], per_voice[self.inverse], mx[self.inverse]
 
     # -------------------------------------------------------------- device buffers (torch tensors, grouped order)
-    def step_device(self, actions, frames=None, out=None, max_out=None, device=None):
+    def step_device(self, actions, frames=None, out=None, max_out=None, device=None, nframes=None):
         """As step(), on the device: frames a float32 CUDA tensor [nvoices, n, 16] in GROUPED order (frames[order] of the caller's).
         Asynchronous on torch's current stream; nothing but the step's small tables crosses PCIe.  Returns (pcm [nvoices, max_m]
         view of `out`, samples per voice uint32[nvoices]), both in grouped order.  `out` (optional): float32 CUDA tensor
         [nvoices, pitch >= max_m]; `max_out` (optional): float32 CUDA tensor [nvoices]."""
         import torch
         a = self._actions(actions)
-        n = 0
+        n, pushed = 0, False
         if np.any(a == TRM_GROUP_PUSH):
             if frames is None or not (frames.is_cuda and frames.dtype == torch.float32 and frames.is_contiguous() and frames.dim() == 3
                                       and frames.shape[0] == self.nvoices and frames.shape[2] == 16 and frames.shape[1] > 0):
                 raise ValueError("a group pushes: frames must be a contiguous float32 CUDA tensor [%d, n >= 1, 16]" % self.nvoices)
             n = frames.shape[1]
-        dev = frames.device if n else out.device if out is not None else device if device is not None \
+            if nframes is not None and int(nframes) != n:
+                raise ValueError("nframes = %r, but the pushed frames are %d" % (nframes, n))
+            pushed = True
+        elif np.any(a == TRM_GROUP_RUN):
+            if nframes is None:
+                raise ValueError("a group runs and none pushes: nframes needed")
+            n = int(nframes)
+        self._max_n = max(getattr(self, "_max_n", 0), n)      # (room for last_frames)
+        dev = frames.device if pushed else out.device if out is not None else device if device is not None \
             else torch.device("cuda", torch.cuda.current_device())
         counts = self._counts(a, n)
         m = self._width(counts)
@@ -705,7 +775,7 @@ class TRMGroupedStream:
             raise ValueError("max_out must be a float32 CUDA tensor of %d values" % self.nvoices)
         nout = np.zeros(self.ngroups, dtype=np.uint32)
         st = torch.cuda.current_stream(dev).cuda_stream
-        check(lib().trm_mixed_stream_step_device(self._h, a.ctypes.data, frames.data_ptr() if n else None, n, out.data_ptr(), out.stride(0),
+        check(lib().trm_mixed_stream_step_device(self._h, a.ctypes.data, frames.data_ptr() if pushed else None, n, out.data_ptr(), out.stride(0),
                                                  nout.ctypes.data, max_out.data_ptr() if max_out is not None else None, st))
         assert np.array_equal(nout.astype(np.int64), counts)
         return out[:, :m], nout[self._vgroup]

@@ -623,6 +623,7 @@ int    trm_mixed_stream_finish_device(trm_mixed_stream *s, float *d_out, size_t 
  *   - The device entry makes the host wait only when the step's shape (nframes, out_pitch) changes or the noise sequence has to
  *     grow, whatever the actions; a step without frames keeps the shape it finds.  Steps are ordered across HIP streams like chunks. */
 enum { TRM_GROUP_IDLE = 0, TRM_GROUP_PUSH = 1, TRM_GROUP_FINISH = 2 };
+enum { TRM_GROUP_RUN = 3 };      /* a group that runs from its event lists: trm_mixed_stream_group_set_events, below */
 int    trm_mixed_stream_create_groups(const trm_input_params *params, size_t nsets, const size_t *set_begin,
                                       const size_t *group_begin, size_t ngroups, int device, trm_mixed_stream **out);
 size_t trm_mixed_stream_groups(const trm_mixed_stream *s);            /* 0: not a grouped stream */
@@ -632,6 +633,41 @@ int    trm_mixed_stream_step(trm_mixed_stream *s, const uint8_t *action, const f
                              size_t out_pitch, uint32_t *nout, float *max_out);
 int    trm_mixed_stream_step_device(trm_mixed_stream *s, const uint8_t *action, const float *d_frames, size_t nframes,
                                     float *d_out, size_t out_pitch, uint32_t *nout, float *d_max_out, void *hip_stream);
+
+/* Groups that run from event lists: a group is given its event lists once (trm_mixed_stream_group_set_events) and then RUNS.
+ * Every step generates exactly the step's frames on the device -- the control-track generator of trm_*_generate_frames_device,
+ * resumed where the step before left it -- and feeds them to the step's tube launch; when the frames run out the group flushes
+ * and closes by itself.  No frame crosses PCIe and no buffer holds the utterance.
+ *   - set_events: only on a CLOSED group of a grouped stream (TRM_EINVAL otherwise).  Host arrays: voice k of the group (k = 0 ..
+ *     the group's voices - 1) owns events event_offset[k] .. + nevents[k] of event_times / event_values ([..][36]) and
+ *     settings[k] (pitch mean, switches, drift seed, time range).  The group's length F = trm_events_count_frames() of each
+ *     voice: all voices of a group must count the same F >= 1 (TRM_EINVAL otherwise; a group without voices: TRM_EINVAL).  The
+ *     lists are copied to device storage owned by the stream, which grows on demand; the call may wait for the device (the step
+ *     entries gain no host wait).  Calling it again on a closed group replaces the lists.
+ *   - action TRM_GROUP_RUN, with left = F - frames emitted so far:
+ *       left > 0           as TRM_GROUP_PUSH of min(nframes, left) generated frames (nframes == 0: TRM_EINVAL, as for a push); it
+ *                          opens the utterance if the group is closed.  PUSH groups of the same step still push nframes each.
+ *       left == 0, open    as TRM_GROUP_FINISH: the group closes and its events are consumed.
+ *       closed, consumed   nothing, nout[g] = 0.
+ *       never had events   TRM_EINVAL (so is RUN on a group whose utterance was opened by TRM_GROUP_PUSH).
+ *     TRM_GROUP_FINISH on a group with unconsumed events aborts it: an open utterance flushes now, and the events are dropped
+ *     (also those of a group that has not begun to run).  TRM_GROUP_PUSH on a group with unconsumed events: TRM_EINVAL.
+ *     `frames` may be null with nframes > 0 only when no group PUSHes and at least one group's action is TRM_GROUP_RUN.
+ *     trm_mixed_stream_group_samples_for(s, g, TRM_GROUP_RUN, nframes) is the exact count, asked before the step.
+ *   - trm_mixed_stream_group_frames_left: F - emitted, 0 without (unconsumed) events.
+ *   - trm_mixed_stream_last_frames: the reference's parameterLogger: of -generateOutputInTimeRange:.  The frame rows voice `voice`
+ *     (the stream's voice index) consumed in the LAST step, the lead row not counted, to host memory rows[cap_rows][16]; *nrows
+ *     is set.  cap_rows too small: TRM_EINVAL, *nrows untouched.  Synchronous.  Works for groups that PUSH too (0 rows for
+ *     groups that finished or idled in that step).
+ *   - PARITY.  The frames of a running voice, step after step, are bit for bit rows emitted .. emitted + q of what
+ *     trm_mixed_generate_frames_device writes for the same list and settings.  Its PCM, counts and maxima are bit for bit those
+ *     of the same grouped stream driven by TRM_GROUP_PUSH with those frames cut the same way and then TRM_GROUP_FINISH -- by the
+ *     rule above, those of a trm_stream of the group alone.
+ *   - A library built without the track kernel (the host units alone) refuses TRM_GROUP_RUN with TRM_EHIP; all else works. */
+int    trm_mixed_stream_group_set_events(trm_mixed_stream *s, size_t group, const uint32_t *event_times, const double *event_values,
+                                         const uint64_t *event_offset, const uint32_t *nevents, const trm_intonation *settings);
+size_t trm_mixed_stream_group_frames_left(const trm_mixed_stream *s, size_t group);
+int    trm_mixed_stream_last_frames(trm_mixed_stream *s, size_t voice, float *rows, size_t cap_rows, size_t *nrows);
 
 /* Library / device identification. */
 int  trm_device_count(void);

@@ -1,0 +1,154 @@
+"""The HOST engine of grouped streams that run from event lists, without a GPU (gnuspeech_amd/csrc/trm_stream.cc:
+trm_mixed_stream_group_set_events, TRM_GROUP_RUN): the library's host translation units linked with tests/_emul/hip_host_mock.cc
+(the HIP runtime and the stream kernels as hashes of everything they read) and tests/_emul/hip_host_mock_events.cc, which supplies
+the track launcher on the CPU from the oracle's generator.  The bookkeeping -- counts per step, the groups' closing by themselves,
+abort, re-use of a group, the tables of a step, where the lists lie, the refusals -- is then checked against the same schedule
+driven by "push" and "finish" (tests/group_events_common.py).  The kernels' arithmetic is the GPU tests' business."""
+import ctypes as C
+import gc
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import group_events_common as T
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
+HOST_UNITS = ["trm_capi", "trm_stream", "trm_mixed", "trm_setup", "trm_io"]
+
+
+def _build(out, mocks):
+    srcs = [os.path.join(CSRC, u + ".cc") for u in HOST_UNITS]
+    oracle = os.path.join(ROOT, "oracle")
+    if not os.path.exists(os.path.join(oracle, "libtrm_oracle.so")):
+        subprocess.check_call(["make", "-s", "-C", oracle, "libtrm_oracle.so"])
+    link = ["-L" + oracle, "-l:libtrm_oracle.so", "-Wl,-rpath," + oracle] if len(mocks) > 1 else []
+    objs = [os.path.join(CSRC, "build", u + ".o") for u in HOST_UNITS]
+    hdrs = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")] + [os.path.join(ROOT, "include", "trm_c_api.h")]
+    fresh = all(os.path.exists(o) and all(os.path.getmtime(o) >= os.path.getmtime(d) for d in [s] + hdrs) for o, s in zip(objs, srcs))
+    flags = ["-O1", "-std=c++17", "-fPIC"]
+    mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in mocks]
+    # (-Bsymbolic: the library's calls into the runtime bind to the stand-in, whatever else the process has loaded)
+    if fresh:        # the product build's host objects: only the stand-ins are compiled
+        mos = []
+        for i, m in enumerate(mocks):
+            mos.append("%s.%d.o" % (out[:-3], i))
+            subprocess.check_call(["hipcc"] + flags + ["-c", m, "-o", mos[-1]])
+        subprocess.check_call(["g++", "-shared", "-Wl,-Bsymbolic", "-o", out] + mos + objs + link + ["-lpthread", "-lm"])
+    else:
+        subprocess.check_call(["hipcc"] + flags + ["-shared", "-Wl,-Bsymbolic", "-o", out] + mocks + srcs + link + ["-lpthread", "-lm"])
+
+
+@pytest.fixture(scope="module")
+def g(tmp_path_factory):
+    """gnuspeech_amd bound to the host-mock library for the tests of this module, and back to the product afterwards"""
+    import gnuspeech_amd
+    from gnuspeech_amd import _capi
+    out = str(tmp_path_factory.mktemp("hostmock_events") / "libtrm_hostmock_events.so")
+    _build(out, ["hip_host_mock.cc", "hip_host_mock_events.cc"])
+    saved = (_capi._lib, _capi.LIB_PATH)
+    _capi._lib, _capi.LIB_PATH = None, out
+    try:
+        assert _capi.lib().trm_device_count() == 1
+        yield gnuspeech_amd
+    finally:
+        gc.collect()             # (streams of the stand-in are destroyed by the stand-in)
+        _capi._lib, _capi.LIB_PATH = saved
+
+
+@pytest.fixture(params=["quad", "wide"])
+def form(request, monkeypatch):
+    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
+    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
+    return request.param
+
+
+def test_host_engine_frames_step_by_step(g, form):
+    T.check_frames(g, form)
+
+
+@pytest.mark.parametrize("mode", ["framework", "tract"])
+def test_host_engine_run_equals_push_and_finish(g, form, mode):
+    T.check_pcm(g, form, mode)
+
+
+def test_host_engine_mixed_actions_and_independence(g, form):
+    T.check_mixed_actions(g, form)
+
+
+def test_host_engine_abort_and_reuse(g, form):
+    T.check_abort_and_reuse(g, form)
+
+
+def test_host_engine_refusals(g, form):
+    T.check_refusals(g, form)
+
+
+def test_host_engine_device_entry_and_growing_pool(g, form):
+    """trm_mixed_stream_step_device with null frames gives the host entry's bits; and lists set again and again, each longer than
+    the one before, make the stream's pool of events grow while another group is in the middle of its list: that group's frames
+    stay the oracle's."""
+    def device_entry(s, acts, n):
+        a = s._actions(acts)
+        counts = s._counts(a, n)
+        pitch = max(int(counts.max()), 1) + 3
+        out = np.full((s.nvoices, pitch), 7.0, dtype=np.float32)
+        mx = np.full(s.nvoices, -1.0, dtype=np.float32)
+        nout = np.zeros(s.ngroups, dtype=np.uint32)
+        assert g.lib().trm_mixed_stream_step_device(s._h, a.ctypes.data, None, n, out.ctypes.data, pitch, nout.ctypes.data, mx.ctypes.data,
+                                                    None) == 0, g.lib().trm_last_error()
+        assert np.array_equal(nout.astype(np.int64), counts)
+        nv = nout[s._vgroup]
+        for j in range(s.nvoices):
+            assert np.all(out[j, nv[j]:] == 7.0)         # nothing past a voice's samples
+            out[j, nv[j]:] = 0.0
+        return out[s.inverse], nv[s.inverse], mx[s.inverse]
+    T.check_pcm(g, form, "framework", device_entry=device_entry)
+    # the pool grows under a running group
+    rng = np.random.default_rng(5)
+    s, groups = T.new_stream(g, form)
+    lists = T.group_lists(g)
+    ref = T.reference(lists)
+    s.set_events(3, lists[3])
+    v3 = int(np.flatnonzero(groups == 3)[0])
+    rows = []
+    for k in range(T.GROUP_F[3] // 7 + 1):
+        n = 40 * (k + 1)
+        t = np.arange(n, dtype=np.uint32) * 4
+        _, v = T.speechlike(t, rng.uniform(0, 1, (n, 36)))
+        s.set_events(4, [T.Lists(g, t, v, T.intonation())])      # one list for the three voices, longer every time
+        assert s.frames_left(4) == n - 1
+        s.step({3: "run"}, nframes=7)
+        rows.append(s.last_frames(v3))
+    assert s.frames_left(3) == 0
+    assert np.array_equal(np.concatenate(rows).view(np.uint32), ref[3][0].view(np.uint32))
+
+
+def test_library_without_the_track_kernel_refuses_run_only(tmp_path, monkeypatch):
+    """The host units with the first stand-in alone -- no track launcher installed: a RUN step fails with an error text, and
+    everything else works (tests/test_group_stream_host.py runs on such a library)."""
+    import gnuspeech_amd
+    from gnuspeech_amd import _capi
+    monkeypatch.setenv("TRM_TUBE_KERNEL", "quad")
+    out = str(tmp_path / "libtrm_hostmock_plain.so")
+    _build(out, ["hip_host_mock.cc"])
+    saved = (_capi._lib, _capi.LIB_PATH)
+    _capi._lib, _capi.LIB_PATH = None, out
+    try:
+        g = gnuspeech_amd
+        s, groups = T.new_stream(g, "quad")
+        lists = T.group_lists(g)
+        s.set_events(0, lists[0])
+        assert s.frames_left(0) == T.GROUP_F[0]
+        with pytest.raises(g.TrmError) as ei:
+            s.step({0: "run"}, nframes=7)
+        assert ei.value.code == _capi.TRM_EHIP and "track kernel" in str(ei.value)
+        assert s.frames_left(0) == T.GROUP_F[0] and not s.is_open(0)
+        pcm, ns, mx = s.step({0: "finish", 1: "push"}, np.zeros((groups.size, 3, 16), dtype=np.float32))
+        assert s.frames_left(0) == 0 and s.is_open(1) and ns[groups == 1][0] > 0
+        del s
+        gc.collect()
+    finally:
+        _capi._lib, _capi.LIB_PATH = saved
