@@ -1035,11 +1035,8 @@ int trm_multi_synthesize_host_int16(trm_multi *m, size_t nvoices, const float *f
 float trm_drift_seed_after(float seed, size_t ngenerated)
 {
     // MMDriftGenerator.m:65-70 in float, one rounding per operation (x86-64 semantics, like the kernel and the oracle)
-    volatile float sd = seed != 0.0f ? seed : 0.7892347f;
-    for (size_t i = 0; i < ngenerated; i++) {
-        volatile float temp = sd * 377.0f;
-        sd = temp - (float)(int32_t)temp;
-    }
+    float sd = trm::track_seed_start(seed);
+    for (size_t i = 0; i < ngenerated; i++) sd = trm::track_seed_step(sd);
     return sd;
 }
 
@@ -1048,12 +1045,11 @@ int trm_events_count_frames(const uint32_t *times, size_t n, const trm_intonatio
     if (!s || !nframes || (n && !times)) return fail(TRM_EINVAL, "null argument");
     *nframes = 0;
     if (n < 2) return TRM_OK;
-    uint64_t start = s->startTime_ms, end = s->endTime_ms;
-    if (start == 0 && end == 0) end = ~0ull;                      // EventList.m:892-894
+    const trm::TrackRange range = trm::track_range(*s);
     size_t i = 1, count = 0;
     uint64_t t = 0, nextTime = times[1];
     while (i < n) {                                               // the time stepping of EventList.m:970-1027
-        if (t >= start && t <= end) count++;
+        if (trm::track_emits(range, t)) count++;
         t += 4;
         if (t >= nextTime) {
             i++;

@@ -6,6 +6,7 @@
 
 #include "../../include/trm_c_api.h"
 #include "trm_lane.h"
+#include "trm_tracks_lane.h"
 
 namespace trm {
 
@@ -255,13 +256,7 @@ hipError_t launch_tracks_mixed(const MixedTrackArgs &a, hipStream_t stream);
 // the utterance opens}.  The wave writes the voice's rows of the step's tube launch -- frames[voice][0] = the lead row (the
 // frame the period before ended on; the first generated frame where the utterance opens), rows 1 .. the generated frames --
 // and the voice's last frame, as trm_grp_prep_kernel does for the groups that push.  The voice's record lives in lanes / head.
-constexpr uint32_t kTrackRunOpening = 0x80000000u;
-struct TrackRunHead {
-    uint32_t event, emitted;          // the event the time loop stands at; frames emitted so far
-    uint32_t time_lo, time_hi;        // the loop's current time (ms)
-    float seed, prev;                 // MMDriftGenerator's seed and its filter's last value
-    uint32_t pad[2];
-};
+// (kTrackRunOpening and TrackRunHead: trm_tracks_lane.h, where the host model of the generator shares them.)
 struct TrackRunArgs {
     const __attribute__((address_space(4))) uint32_t *event_times;      // the stream's lists: voice v's events at event_offset[v]
     const double *event_values;

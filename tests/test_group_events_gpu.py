@@ -70,3 +70,61 @@ def test_refusals(g, form):
     """6. set_events on an open group, unequal counts, F = 0, RUN without events, PUSH over unconsumed events, null frames with a
     PUSH group."""
     T.check_refusals(g, form)
+
+
+def test_three_generators_agree(g):
+    """7. One arithmetic (gnuspeech_amd/csrc/trm_tracks_lane.h), three kernels: trm_tracks_kernel (a TRMBatch, one launch per
+    setting), trm_tracks_mixed_kernel (a TRMMixedBatch, one launch) and trm_tracks_run_kernel (a grouped stream stepped with "run"
+    at 1 and at 7 frames per step) give the same frame bits for the same lists, and those are the oracle's: a list with irregular
+    times, a NaN-heavy one, one with smooth intonation and drift, one with a time range."""
+    import torch
+    from test_events import random_events
+    rng = np.random.default_rng(58)          # (a list whose late deltas stay finite: the stream's tube consumes the frames)
+    n = 20
+    irregular = np.concatenate([[0], np.cumsum(rng.integers(2, 11, size=n - 1))]).astype(np.uint32)     # no multiples of 4 ms, several per frame
+    voices = [
+        T.Lists(g, *T.speechlike(irregular, random_events(rng, n)[1], offsets=True), T.intonation(pitch=-7.25)),
+        T.Lists(g, *T.speechlike(*random_events(rng, 30, span=16, nan_frac=0.85)), T.intonation(macro=0, pitch=-3.0)),
+        T.Lists(g, *T.speechlike(*random_events(rng, 25, span=20, smooth=True)), T.intonation(smooth=1, drift=1, dev=1.3, cutoff=2.5, seed=0.3125)),
+        T.Lists(g, *T.speechlike(*random_events(rng, 22, span=24)), T.intonation(drift=1, start=20, end=200)),
+    ]
+    want = [l.frames() for l in voices]
+    assert all(len(l.t) <= 30 and 1 <= w.shape[0] <= 150 for l, w in zip(voices, want))
+    assert np.any(irregular % 4) and np.any(np.diff(irregular) < 4) and want[3].shape[0] == 46         # frames at 20 .. 200 ms
+    assert all(np.all(np.isfinite(w)) for w in want)                       # (the stream's tube consumes them)
+    same = lambda a, b: a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    sets = [0, 1, 2, 0]
+    # the batch generator: one launch per setting
+    b = g.TRMBatch(T.sets(g)[0], device=0)
+    for v, l in enumerate(voices):
+        st = b.prepare_events_device([l.arrays()], l.settings())
+        b.generate_frames_device(st)
+        torch.cuda.synchronize()
+        assert int(st["nframes_generated"].cpu().numpy()[0]) == want[v].shape[0], v
+        assert same(st["frames"].cpu().numpy()[:want[v].shape[0]], want[v]), ("batch", v)
+    # the mixed-parameter instance: one launch
+    m = g.TRMMixedBatch(T.sets(g), device=0)
+    st = m.prepare_events_device([l.arrays() for l in voices], sets, [l.settings() for l in voices])
+    m.generate_frames_device(st)
+    torch.cuda.synchronize()
+    frames, ngen, foff = st["frames"].cpu().numpy(), st["nframes_generated"].cpu().numpy(), st["frame_offset"].cpu().numpy()
+    for j, v in enumerate(st["order"]):
+        assert same(frames[int(foff[j]):int(foff[j]) + int(ngen[j])], want[int(v)]), ("mixed", int(v))
+    # the resumable instance: every voice a group of its own, all running from the first step
+    for q in (1, 7):
+        s = g.TRMGroupedStream(T.sets(g), sets, [0, 1, 2, 3], device=0, ngroups=4)
+        for gr, l in enumerate(voices):
+            s.set_events(gr, [l])
+        got = [[] for _ in voices]
+        steps = 0
+        while any(s.frames_left(gr) or s.is_open(gr) for gr in range(4)):
+            left = [s.frames_left(gr) for gr in range(4)]
+            s.step({gr: "run" for gr in range(4)}, nframes=q)
+            for v in range(4):
+                rows = s.last_frames(v)
+                assert rows.shape[0] == min(q, left[v]), (q, steps, v)
+                got[v].append(rows)
+            steps += 1
+            assert steps <= 160
+        for v in range(4):
+            assert same(np.concatenate(got[v]), want[v]), ("run", q, v)
