@@ -93,6 +93,7 @@ struct trm_stream_engine {
     DevBuf<double2> dTrkLanes;               // the generator's record: [nvoices][64] {value, delta} ...
     DevBuf<trm::TrackRunHead> dTrkHead;      // ... and [nvoices] heads (trm_kernels.h: TrackRunArgs)
     uint64_t evUsed = 0;                     // events of the pool handed out
+    uint64_t evCap = 0;                      // events the pool holds: what BOTH its buffers have room for (events_room)
     ~trm_stream_engine()
     {
         for (StepCopy &c : stepCopies) {
@@ -1026,7 +1027,7 @@ size_t trm_mixed_stream_group_samples_for(const trm_mixed_stream *s, size_t grou
 // caller has waited for the device; group `skip`'s lists are the ones about to be replaced).
 static int events_room(trm_stream_engine *s, size_t skip, uint64_t need)
 {
-    if (s->evUsed + need <= s->dEvTimes.cap && s->dEvTimes.p) return TRM_OK;
+    if (s->evUsed + need <= s->evCap) return TRM_OK;
     uint64_t live = 0;
     for (size_t g = 0; g < s->gev.size(); g++)
         if (g != skip && s->gev[g].state == trm_stream_engine::kEvPending) live += s->gev[g].times.size();
@@ -1037,6 +1038,8 @@ static int events_room(trm_stream_engine *s, size_t skip, uint64_t need)
     if ((rc = t.reserve(want)) || (rc = v.reserve(want * TRM_EVENT_VALUES))) return rc;
     std::swap(t.p, s->dEvTimes.p); std::swap(t.cap, s->dEvTimes.cap);
     std::swap(v.p, s->dEvValues.p); std::swap(v.cap, s->dEvValues.cap);
+    // (each buffer was given slack of its own, and the values' is the smaller one counted in events)
+    s->evCap = std::min<uint64_t>(s->dEvTimes.cap, s->dEvValues.cap / TRM_EVENT_VALUES);
     s->evUsed = 0;
     std::vector<uint64_t> off;
     for (size_t g = 0; g < s->gev.size(); g++) {

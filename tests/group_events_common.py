@@ -407,3 +407,133 @@ def check_refusals(g, form):
     assert L.trm_mixed_stream_group_set_events(m._h, 0, t.ctypes.data, v.ctypes.data, off.ctypes.data, nev.ctypes.data, C.byref(st)) == E
     assert L.trm_mixed_stream_group_frames_left(m._h, 0) == 0
     s.step({1: "finish", 4: "finish"})
+
+
+# ------------------------------------------------------------------------------------------------ 7. the pool of events
+# The lists of all groups of a stream lie in one device pool, which is allocated anew and refilled from the host copies when it
+# is full.  These checks fill it: far more events than the schedules above, so that the pool grows under lists that wait and run.
+def sized_list(rng, n, F):
+    """an event list of exactly n events (2 <= n <= F + 1) whose last lies at 4 * F ms: F frames"""
+    assert 2 <= n <= F + 1
+    inner = np.sort(rng.choice(np.arange(1, F), size=n - 2, replace=False)) if n > 2 else np.zeros(0, dtype=np.int64)
+    t = (np.concatenate([[0], inner, [F]]) * 4).astype(np.uint32)
+    return speechlike(t, random_events(rng, n)[1])
+
+
+def pool_stream(g, form, ngroups):
+    """`ngroups` groups of one voice each, dealt over the three sets: voice v is group v"""
+    s = g.TRMGroupedStream(sets(g), np.arange(ngroups) % len(PDS), np.arange(ngroups), device=0, ngroups=ngroups)
+    assert s.kernel == form
+    return s
+
+
+POOL_GROUPS, POOL_EVENTS = 64, 40
+
+
+def pool_lists(g):
+    """64 lists of 40 events and 96 .. 104 frames, no two alike, and the oracle's frames of each (computed once)"""
+    if "pool" not in _REF:
+        rng = np.random.default_rng(21)
+        kinds = [dict(), dict(drift=1, dev=0.8), dict(macro=0), dict(drift=1, seed=0.3125)]
+        lists = [Lists(g, *sized_list(rng, POOL_EVENTS, 96 + i % 9), intonation(pitch=float(rng.uniform(-14, 2)), **kinds[i % 4])) for i in range(POOL_GROUPS)]
+        frames = [l.frames() for l in lists]
+        assert all(f.shape == (96 + i % 9, 16) for i, f in enumerate(frames))
+        _REF["pool"] = (lists, frames)
+    lists, frames = _REF["pool"]
+    return [Lists(g, l.t, l.v, l.s) for l in lists], frames
+
+
+def _same_step(i, gr, pcm, ns, mx, rp, rn, rm, want):
+    assert ns[gr] == want == rn[gr], (i, gr, ns[gr], rn[gr], want)
+    assert eq(pcm[gr, :want], rp[gr, :want]) and eq(mx[gr], rm[gr]), (i, gr)
+
+
+def check_pool_fill(g, form, frames_of=None):
+    """64 one-voice groups are given 40 events each -- 2560 events, through the first pool and its first growth -- and then all
+    run 25 frames per step to the end.  Every set_events succeeds; last_frames of the groups `frames_of` (default: all),
+    concatenated, are the oracle's frames of the group's list bit for bit (the growth kept every waiting list and where it lies);
+    PCM, counts and maxima of all 64 voices are those of a second stream driven by "push" with the oracle's frames cut the same
+    way and then "finish"."""
+    lists, ref = pool_lists(g)
+    N = POOL_GROUPS
+    a, b = pool_stream(g, form, N), pool_stream(g, form, N)
+    F = [r.shape[0] for r in ref]
+    for gr in range(N):
+        a.set_events(gr, [lists[gr]])
+        assert a.frames_left(gr) == F[gr] and not a.is_open(gr), gr
+    frames_of = list(range(N) if frames_of is None else frames_of)
+    got = {gr: [] for gr in frames_of}
+    emitted = [0] * N
+    i = 0
+    while any(emitted[gr] < F[gr] or b.is_open(gr) for gr in range(N)):
+        want = [a.samples_for(gr, "run", 25) for gr in range(N)]
+        pcm, ns, mx = a.step({gr: "run" for gr in range(N)}, nframes=25)
+        q = [min(25, F[gr] - emitted[gr]) for gr in range(N)]
+        for gr in frames_of:
+            rows = a.last_frames(gr)
+            assert rows.shape[0] == q[gr], (i, gr)
+            got[gr].append(rows)
+        # the push-driven stream: the groups that push the same number of frames in one step, then the ones that finish
+        for qq in sorted(set(q) - {0}):
+            grs = [gr for gr in range(N) if q[gr] == qq]
+            f = np.zeros((N, qq, 16), dtype=np.float32)
+            for gr in grs:
+                f[gr] = ref[gr][emitted[gr]:emitted[gr] + qq]
+                assert b.samples_for(gr, "push", qq) == want[gr], (i, gr)
+            rp, rn, rm = b.step({gr: "push" for gr in grs}, f)
+            for gr in grs:
+                _same_step(i, gr, pcm, ns, mx, rp, rn, rm, want[gr])
+        fin = [gr for gr in range(N) if q[gr] == 0 and b.is_open(gr)]
+        if fin:
+            rp, rn, rm = b.step({gr: "finish" for gr in fin})
+            for gr in fin:
+                assert want[gr] > 0
+                _same_step(i, gr, pcm, ns, mx, rp, rn, rm, want[gr])
+        for gr in range(N):
+            if q[gr] == 0 and gr not in fin:
+                assert ns[gr] == 0 and mx[gr] == 0.0 and want[gr] == 0, (i, gr)
+            emitted[gr] += q[gr]
+            assert a.frames_left(gr) == F[gr] - emitted[gr] and a.is_open(gr) == b.is_open(gr), (i, gr)
+        i += 1
+        assert i < 10
+    assert not any(a.is_open(gr) or a.frames_left(gr) for gr in range(N))
+    for gr in frames_of:
+        have = np.concatenate(got[gr])
+        assert have.shape == ref[gr].shape and np.array_equal(have.view(np.uint32), ref[gr].view(np.uint32)), gr
+    assert np.any(ref[0] != 0.0)
+
+
+def check_growth_under_running_group(g, form):
+    """Group 3 runs 7 frames per step; between its steps group 4 is given one list for its three voices, longer every time
+    (40 * (k + 1) events), so the pool grows and is refilled several times under group 3.  Group 3's frames stay the oracle's bit
+    for bit, and its PCM, counts and maxima those of the stream driven by "push" and "finish"."""
+    rng = np.random.default_rng(5)
+    a, groups = new_stream(g, form)
+    b, _ = new_stream(g, form)
+    lists = group_lists(g)
+    ref = reference(lists)
+    a.set_events(3, lists[3])
+    v3 = int(np.flatnonzero(groups == 3)[0])
+    V, F = groups.size, GROUP_F[3]
+    rows, events = [], 0
+    for k in range(F // 7 + 2):
+        n = 40 * (k + 1)
+        t = np.arange(n, dtype=np.uint32) * 4
+        _, v = speechlike(t, rng.uniform(0, 1, (n, 36)))
+        a.set_events(4, [Lists(g, t, v, intonation())])          # one list for the three voices
+        events += 3 * n
+        assert a.frames_left(4) == n - 1 and not a.is_open(4)
+        want = a.samples_for(3, "run", 7)
+        pcm, ns, mx = a.step({3: "run"}, nframes=7)
+        q = min(7, F - 7 * k)
+        if q > 0:
+            rp, rn, rm = b.step({3: "push"}, push_frames(groups, V, 3, [ref[3][0][7 * k:7 * k + q]]))
+            rows.append(a.last_frames(v3))
+            assert rows[-1].shape[0] == q
+        else:
+            rp, rn, rm = b.step({3: "finish"})
+        assert want > 0
+        _same_step(k, v3, pcm, ns, mx, rp, rn, rm, want)
+        assert a.frames_left(3) == max(F - 7 * k - 7, 0) and a.is_open(3) == b.is_open(3)
+    assert not a.is_open(3) and events > 8 * 1024                # (several pools' worth)
+    assert np.array_equal(np.concatenate(rows).view(np.uint32), ref[3][0].view(np.uint32))

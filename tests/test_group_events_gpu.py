@@ -72,6 +72,19 @@ def test_refusals(g, form):
     T.check_refusals(g, form)
 
 
+def test_pool_fill_on_the_device(g, form):
+    """8. 64 one-voice groups x 40 events: more events than the stream's first pool holds, so the pool grows and is refilled under
+    lists that wait.  Every set_events succeeds; the frames of groups 0, 31, 32, 33 and 63 are the oracle's; PCM, counts and
+    maxima of all 64 voices are those of the stream driven by "push" and "finish"."""
+    T.check_pool_fill(g, form, frames_of=(0, 31, 32, 33, 63))
+
+
+def test_pool_grows_under_a_running_group_on_the_device(g, form):
+    """9. Group 3 runs 7 frames per step while group 4 is given longer and longer lists between its steps: the pool is allocated
+    anew several times under group 3, whose frames and PCM do not change."""
+    T.check_growth_under_running_group(g, form)
+
+
 def test_three_generators_agree(g):
     """7. One arithmetic (gnuspeech_amd/csrc/trm_tracks_lane.h), three kernels: trm_tracks_kernel (a TRMBatch, one launch per
     setting), trm_tracks_mixed_kernel (a TRMMixedBatch, one launch) and trm_tracks_run_kernel (a grouped stream stepped with "run"

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import group_events_common as T
+import host_mock as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
@@ -65,6 +66,16 @@ def form(request, monkeypatch):
     return request.param
 
 
+@pytest.fixture(autouse=True)
+def heap_stays_clean(g):
+    """every test of this module is a bounds test too: the stand-in's checking heap (tests/_emul/hip_host_mock.cc) saw no copy,
+    memset or kernel span leave its block, and no guard zone was written"""
+    M.violations(g.lib())
+    yield
+    gc.collect()
+    M.assert_clean(g.lib())
+
+
 def test_host_engine_frames_step_by_step(g, form):
     T.check_frames(g, form)
 
@@ -94,11 +105,14 @@ def test_host_engine_device_entry_and_growing_pool(g, form):
         a = s._actions(acts)
         counts = s._counts(a, n)
         pitch = max(int(counts.max()), 1) + 3
-        out = np.full((s.nvoices, pitch), 7.0, dtype=np.float32)
-        mx = np.full(s.nvoices, -1.0, dtype=np.float32)
+        # (the entry's device pointers: blocks of the stand-in's heap, each of exactly its size)
+        d_out, d_mx = M.DeviceArray(g.lib(), (s.nvoices, pitch), np.float32, 7.0), M.DeviceArray(g.lib(), s.nvoices, np.float32, -1.0)
         nout = np.zeros(s.ngroups, dtype=np.uint32)
-        assert g.lib().trm_mixed_stream_step_device(s._h, a.ctypes.data, None, n, out.ctypes.data, pitch, nout.ctypes.data, mx.ctypes.data,
-                                                    None) == 0, g.lib().trm_last_error()
+        rc = g.lib().trm_mixed_stream_step_device(s._h, a.ctypes.data, None, n, d_out.ptr, pitch, nout.ctypes.data, d_mx.ptr, None)
+        out, mx = d_out.a.copy(), d_mx.a.copy()
+        d_out.free()
+        d_mx.free()
+        assert rc == 0, g.lib().trm_last_error()
         assert np.array_equal(nout.astype(np.int64), counts)
         nv = nout[s._vgroup]
         for j in range(s.nvoices):
@@ -148,7 +162,8 @@ def test_library_without_the_track_kernel_refuses_run_only(tmp_path, monkeypatch
         assert s.frames_left(0) == T.GROUP_F[0] and not s.is_open(0)
         pcm, ns, mx = s.step({0: "finish", 1: "push"}, np.zeros((groups.size, 3, 16), dtype=np.float32))
         assert s.frames_left(0) == 0 and s.is_open(1) and ns[groups == 1][0] > 0
-        del s
+        del s, ei                # (the traceback holds the stream: it must go while its own library is bound)
         gc.collect()
+        M.assert_clean(_capi.lib())
     finally:
         _capi._lib, _capi.LIB_PATH = saved

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_mock as M
 import test_group_stream_gpu as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,6 +60,16 @@ def stream_form(request, monkeypatch):
     T._CACHE.clear()
 
 
+@pytest.fixture(autouse=True)
+def heap_stays_clean(g):
+    """every test of this module is a bounds test too: the stand-in's checking heap (tests/_emul/hip_host_mock.cc) saw no copy,
+    memset or kernel span leave its block, and no guard zone was written"""
+    M.violations(g.lib())
+    yield
+    gc.collect()
+    M.assert_clean(g.lib())
+
+
 @pytest.mark.parametrize("mode", ["framework", "tract"])
 def test_host_engine_bit_for_bit_against_a_stream_per_group(g, mode):
     T.test_bit_for_bit_against_a_stream_per_group(g, mode)
@@ -75,20 +86,25 @@ def test_host_engine_refusals(g):
 @pytest.mark.parametrize("mode", ["framework", "tract"])
 def test_device_entry_equals_the_host_entry_at_one_pitch(g, mode):
     """trm_mixed_stream_step_device (grouped order, ONE pitch for the whole schedule, so that the steps without frames keep the shape
-    they find) returns the host entry's counts, maxima and samples, and writes nothing past a voice's samples."""
+    they find) returns the host entry's counts, maxima and samples, and writes nothing past a voice's samples.  The entry's
+    device pointers are blocks of the stand-in's heap, each of exactly its size."""
     sets, groups, fr, want = T._host_run(g, mode)
     s = g.TRMGroupedStream(T._sets(g), sets, groups, device=0, mode=mode, ngroups=T.G)
     frg = np.ascontiguousarray(fr[s.order])
     pitch = max(int(ns.max()) for _, ns, _ in want) + 9
     at = 0
+    d_out, d_mx = M.DeviceArray(g.lib(), (sets.size, pitch), np.float32), M.DeviceArray(g.lib(), sets.size, np.float32)
+    out, mx = d_out.a, d_mx.a
     for i, (n, acts) in enumerate(T.SCHEDULE):
         a = s._actions(acts)
-        out = np.full((sets.size, pitch), 7.0, dtype=np.float32)
-        mx = np.full(sets.size, -1.0, dtype=np.float32)
+        out[...] = 7.0
+        mx[...] = -1.0
         nout = np.zeros(T.G, dtype=np.uint32)
-        f = np.ascontiguousarray(frg[:, at:at + n]) if n else None
-        assert g.lib().trm_mixed_stream_step_device(s._h, a.ctypes.data, f.ctypes.data if n else None, n, out.ctypes.data, pitch,
-                                                    nout.ctypes.data, mx.ctypes.data, None) == 0, g.lib().trm_last_error()
+        d_f = M.DeviceArray(g.lib(), (sets.size, n, 16), np.float32, frg[:, at:at + n]) if n else None
+        rc = g.lib().trm_mixed_stream_step_device(s._h, a.ctypes.data, d_f.ptr if n else None, n, d_out.ptr, pitch, nout.ctypes.data, d_mx.ptr, None)
+        if n:
+            d_f.free()
+        assert rc == 0, g.lib().trm_last_error()
         pcm, ns, wm = want[i]
         nv = nout[s._vgroup]
         assert np.array_equal(nv, ns[s.order]), i
@@ -97,3 +113,6 @@ def test_device_entry_equals_the_host_entry_at_one_pitch(g, mode):
             assert np.array_equal(out[j, :nv[j]].view(np.uint32), pcm[v, :ns[v]].view(np.uint32)), (i, j)
             assert np.all(out[j, nv[j]:] == 7.0), (i, j)
         at += n
+    out = mx = None
+    d_out.free()
+    d_mx.free()
