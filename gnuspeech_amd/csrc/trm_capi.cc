@@ -470,20 +470,12 @@ double unsplit_cost(const trm_batch *b, size_t nvoices, int which)
     return wide_cost(b, (nvoices + 63) / 64);
 }
 
-// segments of an utterance of P control periods cut every `periods`: the first one is periods + warm long (it has no warm-up
-// of its own: with it that long every workgroup of the launch runs periods + warm control periods)
-uint32_t split_segments(uint32_t P, uint32_t periods, uint32_t warm)
-{
-    const uint32_t first = periods + warm;
-    return P <= first ? 1u : 1u + (P - first + periods - 1) / periods;
-}
-
 // workgroups of a time-split launch that have work: block by block (its longest voice, in control periods) the segments it
 // reaches -- what trm_seg_map_kernel counts on the device
 uint64_t busy_workgroups(const std::vector<uint32_t> &longest, uint32_t periods, uint32_t warm)
 {
     uint64_t n = 0;
-    for (uint32_t per : longest) n += split_segments(per, periods, warm);
+    for (uint32_t per : longest) n += trm::seg_count(per, periods, warm);
     return n;
 }
 
@@ -530,7 +522,7 @@ static int plan_time_split(const trm_batch *b, size_t nvoices, uint32_t max_nfra
     if (setting > 0) {
         periods = (uint32_t)setting;
         // a split asked for by name: in the form asked for by name (four lanes, or one voice per lane), else by size
-        const uint64_t wgsQ = (uint64_t)split_segments(P, periods, warm) * ((nvoices + 15) / 16);
+        const uint64_t wgsQ = (uint64_t)trm::seg_count(P, periods, warm) * ((nvoices + 15) / 16);
         pl.form = (quadOk && (byName == TRM_KERNEL_QUAD || (byName == TRM_KERNEL_AUTO && wgsQ <= (uint64_t)(b->cus > 0 ? b->cus : 256)))) ? TRM_KERNEL_QUAD
                                                                                                                                        : TRM_KERNEL_WIDE;
     } else {
@@ -546,7 +538,7 @@ static int plan_time_split(const trm_batch *b, size_t nvoices, uint32_t max_nfra
         for (uint32_t nseg = 2; nseg <= 4096 && P > warm; nseg++) {
             const uint32_t sp = (P - warm + nseg - 1) / nseg;          // the shortest segments that make `nseg` of them
             if (sp < minPeriods) break;
-            const uint64_t segs = split_segments(P, sp, warm);
+            const uint64_t segs = trm::seg_count(P, sp, warm);
             if (segs < 2) continue;
             // workgroups with work: per segment the blocks of 64 voices that reach it (they are launched first:
             // trm_seg_map_kernel) -- counted where the caller's lengths are known, else every block in every segment
@@ -565,10 +557,10 @@ static int plan_time_split(const trm_batch *b, size_t nvoices, uint32_t max_nfra
             }
         }
     }
-    if (periods == 0 || split_segments(P, periods, warm) < 2) return TRM_OK;      // one segment is the whole utterance
+    if (periods == 0 || trm::seg_count(P, periods, warm) < 2) return TRM_OK;      // one segment is the whole utterance
     {
         const std::vector<uint32_t> &longest = pl.form == TRM_KERNEL_QUAD ? longest16 : longest64;
-        pl.allBusy = !longest.empty() && busy_workgroups(longest, periods, warm) == (uint64_t)split_segments(P, periods, warm) * longest.size();
+        pl.allBusy = !longest.empty() && busy_workgroups(longest, periods, warm) == (uint64_t)trm::seg_count(P, periods, warm) * longest.size();
     }
     pl.periods = periods;
     pl.warm = warm;
@@ -680,7 +672,7 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
     b->lastSplitPeriods = pl.periods;
     b->lastSplitWarm = pl.periods ? pl.warm : 0;
     if (pl.periods) {
-        const uint32_t nseg = split_segments(max_nframes - 1, pl.periods, pl.warm);
+        const uint32_t nseg = trm::seg_count(max_nframes - 1, pl.periods, pl.warm);
         const uint32_t perWg = pl.form == TRM_KERNEL_QUAD ? 16u : 64u;
         const uint32_t wgPerSeg = (uint32_t)((nvoices + perWg - 1) / perWg);
         if ((uint64_t)nseg * wgPerSeg > 0x7FFFFFFFull / 64) return fail(TRM_ERANGE, "time split: too many segments");
@@ -692,13 +684,13 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
         ph.frames = d_frames; ph.frame_offset = d_frame_offset; ph.nframes = d_nframes;
         ph.period_adv = b->dPeriodAdv.p; ph.seg_phase = b->dSegPhase.p; ph.gate = b->dGate; ph.bw_floor = pl.bwFloor;
         ph.nvoices = (uint32_t)nvoices; ph.max_nframes = max_nframes; ph.nseg = nseg;
-        ph.seg_periods = pl.periods; ph.seg_warm = pl.warm; ph.seg_wg_per_seg = wgPerSeg; ph.seg_first = pl.periods + pl.warm;
+        ph.seg_periods = pl.periods; ph.seg_warm = pl.warm; ph.seg_wg_per_seg = wgPerSeg; ph.seg_first = trm::seg_first(pl.periods, pl.warm);
         ph.voices_per_wg = perWg;
         ph.seg_map = pl.allBusy ? nullptr : b->dSegMap.p; ph.block_frames = b->dBlockFrames.p;
         HIP_TRY(trm::launch_phase(b->c, ph, stream));
         trm::TubeArgs sa = a;
         sa.seg_periods = pl.periods; sa.seg_warm = pl.warm; sa.seg_wg_per_seg = wgPerSeg; sa.seg_grid = nseg * wgPerSeg;
-        sa.seg_first = pl.periods + pl.warm;
+        sa.seg_first = ph.seg_first;
         sa.seg_phase = b->dSegPhase.p;
         sa.seg_map = ph.seg_map;
         sa.gate = b->dGate; sa.gate_want = 0;

@@ -20,6 +20,7 @@
 #include "trm_io.h"
 #include "trm_kernels.h"
 #include "trm_setup.h"
+#include "trm_span.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -136,8 +137,7 @@ trm::ScaleArgs scale_args(const trm_batch *b, const float *pcm, const uint64_t *
 // What trm_batch's planner and trm_mixed's share: each fact has one definition, so the two paths cut a set's voices alike.
 // warm-up (tube samples) after which a tube started from rest has forgotten that it was; 0 = never
 uint32_t split_warm_samples(const trm::Const &c);
-// segments of an utterance of P control periods cut every `periods` (the first one periods + warm long)
-uint32_t split_segments(uint32_t P, uint32_t periods, uint32_t warm);
+// (segment boundaries and counts: trm_span.h)
 // workgroups with work: per block (its longest voice, in control periods) the segments it reaches
 uint64_t busy_workgroups(const std::vector<uint32_t> &longest, uint32_t periods, uint32_t warm);
 // predicted ms per second of speech (19 750 tube samples) of the one-voice-per-lane kernel / of a whole-utterance launch in form `which`

@@ -44,14 +44,14 @@ struct TubeArgs {
     unsigned long long *stamps;   // diagnostic builds only (TRM_STAMP); null in the product
     // Streaming: a chunk of a longer utterance.  Null for one-shot synthesis.
     //   stream_state   kStreamFloats floats per voice, carried from one chunk to the next
-    //   stream_flags   bit 0: first chunk (state ignored: the tube starts at rest, the converter with its 25 zeros
-    //                  of pre-roll); bit 1: last chunk (the converter's 2*pad zeros of flush are appended)
+    //   stream_flags   kStreamFirst: first chunk (state ignored: the tube starts at rest, the converter with its 25 zeros
+    //                  of pre-roll); kStreamFlush: last chunk (the converter's 2*pad zeros of flush are appended);
+    //                  kStreamTract: TRAcT's loop order (trm_span.h names the bits)
     //   stream_n_base  tube samples synthesized before this chunk; stream_k_base / stream_k_end: the chunk emits
     //                  converter outputs k_base <= k < k_end (global indices).  Same for every voice of the launch.
     //   A mixed stream (mix_map and stream_state): the sets' control periods and converter increments differ, so the launch
     //   passes what they share -- stream_n_base = control periods before the chunk, stream_k_end = control periods through
-    //   its end (stream_k_base unused) -- and each workgroup derives its set's bases: n_base = periods * controlPeriod,
-    //   k_base = the outputs whose read position lies before n_base, k_end likewise (the flush's formula on the last chunk).
+    //   its end (stream_k_base unused) -- and each workgroup derives its set's bases from them (trm_span.h: stream_range).
     //   lp_noise then arrives NOT advanced (the kernel adds its set's n_base).
     float *stream_state;
     uint32_t stream_flags, stream_n_base, stream_k_base, stream_k_end;
@@ -65,9 +65,7 @@ struct TubeArgs {
     // the kernel sums q = 1 .. its own segment (exact sums: osc_increment).  max_sample is folded with an atomic max
     // (zeroed by the launcher), number_samples written by segment 0.
     uint32_t seg_periods = 0, seg_warm = 0, seg_wg_per_seg = 0;
-    uint32_t seg_first = 0;           // control periods of segment 0 (= seg_periods + seg_warm: it needs no warm-up, so it is that much
-                                      // longer and every workgroup runs the same number of periods); segment s >= 1 starts at
-                                      // seg_first + (s - 1) * seg_periods
+    uint32_t seg_first = 0;           // control periods of segment 0 (trm_span.h: seg_first, seg_begin)
     uint32_t seg_grid = 0;            // workgroups of the launch: seg_wg_per_seg * (segments of the longest voice)
     const double *seg_phase = nullptr;
     // Device-side choice between two launches of one batch (time-split vs whole utterances): a kernel with a gate returns
@@ -96,11 +94,11 @@ struct TubeArgs {
     //   grp_active   workgroup w (wg_base included) runs map entry grp_active[w]: the entries that synthesize in this step,
     //                mix_grid of them (an entry that only exited would still hold its slot: trm_seg_map_kernel's note).  The
     //                one-voice-per-lane form's state block is the ENTRY's.
-    //   grp_clock    per map entry {control periods before the step, control periods through its end, bit 0: the utterance's
-    //                first chunk, bit 1: its flush, bit 3: no lead row; -}: stream_n_base, stream_k_end and the first two
-    //                bits of stream_flags of a mixed stream (bit 2, TRAcT order, stays the launch's stream_flags).
+    //   grp_clock    per map entry {control periods before the step, control periods through its end, kStreamFirst |
+    //                kStreamFlush | kClockNoLead (trm_span.h); -}: stream_n_base, stream_k_end and the first two bits of
+    //                stream_flags of a mixed stream (kStreamTract stays the launch's stream_flags).
     //   frames       [nvoices][max_nframes][16]: row 0 of a voice is its lead row (the frame the period before ended on), rows
-    //                1 .. the pushed frames; an entry runs the rows it has periods for plus one, from row 1 where bit 3 says so
+    //                1 .. the pushed frames; an entry runs the rows it has periods for plus one, from row 1 where kClockNoLead says so
     //                (an utterance opening in Framework order).  frame_offset and nframes are not read.
     // Both tables are typed in the constant address space (ConstTable's reason): their addresses depend on the workgroup alone.
     const __attribute__((address_space(4))) uint32_t *grp_active = nullptr;

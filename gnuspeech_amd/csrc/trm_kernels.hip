@@ -19,6 +19,7 @@
 #include "trm_devutil.h"
 #include "trm_kernels.h"
 #include "trm_lane.h"
+#include "trm_span.h"
 
 // Timing experiments live behind ONE switch (-DTRM_EXPERIMENTS, tools/build_variant.sh); the product build defines none of them.
 #ifndef TRM_EXPERIMENTS
@@ -163,28 +164,18 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     int role = 0;
     for (int i = 0; i < kRoles; i++) role = waveIdx == i ? rolePerm[i] : role;
     // a grouped stream: the workgroup's map entry (it keys the state too) from the list of those that run, and the entry's
-    // clock, both at addresses that depend on the workgroup alone (scalar loads, like the map entry itself).  What follows
-    // from the clock is named through lambdas evaluated where the other instances read the launch's values: those instances'
-    // instructions stay where they were.
-    auto entry_of = [&](uint32_t w) {
-        if constexpr (kGrp) return *(const uint32_t *)(A.grp_active + w);
-        else return w;
-    };
-    const uint32_t wg = entry_of(A.wg_base + blockIdx.x);          // (a large batch is launched in slices: launch_tube)
+    // clock in place of the launch's, both at addresses that depend on the workgroup alone (scalar loads, like the map entry)
+    uint32_t entryOf = A.wg_base + blockIdx.x;       // (a large batch is launched in slices: launch_tube)
     uint4 clk = make_uint4(0u, 0u, 0u, 0u);
-    if constexpr (kGrp) clk = *(const uint4 *)(A.grp_clock + wg);
-    auto stream_bits = [&]() {       // bit 0: first chunk, bit 1: flush
-        if constexpr (kGrp) return clk.z;
-        else return A.stream_flags;
-    };
-    auto periods_before = [&]() {    // (mixed streams: control periods before / through the chunk)
-        if constexpr (kGrp) return clk.x;
-        else return A.stream_n_base;
-    };
-    auto periods_through = [&]() {
-        if constexpr (kGrp) return clk.y;
-        else return A.stream_k_end;
-    };
+    uint32_t streamBits = A.stream_flags, perBefore = A.stream_n_base, perThrough = A.stream_k_end;     // (mixed streams: control periods before / through the chunk)
+    if constexpr (kGrp) {
+        entryOf = *(const uint32_t *)(A.grp_active + entryOf);
+        clk = *(const uint4 *)(A.grp_clock + entryOf);
+        streamBits = clk.z;
+        perBefore = clk.x;
+        perThrough = clk.y;
+    }
+    const uint32_t wg = entryOf;
     // time-split: workgroup -> (segment, block of 64 voices; a mixed launch: map entry)
     uint32_t seg = 0, vblock = wg;
     if (kSeg) {
@@ -207,29 +198,29 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     const uint32_t v = laneValid ? vRaw : vEnd - 1;
     const uint32_t CP = (uint32_t)C.controlPeriod;
     const uint32_t inc = C.timeRegisterIncrement;
-    // converter outputs with a read position before tube sample `end`: k < outputs_before(end) (trm_capi.cc outputs_through)
-    auto outputs_before = [&](uint64_t end) { return end == 0 ? 0u : (uint32_t)(((end << 16) - 1) / inc + 1); };
-
-    // segment s covers the control periods seg_begin(s) .. seg_begin(s + 1): the first segment is a warm-up longer than the
-    // others (it has none of its own), so that every workgroup of the launch runs the same number of periods
-    // (a mixed launch: the warm-up is the set's own, mix.w; the segment length is the launch's)
-    auto seg_begin = [&](uint32_t sgm) {
+    // (trm_span.h: converter outputs, segment boundaries and stream ranges, in this launch's 32-bit indices)
+    auto outputs_before = [&](uint64_t end) { return (uint32_t)trm::outputs_before(end, inc); };
+    auto outputs_with_flush = [&](uint64_t ntube) { return (uint32_t)trm::outputs_with_flush(ntube, (uint32_t)C.padSize, inc); };
+    uint32_t nfrOf;
+    if constexpr (kGrp) nfrOf = perThrough - perBefore + 1u;        // (the rows of the entry's step: its control periods + 1)
+    else nfrOf = min(A.nframes[v], A.max_nframes);
+    const uint32_t nfrAll = nfrOf;
+    // the frames this launch runs for this lane: the utterance's (chunk's), or those of the workgroup's segment with its warm-up
+    // (a mixed launch: the warm-up is the set's own, mix.w; the segment length is the launch's.  Its boundaries are seg_begin's
+    // with first = seg_first(S, mix.w), spelled W + s * S here: with the other spelling this instance, trm_mixseg_kernel, came
+    // out one instruction longer and missed its timing bar, profiles/ab_span_refactor.txt)
+    uint32_t segWarm = A.seg_warm;
+    if constexpr (kMixSeg) segWarm = mix.w;
+    auto seg_begin_of = [&](uint32_t sgm) {
         if constexpr (kMixSeg) return sgm == 0 ? 0u : mix.w + sgm * A.seg_periods;
-        else return sgm == 0 ? 0u : A.seg_first + (sgm - 1) * A.seg_periods;
+        else return seg_begin(sgm, A.seg_first, A.seg_periods);
     };
-    // (a grouped stream: the rows of the entry's step -- its control periods + 1)
-    auto rows_of = [&](uint32_t vv) {
-        if constexpr (kGrp) return clk.y - clk.x + 1u;
-        else return min(A.nframes[vv], A.max_nframes);
-    };
-    const uint32_t nfrAll = rows_of(v);
-    // the frames this launch runs for this lane: the utterance's, or those of the workgroup's segment with its warm-up
     uint32_t nfr = nfrAll, segFrame0 = 0, segOutEnd = 0;
     bool segLast = true;
     if (kSeg) {
         const uint32_t nper = nfrAll > 0 ? nfrAll - 1 : 0;
-        const uint32_t pLo = seg_begin(seg), pEnd = seg_begin(seg + 1);
-        segFrame0 = pLo > (kMixSeg ? mix.w : A.seg_warm) ? pLo - (kMixSeg ? mix.w : A.seg_warm) : 0u;     // (uniform)
+        const uint32_t pLo = seg_begin_of(seg), pEnd = seg_begin_of(seg + 1);
+        segFrame0 = seg_warm_start(pLo, segWarm);                                  // (uniform)
         if (seg > 0 && pLo >= nper) nfr = 0;                                       // the voice ended before this segment
         else if (nfrAll > 0) {
             const uint32_t pHi = pEnd < nper ? pEnd : nper;
@@ -243,16 +234,16 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     // (nfrMax-1) control periods, then the converter's 2*pad zero flush (TRMRingBuffer.m:85-93).
     // Lanes whose utterance is shorter than the group's longest keep stepping on their last frame;
     // the tube stage hands zeros to the converter past a voice's own end.
-    const bool sFirst = !kStream || (stream_bits() & 1u), sLast = !kStream || (stream_bits() & 2u);
-    const bool sHold = kStream && (A.stream_flags & 4u);       // TRAcT's loop order: a period runs on the frame that ends it, held
+    const bool sFirst = !kStream || (streamBits & kStreamFirst), sLast = !kStream || (streamBits & kStreamFlush);
+    const bool sHold = kStream && (A.stream_flags & kStreamTract);       // TRAcT's loop order: a period runs on the frame that ends it, held
     // (segments: a workgroup's lanes either end inside the segment -- their flush follows -- or run to its end: nTotal
     // carries the flush's 2*pad samples either way, lanes that go on stop emitting at segOutEnd)
     // (a mixed stream: stream_n_base / stream_k_end count control periods, the set's tube samples and outputs follow from them)
-    const uint32_t nBase = kMixStream ? periods_before() * CP : kStream ? A.stream_n_base : kSeg ? segFrame0 * CP : 0u;
-    const uint32_t kBase = kMixStream ? outputs_before((uint64_t)nBase) : kStream ? A.stream_k_base : kSeg ? outputs_before((uint64_t)seg_begin(seg) * CP) : 0u;
-    const uint32_t kEnd = !kMixStream ? A.stream_k_end
-                        : sLast ? (uint32_t)((((uint64_t)nBase + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc)
-                                : outputs_before((uint64_t)periods_through() * CP);
+    StreamRange sr = {0, 0, 0, 0};
+    if constexpr (kMixStream) sr = stream_range(perBefore, perThrough, sLast, CP, inc, (uint32_t)C.padSize);
+    const uint32_t nBase = kMixStream ? (uint32_t)sr.nBase : kStream ? A.stream_n_base : kSeg ? segFrame0 * CP : 0u;
+    const uint32_t kBase = kMixStream ? (uint32_t)sr.kBase : kStream ? A.stream_k_base : kSeg ? outputs_before((uint64_t)seg_begin_of(seg) * CP) : 0u;
+    const uint32_t kEnd = kMixStream ? (uint32_t)sr.kEnd : A.stream_k_end;
     // this voice's state record: per workgroup a block of [kStreamFloats fields][64 lanes] floats -- a wave's 64 lanes touch
     // 64 consecutive floats per field (voice-major records cost 64 cache lines per field and instruction) and a field is a
     // CONSTANT 256 bytes from the one before (one base address per lane: per-field 64-bit strides cost the streaming
@@ -288,11 +279,10 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     const uint32_t nSteps = nTotal > 0 ? (nTotal + kTB - 1) / kTB + 3 + 2 * ((kCvtCols * inc / 65536u) / kTB + 2) + 4 : 0;
     // a voice without frames (a silent no-op, TRMTubeModel.m:274-277) reads row 0 of the buffer
     // (a grouped stream: max_nframes rows per voice, the lead row first; an utterance that opens in Framework order has none)
-    auto frames_of = [&](uint32_t vv) {
-        if constexpr (kGrp) return A.frames + ((size_t)vv * A.max_nframes + ((clk.z >> 3) & 1u)) * 16;
-        else return A.frames + (nfr > 0 ? (A.frame_offset[vv] + segFrame0) * 16 : 0);
-    };
-    const float *frames = frames_of(v);
+    const float *framesOf;
+    if constexpr (kGrp) framesOf = A.frames + ((size_t)v * A.max_nframes + ((streamBits & kClockNoLead) ? 1u : 0u)) * 16;
+    else framesOf = A.frames + (nfr > 0 ? (A.frame_offset[v] + segFrame0) * 16 : 0);
+    const float *frames = framesOf;
     const uint32_t ntubeLane = nfr > 0 ? (nfr - 1) * CP : 0;
 
     for (int i = threadIdx.x; i < kWave * kYStride; i += kWave * kRoles) sY[i] = 0.0f;   // 25 zeros of pre-roll
@@ -539,7 +529,7 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
                 // a segment writes its own stretch of the voice's tube-rate row (global index nBase + n), not its warm-up's;
                 // the voice's last segment appends the flush
                 const uint32_t gn = nBase + n;
-                if (tubeOut && laneValid && gn >= seg_begin(seg) * CP && n < ntubeLane + (segLast ? 2u * (uint32_t)C.padSize : 0u))
+                if (tubeOut && laneValid && gn >= seg_begin_of(seg) * CP && n < ntubeLane + (segLast ? 2u * (uint32_t)C.padSize : 0u))
                     tubeOut[gn] = y;
             } else if (tubeOut && laneValid && n < ntubeLane + (sLast ? 2u * (uint32_t)C.padSize : 0u)) tubeOut[n] = y;
         };
@@ -571,14 +561,11 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
         // outputs of this launch per voice: the utterance's (TRMSampleRateConverter.m:160-173); a chunk's: global indices
         // kBase <= k < kEnd, the same for every voice of the workgroup
         uint32_t noutLane = 0;
-        if (nfr > 0) {
-            uint64_t total = (uint64_t)ntubeLane + 2ull * (uint32_t)C.padSize;
-            noutLane = (uint32_t)((total * 65536ull + inc - 1) / inc);
-        }
+        if (nfr > 0) noutLane = outputs_with_flush(ntubeLane);
         if (kStream) noutLane = kEnd - kBase;
         uint32_t noutAll = 0;                   // (segments: the whole utterance's count)
         if (kSeg) {
-            if (nfrAll > 0) noutAll = (uint32_t)((((uint64_t)(nfrAll - 1) * CP + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc);
+            if (nfrAll > 0) noutAll = outputs_with_flush((uint64_t)(nfrAll - 1) * CP);
             noutLane = nfr > 0 ? (segLast ? noutAll : segOutEnd) - kBase : 0u;
         }
         if (!laneValid) noutLane = 0;
@@ -790,8 +777,7 @@ __global__ __launch_bounds__(256) void trm_phase_segment_kernel(const Const C, c
     const uint32_t nfr = min(P.nframes[v], P.max_nframes);
     const uint32_t nper = nfr > 0 ? nfr - 1 : 0;
     auto warm_start = [&](uint32_t sgm) {
-        const uint32_t p = sgm == 0 ? 0u : P.seg_first + (sgm - 1) * P.seg_periods;
-        return p > P.seg_warm ? p - P.seg_warm : 0u;
+        return seg_warm_start(seg_begin(sgm, P.seg_first, P.seg_periods), P.seg_warm);
     };
     uint32_t lo = warm_start(q), hi = warm_start(q + 1);
     lo = lo < nper ? lo : nper;
@@ -835,7 +821,7 @@ __global__ __launch_bounds__(kMapThreads) void trm_seg_map_kernel(const PhaseArg
         const uint32_t sgm = i / P.seg_wg_per_seg, blk = i - sgm * P.seg_wg_per_seg;
         if (sgm == 0) return true;
         const uint32_t nfr = P.block_frames[blk], nper = nfr > 0 ? nfr - 1 : 0;
-        return P.seg_first + (sgm - 1) * P.seg_periods < nper;
+        return seg_has_work(sgm, nper, P.seg_first, P.seg_periods);
     };
     uint32_t mine = 0;
     for (uint32_t i = lo; i < hi; i++) mine += has_work(i) ? 1u : 0u;

@@ -282,7 +282,7 @@ static int mixed_plan_split(const trm_mixed *m, const size_t *set_begin, uint32_
     };
     auto busy = [&](const std::vector<uint4> &map, const std::vector<uint32_t> &lng, uint32_t sp) {
         uint64_t n = 0;
-        for (size_t e = 0; e < map.size(); e++) n += split_segments(lng[e], sp, warm[map[e].x]);
+        for (size_t e = 0; e < map.size(); e++) n += trm::seg_count(lng[e], sp, warm[map[e].x]);
         return n;
     };
     uint32_t periods = 0;
@@ -311,7 +311,7 @@ static int mixed_plan_split(const trm_mixed *m, const size_t *set_begin, uint32_
     if (periods == 0) return TRM_OK;
     // (no voice reaches past its set's first segment: one segment is the whole utterance)
     bool any = false;
-    for (size_t s = 0; s < S; s++) any = any || (set_begin[s + 1] > set_begin[s] && split_segments(P, periods, warm[s]) >= 2);
+    for (size_t s = 0; s < S; s++) any = any || (set_begin[s + 1] > set_begin[s] && trm::seg_count(P, periods, warm[s]) >= 2);
     if (any) {
         periodsOut = periods;
         formOut = form;
@@ -423,14 +423,14 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
             uint32_t nsegMax = 0;
             for (size_t e = 0; e < map.size(); e++) {
                 map[e].w = warm[map[e].x];
-                nsegMax = std::max(nsegMax, split_segments(max_nframes - 1, split, map[e].w));
+                nsegMax = std::max(nsegMax, trm::seg_count(max_nframes - 1, split, map[e].w));
             }
             if ((uint64_t)nsegMax * map.size() > 0x7FFFFFFFull / 64) return fail(TRM_ERANGE, "time split: too many segments");
             for (int pass = 0; pass < 2; pass++)
                 for (uint32_t sgm = 0; sgm < nsegMax; sgm++)
                     for (size_t e = 0; e < map.size(); e++) {
-                        if (sgm >= split_segments(max_nframes - 1, split, map[e].w)) continue;
-                        const bool work = sgm < split_segments(longest[e], split, map[e].w);
+                        if (sgm >= trm::seg_count(max_nframes - 1, split, map[e].w)) continue;
+                        const bool work = trm::seg_has_work(sgm, longest[e], trm::seg_first(split, map[e].w), split);
                         if (work == (pass == 0)) m->hSegMap.push_back(make_uint2(sgm, (uint32_t)e));
                     }
             m->segRows = nsegMax;
@@ -497,8 +497,8 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
             ph.frames = d_frames; ph.frame_offset = d_frame_offset + lo; ph.nframes = d_nframes + lo;
             ph.period_adv = m->dPeriodAdv.p + lo * (size_t)max_nframes; ph.seg_phase = m->dSegPhase.p + entry * perWg; ph.gate = gate;
             ph.bw_floor = split_bw_floor(b, warm[s]);
-            ph.nvoices = (uint32_t)n; ph.max_nframes = max_nframes; ph.nseg = split_segments(max_nframes - 1, split, warm[s]);
-            ph.seg_periods = split; ph.seg_warm = warm[s]; ph.seg_wg_per_seg = m->mapEntries; ph.seg_first = split + warm[s];
+            ph.nvoices = (uint32_t)n; ph.max_nframes = max_nframes; ph.nseg = trm::seg_count(max_nframes - 1, split, warm[s]);
+            ph.seg_periods = split; ph.seg_warm = warm[s]; ph.seg_wg_per_seg = m->mapEntries; ph.seg_first = trm::seg_first(split, warm[s]);
             ph.voices_per_wg = perWg;
             HIP_TRY(trm::launch_phase(b->c, ph, stream));
             entry += (n + perWg - 1) / perWg;

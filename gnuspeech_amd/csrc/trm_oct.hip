@@ -22,6 +22,7 @@
 #include "trm_oct.h"
 #include "trm_quad.h"
 #include "trm_quad_dev.h"
+#include "trm_span.h"
 
 #ifndef TRM_EXPERIMENTS
 #undef TRM_OCT_ROLE_PERM
@@ -151,6 +152,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     const uint32_t nfrMax = wave_max_u32(nfr);
     const uint32_t CP = (uint32_t)C.controlPeriod;
     const uint32_t inc = C.timeRegisterIncrement;
+    auto outputs_with_flush = [&](uint64_t ntube) { return (uint32_t)trm::outputs_with_flush(ntube, (uint32_t)C.padSize, inc); };      // (trm_span.h)
     const uint32_t ntubeMax = nfrMax > 0 ? (nfrMax - 1) * CP : 0;
     // tube samples the tube stage produces: the utterance, then the converter's 2*pad zero flush (TRMRingBuffer.m:85-93)
     const uint32_t nTotal = nfrMax > 0 ? ntubeMax + 2u * (uint32_t)C.padSize : 0;
@@ -392,7 +394,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         uint32_t rowBlk = 0;
         bool rowsInFlight = false;
         float4 rq[4];
-        const uint32_t cvtOutputs = wave_max_u32(laneValid && nfr > 0 ? (uint32_t)((((uint64_t)ntubeLane + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc) : 0u);
+        const uint32_t cvtOutputs = wave_max_u32(laneValid && nfr > 0 ? outputs_with_flush(ntubeLane) : 0u);
         const uint32_t cvtBlocks = C.upsample ? (cvtOutputs + kCvtCols - 1) / kCvtCols : 0;
         STAMP_DECL
         for (uint32_t step = 0; step < nSteps; step++) {
@@ -614,10 +616,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         __builtin_amdgcn_s_setprio(TRM_OCT_PRIO_CVT);
         // ------------------------------------------------------------ convert (lane = output time), 8 voices
         uint32_t noutLane = 0;
-        if (nfr > 0) {
-            uint64_t total = (uint64_t)ntubeLane + 2ull * (uint32_t)C.padSize;
-            noutLane = (uint32_t)((total * 65536ull + inc - 1) / inc);
-        }
+        if (nfr > 0) noutLane = outputs_with_flush(ntubeLane);
         if (!laneValid) noutLane = 0;
         const uintptr_t myOut = reinterpret_cast<uintptr_t>(A.out + A.out_offset[v]);
         const uint32_t noutMax = wave_max_u32(noutLane);
@@ -731,7 +730,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         if (lane < kOV && ov < vEnd && C.upsample) {
             const uint32_t nf = min(A.nframes[ov], A.max_nframes);
             uint32_t nov = 0;
-            if (nf > 0) nov = (uint32_t)((((uint64_t)(nf - 1) * CP + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc);
+            if (nf > 0) nov = outputs_with_flush((uint64_t)(nf - 1) * CP);
             A.number_samples[ov] = nov;
             A.max_sample[ov] = myMax;
         }

@@ -24,6 +24,7 @@
 #include "trm_lane.h"
 #include "trm_quad.h"
 #include "trm_quad_dev.h"
+#include "trm_span.h"
 
 // Timing experiments (tools/bench_variants.sh) live behind ONE switch; the product build defines none of them.
 #ifndef TRM_EXPERIMENTS
@@ -167,14 +168,17 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         }
     }
     // mixed launch: the workgroup's parameter set (C read in place: a reference into the table) and voice range
-    // (a grouped stream: the entry from the list of those that run and its clock, at addresses that depend on the workgroup
-    // alone: scalar loads.  Plain variables set under `if constexpr`, no lambdas: in this file the lambdas moved instructions
-    // of the other instances, in trm_kernels.hip the variables did -- each file has what left its old kernels as they were.)
+    // (a grouped stream: the entry from the list of those that run, and the entry's clock in place of the launch's, both at
+    // addresses that depend on the workgroup alone: scalar loads)
     uint32_t entryOf = kMixSeg ? vblock : blockIdx.x;
     uint4 clk = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t streamBits = A.stream_flags, perBefore = A.stream_n_base, perThrough = A.stream_k_end;     // (mixed streams: control periods before / through the chunk)
     if constexpr (kGrp) {
         entryOf = *(const uint32_t *)(A.grp_active + entryOf);
         clk = *(const uint4 *)(A.grp_clock + entryOf);
+        streamBits = clk.z;
+        perBefore = clk.x;
+        perThrough = clk.y;
     }
     const uint4 mix = kMix ? A.mix_map[entryOf] : make_uint4(0u, 0u, 0u, 0u);
     const Const &C = kMix ? *(const Const *)(A.set_const + mix.x) : Carg;
@@ -184,33 +188,35 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     const uint32_t v = laneValid ? vRaw : vEnd - 1;
     const uint32_t CP = (uint32_t)C.controlPeriod;
     const uint32_t inc = C.timeRegisterIncrement;
-    auto outputs_before = [&](uint64_t end) { return end == 0 ? 0u : (uint32_t)(((end << 16) - 1) / inc + 1); };
-    // (a mixed launch: the warm-up is the set's own, mix.w; the segment length is the launch's -- the boundaries of
-    // trm_mixseg_kernel.  `if constexpr`: the other instances' lambda must not capture mix)
-    auto seg_begin = [&](uint32_t sgm) {
-        if constexpr (kMixSeg) return sgm == 0 ? 0u : mix.w + sgm * A.seg_periods;
-        else return sgm == 0 ? 0u : A.seg_first + (sgm - 1) * A.seg_periods;
-    };
-
+    // (trm_span.h: converter outputs, segment boundaries and stream ranges, in this launch's 32-bit indices)
+    auto outputs_before = [&](uint64_t end) { return (uint32_t)trm::outputs_before(end, inc); };
+    auto outputs_with_flush = [&](uint64_t ntube) { return (uint32_t)trm::outputs_with_flush(ntube, (uint32_t)C.padSize, inc); };
     uint32_t nfrOf;
-    if constexpr (kGrp) nfrOf = clk.y - clk.x + 1u;        // (the rows of the entry's step: its control periods + 1)
+    if constexpr (kGrp) nfrOf = perThrough - perBefore + 1u;        // (the rows of the entry's step: its control periods + 1)
     else nfrOf = min(A.nframes[v], A.max_nframes);
     const uint32_t nfrAll = nfrOf;
     // the frames this launch runs for this lane: the utterance's (chunk's), or those of the workgroup's segment with its warm-up
+    // (a mixed launch: the warm-up is the set's own, mix.w; the segment length is the launch's.  Its boundaries are seg_begin's
+    // with first = seg_first(S, mix.w), spelled W + s * S here as in trm_kernels.hip: with the other spelling this instance,
+    // trm_mixqseg_kernel, missed its timing bar, profiles/ab_span_refactor.txt)
+    uint32_t segWarm = A.seg_warm;
+    if constexpr (kMixSeg) segWarm = mix.w;
+    auto seg_begin_of = [&](uint32_t sgm) {
+        if constexpr (kMixSeg) return sgm == 0 ? 0u : mix.w + sgm * A.seg_periods;
+        else return seg_begin(sgm, A.seg_first, A.seg_periods);
+    };
     uint32_t nfr = nfrAll, segFrame0 = 0, segOutEnd = 0;
     bool segLast = true;
     if (kSeg) {
         const uint32_t nper = nfrAll > 0 ? nfrAll - 1 : 0;
-        const uint32_t pLo = seg_begin(seg), pEnd = seg_begin(seg + 1);
-        uint32_t segWarm = A.seg_warm;
-        if constexpr (kMixSeg) segWarm = mix.w;
-        segFrame0 = pLo > segWarm ? pLo - segWarm : 0u;
-        if (seg > 0 && pLo >= nper) nfr = 0;
+        const uint32_t pLo = seg_begin_of(seg), pEnd = seg_begin_of(seg + 1);
+        segFrame0 = seg_warm_start(pLo, segWarm);                                  // (uniform)
+        if (seg > 0 && pLo >= nper) nfr = 0;                                       // the voice ended before this segment
         else if (nfrAll > 0) {
             const uint32_t pHi = pEnd < nper ? pEnd : nper;
             nfr = pHi - segFrame0 + 1;
             segLast = pHi == nper;
-            segOutEnd = outputs_before((uint64_t)pHi * CP);
+            segOutEnd = outputs_before((uint64_t)pHi * CP);                        // (used when the voice goes on)
         }
     }
     const uint32_t nfrMax = wave_max_u32(nfr);
@@ -218,30 +224,22 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     // streaming: this launch is one chunk of a longer utterance (trm_kernels.h); one-shot = first and last at once
     constexpr bool streaming = kStream;
     constexpr bool saving = kStream && !kSeg;        // state out at the chunk's last sample (a segment starts from rest and leaves nothing)
-    bool sFirstOf = !streaming || kSeg || (A.stream_flags & 1u), sLastOf = !streaming || kSeg || (A.stream_flags & 2u);
-    uint32_t perBase = A.stream_n_base, perEnd = A.stream_k_end;         // (mixed streams: control periods before / through the chunk)
-    if constexpr (kGrp) {            // the entry's clock in place of the launch's
-        sFirstOf = clk.z & 1u;
-        sLastOf = clk.z & 2u;
-        perBase = clk.x;
-        perEnd = clk.y;
-    }
-    const bool sFirst = sFirstOf, sLast = sLastOf;
+    const bool sFirst = !streaming || kSeg || (streamBits & kStreamFirst), sLast = !streaming || kSeg || (streamBits & kStreamFlush);
     // TRAcT's loop (Applications/TRAcT/tube.c:1121-1136) reads the parameter set every sample and never interpolates: a
     // control period then runs on the frame that ENDS it, held (trm_stream_set_mode)
-    const bool sHold = streaming && !kSeg && (A.stream_flags & 4u);
+    const bool sHold = streaming && !kSeg && (A.stream_flags & kStreamTract);
     // (a mixed stream: stream_n_base / stream_k_end count control periods, the set's tube samples and outputs follow from them)
     constexpr bool kMixStream = kMix && kStream && !kSeg;
-    const uint32_t nBase = kSeg ? segFrame0 * CP : kMixStream ? perBase * CP : streaming ? A.stream_n_base : 0u;
-    const uint32_t kBase = kSeg ? outputs_before((uint64_t)seg_begin(seg) * CP) : kMixStream ? outputs_before((uint64_t)nBase) : streaming ? A.stream_k_base : 0u;
-    const uint32_t kEnd = !kMixStream ? A.stream_k_end
-                        : sLast ? (uint32_t)((((uint64_t)nBase + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc)
-                                : outputs_before((uint64_t)perEnd * CP);
+    StreamRange sr = {0, 0, 0, 0};
+    if constexpr (kMixStream) sr = stream_range(perBefore, perThrough, sLast, CP, inc, (uint32_t)C.padSize);
+    const uint32_t nBase = kSeg ? segFrame0 * CP : kMixStream ? (uint32_t)sr.nBase : streaming ? A.stream_n_base : 0u;
+    const uint32_t kBase = kSeg ? outputs_before((uint64_t)seg_begin_of(seg) * CP) : kMixStream ? (uint32_t)sr.kBase : streaming ? A.stream_k_base : 0u;
+    const uint32_t kEnd = kMixStream ? (uint32_t)sr.kEnd : A.stream_k_end;
     float *const st = saving ? A.stream_state + (size_t)v * kStreamFloats : nullptr;
     // outputs of this launch for this lane's voice (segments: its own stretch; the voice's last segment runs to the utterance's end)
     uint32_t noutSeg = 0, noutAll = 0;
     if (kSeg) {
-        if (nfrAll > 0) noutAll = (uint32_t)((((uint64_t)(nfrAll - 1) * CP + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc);
+        if (nfrAll > 0) noutAll = outputs_with_flush((uint64_t)(nfrAll - 1) * CP);
         noutSeg = (nfr > 0 && laneValid) ? (segLast ? noutAll : segOutEnd) - kBase : 0u;
     }
     // tube samples the tube stage produces: the utterance (chunk), then the converter's 2*pad zero flush (TRMRingBuffer.m:85-93)
@@ -250,7 +248,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     const uint32_t nSteps = nTotal > 0 ? (nTotal + kStepN - 1) / kStepN + 5 : 0;
     // (a grouped stream: max_nframes rows per voice, the lead row first; an utterance that opens in Framework order has none)
     const float *framesOf;
-    if constexpr (kGrp) framesOf = A.frames + ((size_t)v * A.max_nframes + ((clk.z >> 3) & 1u)) * 16;
+    if constexpr (kGrp) framesOf = A.frames + ((size_t)v * A.max_nframes + ((streamBits & kClockNoLead) ? 1u : 0u)) * 16;
     else framesOf = A.frames + (nfr > 0 ? (A.frame_offset[v] + segFrame0) * 16 : 0);
     const float *frames = framesOf;
     const uint32_t ntubeLane = nfr > 0 ? (nfr - 1) * CP : 0;
@@ -511,7 +509,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         bool rowsInFlight = false;
         float4 rq[4];
         const uint32_t cvtOutputs = kSeg ? wave_max_u32(noutSeg) : streaming ? kEnd - kBase
-                                              : wave_max_u32(laneValid && nfr > 0 ? (uint32_t)((((uint64_t)ntubeLane + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc) : 0u);
+                                              : wave_max_u32(laneValid && nfr > 0 ? outputs_with_flush(ntubeLane) : 0u);
         const uint32_t cvtBlocks = C.upsample ? (cvtOutputs + kCvtCols - 1) / kCvtCols : 0;
         STAMP_DECL
         for (uint32_t step = 0; step < nSteps; step++) {
@@ -771,8 +769,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         } else if (streaming) {
             noutLane = kEnd - kBase;
         } else if (nfr > 0) {
-            uint64_t total = (uint64_t)ntubeLane + 2ull * (uint32_t)C.padSize;
-            noutLane = (uint32_t)((total * 65536ull + inc - 1) / inc);
+            noutLane = outputs_with_flush(ntubeLane);
         }
         if (!laneValid) noutLane = 0;
         const uintptr_t myOut = reinterpret_cast<uintptr_t>(A.out + A.out_offset[v] + (kSeg ? kBase : 0u));
@@ -910,7 +907,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
             const uint32_t nf = min(A.nframes[ov], A.max_nframes);
             uint32_t nov = 0;
             if (streaming && !kSeg) nov = kEnd - kBase;
-            else if (nf > 0) nov = (uint32_t)((((uint64_t)(nf - 1) * CP + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc);
+            else if (nf > 0) nov = outputs_with_flush((uint64_t)(nf - 1) * CP);
             if (kSeg) {
                 // (max_sample was zeroed by the launcher; non-negative floats order like their bit patterns)
                 if (seg == 0) A.number_samples[ov] = nov;

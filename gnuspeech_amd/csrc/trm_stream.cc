@@ -3,7 +3,7 @@
 // One engine runs both objects.  A stream's voices belong to one or several parameter sets: one trm_batch per set (constants,
 // derived values, down-sampling rows; the first lends its noise sequence and stream) and one tube launch per chunk.  Progress is
 // kept as the count of control periods pushed so far -- the same for every set -- and a set's tube-sample base and output range
-// derive from it (stream_range).  What differs is behind one branch at the launch (stream_chunk_impl):
+// derive from it (unit_range: trm_span.h).  What differs is behind one branch at the launch (stream_chunk_impl):
 //   trm_stream        one set, the uniform streaming instances: the set's Const is the kernel argument, time is passed in tube
 //                     samples and outputs, the noise pointer is advanced
 //   trm_mixed_stream  the mixed instances: a block map {set, first voice, end voice} built at create -- the state is laid out for
@@ -17,7 +17,7 @@
 // and then RUN: the step plans it as a push of the frames it has left, at most the step's, which the resumable track kernel
 // (trm_tracks_run.hip) generates in place in front of the tube launch, and as the flush once they have run out.
 // What a chunk and a step share is stated once: the converter range of a run of
-// control periods (unit_range), the length limit (unit_too_long), the index arrays of a shape (stream_shape), the down-sampling
+// control periods (unit_range), the length limit (range_too_long), the index arrays of a shape (stream_shape), the down-sampling
 // launches around the tube launch (down_history_in, down_convert) and the ordering of calls across HIP streams (stream_ordered).
 #include "trm_host.h"
 
@@ -229,50 +229,28 @@ static int stream_set_mode(trm_stream_engine *s, int mode)
     return TRM_OK;
 }
 
-// converter outputs k with read position e_k = (k * inc) >> 16 <= lastSample, i.e. k < result
-static uint64_t outputs_through(uint64_t lastSamplePlusOne, uint32_t inc)
+// Voices of b's set that have run `periods` control periods and now run rows - 1 more (rows = frame rows per voice on the device),
+// or the flush: their tube samples and converter outputs in global indices (trm_span.h, as the kernels derive them)
+static trm::StreamRange unit_range(const trm_batch *b, uint64_t periods, uint64_t rows, bool flush)
 {
-    if (lastSamplePlusOne == 0) return 0;
-    return ((lastSamplePlusOne << 16) - 1) / inc + 1;
+    return trm::stream_range(periods, periods + rows - 1, flush, (uint32_t)b->d.controlPeriod, b->c.timeRegisterIncrement, (uint32_t)b->d.padSize);
 }
-
-// the converter outputs of voices of b's set that have run `periods` control periods and now run rows - 1 more (rows = frame
-// rows per voice on the device), or the flush: global indices k_base <= k < *kEnd
-static uint64_t unit_range(const trm_batch *b, uint64_t periods, uint64_t rows, bool flush, uint64_t *kEnd)
-{
-    const uint64_t CP = (uint64_t)b->d.controlPeriod, nBase = periods * CP;
-    const uint32_t inc = b->c.timeRegisterIncrement;
-    const uint64_t kBase = outputs_through(nBase, inc);
-    *kEnd = flush ? ((nBase + 2ull * (uint64_t)b->d.padSize) * 65536ull + inc - 1) / inc : outputs_through(nBase + (rows - 1) * CP, inc);
-    return kBase;
-}
-
-// set k's converter outputs of the next chunk
-static uint64_t stream_range(const trm_stream_engine *s, size_t k, uint64_t rows, bool flush, uint64_t *kEnd)
-{
-    return unit_range(s->sets[k], s->periods, rows, flush, kEnd);
-}
-
-// the last tube sample (+ 1, the flush included) of an utterance of b's set through `periods` control periods, and whether the
-// kernels' 32-bit indices no longer hold it or its outputs
-static uint64_t unit_n_hi(const trm_batch *b, uint64_t periods) { return periods * (uint64_t)b->d.controlPeriod + 2ull * (uint64_t)b->d.padSize; }
-static bool unit_too_long(const trm_batch *b, uint64_t periods, uint64_t kEnd) { return unit_n_hi(b, periods) + 512 > 0x7FFFFFFFull || kEnd > 0xFFFFFFFFull; }
+// whether the kernels' 32-bit indices no longer hold the range's last tube sample or its outputs
+static bool range_too_long(const trm::StreamRange &r) { return r.nHi + 512 > 0x7FFFFFFFull || r.kEnd > 0xFFFFFFFFull; }
 
 static size_t stream_samples_for_push(const trm_stream_engine *s, size_t set, size_t nframes)
 {
     if (!s || s->grouped || set >= s->sets.size() || nframes == 0) return 0;
     const bool leadRow = s->haveLast || s->mode == TRM_STREAM_MODE_TRACT;
-    uint64_t kEnd = 0;
-    const uint64_t kBase = stream_range(s, set, nframes + (leadRow ? 1 : 0), false, &kEnd);
-    return (size_t)(kEnd - kBase);
+    const trm::StreamRange r = unit_range(s->sets[set], s->periods, nframes + (leadRow ? 1 : 0), false);
+    return (size_t)(r.kEnd - r.kBase);
 }
 
 static size_t stream_samples_for_finish(const trm_stream_engine *s, size_t set)
 {
     if (!s || s->grouped || set >= s->sets.size() || !s->haveLast) return 0;
-    uint64_t kEnd = 0;
-    const uint64_t kBase = stream_range(s, set, 1, true, &kEnd);
-    return (size_t)(kEnd - kBase);
+    const trm::StreamRange r = unit_range(s->sets[set], s->periods, 1, true);
+    return (size_t)(r.kEnd - r.kBase);
 }
 
 // The index arrays of a shape: `rows` frame rows per voice, PCM rows `out_pitch` apart and, for the down-sampling sets, tube-rate
@@ -365,14 +343,14 @@ static int stream_chunk_impl(trm_stream_engine *s, const float *d_pushed, size_t
     bool anyDown = false;
     for (size_t k = 0; k < S; k++) {
         const trm_batch *b = s->sets[k];
-        kBase[k] = stream_range(s, k, rows, flush, &kEnd[k]);
+        const trm::StreamRange r = unit_range(b, s->periods, rows, flush);
+        kBase[k] = r.kBase; kEnd[k] = r.kEnd;
         if (nout) nout[k] = (uint32_t)(kEnd[k] - kBase[k]);
         if (s->begin[k + 1] == s->begin[k]) continue;
-        const uint64_t nHi = unit_n_hi(b, s->periods + Q);
-        if (unit_too_long(b, s->periods + Q, kEnd[k]))
+        if (range_too_long(r))
             return s->mixed ? fail(TRM_ERANGE, "stream too long (parameter set %zu)", k) : fail(TRM_ERANGE, "stream too long");
         maxCount = std::max(maxCount, kEnd[k] - kBase[k]);
-        noiseNeed = std::max(noiseNeed, nHi + 256u);
+        noiseNeed = std::max(noiseNeed, r.nHi + 256u);
         anyDown = anyDown || !b->c.upsample;
     }
     if (maxCount > 0 && (!d_out || out_pitch < maxCount))
@@ -407,7 +385,7 @@ static int stream_chunk_impl(trm_stream_engine *s, const float *d_pushed, size_t
             a.tube_offset = s->dTubeOff.p;
         }
         a.stream_state = s->dState.p;
-        a.stream_flags = (s->first ? 1u : 0u) | (flush ? 2u : 0u) | (tract ? 4u : 0u);
+        a.stream_flags = (s->first ? trm::kStreamFirst : 0u) | (flush ? trm::kStreamFlush : 0u) | (tract ? trm::kStreamTract : 0u);
         if (s->mixed) {
             // time in control periods, not tube samples, and the noise not advanced: every set's workgroups add their own base
             a.stream_n_base = (uint32_t)s->periods;
@@ -480,7 +458,7 @@ struct GroupPlan {
     bool gen = false;                        // a pushing group whose frames come from its event lists (TRM_GROUP_RUN)
     bool drop = false;                       // the group's event lists end with this step: run to their end, or dropped by a finish
     uint64_t frames = 0;                     // a pushing group: the frames it pushes (the step's; a running group's last stretch: fewer)
-    uint64_t Q = 0, kBase = 0, kEnd = 0;     // control periods of the step; converter outputs kBase <= k < kEnd
+    uint64_t Q = 0, kBase = 0, kEnd = 0, nHi = 0;    // control periods of the step; converter outputs kBase <= k < kEnd; last tube sample + 1
 };
 
 // what TRM_GROUP_RUN means for group g now: push `*frames` generated frames (> 0), flush (returns true with *frames = 0 on an
@@ -531,9 +509,9 @@ static int step_plan(const trm_stream_engine *s, const uint8_t *action, const fl
         const uint64_t rows = p.push ? p.frames + (p.lead ? 1 : 0) : 1;
         p.Q = rows - 1;
         p.runs = p.Q > 0 || p.flush;
-        const trm_batch *b = s->sets[s->gset[g]];
-        p.kBase = unit_range(b, s->gperiods[g], rows, p.flush, &p.kEnd);
-        if (s->gbegin[g + 1] > s->gbegin[g] && unit_too_long(b, s->gperiods[g] + p.Q, p.kEnd))
+        const trm::StreamRange r = unit_range(s->sets[s->gset[g]], s->gperiods[g], rows, p.flush);
+        p.kBase = r.kBase; p.kEnd = r.kEnd; p.nHi = r.nHi;
+        if (s->gbegin[g + 1] > s->gbegin[g] && range_too_long(r))
             return fail(TRM_ERANGE, "utterance too long (group %zu)", g);
     }
     // (frames may stay away where every frame of the step is generated)
@@ -590,7 +568,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
         if (!p.runs || s->gbegin[g + 1] == s->gbegin[g]) continue;
         const trm_batch *b = s->sets[s->gset[g]];
         maxCount = std::max(maxCount, p.kEnd - p.kBase);
-        noiseNeed = std::max(noiseNeed, unit_n_hi(b, s->gperiods[g] + p.Q) + 256u);
+        noiseNeed = std::max(noiseNeed, p.nHi + 256u);
         downRuns = downRuns || !b->c.upsample;
     }
     if (maxCount > 0 && (!d_out || out_pitch < maxCount))
@@ -625,7 +603,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
         for (uint32_t e = s->gentry[g]; e < s->gentry[g + 1]; e++) {
             clock[4 * e] = (uint32_t)s->gperiods[g];
             clock[4 * e + 1] = (uint32_t)(s->gperiods[g] + p.Q);
-            clock[4 * e + 2] = (s->gfirst[g] ? 1u : 0u) | (p.flush ? 2u : 0u) | (p.push && !p.lead ? 8u : 0u);
+            clock[4 * e + 2] = (s->gfirst[g] ? trm::kStreamFirst : 0u) | (p.flush ? trm::kStreamFlush : 0u) | (p.push && !p.lead ? trm::kClockNoLead : 0u);
             active[nActive++] = e;
         }
     }
@@ -655,7 +633,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
         a.tube_offset = s->dTubeOff.p;
     }
     a.stream_state = s->dState.p;
-    a.stream_flags = tract ? 4u : 0u;        // (first chunk and flush: per entry, in the clock)
+    a.stream_flags = tract ? trm::kStreamTract : 0u;        // (first chunk and flush: per entry, in the clock)
     a.mix_map = s->dMap.p;
     a.set_const = (trm::ConstTable)s->sets.dConst;
     a.mix_grid = nActive;
@@ -1017,9 +995,8 @@ size_t trm_mixed_stream_group_samples_for(const trm_mixed_stream *s, size_t grou
     }
     if (!push && !flush) return 0;
     const bool lead = s->gopen[group] || s->mode == TRM_STREAM_MODE_TRACT;
-    uint64_t kEnd = 0;
-    const uint64_t kBase = unit_range(s->sets[s->gset[group]], s->gperiods[group], push ? frames + (lead ? 1 : 0) : 1, flush, &kEnd);
-    return (size_t)(kEnd - kBase);
+    const trm::StreamRange r = unit_range(s->sets[s->gset[group]], s->gperiods[group], push ? frames + (lead ? 1 : 0) : 1, flush);
+    return (size_t)(r.kEnd - r.kBase);
 }
 
 // The device pool of event lists with room for `need` more events: what is there stays where it is while it fits; otherwise

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 #include "../../gnuspeech_amd/csrc/trm_kernels.h"
+#include "../../gnuspeech_amd/csrc/trm_span.h"
 
 // ------------------------------------------------------------------ the checking heap
 namespace {
@@ -301,8 +302,6 @@ hipError_t launch_grp_prep(const GrpPrepArgs &P, hipStream_t)
     return sp.result();
 }
 
-static uint32_t outputs_before(uint64_t end, uint32_t inc) { return end == 0 ? 0u : (uint32_t)(((end << 16) - 1) / inc + 1); }
-
 // a stream chunk of one voice, sensitive to everything the real kernel reads
 static void fake_voice(Spans &sp, const Const &C, const TubeArgs &A, uint32_t v, const float *frames, uint32_t nfr, bool first, bool flush, bool hold,
                        uint32_t nBase, uint32_t kBase, uint32_t kEnd, const float *noise, float *state, size_t stateBytes)
@@ -356,14 +355,14 @@ static hipError_t fake_tube(const Const &c, const TubeArgs &A, bool wide)
 {
     if (!A.stream_state) return hipSuccess;          // (one-shot launches: not modelled)
     Spans sp;
-    const bool hold = A.stream_flags & 4u;
+    const bool hold = A.stream_flags & kStreamTract;
     const uint32_t per = wide ? 64 : 16;
     // the state block: the one-voice-per-lane form's is a workgroup's (64 lanes), the four-lane form's a voice's
     const size_t stateBytes = (wide ? 64 : 1) * (size_t)kStreamFloats * 4;
     if (A.mix_map) {
         for (uint32_t w = 0; w < A.mix_grid; w++) {
             uint32_t entry = w;
-            uint4 clk = make_uint4(A.stream_n_base, A.stream_k_end, A.stream_flags & 3u, 0);
+            uint4 clk = make_uint4(A.stream_n_base, A.stream_k_end, A.stream_flags & (kStreamFirst | kStreamFlush), 0);
             if (A.grp_clock) {
                 if (!sp((const uint32_t *)A.grp_active + w, 4, "tube: grp_active")) continue;
                 entry = *(const uint32_t *)(A.grp_active + w);
@@ -374,14 +373,14 @@ static hipError_t fake_tube(const Const &c, const TubeArgs &A, bool wide)
             const uint4 m = A.mix_map[entry];
             if (!sp((const Const *)A.set_const + m.x, sizeof(Const), "tube: set_const")) continue;
             const Const &C = *(const Const *)(A.set_const + m.x);
-            const uint32_t CP = (uint32_t)C.controlPeriod, inc = C.timeRegisterIncrement;
-            const bool first = clk.z & 1u, flush = clk.z & 2u;
-            const uint32_t nBase = clk.x * CP, kBase = outputs_before(nBase, inc);
-            const uint32_t kEnd = flush ? (uint32_t)((((uint64_t)nBase + 2ull * (uint32_t)C.padSize) * 65536ull + inc - 1) / inc) : outputs_before((uint64_t)clk.y * CP, inc);
+            const bool first = clk.z & kStreamFirst, flush = clk.z & kStreamFlush;
+            // (the entry's time bases as the kernels derive them: trm_span.h)
+            const StreamRange r = stream_range(clk.x, clk.y, flush, (uint32_t)C.controlPeriod, C.timeRegisterIncrement, (uint32_t)C.padSize);
+            const uint32_t nBase = (uint32_t)r.nBase, kBase = (uint32_t)r.kBase, kEnd = (uint32_t)r.kEnd;
             if (m.z - m.y > per) { fprintf(stderr, "MOCK: entry of %u voices\n", m.z - m.y); abort(); }
             for (uint32_t v = m.y; v < m.z; v++) {
                 uint32_t nfr; const float *fr;
-                if (A.grp_clock) { nfr = clk.y - clk.x + 1; fr = A.frames + ((size_t)v * A.max_nframes + ((clk.z >> 3) & 1u)) * 16; }
+                if (A.grp_clock) { nfr = clk.y - clk.x + 1; fr = A.frames + ((size_t)v * A.max_nframes + ((clk.z & kClockNoLead) ? 1u : 0u)) * 16; }
                 else if (!voice_rows(sp, A, v, &nfr, &fr)) continue;
                 float *blk = wide ? A.stream_state + ((size_t)entry * kStreamFloats) * 64 : A.stream_state + (size_t)v * kStreamFloats;
                 if (!sp(blk, stateBytes, "tube: state block")) continue;
@@ -395,7 +394,7 @@ static hipError_t fake_tube(const Const &c, const TubeArgs &A, bool wide)
         if (!voice_rows(sp, A, v, &nfr, &fr)) continue;
         float *blk = wide ? A.stream_state + ((size_t)(v / 64) * kStreamFloats) * 64 : A.stream_state + (size_t)v * kStreamFloats;
         if (!sp(blk, stateBytes, "tube: state block")) continue;
-        fake_voice(sp, c, A, v, fr, nfr, A.stream_flags & 1u, A.stream_flags & 2u, hold, A.stream_n_base, A.stream_k_base, A.stream_k_end, A.lp_noise,
+        fake_voice(sp, c, A, v, fr, nfr, A.stream_flags & kStreamFirst, A.stream_flags & kStreamFlush, hold, A.stream_n_base, A.stream_k_base, A.stream_k_end, A.lp_noise,
                    wide ? blk + (v % 64) * 2 : blk, 8);
     }
     return sp.result();

@@ -11,6 +11,7 @@
 #include "../../gnuspeech_amd/csrc/trm_lane.h"
 #include "../../gnuspeech_amd/csrc/trm_oct.h"
 #include "../../gnuspeech_amd/csrc/trm_setup.h"
+#include "../../gnuspeech_amd/csrc/trm_span.h"
 
 using namespace trm;
 
@@ -137,17 +138,14 @@ extern "C" int trm_emul_synthesize_split(const trm_input_params *p, const float 
         }
     }
     const uint64_t total = count_outputs(d, ntube);
-    auto outputs_through = [&](uint64_t endSample) { return endSample == 0 ? 0ull : ((endSample << 16) - 1) / inc + 1; };
     float mx = 0.f;
-    // segment boundaries as the library lays them (trm_capi.cc split_segments): the first segment is segPeriods + warmPeriods long
-    auto seg_begin = [&](size_t sg) { return sg == 0 ? (size_t)0 : (size_t)segPeriods + warmPeriods + (sg - 1) * segPeriods; };
-    size_t nseg = 1;
-    while (seg_begin(nseg) < nper) nseg++;
-    for (size_t sg = 0; sg < nseg; sg++) {
-        const size_t pLo = seg_begin(sg), pHi = seg_begin(sg + 1) < nper ? seg_begin(sg + 1) : nper;
-        const size_t pStart = pLo > warmPeriods ? pLo - warmPeriods : 0;
+    // segment boundaries and every segment's stretch as the library and the kernels lay them (trm_span.h)
+    const uint32_t segFirst = seg_first(segPeriods, warmPeriods), nseg = seg_count((uint32_t)nper, segPeriods, warmPeriods);
+    for (uint32_t sg = 0; sg < nseg; sg++) {
+        const SegStretch st = seg_stretch((uint32_t)nframes, sg, segFirst, segPeriods, warmPeriods, (uint32_t)CP, inc);
+        const size_t pLo = seg_begin(sg, segFirst, segPeriods), pStart = st.segFrame0, pHi = pStart + st.nfr - 1;
         const size_t nBase = pStart * CP, nLocal = (pHi - pStart) * CP;
-        const bool last = sg + 1 == nseg;
+        const bool last = st.segLast;
         // local tube-rate signal: 25 positions of pre-roll (zeros), the samples, the flush zeros
         std::vector<float> sig(25 + nLocal + 2 * C.padSize + 8, 0.0f);
         ExciteState ES; ExciteTrack ET; CoefTrack CT; TubeState TS;
@@ -164,7 +162,7 @@ extern "C" int trm_emul_synthesize_split(const trm_input_params *p, const float 
                 n++;
             }
         }
-        const uint64_t kLo = outputs_through(pLo * CP), kHi = last ? total : outputs_through(pHi * CP);
+        const uint64_t kLo = outputs_before(pLo * CP, inc), kHi = last ? total : st.segOutEnd;
         for (uint64_t k = kLo; k < kHi; k++) {
             const uint32_t ph = src_phase((uint32_t)k, inc);
             const uint64_t e = ((uint64_t)k * inc) >> 16;          // global read position; local = e - nBase

@@ -22,7 +22,7 @@ LIB = os.path.join(ROOT, "tests", "_emul", "libtrm_emul.so")
 @pytest.fixture(scope="module")
 def emul():
     csrc = os.path.join(ROOT, "gnuspeech_amd", "csrc")
-    deps = [SRC] + [os.path.join(csrc, f) for f in ("trm_lane.h", "trm_quad.h", "trm_oct.h", "trm_setup.cc", "trm_setup.h")]
+    deps = [SRC] + [os.path.join(csrc, f) for f in ("trm_lane.h", "trm_span.h", "trm_quad.h", "trm_oct.h", "trm_setup.cc", "trm_setup.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-o", LIB, SRC,
                                os.path.join(csrc, "trm_setup.cc"), "-lm"])

@@ -37,7 +37,7 @@ def emul():
     src = os.path.join(ROOT, "tests", "_emul", "trm_emul.cc")
     lib = os.path.join(ROOT, "tests", "_emul", "libtrm_emul.so")
     csrc = os.path.join(ROOT, "gnuspeech_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in ("trm_lane.h", "trm_quad.h", "trm_oct.h", "trm_setup.cc", "trm_setup.h")]
+    deps = [src] + [os.path.join(csrc, f) for f in ("trm_lane.h", "trm_span.h", "trm_quad.h", "trm_oct.h", "trm_setup.cc", "trm_setup.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-o", lib, src,
                                os.path.join(csrc, "trm_setup.cc"), "-lm"])
