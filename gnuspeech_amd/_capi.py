@@ -79,6 +79,7 @@ EXPORTS = [
     "trm_mixed_stream_create_groups", "trm_mixed_stream_groups", "trm_mixed_stream_group_open", "trm_mixed_stream_group_samples_for",
     "trm_mixed_stream_step", "trm_mixed_stream_step_device",
     "trm_mixed_stream_group_set_events", "trm_mixed_stream_group_frames_left", "trm_mixed_stream_last_frames",
+    "trm_mixed_stream_step_int16", "trm_mixed_stream_step_device_int16",
 ]
 
 _lib = None
@@ -223,6 +224,8 @@ def lib():
     L.trm_mixed_stream_group_frames_left.argtypes = [vp, C.c_size_t]
     L.trm_mixed_stream_group_frames_left.restype = C.c_size_t
     L.trm_mixed_stream_last_frames.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.trm_mixed_stream_step_int16.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp, vp, vp]
+    L.trm_mixed_stream_step_device_int16.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(L, name)
     _lib = L

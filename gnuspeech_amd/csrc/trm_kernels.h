@@ -6,6 +6,7 @@
 
 #include "../../include/trm_c_api.h"
 #include "trm_lane.h"
+#include "trm_out_lane.h"
 #include "trm_tracks_lane.h"
 
 namespace trm {
@@ -271,6 +272,33 @@ struct TrackRunArgs {
 // The host units do not name the launcher (they are also linked without the kernels: tests/_emul): trm_tracks_run.hip installs
 // it here when the library is loaded.  Null: the library holds no such kernel, and a step that needs it fails.
 extern hipError_t (*tracks_run_launcher)(const TrackRunArgs &a, hipStream_t stream);
+
+// int16 PCM of a grouped stream's step (trm_grp_out.hip: trm_grp_int16_kernel), behind the step's tube launch and whatever follows it
+// (down-sampling, TRAcT order's gain): the fp32 rows of the voices that received samples, scaled against their group's level with
+// their set's volume, balance and channels (trm_out_lane.h), to the caller's int16 rows.  Grid (nentries, tiles): a workgroup per
+// map entry of a group that received samples -- `step` lists them, so no workgroup is launched for a voice that has nothing to
+// do -- and per tile of kGrpOutTileValues values of the entry's rows; one wave per voice of the entry at a time.  Where `clipped`
+// is given, trm_grp_clip_clear_kernel sets all of it to 0 in front and the waves add what they saturated.  The tables are typed
+// in the constant address space (ConstTable's reason).
+//   step   the int16 part of the step's tables: [level of group g as bits | samples per voice of group g (0: receives nothing) |
+//          for_wav_data | the map entries that receive samples, nentries of them]
+constexpr uint32_t kGrpOutTileValues = 1024;
+typedef const __attribute__((address_space(4))) GrpOutSet *GrpOutTable;
+struct GrpInt16Args {
+    const float *pcm;                 // the engine's fp32 rows: voice v at pcm + v * pitch; pitch a multiple of 4, pcm 16-byte aligned
+    uint64_t pitch;
+    int16_t *out16;                   // the caller's: voice v at out16 + v * pitch16, 2-byte aligned and no more
+    uint64_t pitch16;
+    uint32_t *clipped;                // [nvoices], optional
+    const __attribute__((address_space(4))) uint32_t *step;
+    const __attribute__((address_space(4))) uint4 *mix_map;
+    const __attribute__((address_space(4))) uint32_t *voice_group;      // [nvoices]
+    GrpOutTable sets;                 // [parameter sets]
+    uint32_t ngroups, nentries, nvoices;
+    uint32_t tiles;                   // ceil(the step's largest count * channels / kGrpOutTileValues), at least 1
+};
+// (installed by trm_grp_out.hip when the library is loaded, like tracks_run_launcher; null: an int16 step fails)
+extern hipError_t (*grp_int16_launcher)(const GrpInt16Args &a, hipStream_t stream);
 
 // Output of a mixed-parameter batch (trm_mixed_out.hip): int16 PCM or sound-file images, one workgroup per voice, each voice with
 // its own set's scaling and container.  The per-set table is built once at trm_mixed_create.

@@ -16,6 +16,8 @@
 // with its group's clock (TubeArgs::grp_*).  A group may also be given its event lists once (trm_mixed_stream_group_set_events)
 // and then RUN: the step plans it as a push of the frames it has left, at most the step's, which the resumable track kernel
 // (trm_tracks_run.hip) generates in place in front of the tube launch, and as the flush once they have run out.
+// A step may also leave as int16 PCM (trm_mixed_stream_step_int16): the same step into fp32 rows of the engine's, then one launch
+// (trm_grp_out.hip) that scales the rows of the voices that received samples against their group's level.
 // What a chunk and a step share is stated once: the converter range of a run of
 // control periods (unit_range), the length limit (range_too_long), the index arrays of a shape (stream_shape), the down-sampling
 // launches around the tube launch (down_history_in, down_convert) and the ordering of calls across HIP streams (stream_ordered).
@@ -94,6 +96,11 @@ struct trm_stream_engine {
     DevBuf<trm::TrackRunHead> dTrkHead;      // ... and [nvoices] heads (trm_kernels.h: TrackRunArgs)
     uint64_t evUsed = 0;                     // events of the pool handed out
     uint64_t evCap = 0;                      // events the pool holds: what BOTH its buffers have room for (events_room)
+    // ---- int16 steps (trm_mixed_stream_step_int16): the sets' scaling, fixed; the host entry's staging (its fp32 rows: dOut)
+    DevBuf<trm::GrpOutSet> dOutSets;
+    DevBuf<int16_t> dOut16;
+    DevBuf<uint32_t> dClipped;
+    std::vector<int16_t> hostOut16;
     ~trm_stream_engine()
     {
         for (StepCopy &c : stepCopies) {
@@ -105,6 +112,7 @@ struct trm_stream_engine {
 
 namespace trm {
 hipError_t (*tracks_run_launcher)(const TrackRunArgs &a, hipStream_t stream) = nullptr;      // (trm_kernels.h; set by trm_tracks_run.hip)
+hipError_t (*grp_int16_launcher)(const GrpInt16Args &a, hipStream_t stream) = nullptr;        // (trm_kernels.h; set by trm_grp_out.hip)
 }
 
 struct trm_stream : trm_stream_engine {};
@@ -121,6 +129,8 @@ static void stream_destroy(Stream *s)
 
 // words of a step's tables with `nrun` voices that run from event lists: [clock | active entries | group actions | those voices]
 static size_t step_words(const trm_stream_engine *s, size_t nrun) { return (size_t)s->mapEntries * 5 + (s->gbegin.size() - 1) + 2 * nrun; }
+// ... and of what an int16 step adds behind them (trm_kernels.h, GrpInt16Args::step) with `nentries` map entries that receive samples
+static size_t step_words_int16(const trm_stream_engine *s, size_t nentries) { return 2 * (s->gbegin.size() - 1) + 1 + nentries; }
 
 // what create does once the batches exist (on failure the caller destroys the stream)
 static int stream_init(trm_stream_engine *s, const size_t *set_begin)
@@ -201,9 +211,19 @@ static int stream_init(trm_stream_engine *s, const size_t *set_begin)
         std::vector<uint32_t> vg(V);
         for (size_t g = 0; g < G; g++)
             for (size_t v = s->gbegin[g]; v < s->gbegin[g + 1]; v++) vg[v] = (uint32_t)g;
-        if ((rc = s->dVoiceGroup.reserve(V)) || (rc = s->dStep.reserve(step_words(s, V)))) return rc;
+        if ((rc = s->dVoiceGroup.reserve(V)) || (rc = s->dStep.reserve(step_words(s, V) + step_words_int16(s, s->mapEntries))) ||
+            (rc = s->dOutSets.reserve(S)))
+            return rc;
         hipError_t e = hipMemcpy(s->dVoiceGroup.p, vg.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail(TRM_EHIP, "group table: %s", hipGetErrorString(e));
+        // the sets' share of an int16 step's scaling (as trm_mixed's MixOutSet)
+        std::vector<trm::GrpOutSet> os(S);
+        for (size_t k = 0; k < S; k++) {
+            const trm_input_params &p = s->sets[k]->params;
+            os[k] = trm::GrpOutSet{trm::io_amplitude(p.volume), p.balance, p.channels == 2 ? 2 : 1, 0};
+        }
+        e = hipMemcpy(s->dOutSets.p, os.data(), S * sizeof(trm::GrpOutSet), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(TRM_EHIP, "output table: %s", hipGetErrorString(e));
     }
     // The noise sequence of the first 16 s at the fastest tube rate (24 s with ensure_noise's head-room) is fetched now, not chunk
     // by chunk: extending it is a serial kernel, a synchronisation and a re-upload, i.e. a chunk that takes 2 ms longer than its
@@ -553,8 +573,14 @@ static int step_copy(trm_stream_engine *s, size_t words, uint32_t **out)
 // One step on the device (plan: step_plan's): the tables of the step, the frame rows, ONE tube launch over the map entries of the
 // groups that synthesize, then per such group what stream_chunk_impl does per set.  nout[g] = samples per voice of group g.
 // The host waits for the device only on a shape change (frames per push, out_pitch) or when the noise sequence has to grow.
+// An int16 step (o16; d_out then the engine's fp32 rows): its part of the tables rides behind the others in the same upload.
+struct StepInt16 {
+    const float *level;                      // per group, the caller's (checked: step_check_int16)
+    int forWav;
+    uint32_t at = 0, nentries = 0;           // out: where the int16 part lies in dStep; the map entries that receive samples
+};
 static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &plan, const float *d_pushed, size_t nframes, float *d_out,
-                            size_t out_pitch, uint32_t *nout, hipStream_t st)
+                            size_t out_pitch, uint32_t *nout, hipStream_t st, StepInt16 *o16 = nullptr)
 {
     trm_batch *b0 = s->sets[0];
     const size_t G = plan.size(), V = s->nvoices, E = s->mapEntries;
@@ -582,9 +608,9 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     // the step's tables
     size_t nRun = 0;                         // voices whose frames are generated in this step
     for (size_t g = 0; g < G; g++) nRun += plan[g].gen ? s->gbegin[g + 1] - s->gbegin[g] : 0;
-    const size_t words = step_words(s, nRun);
+    size_t words = step_words(s, nRun);
     uint32_t *h = nullptr;
-    if ((rc = step_copy(s, step_words(s, V), &h))) return rc;
+    if ((rc = step_copy(s, step_words(s, V) + step_words_int16(s, E), &h))) return rc;
     uint32_t *clock = h, *active = h + E * 4, *what = active + E, *run = what + G;
     memset(h, 0, words * sizeof(uint32_t));
     uint32_t nActive = 0;
@@ -606,6 +632,23 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
             clock[4 * e + 2] = (s->gfirst[g] ? trm::kStreamFirst : 0u) | (p.flush ? trm::kStreamFlush : 0u) | (p.push && !p.lead ? trm::kClockNoLead : 0u);
             active[nActive++] = e;
         }
+    }
+    if (o16) {
+        // [level bits | samples per voice | for_wav_data | the entries that receive samples] (a group that receives nothing: 0, 0)
+        uint32_t *lev = h + words, *cnt = lev + G, *ent = cnt + G + 1;
+        o16->at = (uint32_t)words;
+        o16->nentries = 0;
+        for (size_t g = 0; g < G; g++) {
+            const GroupPlan &p = plan[g];
+            const bool receives = p.runs && p.kEnd > p.kBase && s->gbegin[g + 1] > s->gbegin[g];
+            lev[g] = cnt[g] = 0;
+            if (!receives) continue;
+            memcpy(&lev[g], &o16->level[g], sizeof(uint32_t));
+            cnt[g] = (uint32_t)(p.kEnd - p.kBase);
+            for (uint32_t e = s->gentry[g]; e < s->gentry[g + 1]; e++) ent[o16->nentries++] = e;
+        }
+        cnt[G] = o16->forWav ? 1u : 0u;
+        words += step_words_int16(s, o16->nentries);
     }
     HIP_TRY(hipMemcpyAsync(s->dStep.p, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(s->stepCopies.back().uploaded, st));
@@ -680,6 +723,24 @@ static int stream_step_device(trm_stream_engine *s, const uint8_t *action, const
     return TRM_OK;
 }
 
+// the frames of the groups that push, from the caller's host rows to dPushed (the rows of the others are not read)
+static int step_frames_in(trm_stream_engine *s, const std::vector<GroupPlan> &plan, const float *frames, size_t nframes, hipStream_t st)
+{
+    const size_t G = plan.size();
+    if (nframes == 0) return TRM_OK;
+    if (int rc = s->dPushed.reserve(s->nvoices * nframes * 16)) return rc;
+    // (runs of neighbouring pushing groups)
+    for (size_t g = 0; g < G;) {
+        if (!plan[g].push || plan[g].gen) { g++; continue; }
+        size_t e = g;
+        while (e < G && plan[e].push && !plan[e].gen) e++;
+        const size_t lo = s->gbegin[g] * nframes * 16, hi = s->gbegin[e] * nframes * 16;
+        if (hi > lo) HIP_TRY(hipMemcpyAsync(s->dPushed.p + lo, frames + lo, (hi - lo) * sizeof(float), hipMemcpyHostToDevice, st));
+        g = e;
+    }
+    return TRM_OK;
+}
+
 // host buffers: H2D of the pushing groups' frames, the step (PCM packed at the largest count), D2H, each voice's samples to `out`
 static int stream_step_host(trm_stream_engine *s, const uint8_t *action, const float *frames, size_t nframes, float *out, size_t out_pitch,
                             uint32_t *nout, float *max_out)
@@ -697,18 +758,7 @@ static int stream_step_host(trm_stream_engine *s, const uint8_t *action, const f
         if (plan[g].runs && s->gbegin[g + 1] > s->gbegin[g]) maxCount = std::max<size_t>(maxCount, plan[g].kEnd - plan[g].kBase);
     if (maxCount > 0 && (!out || out_pitch < maxCount))
         return fail(TRM_EINVAL, "output pitch %zu < %zu samples (the largest count of a group that synthesizes)", out_pitch, maxCount);
-    if (nframes > 0) {
-        if ((rc = s->dPushed.reserve(V * nframes * 16))) return rc;
-        // (runs of neighbouring pushing groups; the rows of the others are not read)
-        for (size_t g = 0; g < G;) {
-            if (!plan[g].push || plan[g].gen) { g++; continue; }
-            size_t e = g;
-            while (e < G && plan[e].push && !plan[e].gen) e++;
-            const size_t lo = s->gbegin[g] * nframes * 16, hi = s->gbegin[e] * nframes * 16;
-            if (hi > lo) HIP_TRY(hipMemcpyAsync(s->dPushed.p + lo, frames + lo, (hi - lo) * sizeof(float), hipMemcpyHostToDevice, st));
-            g = e;
-        }
-    }
+    if ((rc = step_frames_in(s, plan, frames, nframes, st))) return rc;
     if ((rc = s->dOut.reserve(V * maxCount + 64))) return rc;
     std::vector<uint32_t> counts(G);
     if ((rc = stream_ordered(s, st, [&] { return stream_step_impl(s, plan, s->dPushed.p, nframes, s->dOut.p, maxCount, counts.data(), st); }))) return rc;
@@ -724,6 +774,121 @@ static int stream_step_host(trm_stream_engine *s, const uint8_t *action, const f
         for (size_t v = s->gbegin[g]; v < s->gbegin[g + 1] && counts[g] > 0; v++)
             memcpy(out + v * out_pitch, &s->hostOut[v * maxCount], (size_t)counts[g] * sizeof(float));
     if (max_out) memcpy(max_out, mx.data(), V * sizeof(float));
+    step_after(s, plan);
+    return TRM_OK;
+}
+
+// ------------------------------------------------------------------ grouped streams: a step that leaves as int16 PCM
+// What an int16 step is refused for, before any device work: no kernel in this build, a level that is read -- those of the
+// non-empty groups that synthesize -- and is not finite and > 0, rows too short.  *maxVals = the largest count * channels.
+static int step_check_int16(const trm_stream_engine *s, const std::vector<GroupPlan> &plan, const float *level, const int16_t *out16,
+                            size_t out_pitch16, size_t *maxVals)
+{
+    *maxVals = 0;
+    // (the engine's fp32 rows are as wide as the caller's: int16_row_pitch)
+    if (out_pitch16 > 0x7FFFFFFFull) return fail(TRM_EINVAL, "output pitch %zu: at most 2^31 - 1 int16 values", out_pitch16);
+    for (size_t g = 0; g < plan.size(); g++) {
+        const GroupPlan &p = plan[g];
+        if (!p.runs || s->gbegin[g + 1] == s->gbegin[g]) continue;
+        if (!level) return fail(TRM_EINVAL, "null level, and group %zu synthesizes", g);
+        if (!(level[g] > 0.0f && level[g] <= 3.402823466e38f)) return fail(TRM_EINVAL, "group %zu: level %g (a level is finite and > 0)", g, (double)level[g]);
+        const uint64_t vals = (p.kEnd - p.kBase) * (s->sets[s->gset[g]]->params.channels == 2 ? 2u : 1u);
+        // (the int16 launch's grid has a tile of kGrpOutTileValues values per workgroup in y, and y holds 65 535 workgroups)
+        if (vals > 65535ull * trm::kGrpOutTileValues)
+            return fail(TRM_ERANGE, "group %zu: %llu int16 values per voice in one step (at most %llu)", g, (unsigned long long)vals,
+                        65535ull * trm::kGrpOutTileValues);
+        *maxVals = std::max<size_t>(*maxVals, (size_t)vals);
+    }
+    if (*maxVals > 0 && (!out16 || out_pitch16 < *maxVals))
+        return fail(TRM_EINVAL, "output pitch %zu < %zu int16 values (the largest count x channels of a group that synthesizes)", out_pitch16, *maxVals);
+    return TRM_OK;
+}
+
+static int refuse_without_int16_kernel()
+{
+    return trm::grp_int16_launcher ? TRM_OK : fail(TRM_EHIP, "this build of the library holds no int16 output kernel (trm_grp_out.hip)");
+}
+
+// the pitch of the engine's fp32 rows under int16 rows of `out_pitch16` values: a function of that alone (the step's shape
+// must not depend on the actions), rows 16-byte aligned, and >= every count the int16 rows have room for
+static size_t int16_row_pitch(size_t out_pitch16) { return (out_pitch16 + 3) & ~(size_t)3; }
+
+// The step into the engine's fp32 rows (dOut, reserved by the caller) and the int16 launch behind it: work on `st`
+static int stream_step_int16_impl(trm_stream_engine *s, const std::vector<GroupPlan> &plan, const float *d_pushed, size_t nframes, const float *level,
+                                  int for_wav_data, int16_t *d_out16, size_t out_pitch16, size_t maxVals, uint32_t *nout, uint32_t *d_clipped,
+                                  hipStream_t st)
+{
+    const size_t pitch = int16_row_pitch(out_pitch16);
+    StepInt16 o{level, for_wav_data};
+    if (int rc = stream_step_impl(s, plan, d_pushed, nframes, s->dOut.p, pitch, nout, st, &o)) return rc;
+    typedef const __attribute__((address_space(4))) uint32_t *Words;
+    trm::GrpInt16Args a{s->dOut.p, pitch, d_out16, out_pitch16, d_clipped, (Words)(s->dStep.p + o.at),
+                        (const __attribute__((address_space(4))) uint4 *)s->dMap.p, (Words)s->dVoiceGroup.p, (trm::GrpOutTable)s->dOutSets.p,
+                        (uint32_t)plan.size(), o.nentries, (uint32_t)s->nvoices,
+                        (uint32_t)std::max<size_t>((maxVals + trm::kGrpOutTileValues - 1) / trm::kGrpOutTileValues, 1)};
+    HIP_TRY(trm::grp_int16_launcher(a, st));
+    return TRM_OK;
+}
+
+static int stream_step_device_int16(trm_stream_engine *s, const uint8_t *action, const float *d_frames, size_t nframes, const float *level,
+                                    int for_wav_data, int16_t *d_out16, size_t out_pitch16, uint32_t *nout, float *d_max_out, uint32_t *d_clipped,
+                                    void *stream)
+{
+    int rc = step_check(s, action, nframes);
+    if (rc || (rc = refuse_without_int16_kernel())) return rc;
+    std::vector<GroupPlan> plan;
+    size_t maxVals = 0;
+    if ((rc = step_plan(s, action, d_frames, nframes, plan)) || (rc = step_check_int16(s, plan, level, d_out16, out_pitch16, &maxVals))) return rc;
+    HIP_TRY(hipSetDevice(s->sets[0]->device));
+    hipStream_t st = (hipStream_t)stream;
+    // (grows with the shape alone, and a buffer that grows is a shape change's wait)
+    if ((rc = s->dOut.reserve(s->nvoices * int16_row_pitch(out_pitch16) + 64))) return rc;
+    auto work = [&]() -> int {
+        if (int r = stream_step_int16_impl(s, plan, d_frames, nframes, level, for_wav_data, d_out16, out_pitch16, maxVals, nout, d_clipped, st)) return r;
+        if (d_max_out) HIP_TRY(hipMemcpyAsync(d_max_out, s->dMax.p, s->nvoices * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return TRM_OK;
+    };
+    if ((rc = stream_ordered(s, st, work))) return rc;
+    step_after(s, plan);
+    return TRM_OK;
+}
+
+// host buffers: as stream_step_host, the int16 rows packed at the largest count * channels; ONE D2H of int16 values
+static int stream_step_host_int16(trm_stream_engine *s, const uint8_t *action, const float *frames, size_t nframes, const float *level,
+                                  int for_wav_data, int16_t *out16, size_t out_pitch16, uint32_t *nout, float *max_out, uint32_t *clipped)
+{
+    int rc = step_check(s, action, nframes);
+    if (rc || (rc = refuse_without_int16_kernel())) return rc;
+    std::vector<GroupPlan> plan;
+    size_t maxVals = 0;
+    if ((rc = step_plan(s, action, frames, nframes, plan)) || (rc = step_check_int16(s, plan, level, out16, out_pitch16, &maxVals))) return rc;
+    const size_t G = plan.size(), V = s->nvoices;
+    trm_batch *b0 = s->sets[0];
+    HIP_TRY(hipSetDevice(b0->device));
+    hipStream_t st = b0->stream;
+    if ((rc = step_frames_in(s, plan, frames, nframes, st))) return rc;
+    if ((rc = s->dOut.reserve(V * int16_row_pitch(maxVals) + 64)) || (rc = s->dOut16.reserve(V * maxVals + 64)) || (rc = s->dClipped.reserve(V))) return rc;
+    std::vector<uint32_t> counts(G);
+    if ((rc = stream_ordered(s, st, [&] {
+             return stream_step_int16_impl(s, plan, s->dPushed.p, nframes, level, for_wav_data, s->dOut16.p, maxVals, maxVals, counts.data(), s->dClipped.p, st);
+         })))
+        return rc;
+    if (nout) memcpy(nout, counts.data(), G * sizeof(uint32_t));
+    if (maxVals > 0) {
+        s->hostOut16.resize(V * maxVals);
+        HIP_TRY(hipMemcpyAsync(s->hostOut16.data(), s->dOut16.p, V * maxVals * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+    }
+    std::vector<float> mx(V, 0.0f);
+    std::vector<uint32_t> cl(V, 0u);
+    HIP_TRY(hipMemcpyAsync(mx.data(), s->dMax.p, V * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cl.data(), s->dClipped.p, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t g = 0; g < G; g++) {
+        const size_t vals = (size_t)counts[g] * (s->sets[s->gset[g]]->params.channels == 2 ? 2u : 1u);
+        for (size_t v = s->gbegin[g]; v < s->gbegin[g + 1] && vals > 0; v++) memcpy(out16 + v * out_pitch16, &s->hostOut16[v * maxVals], vals * sizeof(int16_t));
+    }
+    if (max_out) memcpy(max_out, mx.data(), V * sizeof(float));
+    if (clipped) memcpy(clipped, cl.data(), V * sizeof(uint32_t));
     step_after(s, plan);
     return TRM_OK;
 }
@@ -1120,6 +1285,19 @@ int trm_mixed_stream_step_device(trm_mixed_stream *s, const uint8_t *action, con
                                  size_t out_pitch, uint32_t *nout, float *d_max_out, void *hip_stream)
 {
     return stream_step_device(s, action, d_frames, nframes, d_out, out_pitch, nout, d_max_out, hip_stream);
+}
+
+int trm_mixed_stream_step_int16(trm_mixed_stream *s, const uint8_t *action, const float *frames, size_t nframes, const float *level,
+                                int for_wav_data, int16_t *out16, size_t out_pitch16, uint32_t *nout, float *max_out, uint32_t *clipped)
+{
+    return stream_step_host_int16(s, action, frames, nframes, level, for_wav_data, out16, out_pitch16, nout, max_out, clipped);
+}
+
+int trm_mixed_stream_step_device_int16(trm_mixed_stream *s, const uint8_t *action, const float *d_frames, size_t nframes, const float *level,
+                                       int for_wav_data, int16_t *d_out16, size_t out_pitch16, uint32_t *nout, float *d_max_out,
+                                       uint32_t *d_clipped, void *hip_stream)
+{
+    return stream_step_device_int16(s, action, d_frames, nframes, level, for_wav_data, d_out16, out_pitch16, nout, d_max_out, d_clipped, hip_stream);
 }
 
 }  // extern "C"

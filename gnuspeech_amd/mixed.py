@@ -584,6 +584,10 @@ class TRMGroupedStream:
         self.nvoices = int(sets.size)
         self.ngroups = int(self._gindex.size)
         self._vgroup = self._gindex[groups[self.order]]      # the library's group of every voice, grouped order
+        # channels of every group, the library's order: 2 where the group has voices and their set is stereo
+        self._gchannels = np.ones(self.ngroups, dtype=np.int64)
+        stereo = np.array([p.channels == 2 for p in self.param_sets], dtype=bool)
+        self._gchannels[self._gindex[groups[stereo[sets]]]] = 2
         arr = (TrmInputParams * nsets)(*[p.c for p in self.param_sets])
         sb = np.ascontiguousarray(self.set_begin, dtype=np.uint64)
         gb = np.ascontiguousarray(self.group_begin, dtype=np.uint64)
@@ -705,14 +709,8 @@ class TRMGroupedStream:
         nonempty = np.diff(self.group_begin.astype(np.int64)) > 0
         return int(counts[nonempty].max()) if np.any(nonempty) else 0
 
-    # -------------------------------------------------------------- host buffers (caller's voice order)
-    def step(self, actions, frames=None, nframes=None):
-        """actions: ngroups entries ("push" | "finish" | "idle" / None | "run"), or a dict {group: action} (the others idle).
-        frames: [nvoices, n, 16] in the caller's order, needed when a group pushes; only the rows of pushing groups are read.
-        nframes: the frames of the step where no group pushes and groups "run" (with frames given it must be their count).
-        Returns (pcm [nvoices, max_m] float32, samples per voice uint32[nvoices], max |sample| per voice float32[nvoices]);
-        voice i's samples are pcm[i, :count[i]]."""
-        a = self._actions(actions)
+    def _host_frames(self, a, frames, nframes):
+        """(frames of the step, the pushed frames in grouped order or None) of a host entry with the library's actions `a`"""
         n, f = 0, None
         if np.any(a == TRM_GROUP_PUSH):
             if frames is None:
@@ -729,25 +727,11 @@ class TRMGroupedStream:
                 raise ValueError("a group runs and none pushes: nframes needed")
             n = int(nframes)
         self._max_n = max(getattr(self, "_max_n", 0), n)      # (room for last_frames)
-        counts = self._counts(a, n)
-        m = self._width(counts)
-        out = np.zeros((self.nvoices, max(m, 1)), dtype=np.float32)
-        mx = np.zeros(self.nvoices, dtype=np.float32)
-        nout = np.zeros(self.ngroups, dtype=np.uint32)
-        check(lib().trm_mixed_stream_step(self._h, a.ctypes.data, f.ctypes.data if f is not None else None, n, out.ctypes.data, max(m, 1),
-                                          nout.ctypes.data, mx.ctypes.data))
-        assert np.array_equal(nout.astype(np.int64), counts)
-        per_voice = nout[self._vgroup]
-        return out[self.inverse, :m], per_voice[self.inverse], mx[self.inverse]
+        return n, f
 
-    # -------------------------------------------------------------- device buffers (torch tensors, grouped order)
-    def step_device(self, actions, frames=None, out=None, max_out=None, device=None, nframes=None):
-        """As step(), on the device: frames a float32 CUDA tensor [nvoices, n, 16] in GROUPED order (frames[order] of the caller's).
-        Asynchronous on torch's current stream; nothing but the step's small tables crosses PCIe.  Returns (pcm [nvoices, max_m]
-        view of `out`, samples per voice uint32[nvoices]), both in grouped order.  `out` (optional): float32 CUDA tensor
-        [nvoices, pitch >= max_m]; `max_out` (optional): float32 CUDA tensor [nvoices]."""
+    def _device_frames(self, a, frames, nframes):
+        """(frames of the step, whether a group pushes) of a device entry with the library's actions `a`"""
         import torch
-        a = self._actions(actions)
         n, pushed = 0, False
         if np.any(a == TRM_GROUP_PUSH):
             if frames is None or not (frames.is_cuda and frames.dtype == torch.float32 and frames.is_contiguous() and frames.dim() == 3
@@ -762,6 +746,124 @@ class TRMGroupedStream:
                 raise ValueError("a group runs and none pushes: nframes needed")
             n = int(nframes)
         self._max_n = max(getattr(self, "_max_n", 0), n)      # (room for last_frames)
+        return n, pushed
+
+    # -------------------------------------------------------------- host buffers (caller's voice order)
+    def step(self, actions, frames=None, nframes=None):
+        """actions: ngroups entries ("push" | "finish" | "idle" / None | "run"), or a dict {group: action} (the others idle).
+        frames: [nvoices, n, 16] in the caller's order, needed when a group pushes; only the rows of pushing groups are read.
+        nframes: the frames of the step where no group pushes and groups "run" (with frames given it must be their count).
+        Returns (pcm [nvoices, max_m] float32, samples per voice uint32[nvoices], max |sample| per voice float32[nvoices]);
+        voice i's samples are pcm[i, :count[i]]."""
+        a = self._actions(actions)
+        n, f = self._host_frames(a, frames, nframes)
+        counts = self._counts(a, n)
+        m = self._width(counts)
+        out = np.zeros((self.nvoices, max(m, 1)), dtype=np.float32)
+        mx = np.zeros(self.nvoices, dtype=np.float32)
+        nout = np.zeros(self.ngroups, dtype=np.uint32)
+        check(lib().trm_mixed_stream_step(self._h, a.ctypes.data, f.ctypes.data if f is not None else None, n, out.ctypes.data, max(m, 1),
+                                          nout.ctypes.data, mx.ctypes.data))
+        assert np.array_equal(nout.astype(np.int64), counts)
+        per_voice = nout[self._vgroup]
+        return out[self.inverse, :m], per_voice[self.inverse], mx[self.inverse]
+
+    # -------------------------------------------------------------- int16 PCM per step (include/trm_c_api.h: trm_mixed_stream_step_int16)
+    def channels(self, group):
+        """Channels of the caller's group `group`: 2 where its set is stereo (a step's int16 values are then interleaved), else 1;
+        1 for a group without voices."""
+        g = int(group)
+        if not 0 <= g < self.ngroups:
+            raise ValueError("group %r outside 0 .. %d" % (group, self.ngroups - 1))
+        return int(self._gchannels[self._gindex[g]])
+
+    def _levels(self, levels):
+        """the library's level array (its group order) from a sequence of ngroups levels or a dict {group: level}; None: no array"""
+        if levels is None:
+            return None
+        lv = np.zeros(self.ngroups, dtype=np.float32)
+        if isinstance(levels, dict):
+            items = levels.items()
+        else:
+            levels = list(levels)
+            if len(levels) != self.ngroups:
+                raise ValueError("%d levels for %d groups" % (len(levels), self.ngroups))
+            items = enumerate(levels)
+        for g, level in items:
+            if not 0 <= int(g) < self.ngroups:
+                raise ValueError("group %r outside 0 .. %d" % (g, self.ngroups - 1))
+            lv[self._gindex[int(g)]] = level
+        return lv
+
+    def _values(self, counts):
+        """int16 values per voice of every group (the library's order) from its samples per voice: x 2 for the groups of stereo sets"""
+        return counts * self._gchannels
+
+    def step_int16(self, actions, frames=None, nframes=None, levels=None, for_wav_data=False):
+        """As step(), the PCM as int16 scaled on the device against each group's level -- the maximumSampleValue its utterance is
+        normalised against -- as -saveOutputToFile: (for_wav_data: -generateWAVData) scales it, saturated where the level is too
+        low.  levels: ngroups entries or a dict {group: level}, needed for the groups that synthesize.
+        Returns (pcm16 [nvoices, max values] int16, values per voice uint32[nvoices], max |sample| per voice float32[nvoices] of
+        the fp32 samples, clipped values per voice uint32[nvoices]); a stereo voice has two interleaved values per sample."""
+        a = self._actions(actions)
+        lv = self._levels(levels)
+        n, f = self._host_frames(a, frames, nframes)
+        counts = self._counts(a, n)
+        values = self._values(counts)
+        m = self._width(values)
+        out = np.zeros((self.nvoices, max(m, 1)), dtype=np.int16)
+        mx = np.zeros(self.nvoices, dtype=np.float32)
+        cl = np.zeros(self.nvoices, dtype=np.uint32)
+        nout = np.zeros(self.ngroups, dtype=np.uint32)
+        check(lib().trm_mixed_stream_step_int16(self._h, a.ctypes.data, f.ctypes.data if f is not None else None, n,
+                                                lv.ctypes.data if lv is not None else None, int(bool(for_wav_data)), out.ctypes.data, max(m, 1),
+                                                nout.ctypes.data, mx.ctypes.data, cl.ctypes.data))
+        assert np.array_equal(nout.astype(np.int64), counts)
+        per_voice = values.astype(np.uint32)[self._vgroup]
+        return out[self.inverse, :m], per_voice[self.inverse], mx[self.inverse], cl[self.inverse]
+
+    def step_device_int16(self, actions, frames=None, out=None, max_out=None, clipped=None, device=None, nframes=None, levels=None,
+                          for_wav_data=False):
+        """As step_device(), the PCM as int16 (step_int16): everything in GROUPED order, asynchronous on torch's current stream.
+        Returns (pcm16 [nvoices, max values] view of `out`, values per voice uint32[nvoices]).  `out` (optional): int16 CUDA tensor
+        [nvoices, pitch >= max values], any pitch, odd ones too; `max_out` (optional): float32 CUDA tensor [nvoices];
+        `clipped` (optional): int32 CUDA tensor [nvoices] (the counts, which stay far below 2^31)."""
+        import torch
+        a = self._actions(actions)
+        lv = self._levels(levels)
+        n, pushed = self._device_frames(a, frames, nframes)
+        dev = frames.device if pushed else out.device if out is not None else device if device is not None \
+            else torch.device("cuda", torch.cuda.current_device())
+        counts = self._counts(a, n)
+        values = self._values(counts)
+        m = self._width(values)
+        if out is None:
+            out = torch.empty((self.nvoices, max(m, 1)), dtype=torch.int16, device=dev)
+        if not (out.is_cuda and out.dtype == torch.int16 and out.dim() == 2 and out.shape[0] == self.nvoices and out.stride(1) == 1
+                and out.shape[1] >= m):
+            raise ValueError("out must be an int16 CUDA tensor [%d, >= %d] with unit column stride" % (self.nvoices, m))
+        if max_out is not None and not (max_out.is_cuda and max_out.dtype == torch.float32 and max_out.numel() >= self.nvoices):
+            raise ValueError("max_out must be a float32 CUDA tensor of %d values" % self.nvoices)
+        if clipped is not None and not (clipped.is_cuda and clipped.dtype == torch.int32 and clipped.is_contiguous() and clipped.numel() >= self.nvoices):
+            raise ValueError("clipped must be a contiguous int32 CUDA tensor of %d values" % self.nvoices)
+        nout = np.zeros(self.ngroups, dtype=np.uint32)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().trm_mixed_stream_step_device_int16(self._h, a.ctypes.data, frames.data_ptr() if pushed else None, n,
+                                                       lv.ctypes.data if lv is not None else None, int(bool(for_wav_data)), out.data_ptr(),
+                                                       out.stride(0), nout.ctypes.data, max_out.data_ptr() if max_out is not None else None,
+                                                       clipped.data_ptr() if clipped is not None else None, st))
+        assert np.array_equal(nout.astype(np.int64), counts)
+        return out[:, :m], values.astype(np.uint32)[self._vgroup]
+
+    # -------------------------------------------------------------- device buffers (torch tensors, grouped order)
+    def step_device(self, actions, frames=None, out=None, max_out=None, device=None, nframes=None):
+        """As step(), on the device: frames a float32 CUDA tensor [nvoices, n, 16] in GROUPED order (frames[order] of the caller's).
+        Asynchronous on torch's current stream; nothing but the step's small tables crosses PCIe.  Returns (pcm [nvoices, max_m]
+        view of `out`, samples per voice uint32[nvoices]), both in grouped order.  `out` (optional): float32 CUDA tensor
+        [nvoices, pitch >= max_m]; `max_out` (optional): float32 CUDA tensor [nvoices]."""
+        import torch
+        a = self._actions(actions)
+        n, pushed = self._device_frames(a, frames, nframes)
         dev = frames.device if pushed else out.device if out is not None else device if device is not None \
             else torch.device("cuda", torch.cuda.current_device())
         counts = self._counts(a, n)

@@ -669,6 +669,50 @@ int    trm_mixed_stream_group_set_events(trm_mixed_stream *s, size_t group, cons
 size_t trm_mixed_stream_group_frames_left(const trm_mixed_stream *s, size_t group);
 int    trm_mixed_stream_last_frames(trm_mixed_stream *s, size_t voice, float *rows, size_t cap_rows, size_t *nrows);
 
+/* int16 PCM per step, scaled on the device: trm_mixed_stream_step[_device] with the last stage of the server chain behind it.
+ * The caller gives every group a LEVEL, the maximumSampleValue its utterance is normalised against (a stream does not know the
+ * true one until the utterance is over: a server knows it from the voice type, or from the max_out of the utterance before), and
+ * the step returns int16 PCM scaled as -saveOutputToFile: / -generateWAVData scale it.  One extra launch over the voices that
+ * received samples (and, where `clipped` is wanted, a small one that clears it); no fp32 sample crosses PCIe.
+ *   - THE RULE.  A voice of group g, in a set with volumeAmp = amplitude(volume), balance and channels, under level[g] and
+ *     for_wav_data, has its gains formed exactly as trm_batch_scale_to_int16_device forms them:
+ *       scale = (32767.0 / (double)level) * volumeAmp
+ *       mono:    value = rint((double)x * scale)
+ *       stereo:  left = -((balance / 2.0) - 0.5) * scale * g2,  right = ((balance / 2.0) + 0.5) * scale * g2,
+ *                g2 = for_wav_data ? 1.0 : 2.0; the two values of a sample are interleaved, left first.
+ *     The batch scalers wrap on overflow like the reference's cast, which is harmless under the true maximum and useless under a
+ *     chosen level, so the stream SATURATES: a rounded value above 32767 becomes 32767, one below -32768 becomes -32768, NaN
+ *     becomes 0.  clipped[v] (optional, nvoices entries) = the int16 values of voice v in this step that were saturated or NaN
+ *     (both channels of a stereo voice count); 0 for voices that received nothing.
+ *   - PARITY.  The int16 values of an utterance streamed under one level L in which nothing clips, concatenated over the steps,
+ *     are byte for byte what trm_batch_scale_to_int16_device writes for the fp32 samples the same stream returns through
+ *     trm_mixed_stream_step_device, with d_max_sample[v] = L and the same for_wav_data.  Where values clip, the result is the
+ *     rule above evaluated in double precision.  nout and max_out of an int16 step are those of the fp32 step (max_out is the
+ *     maximum of the fp32 samples: what the next utterance's level can be taken from).
+ *   - level: a HOST array of ngroups floats in both entries, like action.  Only the entries of non-empty groups that synthesize
+ *     in this step are read; each must be finite and > 0 (TRM_EINVAL naming the group otherwise; a null level with a group
+ *     that synthesizes: TRM_EINVAL).  It may differ from step to step.
+ *   - out_pitch16 counts int16 values; voice v is written at out16 + v * out_pitch16: nout[g] values, 2 * nout[g] for a stereo
+ *     set.  out_pitch16 >= the largest count * channels of a non-empty group that synthesizes (TRM_EINVAL otherwise), and may be
+ *     odd: rows need 2-byte alignment and no more.  Bytes of a row beyond the voice's values, and the rows of voices that received
+ *     nothing, are not written.  The engine stages the step in fp32 rows as wide as out_pitch16: keep it near what a step needs.
+ *   - Every refusal above comes before any device work and leaves the stream as it was.
+ *   - Actions, event lists, samples_for, last_frames, both loop orders (TRAcT order's x100 is applied before the scaling) and
+ *     down-sampling sets are those of the fp32 step, and int16 and fp32 steps of one stream may alternate freely: the tube does
+ *     not know the difference.  The entries refuse a stream without groups (TRM_EINVAL).
+ *   - The device entry gains no host wait: it waits where trm_mixed_stream_step_device waits, on a change of the step's shape
+ *     -- here (nframes, out_pitch16) -- or when the noise sequence has to grow.  The engine keeps ONE shape: an int16 step's is
+ *     (nframes, out_pitch16 rounded up to a multiple of 4), an fp32 step's (nframes, out_pitch).  A caller that alternates the
+ *     two DEVICE entries therefore changes the shape with every step -- a host wait and a re-upload of the index arrays each
+ *     time -- unless it gives the fp32 steps out_pitch = out_pitch16 rounded up to a multiple of 4.
+ *   - A library built without the int16 kernel (the host units alone) refuses these entries with TRM_EHIP; all else works. */
+int    trm_mixed_stream_step_int16(trm_mixed_stream *s, const uint8_t *action, const float *frames, size_t nframes,
+                                   const float *level, int for_wav_data, int16_t *out16, size_t out_pitch16, uint32_t *nout,
+                                   float *max_out, uint32_t *clipped);
+int    trm_mixed_stream_step_device_int16(trm_mixed_stream *s, const uint8_t *action, const float *d_frames, size_t nframes,
+                                          const float *level, int for_wav_data, int16_t *d_out16, size_t out_pitch16,
+                                          uint32_t *nout, float *d_max_out, uint32_t *d_clipped, void *hip_stream);
+
 /* Library / device identification. */
 int  trm_device_count(void);
 const char *trm_build_info(void);
