@@ -80,6 +80,7 @@ EXPORTS = [
     "trm_mixed_stream_step", "trm_mixed_stream_step_device",
     "trm_mixed_stream_group_set_events", "trm_mixed_stream_group_frames_left", "trm_mixed_stream_last_frames",
     "trm_mixed_stream_step_int16", "trm_mixed_stream_step_device_int16",
+    "trm_mixed_stream_group_bind", "trm_mixed_stream_group_bound_set", "trm_mixed_stream_set_params",
 ]
 
 _lib = None
@@ -226,6 +227,10 @@ def lib():
     L.trm_mixed_stream_last_frames.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.trm_mixed_stream_step_int16.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp, vp, vp]
     L.trm_mixed_stream_step_device_int16.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp, vp, vp, vp]
+    L.trm_mixed_stream_group_bind.argtypes = [vp, C.c_size_t, C.c_size_t]
+    L.trm_mixed_stream_group_bound_set.argtypes = [vp, C.c_size_t]
+    L.trm_mixed_stream_group_bound_set.restype = C.c_size_t
+    L.trm_mixed_stream_set_params.argtypes = [vp, C.c_size_t, C.POINTER(TrmInputParams)]
     for name in EXPORTS:
         getattr(L, name)
     _lib = L

@@ -18,6 +18,10 @@
 // (trm_tracks_run.hip) generates in place in front of the tube launch, and as the flush once they have run out.
 // A step may also leave as int16 PCM (trm_mixed_stream_step_int16): the same step into fp32 rows of the engine's, then one launch
 // (trm_grp_out.hip) that scales the rows of the voices that received samples against their group's level.
+// A closed group may be bound to another of the stream's sets (trm_mixed_stream_group_bind) and a set that no open group runs
+// may be given other parameters (trm_mixed_stream_set_params): both make the storage that depends on the binding current
+// themselves -- the group's map entries, the history rows, the tube-rate offsets (rebind_plan, rebind_commit) -- so a step finds
+// it as it would have after create.
 // What a chunk and a step share is stated once: the converter range of a run of
 // control periods (unit_range), the length limit (range_too_long), the index arrays of a shape (stream_shape), the down-sampling
 // launches around the tube launch (down_history_in, down_convert) and the ordering of calls across HIP streams (stream_ordered).
@@ -63,6 +67,11 @@ struct trm_stream_engine {
     std::vector<size_t> gbegin;              // group_begin: voices gbegin[g] .. gbegin[g + 1] - 1 are group g's
     std::vector<uint32_t> gset;              // the group's parameter set (an empty group: 0)
     std::vector<uint32_t> gentry;            // the group's map entries are gentry[g] .. gentry[g + 1] - 1
+    std::vector<uint4> hMap;                 // the block map's host copy (trm_mixed_stream_group_bind rewrites a group's entries)
+    // the history rows of the groups bound to down-sampling sets lie group after group, group g's at ghistAt[g] -- at create
+    // that is the lock-step layout, set after set; anyDown: some group with voices is bound to such a set
+    std::vector<uint64_t> ghistAt;
+    bool anyDown = false;
     std::vector<uint64_t> gperiods;          // control periods of the group's open utterance so far
     std::vector<uint8_t> gopen, gfirst;      // an utterance is open / no chunk of it has been synthesized yet
     DevBuf<uint32_t> dVoiceGroup;            // [nvoices], fixed
@@ -132,21 +141,29 @@ static size_t step_words(const trm_stream_engine *s, size_t nrun) { return (size
 // ... and of what an int16 step adds behind them (trm_kernels.h, GrpInt16Args::step) with `nentries` map entries that receive samples
 static size_t step_words_int16(const trm_stream_engine *s, size_t nentries) { return 2 * (s->gbegin.size() - 1) + 1 + nentries; }
 
+// whether set k's batch b can stream: an up-sampling set, or one whose chunks the tiled down-sampling kernel converts
+static int down_streams(const trm_stream_engine *s, size_t k, const trm_batch *b)
+{
+    if (!b->c.upsample && (!b->dDownRows || b->downR > (uint32_t)b->d.padSize || b->downL > (uint32_t)b->d.padSize + 1u ||
+                           !trm::downsample_tiled_fits(b->c, b->downL, b->downR))) {
+        // (a chunk emits the outputs whose read position lies inside it; their right wing must end there too)
+        char set[40] = "";
+        if (s->mixed) snprintf(set, sizeof set, "parameter set %zu: ", k);
+        return fail(TRM_ERANGE, "%sstreaming: output rate too far below the tube rate (%d Hz) for the tiled down-sampling kernel", set, b->d.sampleRate);
+    }
+    return TRM_OK;
+}
+
+// a set's share of an int16 step's scaling (as trm_mixed's MixOutSet)
+static trm::GrpOutSet grp_out_set(const trm_input_params &p) { return trm::GrpOutSet{trm::io_amplitude(p.volume), p.balance, p.channels == 2 ? 2 : 1, 0}; }
+
 // what create does once the batches exist (on failure the caller destroys the stream)
 static int stream_init(trm_stream_engine *s, const size_t *set_begin)
 {
     const size_t S = s->sets.size(), V = set_begin[S];
     int rc;
-    for (size_t k = 0; k < S; k++) {
-        const trm_batch *b = s->sets[k];
-        if (!b->c.upsample && (!b->dDownRows || b->downR > (uint32_t)b->d.padSize || b->downL > (uint32_t)b->d.padSize + 1u ||
-                               !trm::downsample_tiled_fits(b->c, b->downL, b->downR))) {
-            // (a chunk emits the outputs whose read position lies inside it; their right wing must end there too)
-            char set[40] = "";
-            if (s->mixed) snprintf(set, sizeof set, "parameter set %zu: ", k);
-            return fail(TRM_ERANGE, "%sstreaming: output rate too far below the tube rate (%d Hz) for the tiled down-sampling kernel", set, b->d.sampleRate);
-        }
-    }
+    for (size_t k = 0; k < S; k++)
+        if ((rc = down_streams(s, k, s->sets[k]))) return rc;
     s->begin.assign(set_begin, set_begin + S + 1);
     s->nvoices = V;
     trm_batch *b0 = s->sets[0];
@@ -196,6 +213,13 @@ static int stream_init(trm_stream_engine *s, const size_t *set_begin)
         s->histBase[k] = s->histFloats;
         s->histFloats += (uint64_t)(set_begin[k + 1] - set_begin[k]) * s->hist[k];
     }
+    s->ghistAt.assign(G, 0);
+    for (size_t g = 0; g < G; g++) {
+        const size_t k = s->gset[g];
+        if (s->gbegin[g + 1] == s->gbegin[g] || s->hist[k] == 0) continue;
+        s->ghistAt[g] = s->histBase[k] + (uint64_t)(s->gbegin[g] - set_begin[k]) * s->hist[k];
+        s->anyDown = true;
+    }
     // state: per 64 voices; the mixed wide form keys it by map entry (64 lanes each)
     const size_t stateVoices = s->mixed && s->wide ? (size_t)s->mapEntries * 64 : (V + 63) / 64 * 64;
     if ((rc = s->dState.reserve(stateVoices * trm::kStreamFloats)) || (rc = s->dLast.reserve(V * 16)) || (rc = s->dFrameOff.reserve(V)) ||
@@ -207,6 +231,7 @@ static int stream_init(trm_stream_engine *s, const size_t *set_begin)
         hipError_t e = hipMemcpy(s->dMap.p, map.data(), map.size() * sizeof(uint4), hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail(TRM_EHIP, "block map: %s", hipGetErrorString(e));
     }
+    if (s->grouped) s->hMap.swap(map);
     if (s->grouped) {
         std::vector<uint32_t> vg(V);
         for (size_t g = 0; g < G; g++)
@@ -216,12 +241,8 @@ static int stream_init(trm_stream_engine *s, const size_t *set_begin)
             return rc;
         hipError_t e = hipMemcpy(s->dVoiceGroup.p, vg.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail(TRM_EHIP, "group table: %s", hipGetErrorString(e));
-        // the sets' share of an int16 step's scaling (as trm_mixed's MixOutSet)
         std::vector<trm::GrpOutSet> os(S);
-        for (size_t k = 0; k < S; k++) {
-            const trm_input_params &p = s->sets[k]->params;
-            os[k] = trm::GrpOutSet{trm::io_amplitude(p.volume), p.balance, p.channels == 2 ? 2 : 1, 0};
-        }
+        for (size_t k = 0; k < S; k++) os[k] = grp_out_set(s->sets[k]->params);
         e = hipMemcpy(s->dOutSets.p, os.data(), S * sizeof(trm::GrpOutSet), hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail(TRM_EHIP, "output table: %s", hipGetErrorString(e));
     }
@@ -273,6 +294,46 @@ static size_t stream_samples_for_finish(const trm_stream_engine *s, size_t set)
     return (size_t)(r.kEnd - r.kBase);
 }
 
+// The tube-rate rows of a grouped stream under binding `gset`, group after group over the groups bound to down-sampling sets
+// (hist[k] floats of history and rows `pitch[k]` apart for set k; hist[k] == 0: an up-sampling set): every voice's row and where
+// the tube stage writes in it.  Returns the floats of all rows.
+static uint64_t group_tube_rows(const trm_stream_engine *s, const std::vector<uint32_t> &gset, const std::vector<uint32_t> &hist,
+                                const std::vector<uint64_t> &pitch, std::vector<uint64_t> &off0, std::vector<uint64_t> &off)
+{
+    off0.assign(s->nvoices, 0); off.assign(s->nvoices, 0);
+    uint64_t at = 0;
+    for (size_t g = 0; g + 1 < s->gbegin.size(); g++) {
+        const size_t k = gset[g];
+        for (size_t v = s->gbegin[g]; hist[k] > 0 && v < s->gbegin[g + 1]; v++) {
+            off0[v] = at;
+            off[v] = at + hist[k];
+            at += pitch[k];
+        }
+    }
+    return at;
+}
+
+// The tube-rate rows of a shape of Q control periods (host copies): set after set over the voices of the down-sampling sets; a
+// grouped stream's by its binding (group_tube_rows) -- the same rows until a group is bound anew.
+static void tube_layout(trm_stream_engine *s, uint64_t Q)
+{
+    const size_t S = s->sets.size(), V = s->nvoices;
+    if (!s->grouped) { s->hTubeOff0.assign(V, 0); s->hTubeOff.assign(V, 0); }
+    uint64_t at = 0;
+    for (size_t k = 0; k < S; k++) {
+        const trm_batch *b = s->sets[k];
+        if (b->c.upsample) continue;
+        s->rowPitch[k] = tube_row_pitch(b, (uint64_t)s->hist[k] + Q * (uint64_t)b->d.controlPeriod);
+        s->tubeBase[k] = at;
+        for (size_t v = s->begin[k]; !s->grouped && v < s->begin[k + 1]; v++) {
+            s->hTubeOff0[v] = at;
+            s->hTubeOff[v] = at + s->hist[k];
+            at += s->rowPitch[k];
+        }
+    }
+    s->tubeFloats = s->grouped ? group_tube_rows(s, s->gset, s->hist, s->rowPitch, s->hTubeOff0, s->hTubeOff) : at;
+}
+
 // The index arrays of a shape: `rows` frame rows per voice, PCM rows `out_pitch` apart and, for the down-sampling sets, tube-rate
 // rows of [history | Q control periods (| the flush zeros)], 16-byte aligned, set after set.  They depend on the shape only:
 // rebuilt when it changes (the host copies live in the stream object).  The last chunk that read them -- and whose uploads read
@@ -281,7 +342,7 @@ static size_t stream_samples_for_finish(const trm_stream_engine *s, size_t set)
 static int stream_shape(trm_stream_engine *s, size_t rows, size_t out_pitch, uint64_t Q, bool anyDown, hipStream_t st)
 {
     if (s->shapeRows == rows && s->shapePitch == out_pitch) return TRM_OK;
-    const size_t S = s->sets.size(), V = s->nvoices;
+    const size_t V = s->nvoices;
     if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
     s->hFrameOff.resize(V); s->hOutOff.resize(V); s->hNFrames.assign(V, (uint32_t)rows);
     for (size_t v = 0; v < V; v++) { s->hFrameOff[v] = v * rows; s->hOutOff[v] = v * out_pitch; }
@@ -289,20 +350,7 @@ static int stream_shape(trm_stream_engine *s, size_t rows, size_t out_pitch, uin
     HIP_TRY(hipMemcpyAsync(s->dOutOff.p, s->hOutOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(s->dNFrames.p, s->hNFrames.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if (anyDown) {
-        s->hTubeOff0.assign(V, 0); s->hTubeOff.assign(V, 0);
-        uint64_t at = 0;
-        for (size_t k = 0; k < S; k++) {
-            const trm_batch *b = s->sets[k];
-            if (b->c.upsample) continue;
-            s->rowPitch[k] = tube_row_pitch(b, (uint64_t)s->hist[k] + Q * (uint64_t)b->d.controlPeriod);
-            s->tubeBase[k] = at;
-            for (size_t v = s->begin[k]; v < s->begin[k + 1]; v++) {
-                s->hTubeOff0[v] = at;
-                s->hTubeOff[v] = at + s->hist[k];
-                at += s->rowPitch[k];
-            }
-        }
-        s->tubeFloats = at;
+        tube_layout(s, Q);
         HIP_TRY(hipMemcpyAsync(s->dTubeOff0.p, s->hTubeOff0.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(s->dTubeOff.p, s->hTubeOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     }
@@ -310,11 +358,11 @@ static int stream_shape(trm_stream_engine *s, size_t rows, size_t out_pitch, uin
     return TRM_OK;
 }
 
-// Voices [lo, lo + n) of down-sampling set k, in front of the tube launch: their history -- zeros when their utterance opens --
-// to the head of their tube-rate rows (the tube stage writes behind it)
-static int down_history_in(trm_stream_engine *s, size_t k, size_t lo, size_t n, bool first, hipStream_t st)
+// Voices [lo, lo + n) of down-sampling set k, whose history rows lie at `histAt`, in front of the tube launch: their history --
+// zeros when their utterance opens -- to the head of their tube-rate rows (the tube stage writes behind it)
+static int down_history_in(trm_stream_engine *s, size_t k, size_t lo, size_t n, uint64_t histAt, bool first, hipStream_t st)
 {
-    float *hist = s->dHist.p + s->histBase[k] + (uint64_t)(lo - s->begin[k]) * s->hist[k];
+    float *hist = s->dHist.p + histAt;
     if (first) HIP_TRY(hipMemsetAsync(hist, 0, (uint64_t)n * s->hist[k] * sizeof(float), st));
     HIP_TRY(hipMemcpy2DAsync(s->dTube.p + s->hTubeOff0[lo], s->rowPitch[k] * sizeof(float), hist, s->hist[k] * sizeof(float),
                              s->hist[k] * sizeof(float), n, hipMemcpyDeviceToDevice, st));
@@ -323,8 +371,8 @@ static int down_history_in(trm_stream_engine *s, size_t k, size_t lo, size_t n, 
 
 // ... and behind it: the conversion of the Q control periods they ran from `periods` on (or of the flush) to the outputs
 // kBase <= k < kEnd, and the history for their next chunk
-static int down_convert(trm_stream_engine *s, const trm::TubeArgs &a, size_t k, size_t lo, size_t n, uint64_t periods, uint64_t Q, bool flush,
-                        uint64_t kBase, uint64_t kEnd, hipStream_t st)
+static int down_convert(trm_stream_engine *s, const trm::TubeArgs &a, size_t k, size_t lo, size_t n, uint64_t histAt, uint64_t periods, uint64_t Q,
+                        bool flush, uint64_t kBase, uint64_t kEnd, hipStream_t st)
 {
     const trm_batch *b = s->sets[k];
     const uint64_t nBase = periods * (uint64_t)b->d.controlPeriod, N = Q * (uint64_t)b->d.controlPeriod;
@@ -336,7 +384,7 @@ static int down_convert(trm_stream_engine *s, const trm::TubeArgs &a, size_t k, 
         HIP_TRY(hipMemsetAsync(s->dMax.p + lo, 0, n * sizeof(float), st));
     }
     // the next chunk's history: the voices' last hist tube samples so far (row positions N .. N + hist - 1)
-    HIP_TRY(hipMemcpy2DAsync(s->dHist.p + s->histBase[k] + (uint64_t)(lo - s->begin[k]) * s->hist[k], s->hist[k] * sizeof(float),
+    HIP_TRY(hipMemcpy2DAsync(s->dHist.p + histAt, s->hist[k] * sizeof(float),
                              s->dTube.p + s->hTubeOff0[lo] + N, s->rowPitch[k] * sizeof(float), s->hist[k] * sizeof(float), n,
                              hipMemcpyDeviceToDevice, st));
     return TRM_OK;
@@ -399,7 +447,7 @@ static int stream_chunk_impl(trm_stream_engine *s, const float *d_pushed, size_t
             for (size_t k = 0; k < S; k++) {
                 const size_t n = s->begin[k + 1] - s->begin[k];
                 if (s->sets[k]->c.upsample || n == 0) continue;
-                if ((rc = down_history_in(s, k, s->begin[k], n, false, st))) return rc;
+                if ((rc = down_history_in(s, k, s->begin[k], n, s->histBase[k], false, st))) return rc;
             }
             a.tube_out = s->dTube.p;
             a.tube_offset = s->dTubeOff.p;
@@ -430,7 +478,7 @@ static int stream_chunk_impl(trm_stream_engine *s, const float *d_pushed, size_t
             const trm_batch *b = s->sets[k];
             if (n == 0) continue;
             const uint64_t count = kEnd[k] - kBase[k];
-            if (!b->c.upsample && (rc = down_convert(s, a, k, lo, n, s->periods, Q, flush, kBase[k], kEnd[k], st))) return rc;
+            if (!b->c.upsample && (rc = down_convert(s, a, k, lo, n, s->histBase[k], s->periods, Q, flush, kBase[k], kEnd[k], st))) return rc;
             // tube.c:1177 multiplies the tube-rate sample by 100 before its converter; the converter is linear, so the gain
             // is applied to what it returns (one fp32 rounding of difference), per set over its voices and count
             if (tract && count > 0)
@@ -586,8 +634,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     const size_t G = plan.size(), V = s->nvoices, E = s->mapEntries;
     const bool tract = s->mode == TRM_STREAM_MODE_TRACT;
     uint64_t maxCount = 0, noiseNeed = 0;
-    bool downRuns = false, anyDown = false;
-    for (size_t k = 0; k < s->sets.size(); k++) anyDown = anyDown || (!s->sets[k]->c.upsample && s->begin[k + 1] > s->begin[k]);
+    bool downRuns = false;
     for (size_t g = 0; g < G; g++) {
         const GroupPlan &p = plan[g];
         if (nout) nout[g] = (uint32_t)(p.kEnd - p.kBase);
@@ -604,7 +651,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     const size_t rows = nframes == 0 && s->shapeRows > 0 && s->shapePitch == out_pitch ? s->shapeRows : nframes + 1;
     int rc;
     if ((rc = s->dFrames.reserve(V * rows * 16))) return rc;
-    if ((rc = stream_shape(s, rows, out_pitch, rows - 1, anyDown, st))) return rc;
+    if ((rc = stream_shape(s, rows, out_pitch, rows - 1, s->anyDown, st))) return rc;
     // the step's tables
     size_t nRun = 0;                         // voices whose frames are generated in this step
     for (size_t g = 0; g < G; g++) nRun += plan[g].gen ? s->gbegin[g + 1] - s->gbegin[g] : 0;
@@ -670,7 +717,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
         for (size_t g = 0; g < G; g++) {
             const size_t lo = s->gbegin[g], n = s->gbegin[g + 1] - lo, k = s->gset[g];
             if (!plan[g].runs || n == 0 || s->sets[k]->c.upsample) continue;
-            if ((rc = down_history_in(s, k, lo, n, s->gfirst[g], st))) return rc;        // (zeroed when the GROUP opens)
+            if ((rc = down_history_in(s, k, lo, n, s->ghistAt[g], s->gfirst[g], st))) return rc;        // (zeroed when the GROUP opens)
         }
         a.tube_out = s->dTube.p;
         a.tube_offset = s->dTubeOff.p;
@@ -688,7 +735,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
         const GroupPlan &p = plan[g];
         const size_t lo = s->gbegin[g], n = s->gbegin[g + 1] - lo, k = s->gset[g];
         if (!p.runs || n == 0) continue;
-        if (!s->sets[k]->c.upsample && (rc = down_convert(s, a, k, lo, n, s->gperiods[g], p.Q, p.flush, p.kBase, p.kEnd, st))) return rc;
+        if (!s->sets[k]->c.upsample && (rc = down_convert(s, a, k, lo, n, s->ghistAt[g], s->gperiods[g], p.Q, p.flush, p.kBase, p.kEnd, st))) return rc;
         if (tract && p.kEnd > p.kBase)       // (TRAcT order's x100: stream_chunk_impl)
             HIP_TRY(trm::launch_gain(d_out + lo * out_pitch, out_pitch, (uint32_t)(p.kEnd - p.kBase), (uint32_t)n, s->dMax.p + lo, 100.0f, st));
     }
@@ -1272,6 +1319,182 @@ int trm_mixed_stream_last_frames(trm_mixed_stream *s, size_t voice, float *rows,
     if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
     // (the step's rows of the voice behind its lead row)
     HIP_TRY(hipMemcpy(rows, s->dFrames.p + ((size_t)voice * s->shapeRows + 1) * 16, q * 16 * sizeof(float), hipMemcpyDeviceToHost));
+    return TRM_OK;
+}
+
+// ------------------------------------------------------------------ grouped trm_mixed_stream: groups change sets, sets change parameters
+// The storage that depends on which set every group is bound to: the history rows (dHist, group after group: ghistAt), the
+// tube-rate rows and their offsets for the current shape (dTube, dTubeOff / dTubeOff0) and the set field of the map entries.  A
+// bind or a change of a set's parameters makes all of it current itself, in three parts: rebind_plan does everything that can
+// fail for want of memory and touches nothing the stream uses; the device copies follow (the caller's, then rebind_upload);
+// rebind_commit, which cannot fail, makes the host's books say the same.  The caller has waited for the device.
+struct RebindPlan {
+    std::vector<uint64_t> at;                // ghistAt under the new binding
+    uint64_t floats = 0;
+    bool anyDown = false;
+    DevBuf<float> fresh;                     // the history rows' new buffer, where the old one cannot serve
+    bool shaped = false;                     // a shape exists and a group down-samples: the tube-rate rows are laid out for it
+    std::vector<uint64_t> pitch, off0, off;  // the sets' row pitches under that shape; the voices' offsets
+    uint64_t tubeFloats = 0;
+    DevBuf<float> freshTube;                 // the tube-rate rows' new buffer, where the old one is too small (they hold nothing between steps)
+};
+
+// gset / hist / batches: the binding, the sets' history lengths (0: an up-sampling set) and their batches to lay the rows out for
+static int rebind_plan(trm_stream_engine *s, const std::vector<uint32_t> &gset, const std::vector<uint32_t> &hist,
+                       const std::vector<trm_batch *> &batches, RebindPlan &p)
+{
+    const size_t G = s->gbegin.size() - 1, S = s->sets.size();
+    p.at.assign(G, 0);
+    bool moved = false;                      // an open group's rows lie elsewhere: they hold its history between steps
+    for (size_t g = 0; g < G; g++) {
+        const uint64_t nv = s->gbegin[g + 1] - s->gbegin[g], h = hist[gset[g]];
+        if (nv == 0 || h == 0) continue;
+        p.at[g] = p.floats;
+        p.floats += nv * h;
+        p.anyDown = true;
+        moved = moved || (s->gopen[g] && p.at[g] != s->ghistAt[g]);
+    }
+    if (!p.anyDown) return TRM_OK;
+    int rc;
+    if ((rc = s->dTubeOff.reserve(s->nvoices)) || (rc = s->dTubeOff0.reserve(s->nvoices))) return rc;      // (there since create where a set with voices down-sampled)
+    if (moved || p.floats > s->dHist.cap) {
+        if ((rc = p.fresh.reserve(p.floats))) return rc;
+        // (an open group keeps its set and that set its parameters: the length of its rows is s->hist's)
+        for (size_t g = 0; g < G; g++) {
+            const uint64_t nv = s->gbegin[g + 1] - s->gbegin[g], h = s->hist[s->gset[g]];
+            if (!s->gopen[g] || nv == 0 || h == 0) continue;
+            HIP_TRY(hipMemcpy(p.fresh.p + p.at[g], s->dHist.p + s->ghistAt[g], nv * h * sizeof(float), hipMemcpyDeviceToDevice));
+        }
+    }
+    if (s->shapeRows == 0) return TRM_OK;    // (no shape yet: the first step lays the tube-rate rows out, and waits as a first step does)
+    // the tube-rate rows of the current shape, so that the step behind this call neither allocates nor waits for them
+    p.shaped = true;
+    p.pitch.assign(S, 0);
+    for (size_t k = 0; k < S; k++)
+        if (hist[k] > 0) p.pitch[k] = tube_row_pitch(batches[k], (uint64_t)hist[k] + (uint64_t)(s->shapeRows - 1) * (uint64_t)batches[k]->d.controlPeriod);
+    p.tubeFloats = group_tube_rows(s, gset, hist, p.pitch, p.off0, p.off);
+    if (p.tubeFloats + 4 > s->dTube.cap && (rc = p.freshTube.reserve(p.tubeFloats + 4))) return rc;
+    return TRM_OK;
+}
+
+// the offsets of the plan's tube-rate rows to the device
+static int rebind_upload(trm_stream_engine *s, const RebindPlan &p)
+{
+    if (!p.shaped) return TRM_OK;
+    HIP_TRY(hipMemcpy(s->dTubeOff0.p, p.off0.data(), s->nvoices * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->dTubeOff.p, p.off.data(), s->nvoices * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return TRM_OK;
+}
+
+// (s->gset, s->hist and the sets are the new ones by now)
+static void rebind_commit(trm_stream_engine *s, RebindPlan &p)
+{
+    if (p.fresh.p) { std::swap(p.fresh.p, s->dHist.p); std::swap(p.fresh.cap, s->dHist.cap); }
+    if (p.freshTube.p) { std::swap(p.freshTube.p, s->dTube.p); std::swap(p.freshTube.cap, s->dTube.cap); }
+    s->ghistAt.swap(p.at);
+    s->histFloats = p.floats;
+    s->anyDown = p.anyDown;
+    if (!p.shaped) return;
+    s->hTubeOff0.swap(p.off0);
+    s->hTubeOff.swap(p.off);
+    s->tubeFloats = p.tubeFloats;
+    for (size_t k = 0; k < p.pitch.size(); k++)
+        if (p.pitch[k]) s->rowPitch[k] = p.pitch[k];
+}
+
+// whether the stream's form runs set `set` with constants c: the four-lane form converts at most four outputs per tube sample
+static int form_runs(const trm_stream_engine *s, size_t set, const trm::Const &c)
+{
+    if (!s->wide && quad_ratio_too_high(c))
+        return fail(TRM_ERANGE, "parameter set %zu: more than four outputs per tube sample, which the stream's four-lane form cannot run", set);
+    return TRM_OK;
+}
+
+int trm_mixed_stream_group_bind(trm_mixed_stream *s, size_t group, size_t set)
+{
+    if (!s) return fail(TRM_EINVAL, "null stream");
+    if (!s->grouped) return fail(TRM_EINVAL, "not a grouped stream (trm_mixed_stream_create_groups)");
+    if (group + 1 >= s->gbegin.size()) return fail(TRM_EINVAL, "group %zu of %zu", group, s->gbegin.size() - 1);
+    if (set >= s->sets.size()) return fail(TRM_EINVAL, "parameter set %zu of %zu", set, s->sets.size());
+    if (s->gopen[group]) return fail(TRM_EINVAL, "group %zu has an utterance open: a group changes its set while it is closed", group);
+    if (s->gbegin[group + 1] == s->gbegin[group] || s->gset[group] == set) return TRM_OK;
+    int rc = form_runs(s, set, s->sets[set]->c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->sets[0]->device));
+    // the steps so far may still read the map and the offsets, on whichever HIP stream: the one wait of this entry
+    if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
+    std::vector<uint32_t> gset = s->gset;
+    gset[group] = (uint32_t)set;
+    RebindPlan p;
+    if ((rc = rebind_plan(s, gset, s->hist, s->sets.b, p))) return rc;
+    // the device first: the group's map entries, the offsets; then the host's books
+    const uint32_t e0 = s->gentry[group], e1 = s->gentry[group + 1];
+    std::vector<uint4> entries(s->hMap.begin() + e0, s->hMap.begin() + e1);
+    for (uint4 &m : entries) m.x = (uint32_t)set;
+    HIP_TRY(hipMemcpy(s->dMap.p + e0, entries.data(), entries.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    if ((rc = rebind_upload(s, p))) return rc;
+    std::copy(entries.begin(), entries.end(), s->hMap.begin() + e0);
+    s->gset.swap(gset);
+    rebind_commit(s, p);
+    return TRM_OK;
+}
+
+size_t trm_mixed_stream_group_bound_set(const trm_mixed_stream *s, size_t group)
+{
+    return s && s->grouped && group + 1 < s->gbegin.size() ? s->gset[group] : 0;
+}
+
+int trm_mixed_stream_set_params(trm_mixed_stream *s, size_t set, const trm_input_params *params)
+{
+    if (!s || !params) return fail(TRM_EINVAL, "null argument");
+    if (!s->grouped) return fail(TRM_EINVAL, "not a grouped stream (trm_mixed_stream_create_groups)");
+    if (set >= s->sets.size()) return fail(TRM_EINVAL, "parameter set %zu of %zu", set, s->sets.size());
+    const size_t G = s->gbegin.size() - 1;
+    bool bound = false;                      // groups with voices run the set
+    for (size_t g = 0; g < G; g++) {
+        if (s->gset[g] != set || s->gbegin[g + 1] == s->gbegin[g]) continue;
+        if (s->gopen[g]) return fail(TRM_EINVAL, "parameter set %zu: group %zu runs an utterance with it", set, g);
+        bound = true;
+    }
+    trm_batch *b = s->sets[set], *b0 = s->sets[0];
+    // the set as create checks one: a batch of its own, whose constants and tables the set's batch then takes over
+    trm_batch *nb = nullptr;
+    int rc = trm_batch_create(params, b->device, &nb);
+    if (rc) {
+        const std::string err = trm_last_error();
+        return fail(rc, "parameter set %zu: %s", set, err.c_str());
+    }
+    struct Drop { trm_batch *b; ~Drop() { trm_batch_destroy(b); } } drop{nb};
+    if ((rc = down_streams(s, set, nb)) || (bound && (rc = form_runs(s, set, nb->c)))) return rc;
+    HIP_TRY(hipSetDevice(b0->device));
+    // the steps so far may still read the tables, on whichever HIP stream: the one wait of this entry
+    if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
+    std::vector<uint32_t> hist = s->hist;
+    hist[set] = nb->c.upsample ? 0u : (uint32_t)tube_row_pitch(nb, 0);
+    std::vector<trm_batch *> batches = s->sets.b;
+    batches[set] = nb;
+    RebindPlan p;
+    if ((rc = rebind_plan(s, s->gset, hist, batches, p))) return rc;
+    uint32_t noiseRate = (uint32_t)nb->d.sampleRate;
+    for (size_t k = 0; k < s->sets.size(); k++)
+        if (k != set) noiseRate = std::max(noiseRate, (uint32_t)s->sets[k]->d.sampleRate);
+    if ((rc = ensure_noise(b0, 16u * noiseRate, b0->stream))) return rc;      // (as create: stream_init)
+    trm::Const c = nb->c;
+    c.fricGain = s->mode == TRM_STREAM_MODE_TRACT ? 10.0f : 1.0f;             // (the stream's loop order: stream_set_mode)
+    const trm::GrpOutSet os = grp_out_set(*params);
+    // the device first: the set's entries of the two tables, the offsets; then the host's books
+    HIP_TRY(hipMemcpy(s->sets.dConst + set, &c, sizeof c, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->dConst, &c, sizeof c, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->dOutSets.p + set, &os, sizeof os, hipMemcpyHostToDevice));
+    if ((rc = rebind_upload(s, p))) return rc;
+    b->params = *params;
+    b->c = c;
+    b->d = nb->d;
+    b->dFine = nb->dFine;
+    b->dDownRows = nb->dDownRows;
+    b->downL = nb->downL; b->downR = nb->downR; b->downPitch = nb->downPitch;
+    s->hist.swap(hist);
+    rebind_commit(s, p);
     return TRM_OK;
 }
 

@@ -580,7 +580,7 @@ class TRMGroupedStream:
         if sets.size == 0:
             raise ValueError("no voices")
         self.order, self.set_begin, self.group_begin, self._gindex, self.inverse = group_voices_by_group(sets, groups, nsets, ngroups)
-        self.sets, self.groups = sets, groups
+        self.sets, self.groups = sets.copy(), groups      # (sets follows the binding: bind())
         self.nvoices = int(sets.size)
         self.ngroups = int(self._gindex.size)
         self._vgroup = self._gindex[groups[self.order]]      # the library's group of every voice, grouped order
@@ -632,6 +632,47 @@ class TRMGroupedStream:
     def samples_for(self, group, action, nframes=0):
         """Samples every voice of the caller's group receives from `action` ("push" or "run" of nframes frames, "finish", "idle") now."""
         return lib().trm_mixed_stream_group_samples_for(self._h, int(self._gindex[int(group)]), self._ACTIONS[action], int(nframes))
+
+    # -------------------------------------------------------------- groups change sets, sets change parameters
+    def _group(self, group):
+        g = int(group)
+        if not 0 <= g < self.ngroups:
+            raise ValueError("group %r outside 0 .. %d" % (group, self.ngroups - 1))
+        return g
+
+    def _set(self, set):
+        k = int(set)
+        if not 0 <= k < self.nsets:
+            raise ValueError("parameter set %r outside 0 .. %d" % (set, self.nsets - 1))
+        return k
+
+    def _bound(self, g, k):
+        """what follows the binding on this side: the group's channels and its voices' entries of `sets`"""
+        self._gchannels[self._gindex[g]] = 2 if self.param_sets[k].channels == 2 and np.any(self.groups == g) else 1
+        self.sets[self.groups == g] = k
+
+    def bind(self, group, set):
+        """Binds the caller's CLOSED group `group` to parameter set `set` (include/trm_c_api.h: trm_mixed_stream_group_bind):
+        from its next utterance on its voices are those of a TRMStream of that set.  channels(), samples_for(), the widths of
+        step_int16() and `sets` follow.  Event lists that wait on the group stay.  May wait for the device once."""
+        g, k = self._group(group), self._set(set)
+        check(lib().trm_mixed_stream_group_bind(self._h, int(self._gindex[g]), k))
+        if np.any(self.groups == g):           # (a group without voices keeps what it has)
+            self._bound(g, k)
+
+    def set_of(self, group):
+        """The parameter set the caller's group `group` is bound to."""
+        return int(lib().trm_mixed_stream_group_bound_set(self._h, int(self._gindex[self._group(group)])))
+
+    def replace_set(self, set, params):
+        """Replaces the parameters of set `set` (a TRMInputParameters) while no group bound to it is open
+        (trm_mixed_stream_set_params); closed groups bound to it run the new ones from their next utterance."""
+        k = self._set(set)
+        check(lib().trm_mixed_stream_set_params(self._h, k, C.byref(params.c)))
+        self.param_sets[k] = params
+        for g in range(self.ngroups):
+            if np.any(self.groups == g) and self.set_of(g) == k:
+                self._bound(g, k)
 
     def set_events(self, group, event_lists, settings=None):
         """Event lists for the caller's CLOSED group `group`, which then advances by the action "run": one EventList per voice of

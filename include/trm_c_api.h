@@ -713,6 +713,36 @@ int    trm_mixed_stream_step_device_int16(trm_mixed_stream *s, const uint8_t *ac
                                           const float *level, int for_wav_data, int16_t *d_out16, size_t out_pitch16,
                                           uint32_t *nout, float *d_max_out, uint32_t *d_clipped, void *hip_stream);
 
+/* Groups change their voice type, sets their parameters.  Which set a group runs is decided utterance by utterance: a CLOSED
+ * group is bound to another of the stream's sets (trm_mixed_stream_group_bind), and a set that no open group runs is given other
+ * parameters (trm_mixed_stream_set_params).  A server creates its group slots over the voice types it knows, with spare empty
+ * sets if it likes, and binds a free slot when a sentence arrives.  Group sizes and the number of sets stay fixed.
+ *   - THE RULE.  "The group's set" in the rules above is the set bound, with the parameters it had, when the utterance OPENED.
+ *     From the next utterance on every voice of a re-bound group receives, bit for bit, what a trm_stream of the new set with
+ *     the group's voices returns in the same kernel form for the group's pushes and finishes alone: samples, counts, maxima; for
+ *     PUSH, FINISH and RUN, both loop orders, fp32 and int16 steps.  trm_mixed_stream_group_samples_for answers for the new set,
+ *     an int16 step scales the group's rows with the new set's volume, balance and channels (its rows are as wide as those
+ *     channels).  Other groups, open or closed, are not disturbed: one that is mid-utterance keeps its bits.
+ *   - group_bind refuses, before any device work and leaving the stream as it was: a stream without groups, a group or set out
+ *     of range, an OPEN group (TRM_EINVAL); a set the stream's form cannot run (TRM_ERANGE, trm_last_error names the set: in a
+ *     four-lane stream a set with more than four outputs per tube sample).  The set the group already has, and a group without
+ *     voices, succeed and change nothing.  Event lists that wait on the closed group stay: frames do not depend on the tube
+ *     parameters, and TRM_GROUP_RUN opens the utterance in the new set.
+ *   - set_params replaces set `set`'s parameters while no group bound to it is open (TRM_EINVAL otherwise; closed groups bound to
+ *     it run the new parameters from their next utterance).  The parameters are checked as trm_mixed_stream_create checks a
+ *     set, with the same codes and trm_last_error naming the set; TRM_ERANGE also where groups with voices are bound to the set
+ *     and the stream's form cannot run the new parameters.  The new constants take the stream's current loop order.
+ *   - trm_mixed_stream_group_bound_set: the set a group is bound to (0 for a stream without groups or a group out of range).
+ *   - Both calls may wait for the device once, as trm_mixed_stream_group_set_events does; the step entries gain no host wait and
+ *     no launch: history rows, tube-rate rows of the shape the steps have, and their offsets are made current by the call.
+ *     Storage for down-sampling voice types that had no voices at create is allocated by the call that first binds a group to
+ *     one (before the stream's first step there is no shape yet: that step sizes the tube-rate rows, as it always did).  A
+ *     call that fails for want of memory leaves the stream whole, under its old binding and parameters.  A stream on which
+ *     neither call is made does exactly what it did without them. */
+int    trm_mixed_stream_group_bind(trm_mixed_stream *s, size_t group, size_t set);
+size_t trm_mixed_stream_group_bound_set(const trm_mixed_stream *s, size_t group);
+int    trm_mixed_stream_set_params(trm_mixed_stream *s, size_t set, const trm_input_params *params);
+
 /* Library / device identification. */
 int  trm_device_count(void);
 const char *trm_build_info(void);

@@ -1,0 +1,25 @@
+"""The host code of trm_mixed_stream_group_bind and trm_mixed_stream_set_params under AddressSanitizer and UBSan, on the CPU: the
+library's host translation units and the CPU stand-ins of the HIP runtime are compiled, their host code instrumented by both
+sanitizers and no device code with either, into a stand-alone program with its own main (tests/_emul/group_bind_sanitize.cc), which drives create, steps, binds with groups
+mid-utterance, the first bind to a down-sampling set, replaced sets, allocations that fail inside both calls, int16 steps and
+destroy in both kernel forms.  The program is run as it is: nothing is loaded into this interpreter."""
+import os
+import subprocess
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
+HOST_UNITS = ["trm_capi", "trm_stream", "trm_mixed", "trm_setup", "trm_io"]
+
+
+def test_bind_and_set_params_are_clean_under_asan_and_ubsan(tmp_path):
+    exe = str(tmp_path / "group_bind_sanitize")
+    srcs = [os.path.join(ROOT, "tests", "_emul", f) for f in ("group_bind_sanitize.cc", "hip_host_mock.cc", "hip_host_mock_out.cc")]
+    srcs += [os.path.join(CSRC, u + ".cc") for u in HOST_UNITS]
+    # (the sanitizers are the host compilation's alone: -Xarch_host in front of each of their options)
+    subprocess.check_call(["hipcc", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                           "-o", exe] + srcs + ["-lpthread", "-lm"])
+    env = {k: v for k, v in os.environ.items() if k != "TRM_QUAD_CUS"}      # (the program chooses its kernel forms itself)
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0 and "group_bind_sanitize: ok (instrumented)" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
