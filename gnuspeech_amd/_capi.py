@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("TRM_LIB") or os.path.join(_HERE, "libtrm_hip.so")
 TRM_OK = 0
 TRM_KERNEL_AUTO, TRM_KERNEL_WIDE, TRM_KERNEL_QUAD = 0, 1, 2
 TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_FINISH, TRM_GROUP_RUN = 0, 1, 2, 3      # what a group of a grouped stream does in a step
+TRM_GROUP_CONVERT_PER_GROUP, TRM_GROUP_CONVERT_ONE_LAUNCH = 0, 1      # how a grouped stream converts its down-sampling groups
 (TRM_EINVAL, TRM_EINVAL_LENGTH, TRM_EFIR, TRM_ENOMEM, TRM_EHIP, TRM_ENODEVICE, TRM_EIO, TRM_EPARSE,
  TRM_ESILENT, TRM_ERANGE) = range(1, 11)
 
@@ -81,6 +82,7 @@ EXPORTS = [
     "trm_mixed_stream_group_set_events", "trm_mixed_stream_group_frames_left", "trm_mixed_stream_last_frames",
     "trm_mixed_stream_step_int16", "trm_mixed_stream_step_device_int16",
     "trm_mixed_stream_group_bind", "trm_mixed_stream_group_bound_set", "trm_mixed_stream_set_params",
+    "trm_mixed_stream_set_group_convert", "trm_mixed_stream_group_convert",
 ]
 
 _lib = None
@@ -231,6 +233,8 @@ def lib():
     L.trm_mixed_stream_group_bound_set.argtypes = [vp, C.c_size_t]
     L.trm_mixed_stream_group_bound_set.restype = C.c_size_t
     L.trm_mixed_stream_set_params.argtypes = [vp, C.c_size_t, C.POINTER(TrmInputParams)]
+    L.trm_mixed_stream_set_group_convert.argtypes = [vp, C.c_int]
+    L.trm_mixed_stream_group_convert.argtypes = [vp]
     for name in EXPORTS:
         getattr(L, name)
     _lib = L

@@ -300,6 +300,57 @@ struct GrpInt16Args {
 // (installed by trm_grp_out.hip when the library is loaded, like tracks_run_launcher; null: an int16 step fails)
 extern hipError_t (*grp_int16_launcher)(const GrpInt16Args &a, hipStream_t stream);
 
+// The down-sampling groups of a grouped stream's step in two launches, whatever their number (trm_grp_down.hip; include/trm_c_api.h:
+// trm_mixed_stream_set_group_convert).  `step` is the stretch of the step's tables that names them:
+//   [kGrpDownWords words per converting group | the work list: {index of the group in the stretch, first voice of the block} per
+//    block of kGrpDownVoices voices of such a group, nwork of them]
+// trm_grp_hist_in_kernel, in front of the tube launch, grid (nwork): every listed voice's history row to the head of its tube-rate
+// row -- zeros to both where the group opens -- and max_sample = 0 (the tube launch writes neither for a down-sampling voice).
+// trm_grp_convert_kernel, behind it, grid (nwork, tiles + 1): tile t < tiles converts outputs k_base + 64 t .. + 63 of the block's
+// voices with trm_downsample_rows_kernel's arithmetic (a tile behind its own group's outputs exits), tile `tiles` writes the
+// block's number_samples and saves its next history, row positions keep .. keep + hist - 1.  Group words and the sets' converter
+// values are read at workgroup-uniform addresses in the constant address space (ConstTable's reason).
+constexpr uint32_t kGrpDownVoices = 16;       // voices of a block
+constexpr uint32_t kGrpDownCols = 64;         // outputs of a tile
+struct GrpDownGroup {
+    uint32_t k_base, k_end;           // the step's outputs of the group, global indices
+    uint32_t nt;                      // tube samples present in a row from its head: n_hi - n_origin
+    uint32_t hist;                    // floats of a history row
+    uint32_t first, count;            // the group's voices
+    uint32_t set;
+    uint32_t keep;                    // row position of the next history: the tube samples the step ran
+    int32_t n_origin;                 // global tube sample at the head of the row
+    uint32_t opening;                 // no chunk of the utterance has run: the history is zeros
+    uint32_t hist_lo, hist_hi;        // where the group's history rows begin in `hist` (floats, 64 bits)
+};
+constexpr uint32_t kGrpDownWords = sizeof(GrpDownGroup) / 4;
+struct GrpDownSet {
+    const float *rows;                // per-phase coefficient rows (DownArgs::rows) ...
+    uint32_t lmax, rmax, pitch;       // ... their wings and pitch
+    uint32_t inc, pad;                // timeRegisterIncrement, padSize
+    uint32_t xlen;                    // tube samples a tile's window spans: ((kGrpDownCols - 1) * inc >> 16) + 2 + lmax + rmax
+};
+typedef const __attribute__((address_space(4))) GrpDownSet *GrpDownTable;
+// dynamic LDS of a convert tile of set t: 64 coefficient rows at an odd pitch + the block's windows
+inline size_t grp_down_lds(const GrpDownSet &t) { return ((size_t)kGrpDownCols * ((t.lmax + t.rmax) | 1u) + (size_t)kGrpDownVoices * t.xlen) * sizeof(float); }
+struct GrpDownArgs {
+    const __attribute__((address_space(4))) uint32_t *step;      // the stretch above; the work list begins at step + kGrpDownWords * ngroups
+    GrpDownTable sets;                // [parameter sets]
+    float *tube;                      // the tube-rate rows: voice v's at tube + tube_offset0[v], its history head first
+    const uint64_t *tube_offset0;
+    float *hist;                      // the history rows
+    float *out;                       // PCM: voice v's at out + out_offset[v]
+    const uint64_t *out_offset;
+    uint32_t *number_samples;
+    float *max_sample;
+    uint32_t ngroups, nwork;          // converting groups, blocks
+    uint32_t tiles;                   // ceil(the widest converting group's outputs / kGrpDownCols); may be 0
+    uint32_t lds;                     // the largest grp_down_lds among the converting groups' sets
+};
+// (installed by trm_grp_down.hip when the library is loaded, like tracks_run_launcher; null: TRM_GROUP_CONVERT_ONE_LAUNCH is refused)
+extern hipError_t (*grp_hist_in_launcher)(const GrpDownArgs &a, hipStream_t stream);
+extern hipError_t (*grp_convert_launcher)(const GrpDownArgs &a, hipStream_t stream);
+
 // Output of a mixed-parameter batch (trm_mixed_out.hip): int16 PCM or sound-file images, one workgroup per voice, each voice with
 // its own set's scaling and container.  The per-set table is built once at trm_mixed_create.
 struct MixOutSet {

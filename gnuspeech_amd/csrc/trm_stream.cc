@@ -22,6 +22,10 @@
 // may be given other parameters (trm_mixed_stream_set_params): both make the storage that depends on the binding current
 // themselves -- the group's map entries, the history rows, the tube-rate offsets (rebind_plan, rebind_commit) -- so a step finds
 // it as it would have after create.
+// A grouped stream may convert its down-sampling groups in one launch (trm_mixed_stream_set_group_convert; trm_grp_down.hip):
+// the step's tables then name the groups that convert and blocks of their voices, one launch in front of the tube launch brings
+// every history in and one behind it converts and saves every history, on the same rows as the per-group path and leaving them
+// in the same state, so the path may change between any two steps.
 // What a chunk and a step share is stated once: the converter range of a run of
 // control periods (unit_range), the length limit (range_too_long), the index arrays of a shape (stream_shape), the down-sampling
 // launches around the tube launch (down_history_in, down_convert) and the ordering of calls across HIP streams (stream_ordered).
@@ -110,6 +114,14 @@ struct trm_stream_engine {
     DevBuf<int16_t> dOut16;
     DevBuf<uint32_t> dClipped;
     std::vector<int16_t> hostOut16;
+    // ---- down-sampling groups in one launch (trm_mixed_stream_set_group_convert).  The first call that asks for it gives the
+    // step's tables room for the stretch that names the converting groups and their blocks (downRoom: dStep and the pinned
+    // copies are then sized for every group converting) and builds the sets' converter values, which set_params keeps current.
+    int convert = TRM_GROUP_CONVERT_PER_GROUP;
+    bool downRoom = false;
+    size_t downBlocks = 0;                   // blocks of kGrpDownVoices voices over all groups
+    std::vector<trm::GrpDownSet> hDownSets;  // per set (an up-sampling set: zeros)
+    DevBuf<trm::GrpDownSet> dDownSets;
     ~trm_stream_engine()
     {
         for (StepCopy &c : stepCopies) {
@@ -122,6 +134,8 @@ struct trm_stream_engine {
 namespace trm {
 hipError_t (*tracks_run_launcher)(const TrackRunArgs &a, hipStream_t stream) = nullptr;      // (trm_kernels.h; set by trm_tracks_run.hip)
 hipError_t (*grp_int16_launcher)(const GrpInt16Args &a, hipStream_t stream) = nullptr;        // (trm_kernels.h; set by trm_grp_out.hip)
+hipError_t (*grp_hist_in_launcher)(const GrpDownArgs &a, hipStream_t stream) = nullptr;       // (trm_kernels.h; both set by trm_grp_down.hip)
+hipError_t (*grp_convert_launcher)(const GrpDownArgs &a, hipStream_t stream) = nullptr;
 }
 
 struct trm_stream : trm_stream_engine {};
@@ -140,6 +154,13 @@ static void stream_destroy(Stream *s)
 static size_t step_words(const trm_stream_engine *s, size_t nrun) { return (size_t)s->mapEntries * 5 + (s->gbegin.size() - 1) + 2 * nrun; }
 // ... and of what an int16 step adds behind them (trm_kernels.h, GrpInt16Args::step) with `nentries` map entries that receive samples
 static size_t step_words_int16(const trm_stream_engine *s, size_t nentries) { return 2 * (s->gbegin.size() - 1) + 1 + nentries; }
+// ... and of the stretch of the groups that convert in one launch (trm_kernels.h, GrpDownArgs::step): `ngroups` of them in `nblocks` blocks
+static size_t step_words_down(size_t ngroups, size_t nblocks) { return trm::kGrpDownWords * ngroups + 2 * nblocks; }
+// the words the step's tables have room for, on the device and in every pinned copy
+static size_t step_words_room(const trm_stream_engine *s, bool downRoom)
+{
+    return step_words(s, s->nvoices) + step_words_int16(s, s->mapEntries) + (downRoom ? step_words_down(s->gbegin.size() - 1, s->downBlocks) : 0);
+}
 
 // whether set k's batch b can stream: an up-sampling set, or one whose chunks the tiled down-sampling kernel converts
 static int down_streams(const trm_stream_engine *s, size_t k, const trm_batch *b)
@@ -152,6 +173,18 @@ static int down_streams(const trm_stream_engine *s, size_t k, const trm_batch *b
         return fail(TRM_ERANGE, "%sstreaming: output rate too far below the tube rate (%d Hz) for the tiled down-sampling kernel", set, b->d.sampleRate);
     }
     return TRM_OK;
+}
+
+// a set's converter values for the groups that convert in one launch (an up-sampling set: zeros)
+static trm::GrpDownSet grp_down_set(const trm_batch *b)
+{
+    trm::GrpDownSet t{};
+    if (b->c.upsample) return t;
+    t.rows = b->dDownRows;
+    t.lmax = b->downL; t.rmax = b->downR; t.pitch = b->downPitch;
+    t.inc = b->c.timeRegisterIncrement; t.pad = (uint32_t)b->c.padSize;
+    t.xlen = (uint32_t)(((uint64_t)(trm::kGrpDownCols - 1) * t.inc) >> 16) + 2u + t.lmax + t.rmax;
+    return t;
 }
 
 // a set's share of an int16 step's scaling (as trm_mixed's MixOutSet)
@@ -199,6 +232,7 @@ static int stream_init(trm_stream_engine *s, const size_t *set_begin)
         s->gfirst.assign(G, 1);
         s->gev.assign(G, trm_stream_engine::GroupEvents());
         s->glastq.assign(G, 0);
+        for (size_t g = 0; g < G; g++) s->downBlocks += (s->gbegin[g + 1] - s->gbegin[g] + trm::kGrpDownVoices - 1) / trm::kGrpDownVoices;
     } else if (s->mixed) build_block_map(set_begin, S, s->wide ? 64 : 16, map);
     s->mapEntries = (uint32_t)map.size();
     // history rows of the down-sampling sets
@@ -657,7 +691,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     for (size_t g = 0; g < G; g++) nRun += plan[g].gen ? s->gbegin[g + 1] - s->gbegin[g] : 0;
     size_t words = step_words(s, nRun);
     uint32_t *h = nullptr;
-    if ((rc = step_copy(s, step_words(s, V) + step_words_int16(s, E), &h))) return rc;
+    if ((rc = step_copy(s, step_words_room(s, s->downRoom), &h))) return rc;
     uint32_t *clock = h, *active = h + E * 4, *what = active + E, *run = what + G;
     memset(h, 0, words * sizeof(uint32_t));
     uint32_t nActive = 0;
@@ -697,6 +731,44 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
         cnt[G] = o16->forWav ? 1u : 0u;
         words += step_words_int16(s, o16->nentries);
     }
+    // the groups that convert in one launch: [their words | {group of the stretch, first voice} per block of their voices]
+    const bool oneLaunch = s->convert == TRM_GROUP_CONVERT_ONE_LAUNCH && downRuns;
+    trm::GrpDownArgs down{};
+    if (oneLaunch) {
+        uint32_t nDown = 0, maxOut = 0;
+        for (size_t g = 0; g < G; g++) nDown += plan[g].runs && s->gbegin[g + 1] > s->gbegin[g] && !s->sets[s->gset[g]]->c.upsample ? 1u : 0u;
+        trm::GrpDownGroup *grp = reinterpret_cast<trm::GrpDownGroup *>(h + words);
+        uint32_t *work = h + words + trm::kGrpDownWords * nDown;
+        down.step = (decltype(down.step))(s->dStep.p + words);
+        for (size_t g = 0; g < G; g++) {
+            const GroupPlan &p = plan[g];
+            const size_t lo = s->gbegin[g], n = s->gbegin[g + 1] - lo, k = s->gset[g];
+            const trm_batch *b = s->sets[k];
+            if (!p.runs || n == 0 || b->c.upsample) continue;
+            // (the chunk as down_convert states it: the row's head is tube sample nBase - hist, N samples ran, the flush adds its zeros)
+            const uint64_t nBase = s->gperiods[g] * (uint64_t)b->d.controlPeriod, N = p.Q * (uint64_t)b->d.controlPeriod;
+            trm::GrpDownGroup &d = grp[down.ngroups];
+            d.k_base = (uint32_t)p.kBase; d.k_end = (uint32_t)p.kEnd;
+            d.nt = (uint32_t)(s->hist[k] + N + (p.flush ? 2ull * (uint64_t)b->d.padSize : 0ull));
+            d.hist = s->hist[k];
+            d.first = (uint32_t)lo; d.count = (uint32_t)n;
+            d.set = (uint32_t)k;
+            d.keep = (uint32_t)N;
+            d.n_origin = (int32_t)((long long)nBase - (long long)s->hist[k]);
+            d.opening = s->gfirst[g] ? 1u : 0u;
+            d.hist_lo = (uint32_t)s->ghistAt[g]; d.hist_hi = (uint32_t)(s->ghistAt[g] >> 32);
+            for (size_t f = lo; f < lo + n; f += trm::kGrpDownVoices) {
+                work[2 * down.nwork] = down.ngroups;
+                work[2 * down.nwork++ + 1] = (uint32_t)f;
+            }
+            down.ngroups++;
+            maxOut = std::max(maxOut, d.k_end - d.k_base);
+            down.lds = std::max(down.lds, (uint32_t)trm::grp_down_lds(s->hDownSets[k]));
+        }
+        down.tiles = (maxOut + trm::kGrpDownCols - 1) / trm::kGrpDownCols;
+        if (down.tiles >= 65535u) return fail(TRM_ERANGE, "%u outputs per voice in one step: too many for the one-launch converter", maxOut);
+        words += step_words_down(down.ngroups, down.nwork);
+    }
     HIP_TRY(hipMemcpyAsync(s->dStep.p, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(s->stepCopies.back().uploaded, st));
     trm::GrpPrepArgs prep{s->dFrames.p, s->dLast.p, d_pushed, s->dVoiceGroup.p, s->dStep.p + E * 5, s->dMax.p, (uint32_t)V, (uint32_t)rows};
@@ -714,7 +786,15 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     trm::TubeArgs a = tube_args(b0, s->dFrames.p, s->dFrameOff.p, s->dNFrames.p, d_out, s->dOutOff.p, s->dNSamples.p, s->dMax.p, V, (uint32_t)rows);
     if (downRuns) {
         if ((rc = s->dTube.reserve(s->tubeFloats + 4))) return rc;
-        for (size_t g = 0; g < G; g++) {
+        if (oneLaunch) {
+            down.sets = (trm::GrpDownTable)s->dDownSets.p;
+            down.tube = s->dTube.p; down.tube_offset0 = s->dTubeOff0.p;
+            down.hist = s->dHist.p;
+            down.out = d_out; down.out_offset = s->dOutOff.p;
+            down.number_samples = s->dNSamples.p; down.max_sample = s->dMax.p;
+            HIP_TRY(trm::grp_hist_in_launcher(down, st));
+        }
+        for (size_t g = 0; !oneLaunch && g < G; g++) {
             const size_t lo = s->gbegin[g], n = s->gbegin[g + 1] - lo, k = s->gset[g];
             if (!plan[g].runs || n == 0 || s->sets[k]->c.upsample) continue;
             if ((rc = down_history_in(s, k, lo, n, s->ghistAt[g], s->gfirst[g], st))) return rc;        // (zeroed when the GROUP opens)
@@ -731,11 +811,12 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     a.grp_active = (decltype(a.grp_active))(s->dStep.p + E * 4);
     if (s->wide) HIP_TRY(trm::launch_tube(b0->c, a, st));
     else HIP_TRY(trm::launch_tube_quad(b0->c, a, st, b0->cus));
+    if (oneLaunch) HIP_TRY(trm::grp_convert_launcher(down, st));
     for (size_t g = 0; g < G; g++) {
         const GroupPlan &p = plan[g];
         const size_t lo = s->gbegin[g], n = s->gbegin[g + 1] - lo, k = s->gset[g];
         if (!p.runs || n == 0) continue;
-        if (!s->sets[k]->c.upsample && (rc = down_convert(s, a, k, lo, n, s->ghistAt[g], s->gperiods[g], p.Q, p.flush, p.kBase, p.kEnd, st))) return rc;
+        if (!oneLaunch && !s->sets[k]->c.upsample && (rc = down_convert(s, a, k, lo, n, s->ghistAt[g], s->gperiods[g], p.Q, p.flush, p.kBase, p.kEnd, st))) return rc;
         if (tract && p.kEnd > p.kBase)       // (TRAcT order's x100: stream_chunk_impl)
             HIP_TRY(trm::launch_gain(d_out + lo * out_pitch, out_pitch, (uint32_t)(p.kEnd - p.kBase), (uint32_t)n, s->dMax.p + lo, 100.0f, st));
     }
@@ -1482,11 +1563,14 @@ int trm_mixed_stream_set_params(trm_mixed_stream *s, size_t set, const trm_input
     trm::Const c = nb->c;
     c.fricGain = s->mode == TRM_STREAM_MODE_TRACT ? 10.0f : 1.0f;             // (the stream's loop order: stream_set_mode)
     const trm::GrpOutSet os = grp_out_set(*params);
+    const trm::GrpDownSet ds = grp_down_set(nb);
     // the device first: the set's entries of the two tables, the offsets; then the host's books
     HIP_TRY(hipMemcpy(s->sets.dConst + set, &c, sizeof c, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->dConst, &c, sizeof c, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->dOutSets.p + set, &os, sizeof os, hipMemcpyHostToDevice));
+    if (s->downRoom) HIP_TRY(hipMemcpy(s->dDownSets.p + set, &ds, sizeof ds, hipMemcpyHostToDevice));
     if ((rc = rebind_upload(s, p))) return rc;
+    if (s->downRoom) s->hDownSets[set] = ds;
     b->params = *params;
     b->c = c;
     b->d = nb->d;
@@ -1497,6 +1581,43 @@ int trm_mixed_stream_set_params(trm_mixed_stream *s, size_t set, const trm_input
     rebind_commit(s, p);
     return TRM_OK;
 }
+
+int trm_mixed_stream_set_group_convert(trm_mixed_stream *s, int mode)
+{
+    if (!s) return fail(TRM_EINVAL, "null stream");
+    if (!s->grouped) return fail(TRM_EINVAL, "not a grouped stream (trm_mixed_stream_create_groups)");
+    if (mode != TRM_GROUP_CONVERT_PER_GROUP && mode != TRM_GROUP_CONVERT_ONE_LAUNCH) return fail(TRM_EINVAL, "unknown group conversion %d", mode);
+    if (mode == TRM_GROUP_CONVERT_ONE_LAUNCH && !(trm::grp_hist_in_launcher && trm::grp_convert_launcher))
+        return fail(TRM_EHIP, "this build of the library holds no one-launch converter kernels (trm_grp_down.hip)");
+    if (mode == TRM_GROUP_CONVERT_ONE_LAUNCH && !s->downRoom) {
+        // Room for the stretch in the step's tables, once: everything that can fail first, into buffers of its own.  The steps so
+        // far may still read the tables and their uploads the pinned copies, on whichever HIP stream: the one wait of this entry.
+        const size_t S = s->sets.size();
+        HIP_TRY(hipSetDevice(s->sets[0]->device));
+        DevBuf<uint32_t> step;
+        DevBuf<trm::GrpDownSet> sets;
+        int rc;
+        if ((rc = step.reserve(step_words_room(s, true))) || (rc = sets.reserve(S))) return rc;
+        std::vector<trm::GrpDownSet> h(S);
+        for (size_t k = 0; k < S; k++) h[k] = grp_down_set(s->sets[k]);
+        HIP_TRY(hipMemcpy(sets.p, h.data(), S * sizeof(trm::GrpDownSet), hipMemcpyHostToDevice));
+        if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
+        std::swap(step.p, s->dStep.p); std::swap(step.cap, s->dStep.cap);
+        std::swap(sets.p, s->dDownSets.p); std::swap(sets.cap, s->dDownSets.cap);
+        s->hDownSets.swap(h);
+        // (the pinned copies were sized without the stretch: the next steps allocate theirs anew)
+        for (trm_stream_engine::StepCopy &c : s->stepCopies) {
+            if (c.uploaded) (void)hipEventDestroy(c.uploaded);
+            if (c.p) (void)hipHostFree(c.p);
+        }
+        s->stepCopies.clear();
+        s->downRoom = true;
+    }
+    s->convert = mode;
+    return TRM_OK;
+}
+
+int trm_mixed_stream_group_convert(const trm_mixed_stream *s) { return s && s->grouped ? s->convert : TRM_GROUP_CONVERT_PER_GROUP; }
 
 int trm_mixed_stream_step(trm_mixed_stream *s, const uint8_t *action, const float *frames, size_t nframes, float *out, size_t out_pitch,
                           uint32_t *nout, float *max_out)

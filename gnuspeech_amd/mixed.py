@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import TRM_GROUP_FINISH, TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_RUN, TrmDerived, TrmInputParams, TrmIntonation, check, lib
+from ._capi import TRM_GROUP_CONVERT_ONE_LAUNCH, TRM_GROUP_CONVERT_PER_GROUP, TRM_GROUP_FINISH, TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_RUN, TrmDerived, TrmInputParams, TrmIntonation, check, lib
 
 _KERNELS = {"auto": 0, "wide": 1, "quad": 2, "oct": 3}
 
@@ -624,6 +624,21 @@ class TRMGroupedStream:
     @property
     def mode(self):
         return {0: "framework", 1: "tract"}[lib().trm_mixed_stream_mode(self._h)]
+
+    _CONVERT = {"per_group": TRM_GROUP_CONVERT_PER_GROUP, "one_launch": TRM_GROUP_CONVERT_ONE_LAUNCH}
+
+    def set_convert(self, convert):
+        """How the steps convert the groups bound to down-sampling sets (trm_mixed_stream_set_group_convert): "per_group", group
+        after group (the default), or "one_launch", all of them in one launch behind the tube launch and their histories in one
+        launch in front of it.  Same bits either way; allowed between any two steps, mid-utterance included.  The first call
+        that asks for "one_launch" may wait for the device once."""
+        if convert not in self._CONVERT:
+            raise ValueError("unknown conversion %r (per_group, one_launch)" % (convert,))
+        check(lib().trm_mixed_stream_set_group_convert(self._h, self._CONVERT[convert]))
+
+    @property
+    def convert(self):
+        return {0: "per_group", 1: "one_launch"}[lib().trm_mixed_stream_group_convert(self._h)]
 
     def is_open(self, group):
         """Whether the caller's group `group` has an utterance open."""

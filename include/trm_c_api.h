@@ -743,6 +743,30 @@ int    trm_mixed_stream_group_bind(trm_mixed_stream *s, size_t group, size_t set
 size_t trm_mixed_stream_group_bound_set(const trm_mixed_stream *s, size_t group);
 int    trm_mixed_stream_set_params(trm_mixed_stream *s, size_t set, const trm_input_params *params);
 
+/* Down-sampling groups converted in one launch.  A group bound to a down-sampling set runs its tube above its output rate, and
+ * a step converts its tube-rate samples behind the tube launch.  By default that is done group after group
+ * (TRM_GROUP_CONVERT_PER_GROUP): per active down-sampling group a memset (when it opens) and a 2-D copy in front of the tube launch,
+ * three launches and another 2-D copy behind it.  Under TRM_GROUP_CONVERT_ONE_LAUNCH one launch in front of the tube launch
+ * brings every such group's history in and one launch behind it converts all of them and saves their histories: the number of
+ * operations of a step no longer grows with the number of groups, and a step holds no memset and no 2-D copy.
+ *   - THE RULE.  Same bits, switchable between any two steps.  Every value a step returns -- samples, counts, maxima, int16
+ *     values and clip counts; PUSH, FINISH and RUN; both loop orders -- is bit for bit what the per-group path returns, which is
+ *     what a trm_stream per group returns (the rules above).  Both paths keep the same history rows and tube-rate rows and leave
+ *     them in the same state, so the call is allowed between any two steps, mid-utterance included, and changes no sample.
+ *   - The mode is the stream's; every step entry takes it into account (step, step_device, step_int16, step_device_int16), and
+ *     group_bind and set_params keep what it needs current.  TRAcT order's x100 stays a launch per group in both modes.
+ *   - set_group_convert refuses a stream without groups and an unknown mode (TRM_EINVAL).  A library built without the kernels
+ *     (the host units alone) refuses ONE_LAUNCH with TRM_EHIP; all else works there.  group_convert returns the mode
+ *     (PER_GROUP for a stream without groups).
+ *   - The first call that asks for ONE_LAUNCH may wait for the device once and allocates: the step's tables grow by the stretch
+ *     that names the converting groups (sized for every group converting) and the sets' converter values are built.  After it
+ *     the step entries gain no host wait in either mode (the pinned copies of the tables are allocated anew by the steps
+ *     that follow, as a stream's first steps allocate them).  A call that fails for want of memory leaves the
+ *     stream as it was.  A stream on which the call is never made enqueues exactly what it did without it. */
+enum trm_group_convert { TRM_GROUP_CONVERT_PER_GROUP = 0, TRM_GROUP_CONVERT_ONE_LAUNCH = 1 };      /* (an enum of its own, apart from the actions') */
+int    trm_mixed_stream_set_group_convert(trm_mixed_stream *s, int mode);
+int    trm_mixed_stream_group_convert(const trm_mixed_stream *s);
+
 /* Library / device identification. */
 int  trm_device_count(void);
 const char *trm_build_info(void);
