@@ -11,6 +11,7 @@ TRM_OK = 0
 TRM_KERNEL_AUTO, TRM_KERNEL_WIDE, TRM_KERNEL_QUAD = 0, 1, 2
 TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_FINISH, TRM_GROUP_RUN = 0, 1, 2, 3      # what a group of a grouped stream does in a step
 TRM_GROUP_CONVERT_PER_GROUP, TRM_GROUP_CONVERT_ONE_LAUNCH = 0, 1      # how a grouped stream converts its down-sampling groups
+TRM_SPLIT_WARMUP_DEFAULT, TRM_SPLIT_WARMUP_COUPLED = 0, -1            # the warm-up rule of a time split (a value above 0: control periods)
 (TRM_EINVAL, TRM_EINVAL_LENGTH, TRM_EFIR, TRM_ENOMEM, TRM_EHIP, TRM_ENODEVICE, TRM_EIO, TRM_EPARSE,
  TRM_ESILENT, TRM_ERANGE) = range(1, 11)
 
@@ -68,6 +69,8 @@ EXPORTS = [
     "trm_stream_push", "trm_stream_finish", "trm_stream_set_mode", "trm_stream_mode", "trm_stream_set_slice", "trm_stream_slice", "trm_stream_push_device", "trm_stream_finish_device", "trm_stream_kernel",
     "trm_events_count_frames", "trm_drift_seed_after", "trm_batch_generate_frames_device", "trm_batch_generate_frames_host",
     "trm_batch_set_kernel", "trm_batch_last_kernel", "trm_batch_set_time_split", "trm_batch_last_time_split", "trm_batch_hint_frames",
+    "trm_batch_set_split_warmup", "trm_batch_split_warmup", "trm_split_warm_periods", "trm_tube_set_split_warmup",
+    "trm_mixed_set_split_warmup", "trm_mixed_split_warmup",
     "trm_batch_kernel_time_ms", "trm_batch_set_timing", "trm_batch_noise_table", "trm_device_count", "trm_build_info", "trm_kernel_blocks_per_cu", "trm_kernel_blocks_per_cu_form",
     "trm_mixed_create", "trm_mixed_destroy", "trm_mixed_derived", "trm_mixed_samples_for_frames", "trm_mixed_synthesize_device",
     "trm_mixed_synthesize_host", "trm_mixed_synthesize_host_int16", "trm_mixed_set_kernel", "trm_mixed_last_kernel",
@@ -182,6 +185,13 @@ def lib():
     L.trm_batch_set_time_split.argtypes = [vp, C.c_int]
     L.trm_batch_last_time_split.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.trm_batch_hint_frames.argtypes = [vp, vp, C.c_size_t]
+    L.trm_batch_set_split_warmup.argtypes = [vp, C.c_int]
+    L.trm_batch_split_warmup.argtypes = [vp]
+    L.trm_split_warm_periods.argtypes = [C.POINTER(TrmInputParams), C.c_int]
+    L.trm_split_warm_periods.restype = C.c_uint32
+    L.trm_tube_set_split_warmup.argtypes = [vp, C.c_int]
+    L.trm_mixed_set_split_warmup.argtypes = [vp, C.c_int]
+    L.trm_mixed_split_warmup.argtypes = [vp]
     L.trm_batch_noise_table.argtypes = [vp, vp, C.c_size_t]
     L.trm_mixed_create.argtypes = [C.POINTER(TrmInputParams), C.c_size_t, C.c_int, C.POINTER(vp)]
     L.trm_mixed_destroy.argtypes = [vp]
@@ -239,6 +249,32 @@ def lib():
         getattr(L, name)
     _lib = L
     return L
+
+
+def split_warmup_code(warmup, periods_ok=True):
+    """'default' | 'coupled' | control periods (an int above 0, where periods_ok) -> the C interface's value; anything else is
+    refused here, with the names that are accepted."""
+    rules = {"default": TRM_SPLIT_WARMUP_DEFAULT, "coupled": TRM_SPLIT_WARMUP_COUPLED}
+    if isinstance(warmup, str):
+        if warmup not in rules:
+            raise ValueError("split warm-up %r: 'default' or 'coupled'%s" % (warmup, ", or control periods" if periods_ok else ""))
+        return rules[warmup]
+    if isinstance(warmup, bool) or int(warmup) != warmup or warmup <= 0:
+        raise ValueError("split warm-up %r: 'default', 'coupled'%s" % (warmup, " or a whole number of control periods above 0" if periods_ok else ""))
+    if not periods_ok:
+        raise ValueError("split warm-up %r: a mixed batch takes 'default' or 'coupled' (every set gets the rule's value for its own constants)" % (warmup,))
+    return int(warmup)
+
+
+def split_warmup_name(code):
+    return {TRM_SPLIT_WARMUP_DEFAULT: "default", TRM_SPLIT_WARMUP_COUPLED: "coupled"}.get(code, code)
+
+
+def split_warm_periods(inputParameters, rule="default"):
+    """The warm-up in control periods a time split of these parameters would use under `rule` ('default' | 'coupled'); 0 = the
+    tube never forgets.  Host-only (trm_split_warm_periods): no device, no batch object."""
+    c = getattr(inputParameters, "c", inputParameters)
+    return int(lib().trm_split_warm_periods(C.byref(c), split_warmup_code(rule, periods_ok=False)))
 
 
 def check(rc):

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import TrmDerived, check, lib
+from ._capi import TrmDerived, check, lib, split_warmup_code, split_warmup_name
 
 
 class TRMBatch:
@@ -231,6 +231,17 @@ class TRMBatch:
         check(lib().trm_batch_last_time_split(self._h, C.byref(p), C.byref(w)))
         return p.value, w.value
 
+    def set_split_warmup(self, warmup):
+        """'default' | 'coupled' | control periods: the warm-up of a time split (include/trm_c_api.h:
+        trm_batch_set_split_warmup).  'coupled' also covers the loops the mouth and nose reflection filters sit in, for tube
+        parameters far from Monet's; periods may lengthen the default rule's warm-up, never shorten it (TrmError, TRM_ERANGE)."""
+        check(lib().trm_batch_set_split_warmup(self._h, split_warmup_code(warmup)))
+
+    @property
+    def split_warmup(self):
+        """'default' | 'coupled' | control periods, as set."""
+        return split_warmup_name(lib().trm_batch_split_warmup(self._h))
+
     def set_timing(self, on):
         """Launch timing on / off; off, synthesize_device is pure stream work and can be captured into a HIP graph."""
         check(lib().trm_batch_set_timing(self._h, int(bool(on))))
@@ -295,5 +306,5 @@ class TRMMultiBatch(TRMBatch):
 
     prepare_device = synthesize_device = scale_to_int16_device = prepare_events_device = generate_frames_device = _device_only
     sound_files_device = _device_only
-    noise_table = set_kernel = kernel_time_ms = set_timing = set_time_split = _device_only
-    last_kernel = last_time_split = property(_device_only)
+    noise_table = set_kernel = kernel_time_ms = set_timing = set_time_split = set_split_warmup = _device_only
+    last_kernel = last_time_split = split_warmup = property(_device_only)

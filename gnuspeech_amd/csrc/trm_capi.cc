@@ -425,28 +425,15 @@ struct SplitPlan {
     int form = TRM_KERNEL_WIDE;   // the segment instance that runs it: one voice per lane (64 voices per workgroup) or four lanes per voice (16)
     float bwFloor = 0.0f;         // frication bandwidths below this need a longer warm-up: the launch falls back (device-side)
 };
-// ln(1e-5): what is left of the state the warm-up starts without.  Measured (tools/timesplit_study.py, 180 random and
-// adversarial voices on the host model): with this warm-up (30 control periods at Monet's defaults) the split path differs from
-// the whole-utterance path by its fp32 noise floor -- worst single sample 8.5e-6 of the maximum, RMS 1.5e-6 -- exactly as with
-// 1.1x and 1.2x the warm-up; with 0.9x it starts to show (1.1e-5 / 1.6e-6).  The output error is ~0.15 of the bound for the
-// voice that forgets slowest (mouth and velum closed).
-constexpr double kSplitLogEps = -11.512925464970229;
 }  // namespace
 
 // (declared in trm_host.h: trm_mixed.cc plans its time split with the same functions)
 extern "C++" {
 
-// warm-up (tube samples) after which a tube started from rest has forgotten that it was; 0 = never (a pole on the unit circle)
-uint32_t split_warm_samples(const trm::Const &c)
+uint32_t batch_split_warm(const trm_batch *b)
 {
-    double pole = fabs((double)c.damping);
-    const double others[] = {fabs((double)c.mCoeff), fabs((double)c.nCoeff), fabs((double)c.tb1)};
-    for (double o : others) pole = o > pole ? o : pole;
-    if (!(pole < 0.99999)) return 0;
-    const double w = kSplitLogEps / log(pole);
-    if (!(w < 1.0e6)) return 0;
-    // + the oscillator FIR's 24 samples of history, the converter's 26-sample window and the pipeline's block granularity
-    return (uint32_t)ceil(w) + 64u;
+    const uint32_t byRule = trm::split_warm_periods(b->c, b->splitWarmup == TRM_SPLIT_WARMUP_COUPLED ? trm::kWarmCoupled : trm::kWarmDefault);
+    return b->splitWarmup > 0 && byRule != 0 ? (uint32_t)b->splitWarmup : byRule;
 }
 
 // Predicted launch time in ms per second of speech at Monet's rates (19 750 tube samples), from the measured figures of the
@@ -484,7 +471,7 @@ uint64_t busy_workgroups(const std::vector<uint32_t> &longest, uint32_t periods,
 float split_bw_floor(const trm_batch *b, uint32_t warm)
 {
     const uint32_t CP = (uint32_t)b->c.controlPeriod;
-    const double r2 = exp(2.0 * kSplitLogEps / (double)(warm * CP - 64u));
+    const double r2 = exp(2.0 * trm::kSplitLogEps / (double)(warm * CP - 64u));
     const double t = (1.0 - r2) / (1.0 + r2);
     return (float)((double)b->d.sampleRate * atan(t) / 3.14159265358979323846);
 }
@@ -510,12 +497,11 @@ static int plan_time_split(const trm_batch *b, size_t nvoices, uint32_t max_nfra
             longest16[v / 16] = longest16[v / 16] > per ? longest16[v / 16] : per;
         }
     }
-    const uint32_t ws = split_warm_samples(b->c);
-    if (ws == 0) {
+    const uint32_t warm = batch_split_warm(b);
+    if (warm == 0) {
         if (setting > 0) return fail(TRM_ERANGE, "time split: the tube never forgets (loss factor %g %%)", b->params.lossFactor);
         return TRM_OK;
     }
-    const uint32_t warm = (ws + CP - 1) / CP;
     uint32_t periods = 0;
     // the four-lane segment instance: up-sampling batches whose converter makes at most four outputs per tube sample
     const bool quadOk = b->c.upsample && !quad_ratio_too_high(b->c) && which != TRM_KERNEL_WIDE;
@@ -593,6 +579,34 @@ int trm_batch_set_time_split(trm_batch *b, int periods)
     if (periods < TRM_TIME_SPLIT_AUTO) return fail(TRM_EINVAL, "time split: %d", periods);
     b->splitSetting = periods;
     return TRM_OK;
+}
+
+int trm_batch_set_split_warmup(trm_batch *b, int rule_or_periods)
+{
+    if (!b) return fail(TRM_EINVAL, "null batch");
+    if (rule_or_periods < TRM_SPLIT_WARMUP_COUPLED) return fail(TRM_EINVAL, "split warm-up: unknown rule %d", rule_or_periods);
+    if (rule_or_periods > 0) {
+        // longer than the library's own rule, never shorter: the kernels have never run with less
+        const uint32_t CP = (uint32_t)b->c.controlPeriod, least = trm::split_warm_periods(b->c, trm::kWarmDefault);
+        if (least == 0) return fail(TRM_ERANGE, "split warm-up: the tube never forgets (loss factor %g %%), no warm-up covers it", b->params.lossFactor);
+        if ((uint32_t)rule_or_periods < least)
+            return fail(TRM_ERANGE, "split warm-up: %d control periods is below the default rule's %u for these parameters", rule_or_periods, least);
+        // ... and within what a rule can give (1e6 tube samples + 64)
+        if ((uint64_t)rule_or_periods * CP > 1000064ull + CP)
+            return fail(TRM_ERANGE, "split warm-up: %d control periods of %u tube samples is beyond the rules' own limit", rule_or_periods, CP);
+    }
+    b->splitWarmup = rule_or_periods;
+    return TRM_OK;
+}
+
+int trm_batch_split_warmup(const trm_batch *b) { return b ? b->splitWarmup : TRM_SPLIT_WARMUP_DEFAULT; }
+
+uint32_t trm_split_warm_periods(const trm_input_params *params, int rule)
+{
+    trm::Const c;
+    trm_derived d;
+    if (!params || (rule != TRM_SPLIT_WARMUP_DEFAULT && rule != TRM_SPLIT_WARMUP_COUPLED) || trm::build_const(*params, c, d) != TRM_OK) return 0;
+    return trm::split_warm_periods(c, rule);
 }
 
 int trm_batch_last_time_split(const trm_batch *b, uint32_t *periods, uint32_t *warm_periods)
@@ -1202,6 +1216,12 @@ int trm_tube_synthesize(trm_tube *t, const trm_parameters *frames, size_t nframe
     t->numberSamples = ns;
     t->maxSample = mx;
     return TRM_OK;
+}
+
+int trm_tube_set_split_warmup(trm_tube *t, int rule_or_periods)
+{
+    if (!t) return fail(TRM_EINVAL, "null tube");
+    return trm_batch_set_split_warmup(t->b, rule_or_periods);
 }
 
 size_t trm_tube_number_samples(const trm_tube *t) { return t ? t->numberSamples : 0; }

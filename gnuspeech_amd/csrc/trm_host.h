@@ -21,6 +21,7 @@
 #include "trm_kernels.h"
 #include "trm_setup.h"
 #include "trm_span.h"
+#include "trm_warm.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -94,6 +95,7 @@ struct trm_batch {
     int splitSetting = TRM_TIME_SPLIT_AUTO;      // AUTO, OFF, or a segment length in control periods
     uint32_t lastSplitPeriods = 0, lastSplitWarm = 0;      // what the last launch did (0: whole utterances)
     int lastSplitForm = TRM_KERNEL_WIDE;
+    int splitWarmup = TRM_SPLIT_WARMUP_DEFAULT;  // trm_batch_set_split_warmup: a rule, or (> 0) a warm-up in control periods
     DevBuf<double> dSegPhase, dPeriodAdv;
     DevBuf<uint2> dSegMap;               // a time-split grid's launch order (trm_seg_map_kernel)
     DevBuf<uint32_t> dBlockFrames;
@@ -135,9 +137,9 @@ trm::ScaleArgs scale_args(const trm_batch *b, const float *pcm, const uint64_t *
 
 // ------------------------------------------------------------------ time-split planning, stated once (trm_capi.cc)
 // What trm_batch's planner and trm_mixed's share: each fact has one definition, so the two paths cut a set's voices alike.
-// warm-up (tube samples) after which a tube started from rest has forgotten that it was; 0 = never
-uint32_t split_warm_samples(const trm::Const &c);
-// (segment boundaries and counts: trm_span.h)
+// (the warm-up rules: trm_warm.h; segment boundaries and counts: trm_span.h)
+// the warm-up a plan of b uses, in control periods: its rule's for b's constants, or the caller's own; 0 = the tube never forgets
+uint32_t batch_split_warm(const trm_batch *b);
 // workgroups with work: per block (its longest voice, in control periods) the segments it reaches
 uint64_t busy_workgroups(const std::vector<uint32_t> &longest, uint32_t periods, uint32_t warm);
 // predicted ms per second of speech (19 750 tube samples) of the one-voice-per-lane kernel / of a whole-utterance launch in form `which`

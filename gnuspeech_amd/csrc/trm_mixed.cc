@@ -68,7 +68,7 @@ extern "C" {
 // ------------------------------------------------------------------ mixed-parameter batches
 // One trm_batch per parameter set (SetBatches).  The launch itself is one grid: workgroup w runs voices map[w].y .. map[w].z - 1 of set map[w].x with that set's constants
 // (trm_kernels.h, TubeArgs::mix_map).  Whole utterances unless trm_mixed_set_time_split asks for the time split: then a workgroup
-// is one segment of one map entry, cut with the launch's segment length S and the SET's own warm-up W (split_warm_samples),
+// is one segment of one map entry, cut with the launch's segment length S and the SET's own warm-up W (trm_warm.h, by the batch's rule),
 // so that every voice gets bit for bit what a trm_batch of its set computes with trm_batch_set_time_split(S) in the
 // form of the plan (trm_mixed_last_kernel) -- the boundaries depend on S and W alone, a voice's lane neighbours do not enter
 // its arithmetic.  The form is the one-voice-per-lane one (64-voice map entries) unless the caller NAMED the four-lane form
@@ -88,7 +88,8 @@ struct trm_mixed {
     bool haveShape = false;
     // time split (trm_mixed_set_time_split): OFF unless asked for; TRM_TIME_SPLIT in the environment is not read here
     int splitSetting = TRM_TIME_SPLIT_OFF;
-    uint32_t lastSplitPeriods = 0;           // what the last launch did (0: whole utterances)
+    int splitWarmup = TRM_SPLIT_WARMUP_DEFAULT;   // trm_mixed_set_split_warmup: the rule every set's warm-up is taken from (trm_warm.h)
+    uint32_t lastSplitPeriods = 0;          // what the last launch did (0: whole utterances)
     std::vector<uint32_t> lastWarm;          // ... and every set's warm-up in control periods then
     std::vector<uint32_t> hintFrames;        // trm_mixed_hint_frames / the host entries: every voice's length, for the launch that follows
     // a split launch's part of the shape: the segment length, the lengths its launch order was built from, the order itself
@@ -200,6 +201,19 @@ int trm_mixed_set_time_split(trm_mixed *m, int periods)
     return TRM_OK;
 }
 
+int trm_mixed_set_split_warmup(trm_mixed *m, int rule)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    if (rule != TRM_SPLIT_WARMUP_DEFAULT && rule != TRM_SPLIT_WARMUP_COUPLED)
+        return fail(TRM_EINVAL, "split warm-up: %d is not a rule (a mixed batch takes every set's warm-up from a rule)", rule);
+    // (the block map of a split launch carries every set's warm-up: the next launch builds it again)
+    if (rule != m->splitWarmup) m->haveShape = false;
+    m->splitWarmup = rule;
+    return TRM_OK;
+}
+
+int trm_mixed_split_warmup(const trm_mixed *m) { return m ? m->splitWarmup : TRM_SPLIT_WARMUP_DEFAULT; }
+
 int trm_mixed_last_time_split(const trm_mixed *m, uint32_t *periods, uint32_t *warm_periods, size_t nsets)
 {
     if (!m) return fail(TRM_EINVAL, "null handle");
@@ -262,10 +276,10 @@ static int mixed_plan_split(const trm_mixed *m, const size_t *set_begin, uint32_
     double wholeSamples = 0.0;
     for (size_t s = 0; s < S; s++) {
         const trm_batch *b = m->sets[s];
-        const uint32_t CP = (uint32_t)b->c.controlPeriod, ws = split_warm_samples(b->c);
-        warm[s] = (ws + CP - 1) / CP;
+        const uint32_t CP = (uint32_t)b->c.controlPeriod;
+        warm[s] = trm::split_warm_periods(b->c, m->splitWarmup);
         if (set_begin[s + 1] == set_begin[s]) continue;
-        if (ws == 0) {
+        if (warm[s] == 0) {
             if (setting > 0) return fail(TRM_ERANGE, "time split: the tube of parameter set %zu never forgets (loss factor %g %%)", s, b->params.lossFactor);
             return TRM_OK;
         }

@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import TRM_GROUP_CONVERT_ONE_LAUNCH, TRM_GROUP_CONVERT_PER_GROUP, TRM_GROUP_FINISH, TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_RUN, TrmDerived, TrmInputParams, TrmIntonation, check, lib
+from ._capi import TRM_GROUP_CONVERT_ONE_LAUNCH, TRM_GROUP_CONVERT_PER_GROUP, TRM_GROUP_FINISH, TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_RUN, TrmDerived, TrmInputParams, TrmIntonation, check, lib, split_warmup_code, split_warmup_name
 
 _KERNELS = {"auto": 0, "wide": 1, "quad": 2, "oct": 3}
 
@@ -407,6 +407,16 @@ class TRMMixedBatch:
         w = (C.c_uint32 * max(1, self.nsets))()
         check(lib().trm_mixed_last_time_split(self._h, C.byref(p), w, self.nsets))
         return p.value, [int(x) for x in w[:self.nsets]]
+
+    def set_split_warmup(self, rule):
+        """'default' | 'coupled': the rule every set's time-split warm-up is taken from, each for its own constants
+        (include/trm_c_api.h: trm_mixed_set_split_warmup); a split launch then gives every voice what a TRMBatch of its set
+        computes with the same set_split_warmup.  A warm-up in periods is refused: one number does not fit several sets."""
+        check(lib().trm_mixed_set_split_warmup(self._h, split_warmup_code(rule, periods_ok=False)))
+
+    @property
+    def split_warmup(self):
+        return split_warmup_name(lib().trm_mixed_split_warmup(self._h))
 
 
 class TRMMixedStream:

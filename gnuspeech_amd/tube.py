@@ -158,6 +158,16 @@ class TRMTubeModel:
             C.memmove(buf, fr.ctypes.data, fr.nbytes)
         check(lib().trm_tube_synthesize(self._h, buf, fr.shape[0]))
 
+    def set_split_warmup(self, warmup):
+        """No reference counterpart.  'default' | 'coupled' | control periods: the warm-up of the time split a long utterance
+        runs as (include/trm_c_api.h: trm_tube_set_split_warmup; TRMBatch.set_split_warmup)."""
+        check(lib().trm_tube_set_split_warmup(self._h, _capi.split_warmup_code(warmup)))
+        self._split_warmup = _capi.split_warmup_name(_capi.split_warmup_code(warmup))
+
+    @property
+    def split_warmup(self):
+        return getattr(self, "_split_warmup", "default")
+
     @property
     def numberSamples(self):
         return lib().trm_tube_number_samples(self._h)

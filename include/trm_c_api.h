@@ -134,6 +134,10 @@ int  trm_tube_print_input_data(const trm_tube *tube, const trm_parameters *frame
 /* -synthesize (TRMTubeModel.m:272-361) over inputData.values = frames[0..nframes):
  * N frames -> N-1 control periods; 0 frames is a silent no-op (:274-277). */
 int  trm_tube_synthesize(trm_tube *tube, const trm_parameters *frames, size_t nframes);
+/* No reference counterpart.  A long utterance runs as a time split (trm_batch_set_time_split, AUTO); this is where arbitrary
+ * tube parameters arrive, so the split's warm-up can be chosen here: forwards to trm_batch_set_split_warmup of the batch
+ * inside the tube (TRM_SPLIT_WARMUP_DEFAULT, TRM_SPLIT_WARMUP_COUPLED or control periods; the same refusals). */
+int  trm_tube_set_split_warmup(trm_tube *tube, int rule_or_periods);
 
 /* TRMSampleRateConverter numberSamples / maximumSampleValue / resampledData
  * (TRMSampleRateConverter.m:206-214,312-315).  The pointer stays valid until the next
@@ -399,8 +403,12 @@ int  trm_batch_last_kernel(const trm_batch *batch);
  * by side -- a workgroup is one segment of 64 voices in the one-voice-per-lane form, of 16 in the four-lane form (small
  * batches, a single utterance: 1 s of speech in 0.6 ms); trm_batch_last_kernel names the form -- each from rest a
  * warm-up ahead of its first period; the warm-up is chosen by the library so that 1e-5 of the forgotten state is left
- * (damping^W <= 1e-5: 30 control periods at Monet's defaults; measured against the oracle in tools/timesplit_study.py
- * and by the parity tests at the one tolerance, 1e-5).  numberSamples and the sample positions are exact as always.
+ * by the slowest of four poles taken one by one -- the damping factor, the mouth and nose reflection filters, the throat
+ * low-pass: pole^W <= 1e-5, 30 control periods at Monet's defaults; measured against the oracle in tools/timesplit_study.py
+ * and by the parity tests at the one tolerance, 1e-5.  That rule does not cover the loops the end filters sit in (section
+ * 10 <-> mouth, nose section 6 <-> nose), which forget more slowly than any of their parts: parameters far from Monet's
+ * (mouthCoef 400 with lossFactor 1) come out 1.5e-4 .. 5e-4 off under it.  trm_batch_set_split_warmup (below) selects a
+ * rule that covers them.  numberSamples and the sample positions are exact as always.
  *   TRM_TIME_SPLIT_AUTO (default)  the library splits when its launch-time model says so (a form set by name with
  *                                  trm_batch_set_kernel / TRM_TUBE_KERNEL runs whole utterances);
  *   TRM_TIME_SPLIT_OFF             whole utterances always;
@@ -416,6 +424,31 @@ int  trm_batch_last_kernel(const trm_batch *batch);
 enum { TRM_TIME_SPLIT_AUTO = -1, TRM_TIME_SPLIT_OFF = 0 };
 int  trm_batch_set_time_split(trm_batch *batch, int periods);
 int  trm_batch_last_time_split(const trm_batch *batch, uint32_t *periods, uint32_t *warm_periods);
+/* The warm-up W of a time split, opt-in (no default changes; no environment variable).  The planner takes W from the setting
+ * and is otherwise the same: TRM_TIME_SPLIT_AUTO prices the longer segments and runs whole utterances by itself where
+ * they no longer pay; trm_batch_last_time_split reports the W that was planned.
+ *   TRM_SPLIT_WARMUP_DEFAULT (default)  the rule above: pole = max(|damping|, |mouth coeff|, |nose coeff|, |throat b1|);
+ *   TRM_SPLIT_WARMUP_COUPLED            with d = |damping| and, for c = |mouth coeff| and c = |nose coeff|, the closed-loop
+ *                                       pole rho_c = (c + sqrt(c^2 + 4 d^2 (1 - c))) / 2 -- the larger root of
+ *                                       rho^2 - c rho - g d^2 (1 - c) = 0, the shortest loop through a one-pole reflection
+ *                                       filter, at loop gain g = 1 (a closed mouth or velum: the static bound; longer loops
+ *                                       decay faster) --: pole = max(d, rho_mouth, rho_nose, |throat b1|).  Then as the
+ *                                       default rule: ceil(ln 1e-5 / ln pole) + 64 tube samples, rounded up to control
+ *                                       periods; never shorter than the default rule (45 periods instead of 30 at Monet's
+ *                                       defaults, 189 instead of 16 for mouthCoef 400, lossFactor 1 at 44.1 kHz);
+ *   periods > 0                         a warm-up of that many control periods.  A caller may lengthen the warm-up and
+ *                                       never shorten it: TRM_ERANGE below the default rule's W for the batch's parameters
+ *                                       (the kernels have never run with less), when the tube never forgets (no warm-up
+ *                                       covers it) and beyond the rules' own limit (1e6 tube samples).
+ * Any other negative value: TRM_EINVAL.  A refused call leaves the setting as it was.  With a tube that never forgets (a rule
+ * gives 0) an explicit segment length is refused with TRM_ERANGE and AUTO runs whole utterances, under every setting.
+ * trm_split_warm_periods is host-only -- no device, no batch object --: the W in control periods a plan for `params` would use
+ * under `rule` (DEFAULT or COUPLED), 0 = never (also for parameters trm_derive refuses and for an unknown rule); a server can
+ * price a voice type with it before choosing.  A stream never splits, so nothing here applies to streams. */
+enum { TRM_SPLIT_WARMUP_DEFAULT = 0, TRM_SPLIT_WARMUP_COUPLED = -1 };
+int  trm_batch_set_split_warmup(trm_batch *batch, int rule_or_periods);
+int  trm_batch_split_warmup(const trm_batch *batch);
+uint32_t trm_split_warm_periods(const trm_input_params *params, int rule);
 /* A ragged batch through the device-buffer entry: the library sees the lengths (d_nframes) only on the device, and AUTO then
  * sizes the segments as if every voice were as long as the longest.  trm_batch_hint_frames hands it a host copy of the
  * nframes array (in the launch's voice order) for the NEXT trm_batch_synthesize_device call: AUTO then counts the workgroups
@@ -521,6 +554,14 @@ int    trm_mixed_set_time_split(trm_mixed *m, int periods);
 /* What the last launch was set up with: *periods (0 = whole utterances) and, where warm_periods is not NULL, every set's
  * warm-up in control periods in warm_periods[0 .. nsets) (nsets at most the batch's; zeros after a whole-utterance launch). */
 int    trm_mixed_last_time_split(const trm_mixed *m, uint32_t *periods, uint32_t *warm_periods, size_t nsets);
+/* The warm-up rule of a mixed batch's time split (see trm_batch_set_split_warmup): TRM_SPLIT_WARMUP_DEFAULT (the default) or
+ * TRM_SPLIT_WARMUP_COUPLED; every set gets the rule's value for its own constants, so a split launch still gives every voice
+ * bit for bit what a trm_batch of its set computes with the same segment length, form and trm_batch_set_split_warmup(rule).
+ * Anything else -- a warm-up in periods included: one number does not fit several sets -- is TRM_EINVAL.  A set that never
+ * forgets is treated as under the default rule (trm_mixed_set_time_split).  A change of the rule changes a split launch's
+ * shape: the next launch uploads its block map again. */
+int    trm_mixed_set_split_warmup(trm_mixed *m, int rule);
+int    trm_mixed_split_warmup(const trm_mixed *m);
 /* A host copy of every voice's length for the next trm_mixed_synthesize_device call, as trm_batch_hint_frames: the plan under
  * AUTO and the launch order of a split use it, the samples never depend on it; consumed by that call whether it succeeds or
  * fails.  The host-buffer entries pass it themselves. */

@@ -1,0 +1,247 @@
+"""The time split's warm-up setting on the GPU (include/trm_c_api.h: trm_batch_set_split_warmup, trm_tube_set_split_warmup).
+
+Under the coupled rule a split launch meets the project's one bar -- normalised RMS <= 1e-5 against the oracle per utterance and
+per control period, exact numberSamples -- on tube parameters the default rule leaves 50x off (VERDICT.md's case: mouthCoef 400,
+lossFactor 1), in both segment forms, on a down-sampling set, through the single-utterance entry, and on draws of the seeded
+population (tests/split_warmup_common.py; tests/test_split_warmup_model.py admits all of these by the host model).  A batch that
+never calls the setter, or sets "default", plans and computes exactly what it always did."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import cases
+import golden_io
+import parity
+import split_warmup_common as W
+from test_time_split import RMS_TOL, nrms, warm_periods
+
+pytestmark = pytest.mark.gpu
+
+COUPLED_W = W.VERDICT_WARM["coupled"]
+
+
+@pytest.fixture(scope="module")
+def g():
+    import gnuspeech_amd
+    assert gnuspeech_amd.lib().trm_device_count() >= 1
+    return gnuspeech_amd
+
+
+@pytest.fixture(autouse=True)
+def _no_plan_by_environment(monkeypatch):
+    monkeypatch.delenv("TRM_TUBE_KERNEL", raising=False)
+    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
+    monkeypatch.delenv("TRM_TIME_SPLIT", raising=False)
+
+
+def _batch(g, pd, split, warmup=None, kernel=None):
+    b = g.TRMBatch(g.TRMInputParameters.from_dict(pd), device=0)
+    b.set_time_split(split)
+    if warmup is not None:
+        b.set_split_warmup(warmup)
+    if kernel is not None:
+        b.set_kernel(kernel)
+    return b
+
+
+_cache = {}
+
+
+def _verdict_voices():
+    """17 voices of the VERDICT case at 2 (S + W) + 7 frames: voice 0 the case itself, the others at pitches of their own, four of
+    them shorter (one ends in the warm-up of the second segment, one just past the first seam).  With their oracle results,
+    computed once and left unchanged."""
+    if "verdict" not in _cache:
+        n = W.split_frames(COUPLED_W)
+        assert n == 425
+        voices = [np.asarray(W.verdict_frames(n, pitch=-12.0 - 0.5 * v), dtype=np.float32) for v in range(17)]
+        for v, cut in ((3, 2), (7, W.SEG + COUPLED_W - 5), (11, W.SEG + COUPLED_W + 3), (13, 300)):
+            voices[v] = voices[v][:cut].copy()
+        _cache["verdict"] = (voices, [W.oracle_of(W.VERDICT_PD, fr) for fr in voices])
+    return _cache["verdict"]
+
+
+def _check(pcm, ns, refs, pd, what):
+    win = parity.window_length_of(pd)
+    worst = 0.0
+    for v, o in enumerate(refs):
+        assert int(ns[v]) == o["numberSamples"], (what, v, int(ns[v]), o["numberSamples"])
+        if o["maximumSampleValue"] > 0:
+            e = nrms(pcm[v], o["samples"], o["maximumSampleValue"])
+            worst = max(worst, e)
+            assert e <= RMS_TOL, (what, v, e)
+            parity.check_oracle(pcm[v], o, win, what="%s voice %d" % (what, v))
+    return worst
+
+
+# ---------------------------------------------------------------- 1. the VERDICT case
+@pytest.mark.parametrize("nvoices", [1, 17])
+@pytest.mark.parametrize("plan", ["wide", "quad", "auto"])
+def test_verdict_case_meets_the_tolerance_under_the_coupled_rule(g, plan, nvoices):
+    voices, refs = _verdict_voices()
+    voices, refs = voices[:nvoices], refs[:nvoices]
+    assert warm_periods(W.VERDICT_PD, 79) == W.VERDICT_WARM["default"] == 16
+    if plan == "auto":
+        b = _batch(g, W.VERDICT_PD, "auto", "coupled")
+    else:
+        b = _batch(g, W.VERDICT_PD, W.SEG, "coupled", kernel=plan)
+    assert b.split_warmup == "coupled"
+    pcm, ns, mx = b.synthesize(voices)
+    if plan == "auto":
+        # a warm-up this long against 424 periods: AUTO may well run whole utterances, which is the right answer; where it
+        # splits, it splits with the coupled W
+        assert b.last_time_split == (0, 0) or b.last_time_split[1] == COUPLED_W, b.last_time_split
+    else:
+        assert b.last_time_split == (W.SEG, COUPLED_W) and b.last_kernel == plan
+    worst = _check(pcm, ns, refs, W.VERDICT_PD, "VERDICT %s x%d" % (plan, nvoices))
+    print("VERDICT case, %s, %d voice(s): plan %s form %s, worst nrms %.3g" % (plan, nvoices, b.last_time_split, b.last_kernel, worst))
+
+
+def test_verdict_case_under_the_default_rule_is_printed_not_pinned(g):
+    """The gap the coupled rule closes, as a figure: the same launch under the default rule (W = 16).  Only the plan is asserted."""
+    voices, refs = _verdict_voices()
+    b = _batch(g, W.VERDICT_PD, W.SEG, kernel="wide")
+    pcm, ns, mx = b.synthesize(voices[:1])
+    assert b.last_time_split == (W.SEG, W.VERDICT_WARM["default"]) and b.split_warmup == "default"
+    assert int(ns[0]) == refs[0]["numberSamples"]
+    print("VERDICT case under the default rule (W = 16): nrms %.3g" % nrms(pcm[0], refs[0]["samples"], refs[0]["maximumSampleValue"]))
+
+
+# ---------------------------------------------------------------- 2. draws of the seeded population
+def test_six_draws_of_the_population_meet_the_tolerance_under_an_explicit_split(g):
+    """Of the draws whose coupled W is at most 120 periods, the six with the longest: where the two rules differ most."""
+    draws = [(k, pd, warm, fr) for k, (pd, warm, fr) in enumerate(W.population()) if fr is not None and warm <= 120]
+    draws = sorted(draws, key=lambda d: -d[2])[:6]
+    assert len(draws) == 6 and all(d[2] > warm_periods(d[1], 79) for d in draws)
+    for k, pd, warm, fr in draws:
+        fr = np.asarray(fr, dtype=np.float32)
+        o = W.oracle_of(pd, fr)
+        b = _batch(g, pd, W.SEG, "coupled", kernel="wide")
+        pcm, ns, mx = b.synthesize([fr])
+        assert b.last_time_split == (W.SEG, warm), (k, b.last_time_split, warm)
+        e = _check(pcm, ns, [o], pd, "draw %d" % k)
+        print("draw %d: W = %d (default rule %d), nrms %.3g" % (k, warm, warm_periods(pd, 79), e))
+
+
+# ---------------------------------------------------------------- 3. a down-sampling set
+def test_down_sampling_set_meets_the_tolerance_under_the_coupled_rule(g):
+    cp = W.control_period_of(W.DOWN_PD)
+    warm = W.rule_periods(W.DOWN_PD, cp, "coupled")
+    assert warm > warm_periods(W.DOWN_PD, cp)
+    voices = [np.asarray(W.verdict_frames(W.split_frames(warm), pitch=-12.0 - 2.0 * v), dtype=np.float32) for v in range(3)]
+    voices[2] = voices[2][:W.SEG + warm + 9].copy()
+    refs = [W.oracle_of(W.DOWN_PD, fr) for fr in voices]
+    b = _batch(g, W.DOWN_PD, W.SEG, "coupled")
+    assert b.derived["sampleRateRatio"] < 1.0
+    pcm, ns, mx = b.synthesize(voices)
+    assert b.last_time_split == (W.SEG, warm) and b.last_kernel == "wide"
+    e = _check(pcm, ns, refs, W.DOWN_PD, "down-sampling")
+    print("down-sampling set: W = %d, worst nrms %.3g" % (warm, e))
+
+
+# ---------------------------------------------------------------- 4. an explicit warm-up
+def test_explicit_periods_equal_the_rule_and_a_shorter_warm_up_is_refused(g):
+    voices, refs = _verdict_voices()
+    voices = voices[:2]
+    by_rule = _batch(g, W.VERDICT_PD, W.SEG, "coupled", kernel="wide")
+    want = by_rule.synthesize(voices)
+    b = _batch(g, W.VERDICT_PD, W.SEG, COUPLED_W, kernel="wide")
+    assert b.split_warmup == COUPLED_W
+    got = b.synthesize(voices)
+    assert b.last_time_split == by_rule.last_time_split == (W.SEG, COUPLED_W)
+    for v in range(len(voices)):
+        assert got[0][v].tobytes() == want[0][v].tobytes(), v
+    assert got[1].tobytes() == want[1].tobytes() and got[2].tobytes() == want[2].tobytes()
+    # below the default rule's 16 periods: refused, the setting stays, the batch stays usable
+    least = W.VERDICT_WARM["default"]
+    for bad in (least - 1, 1):
+        with pytest.raises(g.TrmError) as ei:
+            b.set_split_warmup(bad)
+        assert ei.value.code == g._capi.TRM_ERANGE
+    rc = g.lib().trm_batch_set_split_warmup(b._h, -2)
+    assert rc == g._capi.TRM_EINVAL
+    assert b.split_warmup == COUPLED_W
+    again = b.synthesize(voices)
+    assert b.last_time_split == (W.SEG, COUPLED_W) and again[0][0].tobytes() == want[0][0].tobytes()
+    # the default rule's own value is the least that is taken: the bits of "default"
+    b.set_split_warmup(least)
+    low = b.synthesize(voices[:1])
+    assert b.last_time_split == (W.SEG, least)
+    d = _batch(g, W.VERDICT_PD, W.SEG, "default", kernel="wide")
+    assert d.synthesize(voices[:1])[0][0].tobytes() == low[0][0].tobytes()
+    # a tube that never forgets: no warm-up covers it, and an explicit split is refused as ever
+    n = _batch(g, dict(W.VERDICT_PD, lossFactor=0.0), W.SEG, "coupled")
+    with pytest.raises(g.TrmError) as ei:
+        n.set_split_warmup(500)
+    assert ei.value.code == g._capi.TRM_ERANGE
+    with pytest.raises(g.TrmError) as ei:
+        n.synthesize(voices[:1])
+    assert ei.value.code == g._capi.TRM_ERANGE
+    n.set_time_split("auto")
+    n.synthesize(voices[:1])
+    assert n.last_time_split == (0, 0)
+
+
+# ---------------------------------------------------------------- 5. the single-utterance entry
+def test_tube_model_synthesizes_the_verdict_case_after_set_split_warmup(g):
+    voices, refs = _verdict_voices()
+    dl = g.TRMDataList()
+    dl.inputParameters = g.TRMInputParameters.from_dict(W.VERDICT_PD)
+    L = g.lib()
+    h = C.c_void_p()
+    g._capi.check(L.trm_tube_create(C.byref(dl.inputParameters.c), 0, C.byref(h)))
+    try:
+        g._capi.check(L.trm_tube_set_split_warmup(h, g._capi.TRM_SPLIT_WARMUP_COUPLED))
+        assert L.trm_tube_set_split_warmup(h, 3) == g._capi.TRM_ERANGE and L.trm_tube_set_split_warmup(h, -7) == g._capi.TRM_EINVAL
+        fr = np.ascontiguousarray(voices[0], dtype=np.float64)
+        buf = (g._capi.TrmParameters * len(fr))()
+        C.memmove(buf, fr.ctypes.data, fr.nbytes)
+        g._capi.check(L.trm_tube_synthesize(h, buf, len(fr)))
+        n = L.trm_tube_number_samples(h)
+        y = np.ctypeslib.as_array(L.trm_tube_samples(h), shape=(n,)).copy()
+    finally:
+        L.trm_tube_destroy(h)
+    e = _check([y], [n], refs[:1], W.VERDICT_PD, "trm_tube_synthesize")
+    # ... and through the Python class, which keeps the setting
+    dl.values = [g.TRMParameters(row) for row in voices[0]]
+    t = g.TRMTubeModel.initWithInputData(dl, device=0)
+    assert t.split_warmup == "default"
+    t.set_split_warmup("coupled")
+    assert t.split_warmup == "coupled"
+    t.synthesize()
+    e2 = _check([t.samples()], [t.numberSamples], refs[:1], W.VERDICT_PD, "TRMTubeModel")
+    print("single-utterance entry under the coupled rule: nrms %.3g (C), %.3g (Python class)" % (e, e2))
+
+
+# ---------------------------------------------------------------- 6. the default is untouched
+@pytest.mark.parametrize("split", ["auto", W.SEG])
+@pytest.mark.parametrize("load", ["gnuspeech_input_22k", "monet 64 x 1 s"])
+def test_default_plans_and_bits_are_unchanged(g, load, split):
+    if load == "gnuspeech_input_22k":
+        gold = golden_io.load(load)
+        pd, voices = gold["params_dict"], [np.asarray(gold["frames"], dtype=np.float32)]
+    else:
+        pd, voices = cases.monet_default_params(44100.0), [np.asarray(f, dtype=np.float32) for f in cases.config3_frames(64, nframes=251)]
+    never = _batch(g, pd, split)
+    named = _batch(g, pd, split, "default")
+    assert never.split_warmup == named.split_warmup == "default"
+    a, b = never.synthesize(voices), named.synthesize(voices)
+    cp = never.derived["controlPeriod"]
+    assert never.last_time_split == named.last_time_split and never.last_kernel == named.last_kernel
+    assert never.last_time_split[0] > 0 and never.last_time_split[1] == warm_periods(pd, cp), never.last_time_split
+    if split != "auto":
+        assert never.last_time_split[0] == split
+    assert a[1].tobytes() == b[1].tobytes() and a[2].tobytes() == b[2].tobytes()
+    for x, y in zip(a[0], b[0]):
+        assert x.tobytes() == y.tobytes()
+    # ... and a batch that went to "coupled" and back is the same batch again
+    named.set_split_warmup("coupled")
+    named.set_split_warmup("default")
+    c = named.synthesize(voices)
+    assert named.last_time_split == never.last_time_split
+    for x, y in zip(a[0], c[0]):
+        assert x.tobytes() == y.tobytes()
+    if load == "gnuspeech_input_22k":
+        assert int(a[1][0]) == gold["numberSamples"]
+        parity.check_parity(a[0][0], gold["samples_f32"], gold["maximumSampleValue"], parity.window_length_of(pd), what=load)
