@@ -177,6 +177,44 @@ trm::ScaleArgs scale_args(const trm_batch *b, const float *pcm, const uint64_t *
     return s;
 }
 
+hipError_t launch_form(int which, const trm_batch *b, const trm::Const &c, const trm::TubeArgs &a, hipStream_t stream)
+{
+    if (which == TRM_KERNEL_OCT) return trm::launch_tube_oct(c, a, stream);
+    if (which == TRM_KERNEL_QUAD) return trm::launch_tube_quad(c, a, stream, b->cus);
+    return trm::launch_tube(c, a, stream);
+}
+
+trm::PhaseArgs phase_args(const trm_batch *b, const trm::TubeArgs &a, size_t lo, size_t n, uint32_t S, uint32_t W, uint32_t wgPerSeg,
+                          uint32_t perWg, double *seg_phase, double *period_adv, uint32_t *gate)
+{
+    trm::PhaseArgs ph;
+    ph.frames = a.frames; ph.frame_offset = a.frame_offset + lo; ph.nframes = a.nframes + lo;
+    ph.period_adv = period_adv; ph.seg_phase = seg_phase; ph.gate = gate;
+    ph.bw_floor = split_bw_floor(b, W);
+    ph.nvoices = (uint32_t)n; ph.max_nframes = a.max_nframes; ph.nseg = trm::seg_count(a.max_nframes - 1, S, W);
+    ph.seg_periods = S; ph.seg_warm = W; ph.seg_wg_per_seg = wgPerSeg; ph.seg_first = trm::seg_first(S, W);
+    ph.voices_per_wg = perWg;
+    return ph;
+}
+
+uint64_t noise_need(const trm_batch *b, uint32_t max_nframes)
+{
+    const uint64_t ntube = max_nframes > 0 ? (uint64_t)(max_nframes - 1) * (uint64_t)b->d.controlPeriod : 0;
+    return ntube + 64 > 0x7FFFFFFFull ? 0 : ntube + 2ull * (uint64_t)b->d.padSize + 256u;
+}
+
+int check_kernel_form(int kernel)
+{
+    if (kernel != TRM_KERNEL_AUTO && kernel != TRM_KERNEL_WIDE && kernel != TRM_KERNEL_QUAD && kernel != TRM_KERNEL_OCT) return fail(TRM_EINVAL, "unknown kernel form %d", kernel);
+    return TRM_OK;
+}
+
+int check_time_split(int periods)
+{
+    if (periods < TRM_TIME_SPLIT_AUTO) return fail(TRM_EINVAL, "time split: %d", periods);
+    return TRM_OK;
+}
+
 struct trm_tube {
     trm_batch *b = nullptr;
     std::vector<float> samples;
@@ -417,17 +455,7 @@ static int fold_events(trm_batch *b, bool wait)
 // even a voice with mouth and velum closed -- nothing but the damping factor takes energy out -- is back at the
 // unsplit path's own error, 2e-6 worst sample; open voices get there in two thirds of the time.)  An utterance can so be cut in
 // time and its pieces run side by side: what bounds a small or ragged batch is the serial chain of its longest voice.
-namespace {
-struct SplitPlan {
-    uint32_t periods = 0;         // control periods per segment; 0 = whole utterances
-    uint32_t warm = 0;            // warm-up control periods
-    bool allBusy = false;         // the caller's lengths say every workgroup of the grid has work: no launch order to build
-    int form = TRM_KERNEL_WIDE;   // the segment instance that runs it: one voice per lane (64 voices per workgroup) or four lanes per voice (16)
-    float bwFloor = 0.0f;         // frication bandwidths below this need a longer warm-up: the launch falls back (device-side)
-};
-}  // namespace
-
-// (declared in trm_host.h: trm_mixed.cc plans its time split with the same functions)
+// (declared in trm_host.h: trm_mixed.cc plans its time split with the same planner)
 extern "C++" {
 
 uint32_t batch_split_warm(const trm_batch *b)
@@ -457,15 +485,6 @@ double unsplit_cost(const trm_batch *b, size_t nvoices, int which)
     return wide_cost(b, (nvoices + 63) / 64);
 }
 
-// workgroups of a time-split launch that have work: block by block (its longest voice, in control periods) the segments it
-// reaches -- what trm_seg_map_kernel counts on the device
-uint64_t busy_workgroups(const std::vector<uint32_t> &longest, uint32_t periods, uint32_t warm)
-{
-    uint64_t n = 0;
-    for (uint32_t per : longest) n += trm::seg_count(per, periods, warm);
-    return n;
-}
-
 // the frication band-pass (TRMFilters.m:9-29) has poles of radius sqrt(2 beta), 2 beta = (1 - t) / (1 + t),
 // t = tan(pi BW / SR): the bandwidth at which a warm-up of `warm` control periods leaves 1e-5 of its memory
 float split_bw_floor(const trm_batch *b, uint32_t warm)
@@ -476,83 +495,91 @@ float split_bw_floor(const trm_batch *b, uint32_t warm)
     return (float)((double)b->d.sampleRate * atan(t) / 3.14159265358979323846);
 }
 
-}  // extern "C++"
-
-// `which` = the kernel form the launch would take unsplit.  `totalPeriods` = the control periods of all voices together where
-// the caller knows them (the host-buffer entries; 0: every voice is taken to be as long as the longest).
-static int plan_time_split(const trm_batch *b, size_t nvoices, uint32_t max_nframes, int which, int byName, uint64_t totalPeriods, SplitPlan &pl)
+void hinted_blocks(const size_t *set_begin, size_t nsets, size_t perWg, const std::vector<uint32_t> &hint, uint32_t max_nframes,
+                   std::vector<SplitBlock> &blocks)
 {
-    pl = SplitPlan();
-    const int setting = b->splitSetting;
-    if (setting == TRM_TIME_SPLIT_OFF || max_nframes < 2) return TRM_OK;
-    const uint32_t CP = (uint32_t)b->c.controlPeriod, P = max_nframes - 1;
-    // the longest voice (in control periods) of every block of 64 / 16 voices, where the caller told the lengths
-    std::vector<uint32_t> longest64, longest16;
-    if (b->hintFrames.size() == nvoices && setting <= 0) {
-        longest64.assign((nvoices + 63) / 64, 0);
-        longest16.assign((nvoices + 15) / 16, 0);
-        for (size_t v = 0; v < nvoices; v++) {
-            const uint32_t nfr = b->hintFrames[v] < max_nframes ? b->hintFrames[v] : max_nframes, per = nfr > 0 ? nfr - 1 : 0;
-            longest64[v / 64] = longest64[v / 64] > per ? longest64[v / 64] : per;
-            longest16[v / 16] = longest16[v / 16] > per ? longest16[v / 16] : per;
+    blocks.clear();
+    for (size_t s = 0; s < nsets; s++)
+        for (size_t f = set_begin[s]; f < set_begin[s + 1]; f += perWg) {
+            uint32_t nfr = 0;
+            for (size_t v = f; v < std::min(f + perWg, set_begin[s + 1]); v++) nfr = std::max(nfr, std::min(hint[v], max_nframes));
+            blocks.push_back({(uint32_t)s, nfr > 0 ? nfr - 1 : 0});
         }
-    }
-    const uint32_t warm = batch_split_warm(b);
-    if (warm == 0) {
-        if (setting > 0) return fail(TRM_ERANGE, "time split: the tube never forgets (loss factor %g %%)", b->params.lossFactor);
-        return TRM_OK;
-    }
-    uint32_t periods = 0;
-    // the four-lane segment instance: up-sampling batches whose converter makes at most four outputs per tube sample
-    const bool quadOk = b->c.upsample && !quad_ratio_too_high(b->c) && which != TRM_KERNEL_WIDE;
-    if (setting > 0) {
-        periods = (uint32_t)setting;
-        // a split asked for by name: in the form asked for by name (four lanes, or one voice per lane), else by size
-        const uint64_t wgsQ = (uint64_t)trm::seg_count(P, periods, warm) * ((nvoices + 15) / 16);
-        pl.form = (quadOk && (byName == TRM_KERNEL_QUAD || (byName == TRM_KERNEL_AUTO && wgsQ <= (uint64_t)(b->cus > 0 ? b->cus : 256)))) ? TRM_KERNEL_QUAD
-                                                                                                                                       : TRM_KERNEL_WIDE;
+}
+
+// workgroups of a time-split launch that have work: block by block (its longest voice) the segments it reaches -- what
+// trm_seg_map_kernel counts on the device -- or, where no lengths were told, every block of every set in all of the set's segments
+static uint64_t busy_workgroups(const SplitAsk &ask, bool quad, uint32_t sp)
+{
+    uint64_t n = 0;
+    if (const std::vector<SplitBlock> *cut = quad ? ask.cut16 : ask.cut64) {
+        for (const SplitBlock &blk : *cut) n += trm::seg_count(blk.longest, sp, ask.sets[blk.set].warm);
     } else {
-        // AUTO.  A time-split launch pays when its workgroups -- one per segment and block of 64 voices, every one of them
-        // periods + warm control periods long -- fill the chip's rounds better than whole utterances do (wide_cost): every
+        for (size_t s = 0; s < ask.nsets; s++) n += (quad ? ask.sets[s].blocks16 : ask.sets[s].blocks64) * trm::seg_count(ask.P, sp, ask.sets[s].warm);
+    }
+    return n;
+}
+
+SplitPlan plan_split(const trm_batch *b0, const SplitAsk &ask)
+{
+    SplitPlan pl;
+    const uint64_t cus = (uint64_t)(b0->cus > 0 ? b0->cus : 256);
+    const uint32_t P = ask.P;
+    uint32_t warmMax = 0, minPeriods = 4;
+    uint64_t blocks64 = 0;
+    double wholeSamples = 0.0;
+    for (size_t s = 0; s < ask.nsets; s++) {
+        const SplitSet &set = ask.sets[s];
+        if (set.blocks64 == 0) continue;
+        warmMax = std::max(warmMax, set.warm);
+        minPeriods = std::max(minPeriods, (255u + set.cp) / set.cp);
+        wholeSamples = std::max(wholeSamples, (double)P * set.cp);
+        blocks64 += set.blocks64;
+    }
+    // the launch's longest workgroup, in tube samples, with segments of sp periods
+    auto seg_samples = [&](uint32_t sp) {
+        double x = 0.0;
+        for (size_t s = 0; s < ask.nsets; s++)
+            if (ask.sets[s].blocks64) x = std::max(x, (double)(sp + ask.sets[s].warm) * (double)ask.sets[s].cp);
+        return x;
+    };
+    if (ask.setting > 0) {
+        // a split asked for by name: in the form asked for by name (four lanes, or one voice per lane), else by size
+        pl.periods = (uint32_t)ask.setting;
+        if (ask.quadOk && (ask.byName == TRM_KERNEL_QUAD || (ask.byName == TRM_KERNEL_AUTO && busy_workgroups(ask, true, pl.periods) <= cus)))
+            pl.form = TRM_KERNEL_QUAD;
+    } else {
+        // AUTO.  A time-split launch pays when its workgroups -- one per segment and block of 64 voices, the longest of them
+        // S + W_s control periods of CP_s samples -- fill the chip's rounds better than whole utterances do (wide_cost): every
         // segment count is priced, the shortest predicted launch taken when it beats whole utterances by a tenth.
-        const double whole = unsplit_cost(b, nvoices, which) * P * CP / 19750.0;
+        const double whole = (ask.which == TRM_KERNEL_WIDE ? wide_cost(b0, blocks64) : unsplit_cost(b0, ask.nvoices, ask.which)) * wholeSamples / 19750.0;
         double best = whole * 0.9;
-        // (segments of at least half a warm-up: a launch never does more than three times the arithmetic of whole
+        // (segments of at least half the largest warm-up: a launch never does more than three times the arithmetic of whole
         // utterances -- shorter ones still shorten a nearly empty chip's launch a little, at ten times the work)
-        uint32_t minPeriods = (255u + CP) / CP > 4u ? (255u + CP) / CP : 4u;
-        minPeriods = minPeriods > (warm + 1) / 2 ? minPeriods : (warm + 1) / 2;
-        for (uint32_t nseg = 2; nseg <= 4096 && P > warm; nseg++) {
-            const uint32_t sp = (P - warm + nseg - 1) / nseg;          // the shortest segments that make `nseg` of them
+        minPeriods = std::max(minPeriods, (warmMax + 1) / 2);
+        for (uint32_t nseg = 2; nseg <= 4096 && P > warmMax; nseg++) {
+            const uint32_t sp = (P - warmMax + nseg - 1) / nseg;       // the shortest segments that make `nseg` of them
             if (sp < minPeriods) break;
-            const uint64_t segs = trm::seg_count(P, sp, warm);
-            if (segs < 2) continue;
-            // workgroups with work: per segment the blocks of 64 voices that reach it (they are launched first:
-            // trm_seg_map_kernel) -- counted where the caller's lengths are known, else every block in every segment
-            const uint64_t wgs = !longest64.empty() ? busy_workgroups(longest64, sp, warm)
-                                 : totalPeriods == 0 ? segs * ((nvoices + 63) / 64)
-                                                     : (totalPeriods + 64ull * sp - 1) / (64ull * sp) + (segs + 1) / 2;    // (+ partly filled last blocks)
-            const double t = 0.03 + wide_cost(b, wgs) * (double)(sp + warm) * CP / 19750.0;
-            if (t < best) { best = t; periods = sp; pl.form = TRM_KERNEL_WIDE; }
+            // (sp >= 4 and nseg >= 2: P > sp + warmMax, every candidate has a second segment)
+            const double t = 0.03 + wide_cost(b0, busy_workgroups(ask, false, sp)) * seg_samples(sp) / 19750.0;
+            if (t < best) { best = t; pl.periods = sp; pl.form = TRM_KERNEL_WIDE; }
             // ... or in the four-lane form (16 voices x one segment per workgroup, one workgroup per CU at 3.1 ms per second of
-            // speech): a handful of voices, a single utterance
-            const uint64_t wgsQ = !longest16.empty() ? busy_workgroups(longest16, sp, warm)
-                                  : totalPeriods == 0 ? segs * ((nvoices + 15) / 16) : (totalPeriods + 16ull * sp - 1) / (16ull * sp) + (segs + 1) / 2;
-            if (quadOk && wgsQ <= (uint64_t)(b->cus > 0 ? b->cus : 256)) {
-                const double tq = 0.03 + 3.1 * (double)(sp + warm) * CP / 19750.0;
-                if (tq < best) { best = tq; periods = sp; pl.form = TRM_KERNEL_QUAD; }
+            // speech -- measured for uniform batches at the default warm-up): a handful of voices, a single utterance
+            if (ask.quadOk && busy_workgroups(ask, true, sp) <= cus) {
+                const double tq = 0.03 + 3.1 * seg_samples(sp) / 19750.0;
+                if (tq < best) { best = tq; pl.periods = sp; pl.form = TRM_KERNEL_QUAD; }
             }
         }
     }
-    if (periods == 0 || trm::seg_count(P, periods, warm) < 2) return TRM_OK;      // one segment is the whole utterance
-    {
-        const std::vector<uint32_t> &longest = pl.form == TRM_KERNEL_QUAD ? longest16 : longest64;
-        pl.allBusy = !longest.empty() && busy_workgroups(longest, periods, warm) == (uint64_t)trm::seg_count(P, periods, warm) * longest.size();
-    }
-    pl.periods = periods;
-    pl.warm = warm;
-    pl.bwFloor = split_bw_floor(b, warm);
-    return TRM_OK;
+    // (no voice reaches past its set's first segment: one segment is the whole utterance)
+    bool any = false;
+    for (size_t s = 0; pl.periods && s < ask.nsets; s++) any = any || (ask.sets[s].blocks64 && trm::seg_count(P, pl.periods, ask.sets[s].warm) >= 2);
+    if (!any) return SplitPlan();
+    pl.busy = busy_workgroups(ask, pl.form == TRM_KERNEL_QUAD, pl.periods);
+    return pl;
 }
+
+}  // extern "C++"
 
 // A hint holds for the one launch that follows it, whether that launch runs or fails: an entry drops it on every return
 // (a hint left by a failed call would plan the next launch by lengths that are not its own)
@@ -560,7 +587,6 @@ struct HintDrop {
     trm_batch *b;
     ~HintDrop()
     {
-        b->hintTotalPeriods = 0;
         b->hintFrames.clear();
     }
 };
@@ -576,7 +602,7 @@ int trm_batch_hint_frames(trm_batch *b, const uint32_t *nframes, size_t nvoices)
 int trm_batch_set_time_split(trm_batch *b, int periods)
 {
     if (!b) return fail(TRM_EINVAL, "null batch");
-    if (periods < TRM_TIME_SPLIT_AUTO) return fail(TRM_EINVAL, "time split: %d", periods);
+    if (int rc = check_time_split(periods)) return rc;
     b->splitSetting = periods;
     return TRM_OK;
 }
@@ -630,16 +656,15 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
     if (nvoices > 0xFFFFFFFFull - 64) return fail(TRM_EINVAL, "too many voices");
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(b->device));
-    uint64_t ntubeMax = max_nframes > 0 ? (uint64_t)(max_nframes - 1) * (uint64_t)b->d.controlPeriod : 0;
-    if (ntubeMax + 64 > 0x7FFFFFFFull) return fail(TRM_ERANGE, "utterance too long");
-    // + 2 ring halves of look-ahead that the kernel's LDS-DMA prefetch may touch
-    int rc = ensure_noise(b, (uint32_t)ntubeMax + 2u * (uint32_t)b->d.padSize + 256u, stream);
+    const uint64_t need = noise_need(b, max_nframes);
+    if (!need) return fail(TRM_ERANGE, "utterance too long");
+    int rc = ensure_noise(b, (uint32_t)need, stream);
     if (rc) return rc;
     trm::TubeArgs a = tube_args(b, d_frames, d_frame_offset, d_nframes, d_out, d_out_offset, d_number_samples, d_max_sample, nvoices, max_nframes);
     if (!b->c.upsample) {
         // tube rate above the output rate: tube-rate samples go through HBM to the down-sampling kernel;
         // voice v gets a fixed-pitch row of (max_nframes-1)*controlPeriod + 2*pad floats
-        const uint64_t pitch = tube_row_pitch(b, ntubeMax);
+        const uint64_t pitch = tube_row_pitch(b, max_nframes > 0 ? (uint64_t)(max_nframes - 1) * (uint64_t)b->d.controlPeriod : 0);
         if ((rc = b->dTube.reserve(pitch * nvoices + 1))) return rc;
         if (b->tubeOffPitch != pitch || b->tubeOffVoices < nvoices) {
             // the row offsets pitch * v: uploaded when the batch shape changes, not per launch -- the entry stays pure
@@ -677,16 +702,40 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
     }
     int which = choose_form(b->kernel, b->envKernel, nvoices, (nvoices + 7) / 8, b->c.controlPeriod, quad_ratio_too_high(b->c), b->cus,
                             b->wideThreshold, false);
-    // Time split (above): the utterances cut into segments that run side by side in the one-voice-per-lane form.  A form
-    // the caller asked for by name is run as asked (whole utterances) unless the split was asked for by name too.
+    // Time split (above): the utterances cut into segments that run side by side.  A form the caller asked for by name is run as
+    // asked (whole utterances) unless the split was asked for by name too.
     SplitPlan pl;
-    const bool formByName = b->kernel != TRM_KERNEL_AUTO || b->envKernel != TRM_KERNEL_AUTO;
-    const int byName = b->kernel != TRM_KERNEL_AUTO ? b->kernel : b->envKernel;
-    if (!(formByName && b->splitSetting <= 0) && (rc = plan_time_split(b, nvoices, max_nframes, which, byName, b->hintTotalPeriods, pl))) return rc;
+    bool allBusy = false;         // the caller's lengths say every workgroup of the grid has work: no launch order to build
+    uint32_t warm = 0;
+    const int setting = b->splitSetting, byName = b->kernel != TRM_KERNEL_AUTO ? b->kernel : b->envKernel;
+    if (setting != TRM_TIME_SPLIT_OFF && max_nframes >= 2 && !(byName != TRM_KERNEL_AUTO && setting <= 0)) {
+        if ((warm = batch_split_warm(b)) == 0) {
+            if (setting > 0) return fail(TRM_ERANGE, "time split: the tube never forgets (loss factor %g %%)", b->params.lossFactor);
+        } else {
+            const SplitSet set = {(uint32_t)b->c.controlPeriod, warm, (nvoices + 63) / 64, (nvoices + 15) / 16};
+            SplitAsk ask = {&set, 1, nvoices, max_nframes - 1, setting, which, byName, false, nullptr, nullptr};
+            // the four-lane segment instance: up-sampling batches whose converter makes at most four outputs per tube sample
+            ask.quadOk = b->c.upsample && !quad_ratio_too_high(b->c) && which != TRM_KERNEL_WIDE;
+            // the longest voice of every block of 64 / 16 voices, where the caller told the lengths: AUTO prices the work there is
+            std::vector<SplitBlock> cut64, cut16;
+            const size_t range[2] = {0, nvoices};
+            if (b->hintFrames.size() == nvoices && setting <= 0) {
+                hinted_blocks(range, 1, 64, b->hintFrames, max_nframes, cut64);
+                ask.cut64 = &cut64;
+                if (ask.quadOk) {
+                    hinted_blocks(range, 1, 16, b->hintFrames, max_nframes, cut16);
+                    ask.cut16 = &cut16;
+                }
+            }
+            pl = plan_split(b, ask);
+            allBusy = pl.periods && ask.cut64 &&
+                      pl.busy == (uint64_t)trm::seg_count(max_nframes - 1, pl.periods, warm) * (pl.form == TRM_KERNEL_QUAD ? set.blocks16 : set.blocks64);
+        }
+    }
     b->lastSplitPeriods = pl.periods;
-    b->lastSplitWarm = pl.periods ? pl.warm : 0;
+    b->lastSplitWarm = pl.periods ? warm : 0;
     if (pl.periods) {
-        const uint32_t nseg = trm::seg_count(max_nframes - 1, pl.periods, pl.warm);
+        const uint32_t nseg = trm::seg_count(max_nframes - 1, pl.periods, warm);
         const uint32_t perWg = pl.form == TRM_KERNEL_QUAD ? 16u : 64u;
         const uint32_t wgPerSeg = (uint32_t)((nvoices + perWg - 1) / perWg);
         if ((uint64_t)nseg * wgPerSeg > 0x7FFFFFFFull / 64) return fail(TRM_ERANGE, "time split: too many segments");
@@ -694,22 +743,16 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
             (rc = b->dSegMap.reserve((size_t)nseg * wgPerSeg)) || (rc = b->dBlockFrames.reserve(wgPerSeg))) return rc;
         HIP_TRY(hipMemsetAsync(b->dGate, 0, sizeof(uint32_t), stream));
         HIP_TRY(hipMemsetAsync(d_max_sample, 0, nvoices * sizeof(float), stream));
-        trm::PhaseArgs ph;
-        ph.frames = d_frames; ph.frame_offset = d_frame_offset; ph.nframes = d_nframes;
-        ph.period_adv = b->dPeriodAdv.p; ph.seg_phase = b->dSegPhase.p; ph.gate = b->dGate; ph.bw_floor = pl.bwFloor;
-        ph.nvoices = (uint32_t)nvoices; ph.max_nframes = max_nframes; ph.nseg = nseg;
-        ph.seg_periods = pl.periods; ph.seg_warm = pl.warm; ph.seg_wg_per_seg = wgPerSeg; ph.seg_first = trm::seg_first(pl.periods, pl.warm);
-        ph.voices_per_wg = perWg;
-        ph.seg_map = pl.allBusy ? nullptr : b->dSegMap.p; ph.block_frames = b->dBlockFrames.p;
+        trm::PhaseArgs ph = phase_args(b, a, 0, nvoices, pl.periods, warm, wgPerSeg, perWg, b->dSegPhase.p, b->dPeriodAdv.p, b->dGate);
+        ph.seg_map = allBusy ? nullptr : b->dSegMap.p; ph.block_frames = b->dBlockFrames.p;
         HIP_TRY(trm::launch_phase(b->c, ph, stream));
         trm::TubeArgs sa = a;
-        sa.seg_periods = pl.periods; sa.seg_warm = pl.warm; sa.seg_wg_per_seg = wgPerSeg; sa.seg_grid = nseg * wgPerSeg;
+        sa.seg_periods = pl.periods; sa.seg_warm = warm; sa.seg_wg_per_seg = wgPerSeg; sa.seg_grid = nseg * wgPerSeg;
         sa.seg_first = ph.seg_first;
         sa.seg_phase = b->dSegPhase.p;
         sa.seg_map = ph.seg_map;
         sa.gate = b->dGate; sa.gate_want = 0;
-        if (pl.form == TRM_KERNEL_QUAD) HIP_TRY(trm::launch_tube_quad(b->c, sa, stream, b->cus));
-        else HIP_TRY(trm::launch_tube(b->c, sa, stream));
+        HIP_TRY(launch_form(pl.form, b, b->c, sa, stream));
         b->lastSplitForm = pl.form;
         // ... and, should the pre-pass have found a track the warm-up does not cover, whole utterances (the launch below
         // returns at once otherwise)
@@ -717,12 +760,7 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
         which = TRM_KERNEL_WIDE;
     }
     b->lastKernel = pl.periods ? b->lastSplitForm : which;
-    if (which == TRM_KERNEL_OCT)
-        HIP_TRY(trm::launch_tube_oct(b->c, a, stream));
-    else if (which == TRM_KERNEL_QUAD)
-        HIP_TRY(trm::launch_tube_quad(b->c, a, stream, b->cus));
-    else
-        HIP_TRY(trm::launch_tube(b->c, a, stream));
+    HIP_TRY(launch_form(which, b, b->c, a, stream));
     if (!b->c.upsample) {
         HIP_TRY(trm::launch_downsample(b->c, down_args(b, a, b->dTubeOff.p, 0, nvoices, nullptr), stream));
     }
@@ -741,7 +779,7 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
 int trm_batch_set_kernel(trm_batch *b, int kernel)
 {
     if (!b) return fail(TRM_EINVAL, "null batch");
-    if (kernel != TRM_KERNEL_AUTO && kernel != TRM_KERNEL_WIDE && kernel != TRM_KERNEL_QUAD && kernel != TRM_KERNEL_OCT) return fail(TRM_EINVAL, "unknown kernel form %d", kernel);
+    if (int rc = check_kernel_form(kernel)) return rc;
     b->kernel = kernel;
     return TRM_OK;
 }
@@ -856,13 +894,7 @@ static int synthesize_host_impl(trm_batch *b, size_t nvoices, const float *frame
     HIP_TRY(hipMemcpyAsync(b->dOutOff.p, permuted ? pOutOff.data() : out_offset, nvoices * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b->dNFrames.p, permuted ? pNFrames.data() : nframes, nvoices * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     {
-        // what the time-split planner may know about a ragged batch: its control periods in all (the kernels' voice index
-        // runs from the longest voice down: the segments' workgroups fill up front to back)
-        uint64_t tp = 0;
-        for (size_t v = 0; v < nvoices; v++) tp += nframes[v] > 1 ? nframes[v] - 1 : 0;
-        bool desc = true;
-        for (size_t v = 1; v < nvoices && desc && !permuted; v++) desc = nframes[v] <= nframes[v - 1];
-        b->hintTotalPeriods = (permuted || desc) ? tp : 0;
+        // what the time-split planner may know about a ragged batch: every voice's length, in the kernels' voice order
         const uint32_t *order = permuted ? pNFrames.data() : nframes;
         b->hintFrames.assign(order, order + nvoices);
     }

@@ -1,5 +1,5 @@
 // trm_host.h -- what the host translation units of libtrm_hip share (private; the public interface is include/trm_c_api.h).
-//   trm_capi.cc    errors and info, trm_batch (with the time-split planner and the host entries), trm_tube and the data list,
+//   trm_capi.cc    errors and info, trm_batch (with the time-split planner of every one-shot launch and the host entries), trm_tube and the data list,
 //                  trm_multi, the uniform tracks, int16 and file entries; defines the launch set-up helpers declared here
 //   trm_stream.cc  trm_stream and trm_mixed_stream (lock-step and grouped): one chunk engine over parameter sets
 //   trm_mixed.cc   trm_mixed with its tracks, output and events-to-files entries; SetBatches and the block map
@@ -100,7 +100,6 @@ struct trm_batch {
     DevBuf<uint2> dSegMap;               // a time-split grid's launch order (trm_seg_map_kernel)
     DevBuf<uint32_t> dBlockFrames;
     uint32_t *dGate = nullptr;
-    uint64_t hintTotalPeriods = 0;       // set by the host-buffer entries (they see every voice's length) for the launch that follows
     std::vector<uint32_t> hintFrames;    // every voice's frame count in launch order (trm_batch_hint_frames / the host entries), for that launch
 };
 
@@ -135,18 +134,56 @@ trm::DownArgs down_args(const trm_batch *b, const trm::TubeArgs &a, const uint64
 trm::ScaleArgs scale_args(const trm_batch *b, const float *pcm, const uint64_t *out_offset, const uint32_t *number_samples,
                           const float *max_sample, int16_t *pcm16, int for_wav_data);
 
+// the launcher of kernel form `which` (TRM_KERNEL_OCT, _QUAD, else the one-voice-per-lane kernel) on b's device (its CU count)
+hipError_t launch_form(int which, const trm_batch *b, const trm::Const &c, const trm::TubeArgs &a, hipStream_t stream);
+
+// The pre-pass of a time-split launch (S control periods per segment, the set's warm-up W) over b's voices [lo, lo + n) of the
+// launch behind `a`, workgroups of perWg voices, wgPerSeg of them per segment; seg_phase / period_adv: the range's own rows.
+trm::PhaseArgs phase_args(const trm_batch *b, const trm::TubeArgs &a, size_t lo, size_t n, uint32_t S, uint32_t W, uint32_t wgPerSeg,
+                          uint32_t perWg, double *seg_phase, double *period_adv, uint32_t *gate);
+
+// tube samples of noise a launch of max_nframes frames of b's set needs (+ 2 ring halves of look-ahead that the kernel's LDS-DMA
+// prefetch may touch); 0 = the utterance is too long for the kernels' 32-bit sample index
+uint64_t noise_need(const trm_batch *b, uint32_t max_nframes);
+
+// the argument checks of trm_*_set_kernel and trm_*_set_time_split
+int check_kernel_form(int kernel);
+int check_time_split(int periods);
+
 // ------------------------------------------------------------------ time-split planning, stated once (trm_capi.cc)
-// What trm_batch's planner and trm_mixed's share: each fact has one definition, so the two paths cut a set's voices alike.
 // (the warm-up rules: trm_warm.h; segment boundaries and counts: trm_span.h)
 // the warm-up a plan of b uses, in control periods: its rule's for b's constants, or the caller's own; 0 = the tube never forgets
 uint32_t batch_split_warm(const trm_batch *b);
-// workgroups with work: per block (its longest voice, in control periods) the segments it reaches
-uint64_t busy_workgroups(const std::vector<uint32_t> &longest, uint32_t periods, uint32_t warm);
 // predicted ms per second of speech (19 750 tube samples) of the one-voice-per-lane kernel / of a whole-utterance launch in form `which`
 double wide_cost(const trm_batch *b, uint64_t workgroups);
 double unsplit_cost(const trm_batch *b, size_t nvoices, int which);
 // frication bandwidth (Hz) below which a warm-up of `warm` control periods of b's set is too short: the guard's floor
 float split_bw_floor(const trm_batch *b, uint32_t warm);
+
+// The planner of uniform and mixed batches alike: one segment length S for the launch, every parameter set's own warm-up.
+// A trm_batch is the one-set case.  What the callers differ in arrives as data:
+struct SplitSet { uint32_t cp, warm; uint64_t blocks64, blocks16; };    // control period, warm-up (the caller's choice, > 0), workgroups of 64 / 16 voices (0, 0: no voices)
+struct SplitBlock { uint32_t set, longest; };                            // a workgroup's set and its longest voice in control periods
+struct SplitAsk {
+    const SplitSet *sets;
+    size_t nsets, nvoices;
+    uint32_t P;                               // max_nframes - 1
+    int setting;                              // AUTO or a named S
+    int which, byName;                        // the form the launch would take whole; the form the caller named (AUTO: none)
+    bool quadOk;                              // the four-lane segment form is admissible (the caller's policy)
+    // the 64-voice and the 16-voice cut block by block where a hint told the lengths; null: every block of SplitSet's counts is P long
+    const std::vector<SplitBlock> *cut64, *cut16;
+};
+struct SplitPlan {
+    uint32_t periods = 0;                     // S; 0 = whole utterances
+    int form = TRM_KERNEL_WIDE;               // the segments' form: one voice per lane (the 64-voice cut) or four lanes per voice (the 16-voice cut)
+    uint64_t busy = 0;                        // workgroups of that cut with work
+};
+SplitPlan plan_split(const trm_batch *b0, const SplitAsk &ask);
+// per workgroup of perWg voices (build_block_map's cut) its set and its longest voice by `hint` (frames per voice, cut to
+// max_nframes), in control periods
+void hinted_blocks(const size_t *set_begin, size_t nsets, size_t perWg, const std::vector<uint32_t> &hint, uint32_t max_nframes,
+                   std::vector<SplitBlock> &blocks);
 
 // ------------------------------------------------------------------ parameter sets (trm_mixed.cc)
 // One trm_batch per parameter set -- that set's constants, derived values and down-sampling rows (the read-only device tables

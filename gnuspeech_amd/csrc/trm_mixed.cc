@@ -186,7 +186,7 @@ size_t trm_mixed_samples_for_frames(const trm_mixed *m, size_t set, size_t nfram
 int trm_mixed_set_kernel(trm_mixed *m, int kernel)
 {
     if (!m) return fail(TRM_EINVAL, "null handle");
-    if (kernel != TRM_KERNEL_AUTO && kernel != TRM_KERNEL_WIDE && kernel != TRM_KERNEL_QUAD && kernel != TRM_KERNEL_OCT) return fail(TRM_EINVAL, "unknown kernel form %d", kernel);
+    if (int rc = check_kernel_form(kernel)) return rc;
     m->kernel = kernel;
     return TRM_OK;
 }
@@ -196,7 +196,7 @@ int trm_mixed_last_kernel(const trm_mixed *m) { return m ? m->lastKernel : TRM_K
 int trm_mixed_set_time_split(trm_mixed *m, int periods)
 {
     if (!m) return fail(TRM_EINVAL, "null handle");
-    if (periods < TRM_TIME_SPLIT_AUTO) return fail(TRM_EINVAL, "time split: %d", periods);
+    if (int rc = check_time_split(periods)) return rc;
     m->splitSetting = periods;
     return TRM_OK;
 }
@@ -253,90 +253,10 @@ static int mixed_form(const trm_mixed *m, const size_t *set_begin)
     return choose_form(m->kernel, b0->envKernel, padded16, wgs8, minCP, ratioTooHigh, b0->cus, b0->wideThreshold, false);
 }
 
-// The time split of a mixed launch: one segment length S (control periods) for all sets, every set's own warm-up.  Priced with
-// trm_batch's figures (trm_host.h): a split launch lasts as long as its longest workgroup, S + W_s periods of CP_s samples,
-// at the rate its busy workgroups fill the chip; whole utterances as long as the longest voice of the slowest set.
-// `longest`: per entry of the 64-voice block map its longest voice in control periods (the hint's, else the launch's).
-// `map16`, `longest16`: the same over the 16-voice map where the four-lane segment form is admissible (mixed_split_quad_ok),
-// null otherwise.  `formOut`: the segments' form.  A split asked for by name then takes the four-lane form (the form was asked
-// for by name too: plan_time_split's rule); AUTO prices both forms for every candidate and takes the cheaper.
-static int mixed_plan_split(const trm_mixed *m, const size_t *set_begin, uint32_t max_nframes, int which, const std::vector<uint4> &map64,
-                            const std::vector<uint32_t> &longest, const std::vector<uint4> *map16, const std::vector<uint32_t> *longest16,
-                            uint32_t &periodsOut, std::vector<uint32_t> &warm, int &formOut)
-{
-    const size_t S = m->sets.size();
-    periodsOut = 0;
-    formOut = TRM_KERNEL_WIDE;
-    warm.assign(S, 0);
-    const int setting = m->splitSetting;
-    if (setting == TRM_TIME_SPLIT_OFF || max_nframes < 2) return TRM_OK;
-    const uint32_t P = max_nframes - 1;
-    const trm_batch *b0 = m->sets[0];
-    uint32_t warmMax = 0, minPeriods = 4;
-    double wholeSamples = 0.0;
-    for (size_t s = 0; s < S; s++) {
-        const trm_batch *b = m->sets[s];
-        const uint32_t CP = (uint32_t)b->c.controlPeriod;
-        warm[s] = trm::split_warm_periods(b->c, m->splitWarmup);
-        if (set_begin[s + 1] == set_begin[s]) continue;
-        if (warm[s] == 0) {
-            if (setting > 0) return fail(TRM_ERANGE, "time split: the tube of parameter set %zu never forgets (loss factor %g %%)", s, b->params.lossFactor);
-            return TRM_OK;
-        }
-        warmMax = std::max(warmMax, warm[s]);
-        minPeriods = std::max(minPeriods, (255u + CP) / CP);
-        wholeSamples = std::max(wholeSamples, (double)P * CP);
-    }
-    // the launch's longest workgroup, in tube samples, with segments of sp periods
-    auto seg_samples = [&](uint32_t sp) {
-        double x = 0.0;
-        for (size_t s = 0; s < S; s++)
-            if (set_begin[s + 1] > set_begin[s]) x = std::max(x, (double)(sp + warm[s]) * (double)m->sets[s]->c.controlPeriod);
-        return x;
-    };
-    auto busy = [&](const std::vector<uint4> &map, const std::vector<uint32_t> &lng, uint32_t sp) {
-        uint64_t n = 0;
-        for (size_t e = 0; e < map.size(); e++) n += trm::seg_count(lng[e], sp, warm[map[e].x]);
-        return n;
-    };
-    uint32_t periods = 0;
-    int form = TRM_KERNEL_WIDE;
-    if (setting > 0) {
-        periods = (uint32_t)setting;
-        if (map16) form = TRM_KERNEL_QUAD;
-    } else {
-        // AUTO: trm_batch's search (plan_time_split) with the largest warm-up in its constraints
-        const double whole = (which == TRM_KERNEL_WIDE ? wide_cost(b0, map64.size()) : unsplit_cost(b0, set_begin[S], which)) * wholeSamples / 19750.0;
-        double best = whole * 0.9;
-        minPeriods = std::max(minPeriods, (warmMax + 1) / 2);
-        for (uint32_t nseg = 2; nseg <= 4096 && P > warmMax; nseg++) {
-            const uint32_t sp = (P - warmMax + nseg - 1) / nseg;
-            if (sp < minPeriods) break;
-            const double t = 0.03 + wide_cost(b0, busy(map64, longest, sp)) * seg_samples(sp) / 19750.0;
-            if (t < best) { best = t; periods = sp; form = TRM_KERNEL_WIDE; }
-            // ... or in the four-lane form, one workgroup per CU: trm_batch's figure (plan_time_split), 3.1 ms per second of
-            // speech -- measured for uniform batches; nobody has measured it for a mixed launch
-            if (map16 && busy(*map16, *longest16, sp) <= (uint64_t)(b0->cus > 0 ? b0->cus : 256)) {
-                const double tq = 0.03 + 3.1 * seg_samples(sp) / 19750.0;
-                if (tq < best) { best = tq; periods = sp; form = TRM_KERNEL_QUAD; }
-            }
-        }
-    }
-    if (periods == 0) return TRM_OK;
-    // (no voice reaches past its set's first segment: one segment is the whole utterance)
-    bool any = false;
-    for (size_t s = 0; s < S; s++) any = any || (set_begin[s + 1] > set_begin[s] && trm::seg_count(P, periods, warm[s]) >= 2);
-    if (any) {
-        periodsOut = periods;
-        formOut = form;
-    }
-    return TRM_OK;
-}
-
 // Whether a split launch may run in the four-lane form: the caller named it (the environment alone does not: launches left on
 // AUTO keep the one-voice-per-lane segments and their bits), no set with voices demotes it (mixed_form: more than four outputs
-// per tube sample, a control period below 24 tube samples), and every set with voices up-samples -- plan_time_split's quadOk
-// for each of them.
+// per tube sample, a control period below 24 tube samples), and every set with voices up-samples -- trm_batch's rule for each
+// of them.  (With it, plan_split's named-S rule reads "admissible => four lanes": the form was named.)
 static bool mixed_split_quad_ok(const trm_mixed *m, const size_t *set_begin, int which)
 {
     if (m->kernel != TRM_KERNEL_QUAD || which != TRM_KERNEL_QUAD) return false;
@@ -370,42 +290,49 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
     for (size_t s = 0; s < S; s++) {
         if (set_begin[s + 1] == set_begin[s]) continue;
         const trm_batch *b = m->sets[s];
-        const uint64_t ntube = max_nframes > 0 ? (uint64_t)(max_nframes - 1) * (uint64_t)b->d.controlPeriod : 0;
-        if (ntube + 64 > 0x7FFFFFFFull) return fail(TRM_ERANGE, "utterance too long (parameter set %zu)", s);
-        need = std::max<uint64_t>(need, ntube + 2ull * (uint64_t)b->d.padSize + 256u);
+        const uint64_t needs = noise_need(b, max_nframes);
+        if (!needs) return fail(TRM_ERANGE, "utterance too long (parameter set %zu)", s);
+        need = std::max(need, needs);
         if (!cb || b->c.controlPeriod < cb->c.controlPeriod) cb = b;
     }
     if ((rc = ensure_noise(b0, (uint32_t)need, stream))) return rc;
     int which = mixed_form(m, set_begin);
-    // the time split: planned over the 64-voice block map (the one-voice-per-lane segments', and every split launch's
-    // whole-utterance fallback) and, where the four-lane segment form is admissible, the 16-voice map
+    // The time split: one segment length S (control periods) for all sets, every set's own warm-up by the batch's rule, planned
+    // (plan_split) over the 64-voice cut (the one-voice-per-lane segments', and every split launch's whole-utterance fallback)
+    // and, where the four-lane segment form is admissible, the 16-voice cut; block by block where a hint told the lengths.
     uint32_t split = 0;
     int segForm = TRM_KERNEL_WIDE;
-    std::vector<uint32_t> warm(S, 0), longest;
+    std::vector<uint32_t> warm(S, 0);
+    std::vector<SplitBlock> blocks;       // a split launch under a hint: per entry of the segments' map its longest voice
     const bool hinted = m->hintFrames.size() == nvoices;
     if (m->splitSetting != TRM_TIME_SPLIT_OFF && max_nframes >= 2) {
-        // per entry of a block map its longest voice in control periods: the hint's, else the launch's
-        auto longest_of = [&](const std::vector<uint4> &map, std::vector<uint32_t> &lng) {
-            lng.assign(map.size(), max_nframes - 1);
-            for (size_t e = 0; hinted && e < map.size(); e++) {
-                uint32_t nfr = 0;
-                for (uint32_t v = map[e].y; v < map[e].z; v++) nfr = std::max(nfr, std::min(m->hintFrames[v], max_nframes));
-                lng[e] = nfr > 0 ? nfr - 1 : 0;
-            }
-        };
-        std::vector<uint4> map64, map16;
-        std::vector<uint32_t> longest16;
-        build_block_map(set_begin, S, 64, map64);
-        longest_of(map64, longest);
-        const bool quadOk = mixed_split_quad_ok(m, set_begin, which);
-        if (quadOk) {
-            build_block_map(set_begin, S, 16, map16);
-            longest_of(map16, longest16);
+        std::vector<SplitSet> sets(S);
+        bool forgets = true;          // every set with voices does: else a split asked for by name fails, AUTO runs whole utterances
+        for (size_t s = 0; s < S; s++) {
+            const size_t n = set_begin[s + 1] - set_begin[s];
+            warm[s] = trm::split_warm_periods(m->sets[s]->c, m->splitWarmup);
+            sets[s] = {(uint32_t)m->sets[s]->c.controlPeriod, warm[s], (n + 63) / 64, (n + 15) / 16};
+            if (n == 0 || warm[s] != 0) continue;
+            if (m->splitSetting > 0)
+                return fail(TRM_ERANGE, "time split: the tube of parameter set %zu never forgets (loss factor %g %%)", s, m->sets[s]->params.lossFactor);
+            forgets = false;
         }
-        if ((rc = mixed_plan_split(m, set_begin, max_nframes, which, map64, longest, quadOk ? &map16 : nullptr, quadOk ? &longest16 : nullptr,
-                                   split, warm, segForm)))
-            return rc;
-        if (split && segForm == TRM_KERNEL_QUAD) longest.swap(longest16);       // (the launch order below: per entry of the segments' map)
+        if (forgets) {
+            SplitAsk ask = {sets.data(), S, nvoices, max_nframes - 1, m->splitSetting, which, m->kernel, mixed_split_quad_ok(m, set_begin, which), nullptr, nullptr};
+            std::vector<SplitBlock> blocks16;
+            if (hinted) {
+                hinted_blocks(set_begin, S, 64, m->hintFrames, max_nframes, blocks);
+                ask.cut64 = &blocks;
+                if (ask.quadOk) {
+                    hinted_blocks(set_begin, S, 16, m->hintFrames, max_nframes, blocks16);
+                    ask.cut16 = &blocks16;
+                }
+            }
+            const SplitPlan pl = plan_split(b0, ask);
+            split = pl.periods;
+            segForm = pl.form;
+            if (split && segForm == TRM_KERNEL_QUAD) blocks.swap(blocks16);       // (the launch order below: per entry of the segments' map)
+        }
     }
     m->lastSplitPeriods = split;
     m->lastWarm.assign(S, 0);
@@ -444,7 +371,7 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
                 for (uint32_t sgm = 0; sgm < nsegMax; sgm++)
                     for (size_t e = 0; e < map.size(); e++) {
                         if (sgm >= trm::seg_count(max_nframes - 1, split, map[e].w)) continue;
-                        const bool work = trm::seg_has_work(sgm, longest[e], trm::seg_first(split, map[e].w), split);
+                        const bool work = trm::seg_has_work(sgm, hinted ? blocks[e].longest : max_nframes - 1, trm::seg_first(split, map[e].w), split);
                         if (work == (pass == 0)) m->hSegMap.push_back(make_uint2(sgm, (uint32_t)e));
                     }
             m->segRows = nsegMax;
@@ -507,13 +434,8 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
             const size_t lo = set_begin[s], n = set_begin[s + 1] - lo;
             if (n == 0) continue;
             const trm_batch *b = m->sets[s];
-            trm::PhaseArgs ph;
-            ph.frames = d_frames; ph.frame_offset = d_frame_offset + lo; ph.nframes = d_nframes + lo;
-            ph.period_adv = m->dPeriodAdv.p + lo * (size_t)max_nframes; ph.seg_phase = m->dSegPhase.p + entry * perWg; ph.gate = gate;
-            ph.bw_floor = split_bw_floor(b, warm[s]);
-            ph.nvoices = (uint32_t)n; ph.max_nframes = max_nframes; ph.nseg = trm::seg_count(max_nframes - 1, split, warm[s]);
-            ph.seg_periods = split; ph.seg_warm = warm[s]; ph.seg_wg_per_seg = m->mapEntries; ph.seg_first = trm::seg_first(split, warm[s]);
-            ph.voices_per_wg = perWg;
+            const trm::PhaseArgs ph = phase_args(b, a, lo, n, split, warm[s], m->mapEntries, perWg, m->dSegPhase.p + entry * perWg,
+                                                 m->dPeriodAdv.p + lo * (size_t)max_nframes, gate);
             HIP_TRY(trm::launch_phase(b->c, ph, stream));
             entry += (n + perWg - 1) / perWg;
         }
@@ -522,20 +444,14 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
         sa.seg_phase = m->dSegPhase.p;
         sa.seg_map = m->dSegMap.p;
         sa.gate = gate; sa.gate_want = 0;
+        HIP_TRY(launch_form(segForm, b0, cb->c, sa, stream));
         if (quadSplit) {
-            HIP_TRY(trm::launch_tube_quad(cb->c, sa, stream, b0->cus));
             a.mix_map = m->dMap64.p;
             a.mix_grid = m->map64Entries;
-        } else
-            HIP_TRY(trm::launch_tube(cb->c, sa, stream));
+        }
         a.gate = gate; a.gate_want = 1;
     }
-    if (which == TRM_KERNEL_OCT)
-        HIP_TRY(trm::launch_tube_oct(cb->c, a, stream));
-    else if (which == TRM_KERNEL_QUAD)
-        HIP_TRY(trm::launch_tube_quad(cb->c, a, stream, b0->cus));
-    else
-        HIP_TRY(trm::launch_tube(cb->c, a, stream));
+    HIP_TRY(launch_form(which, b0, cb->c, a, stream));
     // the down-sampling sets: a voice range each, converted by the batch path's kernels with the set's own rows
     for (size_t s = 0; s < S; s++) {
         const size_t lo = set_begin[s], n = set_begin[s + 1] - lo;

@@ -504,8 +504,7 @@ static int stream_chunk_impl(trm_stream_engine *s, const float *d_pushed, size_t
             a.stream_k_end = (uint32_t)kEnd[0];
             b0->lastKernel = s->wide ? TRM_KERNEL_WIDE : TRM_KERNEL_QUAD;
         }
-        if (s->wide) HIP_TRY(trm::launch_tube(b0->c, a, st));
-        else HIP_TRY(trm::launch_tube_quad(b0->c, a, st, b0->cus));
+        HIP_TRY(launch_form(s->wide ? TRM_KERNEL_WIDE : TRM_KERNEL_QUAD, b0, b0->c, a, st));
         s->first = false;
         for (size_t k = 0; k < S; k++) {
             const size_t lo = s->begin[k], n = s->begin[k + 1] - lo;
@@ -809,8 +808,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     a.mix_grid = nActive;
     a.grp_clock = (decltype(a.grp_clock))s->dStep.p;
     a.grp_active = (decltype(a.grp_active))(s->dStep.p + E * 4);
-    if (s->wide) HIP_TRY(trm::launch_tube(b0->c, a, st));
-    else HIP_TRY(trm::launch_tube_quad(b0->c, a, st, b0->cus));
+    HIP_TRY(launch_form(s->wide ? TRM_KERNEL_WIDE : TRM_KERNEL_QUAD, b0, b0->c, a, st));
     if (oneLaunch) HIP_TRY(trm::grp_convert_launcher(down, st));
     for (size_t g = 0; g < G; g++) {
         const GroupPlan &p = plan[g];

@@ -1,0 +1,25 @@
+"""The time-split planner and the launch set-up of trm_batch_synthesize_device and trm_mixed_synthesize_device under
+AddressSanitizer and UBSan, on the CPU: the library's host translation units and the CPU stand-in of the HIP runtime are compiled,
+their host code instrumented by both sanitizers and no device code with either, into a stand-alone program with its own main
+(tests/_emul/split_plan_sanitize.cc), which plans and sets up a sweep of the cases of tests/test_split_plan_host.py.  The program
+is run as it is: nothing is loaded into this interpreter."""
+import os
+import subprocess
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
+HOST_UNITS = ["trm_capi", "trm_stream", "trm_mixed", "trm_setup", "trm_io"]
+
+
+def test_planner_and_launch_set_up_are_clean_under_asan_and_ubsan(tmp_path):
+    exe = str(tmp_path / "split_plan_sanitize")
+    srcs = [os.path.join(ROOT, "tests", "_emul", f) for f in ("split_plan_sanitize.cc", "hip_host_mock.cc")]
+    srcs += [os.path.join(CSRC, u + ".cc") for u in HOST_UNITS]
+    # (the sanitizers are the host compilation's alone: -Xarch_host in front of each of their options)
+    subprocess.check_call(["hipcc", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                           "-o", exe] + srcs + ["-lpthread", "-lm"])
+    env = {k: v for k, v in os.environ.items() if k not in ("TRM_QUAD_CUS", "TRM_TUBE_KERNEL", "TRM_TIME_SPLIT")}
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0 and "split_plan_sanitize: ok (instrumented)" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-4000:]
