@@ -1,7 +1,11 @@
 // trm_host.h -- what the host translation units of libtrm_hip share (private; the public interface is include/trm_c_api.h).
 //   trm_capi.cc    errors and info, trm_batch (with the time-split planner of every one-shot launch and the host entries), trm_tube and the data list,
 //                  trm_multi, the uniform tracks, int16 and file entries; defines the launch set-up helpers declared here
-//   trm_stream.cc  trm_stream and trm_mixed_stream (lock-step and grouped): one chunk engine over parameter sets
+//   trm_stream.cc  trm_stream and trm_mixed_stream, one chunk engine over parameter sets, in three files over
+//                  trm_stream_engine.h and one translation unit (this one carries the other two with an #include):
+//                  create (stream_init), the lock-step chunk, the trm_stream_* and the lock-step trm_mixed_stream_* entries
+//   trm_stream_step.cc    a grouped stream's step: the plan, the step's tables, the launches, the four step entries
+//   trm_stream_groups.cc  what a grouped stream is given between steps: event lists, bindings, parameters, the conversion path
 //   trm_mixed.cc   trm_mixed with its tracks, output and events-to-files entries; SetBatches and the block map
 #pragma once
 
@@ -49,6 +53,7 @@ struct DevBuf {
         cap = want;
         return TRM_OK;
     }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }
 };
 
 struct trm_batch {

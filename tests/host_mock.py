@@ -3,8 +3,31 @@ The stand-in records every hipMalloc / hipHostMalloc block with guard zones arou
 that leave a block, and counts each refusal as a violation; these helpers read that count, walk the guards, and give a test
 "device" memory of its own (a block of the stand-in's heap viewed as a numpy array) for the entries that take device pointers."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
+
+
+def carried_parts(csrc=CSRC):
+    """the .cc files of `csrc` that another .cc of it carries with an #include (the parts of trm_stream.cc): no units of their own"""
+    files = [f for f in os.listdir(csrc) if f.endswith(".cc")]
+    return sorted({m for f in files for m in re.findall(r'^#include "(\w+\.cc)"', open(os.path.join(csrc, f)).read(), re.M)})
+
+
+def host_units(csrc=CSRC):
+    """the library's host translation units: the .cc files of `csrc` but for carried_parts, by name without the suffix.  Read from
+    the directory, so that another commit's tree (a golden's recording) gives that commit's units."""
+    return sorted(f[:-3] for f in os.listdir(csrc) if f.endswith(".cc") and f not in carried_parts(csrc))
+
+
+def unit_dependencies(csrc=CSRC):
+    """what every unit's object may depend on besides its own .cc: the headers, the carried parts and the public header"""
+    return [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h") or f in carried_parts(csrc)] + [os.path.join(ROOT, "include", "trm_c_api.h")]
+
 
 H2D, D2H, D2D = 1, 2, 3                      # hipMemcpyKind
 EINVALID = 1                                 # hipErrorInvalidValue

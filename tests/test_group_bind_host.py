@@ -17,7 +17,7 @@ import pytest
 
 import group_bind_common as B
 import host_mock as M
-from test_group_events_host import CSRC, HOST_UNITS, ROOT
+from test_group_events_host import CSRC, ROOT
 
 MOCKS = ["hip_host_mock.cc", "hip_host_mock_events.cc", "hip_host_mock_out.cc", "hip_op_trace.cc"]
 # what hip_op_trace.cc stands in front of (-Wl,--wrap): every __wrap_<symbol> it defines, read from the file itself
@@ -29,7 +29,7 @@ P, F, I, R = B.P, B.F, B.I, B.R
 
 def build(out, csrc=CSRC):
     """the host units of `csrc` with the stand-ins and the recorder in front of them"""
-    srcs = [os.path.join(csrc, u + ".cc") for u in HOST_UNITS]
+    srcs = [os.path.join(csrc, u + ".cc") for u in M.host_units(csrc)]
     oracle = os.path.join(ROOT, "oracle")
     if not os.path.exists(os.path.join(oracle, "libtrm_oracle.so")):
         subprocess.check_call(["make", "-s", "-C", oracle, "libtrm_oracle.so"])

@@ -21,7 +21,6 @@ import host_mock as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
-HOST_UNITS = ["trm_capi", "trm_stream", "trm_mixed", "trm_setup", "trm_io"]
 MOCKS = ["hip_host_mock.cc", "hip_host_mock_events.cc", "hip_host_mock_out.cc", "hip_op_trace.cc"]
 DOWN = "hip_host_mock_down.cc"
 # what hip_op_trace.cc stands in front of (-Wl,--wrap): every __wrap_<symbol> it defines, read from the file itself
@@ -31,7 +30,7 @@ P, F, I, R = D.P, D.F, D.I, D.R
 
 def build(out, mocks):
     """the host units with the stand-ins `mocks` and the recorder in front of them"""
-    srcs = [os.path.join(CSRC, u + ".cc") for u in HOST_UNITS]
+    srcs = [os.path.join(CSRC, u + ".cc") for u in M.host_units()]
     oracle = os.path.join(ROOT, "oracle")
     if not os.path.exists(os.path.join(oracle, "libtrm_oracle.so")):
         subprocess.check_call(["make", "-s", "-C", oracle, "libtrm_oracle.so"])

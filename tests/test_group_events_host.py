@@ -17,17 +17,16 @@ import host_mock as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
-HOST_UNITS = ["trm_capi", "trm_stream", "trm_mixed", "trm_setup", "trm_io"]
 
 
 def _build(out, mocks):
-    srcs = [os.path.join(CSRC, u + ".cc") for u in HOST_UNITS]
+    srcs = [os.path.join(CSRC, u + ".cc") for u in M.host_units()]
     oracle = os.path.join(ROOT, "oracle")
     if not os.path.exists(os.path.join(oracle, "libtrm_oracle.so")):
         subprocess.check_call(["make", "-s", "-C", oracle, "libtrm_oracle.so"])
     link = ["-L" + oracle, "-l:libtrm_oracle.so", "-Wl,-rpath," + oracle] if len(mocks) > 1 else []
-    objs = [os.path.join(CSRC, "build", u + ".o") for u in HOST_UNITS]
-    hdrs = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")] + [os.path.join(ROOT, "include", "trm_c_api.h")]
+    objs = [os.path.join(CSRC, "build", u + ".o") for u in M.host_units()]
+    hdrs = M.unit_dependencies()
     fresh = all(os.path.exists(o) and all(os.path.getmtime(o) >= os.path.getmtime(d) for d in [s] + hdrs) for o, s in zip(objs, srcs))
     flags = ["-O1", "-std=c++17", "-fPIC"]
     mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in mocks]

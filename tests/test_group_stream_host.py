@@ -17,7 +17,6 @@ import test_group_stream_gpu as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
-HOST_UNITS = ["trm_capi", "trm_stream", "trm_mixed", "trm_setup", "trm_io"]
 
 
 @pytest.fixture(scope="module")
@@ -27,9 +26,9 @@ def g(tmp_path_factory):
     from gnuspeech_amd import _capi
     out = str(tmp_path_factory.mktemp("hostmock") / "libtrm_hostmock.so")
     mock = os.path.join(ROOT, "tests", "_emul", "hip_host_mock.cc")
-    objs = [os.path.join(CSRC, "build", u + ".o") for u in HOST_UNITS]
-    srcs = [os.path.join(CSRC, u + ".cc") for u in HOST_UNITS]
-    hdrs = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")] + [os.path.join(ROOT, "include", "trm_c_api.h")]
+    objs = [os.path.join(CSRC, "build", u + ".o") for u in M.host_units()]
+    srcs = [os.path.join(CSRC, u + ".cc") for u in M.host_units()]
+    hdrs = M.unit_dependencies()
     fresh = all(os.path.exists(o) and all(os.path.getmtime(o) >= os.path.getmtime(d) for d in [s] + hdrs) for o, s in zip(objs, srcs))
     flags = ["-O1", "-std=c++17", "-fPIC"]
     # (-Bsymbolic: the library's calls into the runtime bind to the stand-in, whatever else the process has loaded)

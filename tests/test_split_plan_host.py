@@ -28,7 +28,6 @@ import host_mock as M                        # noqa: E402
 import split_warmup_common as S              # noqa: E402
 
 CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
-HOST_UNITS = ["trm_capi", "trm_stream", "trm_mixed", "trm_setup", "trm_io"]
 MOCKS = ["hip_host_mock.cc", "hip_op_trace_split.cc"]
 WRAPPED = sorted(set(re.findall(r"^hipError_t __wrap_(\w+)\(", open(os.path.join(ROOT, "tests", "_emul", "hip_op_trace_split.cc")).read(), re.M)))
 assert len(WRAPPED) == 11 and any("launch_phase" in w for w in WRAPPED) and any("launch_tube_oct" in w for w in WRAPPED)
@@ -185,7 +184,7 @@ for _c in batch_cases() + mixed_cases():
 # ------------------------------------------------------------------------------------------------ the library on the stand-in
 def build(out, csrc=CSRC):
     """the host units of `csrc` with the stand-in and the recorder in front of it"""
-    srcs = [os.path.join(csrc, u + ".cc") for u in HOST_UNITS]
+    srcs = [os.path.join(csrc, u + ".cc") for u in M.host_units(csrc)]
     mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in MOCKS]
     wrap = ["-Wl,--wrap=" + w for w in WRAPPED]
     # (-Bsymbolic: the library's calls into the runtime bind to the stand-in, whatever else the process has loaded)

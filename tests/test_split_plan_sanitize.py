@@ -6,16 +6,16 @@ is run as it is: nothing is loaded into this interpreter."""
 import os
 import subprocess
 
+import host_mock as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
-HOST_UNITS = ["trm_capi", "trm_stream", "trm_mixed", "trm_setup", "trm_io"]
 
 
 def test_planner_and_launch_set_up_are_clean_under_asan_and_ubsan(tmp_path):
     exe = str(tmp_path / "split_plan_sanitize")
     srcs = [os.path.join(ROOT, "tests", "_emul", f) for f in ("split_plan_sanitize.cc", "hip_host_mock.cc")]
-    srcs += [os.path.join(CSRC, u + ".cc") for u in HOST_UNITS]
+    srcs += [os.path.join(CSRC, u + ".cc") for u in M.host_units()]
     # (the sanitizers are the host compilation's alone: -Xarch_host in front of each of their options)
     subprocess.check_call(["hipcc", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
                            "-o", exe] + srcs + ["-lpthread", "-lm"])
