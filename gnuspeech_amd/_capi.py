@@ -11,6 +11,7 @@ TRM_OK = 0
 TRM_KERNEL_AUTO, TRM_KERNEL_WIDE, TRM_KERNEL_QUAD = 0, 1, 2
 TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_FINISH, TRM_GROUP_RUN = 0, 1, 2, 3      # what a group of a grouped stream does in a step
 TRM_GROUP_CONVERT_PER_GROUP, TRM_GROUP_CONVERT_ONE_LAUNCH = 0, 1      # how a grouped stream converts its down-sampling groups
+TRM_STREAM_MODE_MIXED = -1      # trm_mixed_stream_mode of a grouped stream whose sets differ in loop order (returned only)
 TRM_SPLIT_WARMUP_DEFAULT, TRM_SPLIT_WARMUP_COUPLED = 0, -1            # the warm-up rule of a time split (a value above 0: control periods)
 (TRM_EINVAL, TRM_EINVAL_LENGTH, TRM_EFIR, TRM_ENOMEM, TRM_EHIP, TRM_ENODEVICE, TRM_EIO, TRM_EPARSE,
  TRM_ESILENT, TRM_ERANGE) = range(1, 11)
@@ -86,6 +87,7 @@ EXPORTS = [
     "trm_mixed_stream_step_int16", "trm_mixed_stream_step_device_int16",
     "trm_mixed_stream_group_bind", "trm_mixed_stream_group_bound_set", "trm_mixed_stream_set_params",
     "trm_mixed_stream_set_group_convert", "trm_mixed_stream_group_convert",
+    "trm_mixed_stream_set_mode_of", "trm_mixed_stream_mode_of", "trm_mixed_stream_set_slice", "trm_mixed_stream_slice",
 ]
 
 _lib = None
@@ -245,6 +247,11 @@ def lib():
     L.trm_mixed_stream_set_params.argtypes = [vp, C.c_size_t, C.POINTER(TrmInputParams)]
     L.trm_mixed_stream_set_group_convert.argtypes = [vp, C.c_int]
     L.trm_mixed_stream_group_convert.argtypes = [vp]
+    L.trm_mixed_stream_set_mode_of.argtypes = [vp, C.c_size_t, C.c_int]
+    L.trm_mixed_stream_mode_of.argtypes = [vp, C.c_size_t]
+    L.trm_mixed_stream_set_slice.argtypes = [vp, C.c_size_t, C.c_uint32]
+    L.trm_mixed_stream_slice.argtypes = [vp, C.c_size_t]
+    L.trm_mixed_stream_slice.restype = C.c_uint32
     for name in EXPORTS:
         getattr(L, name)
     _lib = L

@@ -96,8 +96,10 @@ struct TubeArgs {
     //                mix_grid of them (an entry that only exited would still hold its slot: trm_seg_map_kernel's note).  The
     //                one-voice-per-lane form's state block is the ENTRY's.
     //   grp_clock    per map entry {control periods before the step, control periods through its end, kStreamFirst |
-    //                kStreamFlush | kClockNoLead (trm_span.h); -}: stream_n_base, stream_k_end and the first two bits of
-    //                stream_flags of a mixed stream (kStreamTract stays the launch's stream_flags).
+    //                kStreamFlush | kClockNoLead (trm_span.h) |
+    //                kStreamTract; -}: stream_n_base, stream_k_end and stream_flags of a mixed stream.  An entry runs in TRAcT order
+    //                where its clock OR the launch's stream_flags say kStreamTract: the host sets the launch's bit where every set
+    //                has that order and the entries' bits once sets have orders of their own, so sets of either order share a launch.
     //   frames       [nvoices][max_nframes][16]: row 0 of a voice is its lead row (the frame the period before ended on), rows
     //                1 .. the pushed frames; an entry runs the rows it has periods for plus one, from row 1 where kClockNoLead says so
     //                (an utterance opening in Framework order).  frame_offset and nframes are not read.
@@ -350,6 +352,25 @@ struct GrpDownArgs {
 // (installed by trm_grp_down.hip when the library is loaded, like tracks_run_launcher; null: TRM_GROUP_CONVERT_ONE_LAUNCH is refused)
 extern hipError_t (*grp_hist_in_launcher)(const GrpDownArgs &a, hipStream_t stream);
 extern hipError_t (*grp_convert_launcher)(const GrpDownArgs &a, hipStream_t stream);
+
+// TRAcT order's x100 for a whole step of a grouped stream (trm_grp_gain.hip: trm_grp_gain_kernel), behind the tube launch and the
+// conversion of the down-sampling groups, in front of an int16 step's scaling: the rows and max_sample of the voices of every
+// TRAcT-order group that received samples, times 100.0f (launch_gain's arithmetic, one launch instead of one per group).
+//   step   the gain stretch of the step's tables: {map entry, samples per voice of its group} per listed entry, nentries of them
+// Grid (nentries, tiles): workgroup (w, t) runs the values t * kGrpGainTileValues .. of every row of entry step[2 w], on a stride of
+// the grid's y extent.  The tables are typed in the constant address space (ConstTable's reason).
+constexpr uint32_t kGrpGainTileValues = 1024;
+struct GrpGainArgs {
+    float *out;                       // the step's fp32 rows: voice v at out + v * pitch
+    uint64_t pitch;
+    float *max_sample;                // [nvoices]
+    const __attribute__((address_space(4))) uint32_t *step;
+    const __attribute__((address_space(4))) uint4 *mix_map;
+    uint32_t nentries;
+    uint32_t tiles;                   // ceil(the largest listed count / kGrpGainTileValues), at least 1 and at most 65 535
+};
+// (installed by trm_grp_gain.hip when the library is loaded, like tracks_run_launcher; null: the step gains group by group, launch_gain)
+extern hipError_t (*grp_gain_launcher)(const GrpGainArgs &a, hipStream_t stream);
 
 // Output of a mixed-parameter batch (trm_mixed_out.hip): int16 PCM or sound-file images, one workgroup per voice, each voice with
 // its own set's scaling and container.  The per-set table is built once at trm_mixed_create.

@@ -235,7 +235,11 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     // Lanes whose utterance is shorter than the group's longest keep stepping on their last frame;
     // the tube stage hands zeros to the converter past a voice's own end.
     const bool sFirst = !kStream || (streamBits & kStreamFirst), sLast = !kStream || (streamBits & kStreamFlush);
-    const bool sHold = kStream && (A.stream_flags & kStreamTract);       // TRAcT's loop order: a period runs on the frame that ends it, held
+    // TRAcT's loop order: a period runs on the frame that ends it, held (a grouped stream: the launch's where its sets share the
+    // order, else the order of the entry's set, from its clock)
+    uint32_t orderBits = A.stream_flags;
+    if constexpr (kGrp) orderBits |= streamBits;
+    const bool sHold = kStream && (orderBits & kStreamTract);
     // (segments: a workgroup's lanes either end inside the segment -- their flush follows -- or run to its end: nTotal
     // carries the flush's 2*pad samples either way, lanes that go on stop emitting at segOutEnd)
     // (a mixed stream: stream_n_base / stream_k_end count control periods, the set's tube samples and outputs follow from them)

@@ -227,7 +227,10 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     const bool sFirst = !streaming || kSeg || (streamBits & kStreamFirst), sLast = !streaming || kSeg || (streamBits & kStreamFlush);
     // TRAcT's loop (Applications/TRAcT/tube.c:1121-1136) reads the parameter set every sample and never interpolates: a
     // control period then runs on the frame that ENDS it, held (trm_stream_set_mode)
-    const bool sHold = streaming && !kSeg && (A.stream_flags & kStreamTract);
+    // (a grouped stream: the launch's where its sets share the order, else the order of the entry's set, from its clock)
+    uint32_t orderBits = A.stream_flags;
+    if constexpr (kGrp) orderBits |= streamBits;
+    const bool sHold = streaming && !kSeg && (orderBits & kStreamTract);
     // (a mixed stream: stream_n_base / stream_k_end count control periods, the set's tube samples and outputs follow from them)
     constexpr bool kMixStream = kMix && kStream && !kSeg;
     StreamRange sr = {0, 0, 0, 0};

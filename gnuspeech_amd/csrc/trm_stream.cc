@@ -56,7 +56,7 @@ static int groups_tables(trm_stream_engine *s)
     for (size_t g = 0; g < G; g++)
         for (size_t v = s->gbegin[g]; v < s->gbegin[g + 1]; v++) vg[v] = (uint32_t)g;
     int rc;
-    if ((rc = s->dVoiceGroup.reserve(V)) || (rc = s->dStep.reserve(step_words_room(s, false))) || (rc = s->dOutSets.reserve(S))) return rc;
+    if ((rc = s->dVoiceGroup.reserve(V)) || (rc = s->dStep.reserve(step_words_room(s, false, false))) || (rc = s->dOutSets.reserve(S))) return rc;
     hipError_t e = hipMemcpy(s->dVoiceGroup.p, vg.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(TRM_EHIP, "group table: %s", hipGetErrorString(e));
     std::vector<trm::GrpOutSet> os(S);
@@ -76,7 +76,9 @@ int stream_init(trm_stream_engine *s, const size_t *set_begin)
     s->begin.assign(set_begin, set_begin + S + 1);
     s->nvoices = V;
     trm_batch *b0 = s->sets[0];
-    s->controlPeriod0 = b0->c.controlPeriod;
+    s->cp0.resize(S);
+    for (size_t k = 0; k < S; k++) s->cp0[k] = s->sets[k]->c.controlPeriod;
+    if (s->grouped) s->smode.assign(S, TRM_STREAM_MODE_FRAMEWORK);
     // The form, fixed for the stream's life (choose_form).  The count held against the threshold: a trm_stream's voices as they
     // are, a trm_mixed_stream's with every set padded to a workgroup of 64.
     // A grouped stream's: with every non-empty group padded to 64.
@@ -141,8 +143,16 @@ static int stream_set_mode(trm_stream_engine *s, int mode)
     if (mode != TRM_STREAM_MODE_FRAMEWORK && mode != TRM_STREAM_MODE_TRACT) return fail(TRM_EINVAL, "unknown stream mode %d", mode);
     if (s->haveLast) return fail(TRM_EINVAL, s->grouped ? "the stream's mode can only change while every group is closed"
                                                          : "the stream's mode can only change between utterances (before the first push or after finish)");
-    if (mode == s->mode) return TRM_OK;
+    // (a grouped stream: every set takes the order, and every slice returns to its set's control period)
+    bool sliced = false;
+    for (size_t k = 0; s->grouped && k < s->sets.size(); k++) sliced = sliced || s->sets[k]->c.controlPeriod != s->cp0[k];
+    if (mode == s->mode && !sliced) return TRM_OK;
     for (trm_batch *b : s->sets.b) b->c.fricGain = mode == TRM_STREAM_MODE_TRACT ? 10.0f : 1.0f;      // Applications/TRAcT/tube.c:1371
+    for (size_t k = 0; s->grouped && k < s->sets.size(); k++) {
+        s->smode[k] = mode;
+        if (s->sets[k]->c.controlPeriod != s->cp0[k]) set_control_period(s->sets[k], (uint32_t)s->cp0[k]);
+    }
+    if (sliced) s->shapeRows = 0;
     if (s->mixed) {
         HIP_TRY(hipSetDevice(s->sets[0]->device));
         // (between utterances: the last chunk, on whichever stream, may still read the table)
@@ -238,7 +248,7 @@ static int stream_chunk_impl(trm_stream_engine *s, const float *d_pushed, size_t
         }
         HIP_TRY(launch_form(s->wide ? TRM_KERNEL_WIDE : TRM_KERNEL_QUAD, b0, b0->c, a, st));
         s->first = false;
-        if ((rc = down_convert(s, a, units, true, d_out, out_pitch, st))) return rc;
+        if ((rc = down_convert(s, a, units, true, true, d_out, out_pitch, st))) return rc;
     } else {
         HIP_TRY(hipMemsetAsync(s->dMax.p, 0, V * sizeof(float), st));
     }
@@ -312,7 +322,7 @@ int trm_stream_set_mode(trm_stream *s, int mode)
 {
     int rc = stream_set_mode(s, mode);
     if (rc) return rc;
-    if (mode != TRM_STREAM_MODE_TRACT && s->sets[0]->c.controlPeriod != s->controlPeriod0) {      // (slices are TRAcT order's)
+    if (mode != TRM_STREAM_MODE_TRACT && s->sets[0]->c.controlPeriod != s->cp0[0]) {      // (slices are TRAcT order's)
         s->mode = TRM_STREAM_MODE_TRACT;
         rc = trm_stream_set_slice(s, 0);
         s->mode = mode;
@@ -327,16 +337,9 @@ int trm_stream_set_slice(trm_stream *s, uint32_t tube_samples)
     if (!s) return fail(TRM_EINVAL, "null stream");
     if (s->mode != TRM_STREAM_MODE_TRACT) return fail(TRM_EINVAL, "a slice shorter than the control period needs held parameters: TRM_STREAM_MODE_TRACT");
     if (s->haveLast) return fail(TRM_EINVAL, "the slice length can only change between utterances (before the first push or after finish)");
-    const uint32_t cp = tube_samples ? tube_samples : (uint32_t)s->controlPeriod0;
-    if (cp < 4 || cp > 0x100000u) return fail(TRM_EINVAL, "slice of %u tube samples", tube_samples);
-    // the kernels' "control period" is the run of samples one frame row stands for; nothing else of the tube depends on it
-    // (the sample rate and everything derived from it were fixed when the batch was created).  Between utterances the count
-    // of periods is zero, so progress kept in periods survives the change.
-    trm_batch *b = s->sets[0];
-    b->c.controlPeriod = (int32_t)cp;
-    b->c.invControlPeriod = (float)(1.0 / cp);
-    b->c.invControlPeriodD = 1.0 / cp;
-    b->d.controlPeriod = (int32_t)cp;
+    uint32_t cp;
+    if (int rc = slice_period(tube_samples, s->cp0[0], &cp)) return rc;
+    set_control_period(s->sets[0], cp);      // (what a slice is: trm_stream_engine.h)
     s->shapeRows = 0;              // (the chunk shapes are in frames: re-upload the index arrays)
     return TRM_OK;
 }

@@ -23,6 +23,9 @@
 // may be given other parameters (trm_mixed_stream_set_params): both make the storage that depends on the binding current
 // themselves -- the group's map entries, the history rows, the tube-rate offsets (rebind_plan, rebind_commit) -- so a step finds
 // it as it would have after create.
+// The loop order and the slice are a set's (trm_mixed_stream_set_mode_of, trm_mixed_stream_set_slice): what they are is the set's
+// Const (controlPeriod, fricGain), a bit of every map entry's clock (kStreamTract) and the x100 behind the converter, so sets in
+// either order and of any slice run in the one tube launch; every size and rule that depends on them is taken from the group's set.
 // A grouped stream may convert its down-sampling groups in one launch (trm_mixed_stream_set_group_convert; trm_grp_down.hip):
 // the step's tables then name the groups that convert and blocks of their voices, one launch in front of the tube launch brings
 // every history in and one behind it converts and saves every history, on the same rows as the per-group path and leaving them
@@ -43,8 +46,10 @@ struct trm_stream_engine {
     std::vector<size_t> begin;               // set_begin: voices begin[s] .. begin[s + 1] - 1 are set s's
     size_t nvoices = 0;
     bool wide = false;                       // the streaming instance with one voice per lane instead of the one with four lanes per voice
+    // the loop order: a trm_stream's and a lock-step trm_mixed_stream's; a grouped stream's sets each have their own (smode) and
+    // this is the one they share, else TRM_STREAM_MODE_MIXED (shared_order)
     int mode = TRM_STREAM_MODE_FRAMEWORK;
-    int32_t controlPeriod0 = 0;              // trm_stream: the control period the parameters derive (trm_stream_set_slice(.., 0) returns to it)
+    std::vector<int32_t> cp0;                // per set: the control period its parameters derive (a slice of 0 returns to it)
     DevBuf<uint4> dMap;                      // mixed only
     uint32_t mapEntries = 0;
     // dLast: [nvoices][16], the frame the next control period starts from; dPushed / dOut: the host-buffer entries' staging
@@ -76,6 +81,10 @@ struct trm_stream_engine {
     bool grouped = false;
     std::vector<size_t> gbegin;              // group_begin: voices gbegin[g] .. gbegin[g + 1] - 1 are group g's
     std::vector<uint32_t> gset;              // the group's parameter set (an empty group: 0)
+    std::vector<int> smode;                  // per set: its loop order (trm_mixed_stream_set_mode_of); its slice is its batch's controlPeriod
+    // one of the per-set setters has been called: the step's tables have room for the gain stretch and TRAcT order's x100 is
+    // one launch per step (trm_grp_gain.hip) where the library holds the kernel
+    bool perSet = false;
     std::vector<uint32_t> gentry;            // the group's map entries are gentry[g] .. gentry[g + 1] - 1
     std::vector<uint4> hMap;                 // the block map's host copy (trm_mixed_stream_group_bind rewrites a group's entries)
     // the history rows of the groups bound to down-sampling sets lie group after group, group g's at ghistAt[g] -- at create
@@ -165,14 +174,42 @@ static inline int refuse_ungrouped(const trm_stream_engine *s, const char *more 
 static inline size_t group_voices(const trm_stream_engine *s, size_t g) { return s->gbegin[g + 1] - s->gbegin[g]; }
 // whether group g is bound to a down-sampling set and has voices: it converts in the steps in which it runs
 static inline bool group_converts(const trm_stream_engine *s, size_t g) { return group_voices(s, g) > 0 && !s->sets[s->gset[g]]->c.upsample; }
+// whether set `set` runs in TRAcT's loop order (held frames, a lead row on an opening push, x10 frication taps, x100 behind the converter)
+static inline bool set_tract(const trm_stream_engine *s, size_t set) { return (s->grouped ? s->smode[set] : s->mode) == TRM_STREAM_MODE_TRACT; }
+// the order a grouped stream's sets share, else TRM_STREAM_MODE_MIXED
+static inline int shared_order(const trm_stream_engine *s)
+{
+    for (size_t k = 1; k < s->smode.size(); k++)
+        if (s->smode[k] != s->smode[0]) return TRM_STREAM_MODE_MIXED;
+    return s->smode[0];
+}
+// A slice, stated once (trm_stream_set_slice, trm_mixed_stream_set_slice, and the orders' setters that return to the control
+// period): the kernels' "control period" is the run of samples one frame row stands for; nothing else of the tube depends on it
+// (the sample rate and everything derived from it were fixed when the batch was created).  Between utterances the count of
+// periods is zero, so progress kept in periods survives the change.  The chunk shapes are in frames: the caller invalidates
+// the shape, and a mixed stream's caller uploads the constants table.
+static inline int slice_period(uint32_t tube_samples, int32_t cp0, uint32_t *cp)
+{
+    *cp = tube_samples ? tube_samples : (uint32_t)cp0;
+    if (*cp < 4 || *cp > 0x100000u) return fail(TRM_EINVAL, "slice of %u tube samples", tube_samples);
+    return TRM_OK;
+}
+static inline void set_control_period(trm_batch *b, uint32_t cp)
+{
+    b->c.controlPeriod = (int32_t)cp;
+    b->c.invControlPeriod = (float)(1.0 / cp);
+    b->c.invControlPeriodD = 1.0 / cp;
+    b->d.controlPeriod = (int32_t)cp;
+}
 
 // ------------------------------------------------------------------ the step's tables
 // Where the stretches of a step's tables lie in dStep and in a pinned copy (words), and their total
 //   clock   uint4 per map entry (TubeArgs::grp_clock)          active  the entries that run (TubeArgs::grp_active)
 //   what    kGrp* per group (GrpPrepArgs)                      run     {voice, frames | opening} per voice whose frames are generated
 //   int16   an int16 step's part (GrpInt16Args::step)          down    the groups that convert in one launch (GrpDownArgs::step)
-struct StepLayout { size_t clock = 0, active = 0, what = 0, run = 0, int16 = 0, down = 0, words = 0; };
-static inline StepLayout step_layout(size_t E, size_t G, size_t nrun, bool int16, size_t nentries, size_t downGroups, size_t downBlocks)
+//   gain    {map entry, samples per voice} per entry of a TRAcT-order group that received samples (GrpGainArgs::step)
+struct StepLayout { size_t clock = 0, active = 0, what = 0, run = 0, int16 = 0, down = 0, gain = 0, words = 0; };
+static inline StepLayout step_layout(size_t E, size_t G, size_t nrun, bool int16, size_t nentries, size_t downGroups, size_t downBlocks, size_t gainEntries)
 {
     StepLayout l;
     l.active = l.clock + 4 * E;
@@ -180,14 +217,15 @@ static inline StepLayout step_layout(size_t E, size_t G, size_t nrun, bool int16
     l.run = l.what + G;
     l.int16 = l.run + 2 * nrun;
     l.down = l.int16 + (int16 ? 2 * G + 1 + nentries : 0);
-    l.words = l.down + trm::kGrpDownWords * downGroups + 2 * downBlocks;
+    l.gain = l.down + trm::kGrpDownWords * downGroups + 2 * downBlocks;
+    l.words = l.gain + 2 * gainEntries;
     return l;
 }
 // the words the step's tables have room for, on the device and in every pinned copy: the layout at its maxima
-static inline size_t step_words_room(const trm_stream_engine *s, bool downRoom)
+static inline size_t step_words_room(const trm_stream_engine *s, bool downRoom, bool gainRoom)
 {
     const size_t G = s->gbegin.size() - 1;
-    return step_layout(s->mapEntries, G, s->nvoices, true, s->mapEntries, downRoom ? G : 0, downRoom ? s->downBlocks : 0).words;
+    return step_layout(s->mapEntries, G, s->nvoices, true, s->mapEntries, downRoom ? G : 0, downRoom ? s->downBlocks : 0, gainRoom ? s->mapEntries : 0).words;
 }
 
 // ------------------------------------------------------------------ ranges and shapes
@@ -291,9 +329,10 @@ static inline int down_history_in(trm_stream_engine *s, const std::vector<TubeUn
 }
 
 // ... and behind the tube launch `a`: a down-sampling unit's conversion and its next history (convert: not where one launch has
-// done both for all of them), then TRAcT order's x100.  tube.c:1177 multiplies the tube-rate sample by 100 before its converter;
-// the converter is linear, so the gain is applied to what it returns (one fp32 rounding of difference).
-static inline int down_convert(trm_stream_engine *s, const trm::TubeArgs &a, const std::vector<TubeUnit> &units, bool convert, float *d_out,
+// done both for all of them), then TRAcT order's x100 (gain: not where one launch follows for all of them).  tube.c:1177 multiplies
+// the tube-rate sample by 100 before its converter; the converter is linear, so the gain is applied to what it returns (one fp32
+// rounding of difference).
+static inline int down_convert(trm_stream_engine *s, const trm::TubeArgs &a, const std::vector<TubeUnit> &units, bool convert, bool gain, float *d_out,
                                size_t out_pitch, hipStream_t st)
 {
     for (const TubeUnit &u : units) {
@@ -312,7 +351,7 @@ static inline int down_convert(trm_stream_engine *s, const trm::TubeArgs &a, con
             HIP_TRY(hipMemcpy2DAsync(s->dHist.p + u.histAt, h * sizeof(float), s->dTube.p + s->hTubeOff0[u.lo] + N, s->rowPitch[u.set] * sizeof(float),
                                      h * sizeof(float), u.n, hipMemcpyDeviceToDevice, st));
         }
-        if (s->mode == TRM_STREAM_MODE_TRACT && u.kEnd > u.kBase)
+        if (gain && set_tract(s, u.set) && u.kEnd > u.kBase)
             HIP_TRY(trm::launch_gain(d_out + u.lo * out_pitch, out_pitch, (uint32_t)(u.kEnd - u.kBase), (uint32_t)u.n, s->dMax.p + u.lo, 100.0f, st));
     }
     return TRM_OK;

@@ -1,5 +1,6 @@
 // trm_stream_groups.cc -- what a grouped trm_mixed_stream is given apart from its steps: create, event lists and their device pool,
-// last_frames, bindings and sets' parameters (RebindPlan), the conversion path, the getters (the engine: trm_stream_engine.h).
+// last_frames, bindings and sets' parameters (RebindPlan), the conversion path, loop order and slice per set, the getters (the
+// engine: trm_stream_engine.h).
 #include "trm_stream_engine.h"
 
 extern "C" {         // (the entries; what is static stays this unit's)
@@ -55,7 +56,7 @@ size_t trm_mixed_stream_group_samples_for(const trm_mixed_stream *s, size_t grou
         push = push && frames > 0;
     }
     if (!push && !flush) return 0;
-    const bool lead = s->gopen[group] || s->mode == TRM_STREAM_MODE_TRACT;
+    const bool lead = s->gopen[group] || set_tract(s, s->gset[group]);
     const trm::StreamRange r = unit_range(s->sets[s->gset[group]], s->gperiods[group], push ? frames + (lead ? 1 : 0) : 1, flush);
     return (size_t)(r.kEnd - r.kBase);
 }
@@ -328,7 +329,7 @@ int trm_mixed_stream_set_params(trm_mixed_stream *s, size_t set, const trm_input
         if (k != set) noiseRate = std::max(noiseRate, (uint32_t)s->sets[k]->d.sampleRate);
     if ((rc = ensure_noise(b0, 16u * noiseRate, b0->stream))) return rc;      // (as create: stream_init)
     trm::Const c = nb->c;
-    c.fricGain = s->mode == TRM_STREAM_MODE_TRACT ? 10.0f : 1.0f;             // (the stream's loop order: stream_set_mode)
+    c.fricGain = set_tract(s, set) ? 10.0f : 1.0f;                            // (the set keeps its loop order; its slice is the new control period)
     const trm::GrpOutSet os = grp_out_set(*params);
     const trm::GrpDownSet ds = grp_down_set(nb);
     // the device first: the set's entries of the two tables, the offsets; then the host's books
@@ -339,6 +340,7 @@ int trm_mixed_stream_set_params(trm_mixed_stream *s, size_t set, const trm_input
     if ((rc = rebind_upload(s, p))) return rc;
     if (s->downRoom) s->hDownSets[set] = ds;
     b->params = *params;
+    s->cp0[set] = c.controlPeriod;
     b->c = c;
     b->d = nb->d;
     b->dFine = nb->dFine;
@@ -364,7 +366,7 @@ int trm_mixed_stream_set_group_convert(trm_mixed_stream *s, int mode)
         DevBuf<uint32_t> step;
         DevBuf<trm::GrpDownSet> sets;
         int rc;
-        if ((rc = step.reserve(step_words_room(s, true))) || (rc = sets.reserve(S))) return rc;
+        if ((rc = step.reserve(step_words_room(s, true, s->perSet))) || (rc = sets.reserve(S))) return rc;
         std::vector<trm::GrpDownSet> h(S);
         for (size_t k = 0; k < S; k++) h[k] = grp_down_set(s->sets[k]);
         HIP_TRY(hipMemcpy(sets.p, h.data(), S * sizeof(trm::GrpDownSet), hipMemcpyHostToDevice));
@@ -381,5 +383,81 @@ int trm_mixed_stream_set_group_convert(trm_mixed_stream *s, int mode)
 }
 
 int trm_mixed_stream_group_convert(const trm_mixed_stream *s) { return s && s->grouped ? s->convert : TRM_GROUP_CONVERT_PER_GROUP; }
+
+// ------------------------------------------------------------------ grouped trm_mixed_stream: loop order and slice per set
+// what both setters refuse, before any device work: no stream, no groups, a set out of range, an open group bound to the set
+static int per_set_check(const trm_mixed_stream *s, size_t set)
+{
+    if (!s) return fail(TRM_EINVAL, "null stream");
+    if (int rc = refuse_ungrouped(s)) return rc;
+    if (set >= s->sets.size()) return fail(TRM_EINVAL, "parameter set %zu of %zu", set, s->sets.size());
+    for (size_t g = 0; g + 1 < s->gbegin.size(); g++)
+        if (s->gset[g] == set && group_voices(s, g) > 0 && s->gopen[g])
+            return fail(TRM_EINVAL, "parameter set %zu: group %zu runs an utterance with it", set, g);
+    return TRM_OK;
+}
+
+// Set `set` takes loop order `mode` and a control period of `cp` tube samples.  The first call gives the step's tables room for
+// the gain stretch (as set_group_convert gives them the converter's).  The steps so far may still read the tables, on whichever
+// HIP stream: the one wait of these entries (stream_set_mode's rule: wait for the last chunk's event, then upload).  A call that
+// fails leaves the stream as it was.
+static int per_set_commit(trm_mixed_stream *s, size_t set, int mode, uint32_t cp)
+{
+    HIP_TRY(hipSetDevice(s->sets[0]->device));
+    DevBuf<uint32_t> step;
+    if (!s->perSet)
+        if (int rc = step.reserve(step_words_room(s, s->downRoom, true))) return rc;
+    if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
+    trm_batch *b = s->sets[set];
+    const trm::Const c = b->c;
+    const int32_t dcp = b->d.controlPeriod;
+    const bool changes = mode != s->smode[set] || (int32_t)cp != c.controlPeriod;
+    if (changes) {
+        b->c.fricGain = mode == TRM_STREAM_MODE_TRACT ? 10.0f : 1.0f;      // Applications/TRAcT/tube.c:1371
+        set_control_period(b, cp);
+        if (int rc = s->sets.upload()) {
+            b->c = c; b->d.controlPeriod = dcp;
+            return rc;
+        }
+        if ((int32_t)cp != c.controlPeriod) s->shapeRows = 0;      // (tube-rate rows are sized in control periods: the next step lays them out)
+        s->smode[set] = mode;
+        s->mode = shared_order(s);
+    }
+    if (!s->perSet) {
+        s->dStep.swap(step);
+        // (the pinned copies were sized without the stretch: the next steps allocate theirs anew)
+        s->free_step_copies();
+        s->perSet = true;
+    }
+    return TRM_OK;
+}
+
+int trm_mixed_stream_set_mode_of(trm_mixed_stream *s, size_t set, int mode)
+{
+    if (int rc = per_set_check(s, set)) return rc;
+    if (mode != TRM_STREAM_MODE_FRAMEWORK && mode != TRM_STREAM_MODE_TRACT) return fail(TRM_EINVAL, "unknown stream mode %d", mode);
+    // (slices are TRAcT order's: Framework order returns to the control period, as trm_stream_set_mode does)
+    return per_set_commit(s, set, mode, (uint32_t)(mode == TRM_STREAM_MODE_TRACT ? s->sets[set]->c.controlPeriod : s->cp0[set]));
+}
+
+int trm_mixed_stream_mode_of(const trm_mixed_stream *s, size_t set)
+{
+    return s && s->grouped && set < s->sets.size() ? s->smode[set] : TRM_STREAM_MODE_FRAMEWORK;
+}
+
+int trm_mixed_stream_set_slice(trm_mixed_stream *s, size_t set, uint32_t tube_samples)
+{
+    if (int rc = per_set_check(s, set)) return rc;
+    if (!set_tract(s, set))
+        return fail(TRM_EINVAL, "parameter set %zu: a slice shorter than the control period needs held parameters: TRM_STREAM_MODE_TRACT", set);
+    uint32_t cp;
+    if (int rc = slice_period(tube_samples, s->cp0[set], &cp)) return rc;
+    return per_set_commit(s, set, TRM_STREAM_MODE_TRACT, cp);
+}
+
+uint32_t trm_mixed_stream_slice(const trm_mixed_stream *s, size_t set)
+{
+    return s && s->grouped && set < s->sets.size() ? (uint32_t)s->sets[set]->c.controlPeriod : 0u;
+}
 
 }  // extern "C"

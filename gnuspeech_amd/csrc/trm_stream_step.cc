@@ -7,6 +7,7 @@ hipError_t (*tracks_run_launcher)(const TrackRunArgs &a, hipStream_t stream) = n
 hipError_t (*grp_int16_launcher)(const GrpInt16Args &a, hipStream_t stream) = nullptr;        // (trm_kernels.h; set by trm_grp_out.hip)
 hipError_t (*grp_hist_in_launcher)(const GrpDownArgs &a, hipStream_t stream) = nullptr;       // (trm_kernels.h; both set by trm_grp_down.hip)
 hipError_t (*grp_convert_launcher)(const GrpDownArgs &a, hipStream_t stream) = nullptr;
+hipError_t (*grp_gain_launcher)(const GrpGainArgs &a, hipStream_t stream) = nullptr;          // (trm_kernels.h; set by trm_grp_gain.hip)
 }
 
 // ------------------------------------------------------------------ grouped streams: a step
@@ -37,7 +38,6 @@ void run_means(const trm_stream_engine *s, size_t g, size_t nframes, bool *push,
 static int step_plan(const trm_stream_engine *s, const uint8_t *action, const float *frames, size_t nframes, std::vector<GroupPlan> &plan)
 {
     const size_t G = s->gbegin.size() - 1;
-    const bool tract = s->mode == TRM_STREAM_MODE_TRACT;
     plan.assign(G, GroupPlan());
     bool anyRun = false, anyPushed = false;
     for (size_t g = 0; g < G; g++) {
@@ -53,6 +53,10 @@ static int step_plan(const trm_stream_engine *s, const uint8_t *action, const fl
             return fail(TRM_EINVAL, "group %zu pushes, but it has event lists that have not run to their end (TRM_GROUP_RUN, or TRM_GROUP_FINISH to drop them)", g);
         if (action[g] == TRM_GROUP_RUN) {
             if (ev == trm_stream_engine::kEvNone) return fail(TRM_EINVAL, "group %zu runs, but it never had event lists (trm_mixed_stream_group_set_events)", g);
+            // (the generator's frames are 4 ms apart: a slice would replay them at another speed)
+            if (s->sets[s->gset[g]]->c.controlPeriod != s->cp0[s->gset[g]])
+                return fail(TRM_EINVAL, "group %zu runs, but its set %u has a slice of %d tube samples, not its control period (trm_mixed_stream_set_slice)", g,
+                            s->gset[g], s->sets[s->gset[g]]->c.controlPeriod);
             if (ev == trm_stream_engine::kEvConsumed && s->gopen[g])
                 return fail(TRM_EINVAL, "group %zu runs, but its utterance was opened by pushed frames", g);
             run_means(s, g, nframes, &p.push, &p.flush, &p.frames);
@@ -65,8 +69,8 @@ static int step_plan(const trm_stream_engine *s, const uint8_t *action, const fl
         if (p.push && nframes == 0) return fail(TRM_EINVAL, "group %zu pushes, but the step has no frames", g);
         anyPushed = anyPushed || (p.push && !p.gen);
         if (!p.push && !p.flush) continue;
-        // (as stream_chunk_impl: TRAcT order's first period runs on row 1, so an opening push has a lead row too)
-        p.lead = p.push && (s->gopen[g] || tract);
+        // (as stream_chunk_impl: TRAcT order's first period runs on row 1, so an opening push has a lead row too; the order is the set's)
+        p.lead = p.push && (s->gopen[g] || set_tract(s, s->gset[g]));
         const uint64_t rows = p.push ? p.frames + (p.lead ? 1 : 0) : 1;
         p.Q = rows - 1;
         p.runs = p.Q > 0 || p.flush;
@@ -124,9 +128,12 @@ struct StepInt16 {
 // whether group g synthesizes in the step and down-samples (its voices pass the converter), and whether its voices receive samples
 static bool runs_and_converts(const trm_stream_engine *s, const std::vector<GroupPlan> &plan, size_t g) { return plan[g].runs && group_converts(s, g); }
 static bool receives(const trm_stream_engine *s, const GroupPlan &p, size_t g) { return p.runs && p.kEnd > p.kBase && group_voices(s, g) > 0; }
+// whether TRAcT order's x100 is one launch for the step: the stream's sets have orders of their own and the library holds the kernel
+static bool gain_one_launch(const trm_stream_engine *s) { return s->perSet && trm::grp_gain_launcher; }
 
 // what step_tables wrote: where, its counts, and the one-launch converter's arguments that are not pointers
-struct StepTables { StepLayout at; uint32_t nActive = 0, nRun = 0, nInt16 = 0, maxOut = 0; trm::GrpDownArgs down{}; };
+// (nGain / gainMax: the entries of the gain stretch and the largest count among them)
+struct StepTables { StepLayout at; uint32_t nActive = 0, nRun = 0, nInt16 = 0, maxOut = 0, nGain = 0, gainMax = 0; trm::GrpDownArgs down{}; };
 
 // the groups that convert in one launch: [their words | {group of the stretch, first voice} per block of their voices]
 static void tables_down(const trm_stream_engine *s, const std::vector<GroupPlan> &plan, size_t ngroups, uint32_t *h, StepTables &t)
@@ -166,22 +173,27 @@ static void tables_down(const trm_stream_engine *s, const std::vector<GroupPlan>
 static StepTables step_tables(const trm_stream_engine *s, const std::vector<GroupPlan> &plan, const StepInt16 *o16, bool oneLaunch, uint32_t *h)
 {
     const size_t G = plan.size();
-    size_t nrun = 0, nentries = 0, ngroups = 0, nblocks = 0;
+    size_t nrun = 0, nentries = 0, ngroups = 0, nblocks = 0, ngain = 0;
+    const bool gains = gain_one_launch(s);
     for (size_t g = 0; g < G; g++) {
         nrun += plan[g].gen ? group_voices(s, g) : 0;
         nentries += o16 && receives(s, plan[g], g) ? s->gentry[g + 1] - s->gentry[g] : 0;
+        ngain += gains && set_tract(s, s->gset[g]) && receives(s, plan[g], g) ? s->gentry[g + 1] - s->gentry[g] : 0;
         if (!oneLaunch || !runs_and_converts(s, plan, g)) continue;
         ngroups++;
         nblocks += (group_voices(s, g) + trm::kGrpDownVoices - 1) / trm::kGrpDownVoices;
     }
     StepTables t;
-    t.at = step_layout(s->mapEntries, G, nrun, o16 != nullptr, nentries, ngroups, nblocks);
+    t.at = step_layout(s->mapEntries, G, nrun, o16 != nullptr, nentries, ngroups, nblocks, ngain);
     memset(h, 0, t.at.int16 * sizeof(uint32_t));
     uint32_t *clock = h + t.at.clock, *active = h + t.at.active, *what = h + t.at.what, *run = h + t.at.run;
     // an int16 step: [level bits | samples per voice | for_wav_data | the entries that receive samples] (a group that receives nothing: 0, 0)
     uint32_t *lev = h + t.at.int16, *cnt = lev + G, *ent = cnt + G + 1;
+    uint32_t *gain = h + t.at.gain;          // {entry, samples per voice} per entry of a TRAcT-order group that received samples
     for (size_t g = 0; g < G; g++) {
         const GroupPlan &p = plan[g];
+        const bool tract = set_tract(s, s->gset[g]), gained = gains && tract && receives(s, p, g);
+        if (gained) t.gainMax = std::max(t.gainMax, (uint32_t)(p.kEnd - p.kBase));
         // (the rows of a group that generates its frames are the track kernel's: the prep kernel only clears its maxima)
         const bool pushed = p.push && !p.gen;
         what[g] = (pushed ? trm::kGrpPush : 0u) | (p.flush ? trm::kGrpFinish : 0u) | (pushed && !s->gopen[g] ? trm::kGrpOpening : 0u) |
@@ -198,8 +210,10 @@ static StepTables step_tables(const trm_stream_engine *s, const std::vector<Grou
         for (uint32_t e = s->gentry[g]; p.runs && e < s->gentry[g + 1]; e++) {
             clock[4 * e] = (uint32_t)s->gperiods[g];
             clock[4 * e + 1] = (uint32_t)(s->gperiods[g] + p.Q);
-            clock[4 * e + 2] = (s->gfirst[g] ? trm::kStreamFirst : 0u) | (p.flush ? trm::kStreamFlush : 0u) | (p.push && !p.lead ? trm::kClockNoLead : 0u);
+            clock[4 * e + 2] = (s->gfirst[g] ? trm::kStreamFirst : 0u) | (p.flush ? trm::kStreamFlush : 0u) | (p.push && !p.lead ? trm::kClockNoLead : 0u) |
+                               (s->perSet && tract ? trm::kStreamTract : 0u);      // (a stream whose sets have no orders of their own: the launch's flag)
             active[t.nActive++] = e;
+            if (gained) { gain[2 * t.nGain] = e; gain[2 * t.nGain++ + 1] = (uint32_t)(p.kEnd - p.kBase); }
             if (o16 && receives(s, p, g)) ent[t.nInt16++] = e;
         }
     }
@@ -232,7 +246,9 @@ static int step_synthesize(trm_stream_engine *s, const StepTables &t, const std:
         a.tube_offset = s->dTubeOff.p;
     }
     a.stream_state = s->dState.p;
-    a.stream_flags = s->mode == TRM_STREAM_MODE_TRACT ? trm::kStreamTract : 0u;        // (first chunk and flush: per entry, in the clock)
+    // (first chunk and flush: per entry, in the clock; so is the order once sets have orders of their own, and the one they all
+    // share stays stated here)
+    a.stream_flags = s->mode == TRM_STREAM_MODE_TRACT ? trm::kStreamTract : 0u;
     a.mix_map = s->dMap.p;
     a.set_const = (trm::ConstTable)s->sets.dConst;
     a.mix_grid = t.nActive;
@@ -240,7 +256,16 @@ static int step_synthesize(trm_stream_engine *s, const StepTables &t, const std:
     a.grp_active = (decltype(a.grp_active))(s->dStep.p + t.at.active);
     HIP_TRY(launch_form(s->wide ? TRM_KERNEL_WIDE : TRM_KERNEL_QUAD, b0, b0->c, a, st));
     if (oneLaunch) HIP_TRY(trm::grp_convert_launcher(down, st));
-    return down_convert(s, a, units, !oneLaunch, d_out, out_pitch, st);
+    const bool gains = gain_one_launch(s);
+    if ((rc = down_convert(s, a, units, !oneLaunch, !gains, d_out, out_pitch, st))) return rc;
+    if (gains && t.nGain > 0) {
+        // TRAcT order's x100 for every group that received samples, behind the conversion of the down-sampling ones
+        typedef const __attribute__((address_space(4))) uint32_t *Words;
+        const trm::GrpGainArgs g{d_out, out_pitch, s->dMax.p, (Words)(s->dStep.p + t.at.gain), (const __attribute__((address_space(4))) uint4 *)s->dMap.p, t.nGain,
+                                 (uint32_t)std::min<uint64_t>(((uint64_t)t.gainMax + trm::kGrpGainTileValues - 1) / trm::kGrpGainTileValues, 65535u)};
+        HIP_TRY(trm::grp_gain_launcher(g, st));
+    }
+    return TRM_OK;
 }
 
 // One step on the device (plan: step_plan's): the tables of the step, the frame rows, ONE tube launch over the map entries of the
@@ -270,7 +295,7 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     if ((rc = s->dFrames.reserve(V * rows * 16))) return rc;
     if ((rc = stream_shape(s, rows, out_pitch, rows - 1, s->anyDown, st))) return rc;
     uint32_t *h = nullptr;
-    if ((rc = step_copy(s, step_words_room(s, s->downRoom), &h))) return rc;
+    if ((rc = step_copy(s, step_words_room(s, s->downRoom, s->perSet), &h))) return rc;
     const bool oneLaunch = s->convert == TRM_GROUP_CONVERT_ONE_LAUNCH && downRuns;
     const StepTables t = step_tables(s, plan, o16, oneLaunch, h);
     if (t.down.tiles >= 65535u) return fail(TRM_ERANGE, "%u outputs per voice in one step: too many for the one-launch converter", t.maxOut);

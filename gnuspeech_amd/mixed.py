@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import TRM_GROUP_CONVERT_ONE_LAUNCH, TRM_GROUP_CONVERT_PER_GROUP, TRM_GROUP_FINISH, TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_RUN, TrmDerived, TrmInputParams, TrmIntonation, check, lib, split_warmup_code, split_warmup_name
+from ._capi import TRM_GROUP_CONVERT_ONE_LAUNCH, TRM_GROUP_CONVERT_PER_GROUP, TRM_GROUP_FINISH, TRM_GROUP_IDLE, TRM_GROUP_PUSH, TRM_GROUP_RUN, TRM_STREAM_MODE_MIXED, TrmDerived, TrmInputParams, TrmIntonation, check, lib, split_warmup_code, split_warmup_name
 
 _KERNELS = {"auto": 0, "wide": 1, "quad": 2, "oct": 3}
 
@@ -633,7 +633,32 @@ class TRMGroupedStream:
 
     @property
     def mode(self):
-        return {0: "framework", 1: "tract"}[lib().trm_mixed_stream_mode(self._h)]
+        """The loop order the sets share, or "mixed" where they differ (set_mode_of)."""
+        return {0: "framework", 1: "tract", TRM_STREAM_MODE_MIXED: "mixed"}[lib().trm_mixed_stream_mode(self._h)]
+
+    # -------------------------------------------------------------- loop order and slice per set
+    def set_mode_of(self, set, mode):
+        """Gives parameter set `set` the loop order "framework" or "tract" (include/trm_c_api.h: trm_mixed_stream_set_mode_of):
+        its groups' voices are then those of a TRMStream in that order.  Allowed while no group bound to the set is open; groups of
+        other sets, mid-utterance or not, keep their bits.  "framework" returns the set's slice to its control period.  May wait
+        for the device once."""
+        from .stream import MODES
+        if mode not in MODES:
+            raise ValueError("unknown stream mode %r" % (mode,))
+        check(lib().trm_mixed_stream_set_mode_of(self._h, int(set), MODES[mode]))
+
+    def mode_of(self, set):
+        """The loop order of parameter set `set`: "framework" or "tract"."""
+        return {0: "framework", 1: "tract"}[lib().trm_mixed_stream_mode_of(self._h, self._set(set))]
+
+    def set_slice(self, set, tube_samples):
+        """A set in "tract" order only: the tube samples one pushed frame stands for, 4 .. 0x100000 (0 = the set's control
+        period), as TRMStream.set_slice; see trm_mixed_stream_set_slice.  Allowed while no group bound to the set is open."""
+        check(lib().trm_mixed_stream_set_slice(self._h, int(set), int(tube_samples)))
+
+    def slice(self, set):
+        """The tube samples one pushed frame of parameter set `set` stands for."""
+        return lib().trm_mixed_stream_slice(self._h, self._set(set))
 
     _CONVERT = {"per_group": TRM_GROUP_CONVERT_PER_GROUP, "one_launch": TRM_GROUP_CONVERT_ONE_LAUNCH}
 

@@ -614,7 +614,9 @@ int    trm_mixed_events_to_files_host(trm_mixed *m, const size_t *set_begin, con
  *   - Form, fixed at create (trm_mixed_stream_kernel): one voice per lane when the voices, every set padded to 64, fill the
  *     chip, or when a non-empty set makes more than four outputs per tube sample; four lanes per voice otherwise.
  *     TRM_TUBE_KERNEL=wide|quad overrides, with the same demotion.
- *   - trm_mixed_stream_set_mode applies to every set, between utterances only.  Slices (trm_stream_set_slice) are not offered.
+ *   - trm_mixed_stream_set_mode gives every set the same loop order, between utterances only.  A lock-step stream's sets share
+ *     one order and have no slices; the sets of a grouped stream have orders and slices of their own (trm_mixed_stream_set_mode_of,
+ *     trm_mixed_stream_set_slice, below).
  *   - As for trm_stream: chunks are ordered across HIP streams by an event, and the device entries make the host wait only
  *     when the chunk's shape (frames per push, out_pitch) changes or the noise sequence has to grow.
  * frames: fp32 [nvoices][nframes][16]; out: fp32 [nvoices][out_pitch], out_pitch >= the largest count of a set with voices
@@ -625,7 +627,7 @@ int    trm_mixed_stream_create(const trm_input_params *params, size_t nsets, con
                                trm_mixed_stream **out);
 void   trm_mixed_stream_destroy(trm_mixed_stream *s);
 int    trm_mixed_stream_set_mode(trm_mixed_stream *s, int mode);      /* TRM_STREAM_MODE_*, every set; between utterances only */
-int    trm_mixed_stream_mode(const trm_mixed_stream *s);
+int    trm_mixed_stream_mode(const trm_mixed_stream *s);              /* the order the sets share, else TRM_STREAM_MODE_MIXED */
 int    trm_mixed_stream_kernel(const trm_mixed_stream *s);            /* TRM_KERNEL_WIDE or TRM_KERNEL_QUAD, fixed at create */
 size_t trm_mixed_stream_samples_for_push(const trm_mixed_stream *s, size_t set, size_t nframes);
 size_t trm_mixed_stream_samples_for_finish(const trm_mixed_stream *s, size_t set);
@@ -659,7 +661,8 @@ int    trm_mixed_stream_finish_device(trm_mixed_stream *s, float *d_out, size_t 
  *   - The limit on a stream's length (TRM_ERANGE: 2^31 tube samples) applies to a group's open utterance, not to the stream.
  *   - trm_mixed_stream_push / _finish (and their device forms) refuse a grouped stream, the step entries a stream without groups
  *     (TRM_EINVAL); trm_mixed_stream_samples_for_push / _finish return 0 for a grouped stream.  trm_mixed_stream_set_mode is
- *     allowed while every group is closed.
+ *     allowed while every group is closed and sets every set's order (and returns every slice to the control period); one
+ *     set's order and slice change while only ITS groups are closed: "Loop order and slice per set", below.
  *   - Form, fixed at create: as trm_mixed_stream's, the voices counted with every non-empty group padded to 64.
  *   - The device entry makes the host wait only when the step's shape (nframes, out_pitch) changes or the noise sequence has to
  *     grow, whatever the actions; a step without frames keeps the shape it finds.  Steps are ordered across HIP streams like chunks. */
@@ -772,7 +775,8 @@ int    trm_mixed_stream_step_device_int16(trm_mixed_stream *s, const uint8_t *ac
  *   - set_params replaces set `set`'s parameters while no group bound to it is open (TRM_EINVAL otherwise; closed groups bound to
  *     it run the new parameters from their next utterance).  The parameters are checked as trm_mixed_stream_create checks a
  *     set, with the same codes and trm_last_error naming the set; TRM_ERANGE also where groups with voices are bound to the set
- *     and the stream's form cannot run the new parameters.  The new constants take the stream's current loop order.
+ *     and the stream's form cannot run the new parameters.  The set keeps its loop order (trm_mixed_stream_set_mode_of); its
+ *     slice returns to the new parameters' control period.
  *   - trm_mixed_stream_group_bound_set: the set a group is bound to (0 for a stream without groups or a group out of range).
  *   - Both calls may wait for the device once, as trm_mixed_stream_group_set_events does; the step entries gain no host wait and
  *     no launch: history rows, tube-rate rows of the shape the steps have, and their offsets are made current by the call.
@@ -795,7 +799,8 @@ int    trm_mixed_stream_set_params(trm_mixed_stream *s, size_t set, const trm_in
  *     what a trm_stream per group returns (the rules above).  Both paths keep the same history rows and tube-rate rows and leave
  *     them in the same state, so the call is allowed between any two steps, mid-utterance included, and changes no sample.
  *   - The mode is the stream's; every step entry takes it into account (step, step_device, step_int16, step_device_int16), and
- *     group_bind and set_params keep what it needs current.  TRAcT order's x100 stays a launch per group in both modes.
+ *     group_bind and set_params keep what it needs current.  TRAcT order's x100 stays a launch per group in both modes, unless
+ *     the stream's sets have been given orders of their own (below): then it is one launch per step.
  *   - set_group_convert refuses a stream without groups and an unknown mode (TRM_EINVAL).  A library built without the kernels
  *     (the host units alone) refuses ONE_LAUNCH with TRM_EHIP; all else works there.  group_convert returns the mode
  *     (PER_GROUP for a stream without groups).
@@ -807,6 +812,42 @@ int    trm_mixed_stream_set_params(trm_mixed_stream *s, size_t set, const trm_in
 enum trm_group_convert { TRM_GROUP_CONVERT_PER_GROUP = 0, TRM_GROUP_CONVERT_ONE_LAUNCH = 1 };      /* (an enum of its own, apart from the actions') */
 int    trm_mixed_stream_set_group_convert(trm_mixed_stream *s, int mode);
 int    trm_mixed_stream_group_convert(const trm_mixed_stream *s);
+
+/* Loop order and slice per set.  In a grouped stream the loop order (TRM_STREAM_MODE_*) and the slice (trm_stream_set_slice) belong
+ * to a parameter SET, so interactive tubes -- TRAcT order, a slice of a millisecond -- run in the same launch as sentence voices
+ * in Framework order, and sessions on different tubes beside each other.
+ *   - THE RULE.  Every voice's samples, counts and maxima are bit for bit those of a trm_stream of its group alone, in the same
+ *     kernel form, for the same pushes and finishes, where that trm_stream is created with the group's set's parameters, put in
+ *     that set's order (trm_stream_set_mode) and given that set's slice (trm_stream_set_slice).  A group bound to another set
+ *     (trm_mixed_stream_group_bind) takes that set's order and slice with its next utterance.  Counts and sizes follow the set:
+ *     trm_mixed_stream_group_samples_for, the lead row of an opening push, out_pitch's minimum.
+ *   - set_mode_of / set_slice are allowed whenever no group bound to `set` is open -- trm_mixed_stream_set_params' rule; they may
+ *     wait for the device once, a step never waits for it (the step behind a changed slice re-uploads the index arrays and, for
+ *     a down-sampling set, lays the tube-rate rows out again, as the step behind a change of shape does; the stream's
+ *     earlier steps have completed by then).  Groups of other sets that are mid-utterance are not disturbed by a bit.
+ *   - set_slice: tube_samples = the tube samples one pushed frame stands for, 4 .. 0x100000, or 0 for the set's control period
+ *     (trm_stream_set_slice's limits), on a set in TRAcT order; anything else: TRM_EINVAL.  Setting a set back to Framework order
+ *     returns its slice to the control period, as trm_stream_set_mode does.  trm_mixed_stream_set_params keeps the set's order
+ *     and returns its slice to the new parameters' control period.  trm_mixed_stream_set_mode (every set, every group closed)
+ *     also returns every slice to the control period.
+ *   - trm_mixed_stream_mode returns the order the sets share, else TRM_STREAM_MODE_MIXED (returned only, never accepted).
+ *     mode_of: the set's order (TRM_STREAM_MODE_FRAMEWORK for what has none); slice: its slice in tube samples (0 likewise).
+ *   - TRM_GROUP_RUN on a group whose set has a slice other than its control period is refused (TRM_EINVAL, before any device
+ *     work): the track generator makes frames 4 ms apart, and a slice would replay them at another speed.
+ *   - All four calls refuse a stream without groups, a set out of range and an unknown mode (TRM_EINVAL); every refusal comes
+ *     before any device work and leaves the stream as it was.
+ *   - TRAcT order's x100 is one launch per step for all TRAcT-order groups on a stream on which set_mode_of or set_slice has been
+ *     called (a library built without that kernel keeps one launch per group; the bits are the same).  The first such call
+ *     grows the step's tables by the stretch that lists those groups' map entries, as the first
+ *     trm_mixed_stream_set_group_convert(ONE_LAUNCH) does.  A stream on which neither is called enqueues exactly what it did
+ *     without them.
+ *   - NOT OFFERED.  All pushing groups of a step still push the same number of frames: a session with 1 ms slices steps more
+ *     often than the sentence groups need, and those sit idle (TRM_GROUP_IDLE) in the steps between. */
+enum { TRM_STREAM_MODE_MIXED = -1 };      /* returned only: the sets' orders differ */
+int      trm_mixed_stream_set_mode_of(trm_mixed_stream *s, size_t set, int mode);
+int      trm_mixed_stream_mode_of(const trm_mixed_stream *s, size_t set);
+int      trm_mixed_stream_set_slice(trm_mixed_stream *s, size_t set, uint32_t tube_samples);   /* 0: the set's control period */
+uint32_t trm_mixed_stream_slice(const trm_mixed_stream *s, size_t set);
 
 /* Library / device identification. */
 int  trm_device_count(void);
