@@ -215,6 +215,72 @@ int check_time_split(int periods)
     return TRM_OK;
 }
 
+// ------------------------------------------------------------------ host staging (trm_host.h)
+int HostStaging::reserve(size_t frameFloats, size_t outFloats, size_t nvoices)
+{
+    int rc;
+    if ((rc = dFrames.reserve(frameFloats)) || (rc = dOut.reserve(outFloats)) || (rc = dFrameOff.reserve(nvoices)) || (rc = dOutOff.reserve(nvoices)) ||
+        (rc = dNFrames.reserve(nvoices)) || (rc = dNSamples.reserve(nvoices)) || (rc = dMax.reserve(nvoices)))
+        return rc;
+    return TRM_OK;
+}
+
+int copy_back(void *host, const void *dev, size_t elem, const std::vector<HostSpan> &spans, bool dense, hipStream_t st)
+{
+    HostSpan all = {~0ull, 0, 0};         // dense: from the lowest span that has something, the sum of all
+    for (const HostSpan &s : spans) {
+        if (!s.count) continue;
+        if (!dense) HIP_TRY(hipMemcpyAsync((char *)host + s.host * elem, (const char *)dev + s.dev * elem, s.count * elem, hipMemcpyDeviceToHost, st));
+        if (s.host < all.host) { all.host = s.host; all.dev = s.dev; }
+        all.count += s.count;
+    }
+    if (dense && all.count) HIP_TRY(hipMemcpyAsync((char *)host + all.host * elem, (const char *)dev + all.dev * elem, all.count * elem, hipMemcpyDeviceToHost, st));
+    return TRM_OK;
+}
+
+HostCall::HostCall(size_t nvoices, const size_t *set_begin, size_t nsets, const uint32_t *nframes, bool batchRule) : V(nvoices)
+{
+    if (batchRule) {
+        bool sorted = true;
+        for (size_t v = 1; v < V && sorted; v++) sorted = nframes[v] <= nframes[v - 1];
+        if (sorted || V <= 16) return;
+    }
+    perm.resize(V);
+    for (size_t v = 0; v < V; v++) perm[v] = (uint32_t)v;
+    for (size_t s = 0; s < nsets; s++)
+        std::stable_sort(perm.begin() + set_begin[s], perm.begin() + set_begin[s + 1], [&](uint32_t x, uint32_t y) { return nframes[x] > nframes[y]; });
+}
+
+int HostCall::upload(HostStaging &d, const float *frames, uint64_t frameRows, const uint64_t *frame_offset, const uint64_t *out_offset,
+                     const uint32_t *nframes, std::vector<uint32_t> &hint, hipStream_t st)
+{
+    const uint32_t *launchFrames = in_launch_order(nframes);
+    HIP_TRY(hipMemcpyAsync(d.dFrames.p, frames, frameRows * 16 * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.dFrameOff.p, in_launch_order(frame_offset), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.dOutOff.p, in_launch_order(out_offset), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.dNFrames.p, launchFrames, V * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    hint.assign(launchFrames, launchFrames + V);
+    return TRM_OK;
+}
+
+int HostCall::results(HostStaging &d, hipStream_t st, uint32_t *number_samples, float *max_sample, const uint32_t *wantFrames)
+{
+    const bool direct = perm.empty();
+    uint32_t *nf = wantFrames ? keep<uint32_t>() : nullptr, *ns = direct ? number_samples : keep<uint32_t>();
+    float *mx = direct ? max_sample : keep<float>();
+    if (nf) HIP_TRY(hipMemcpyAsync(nf, d.dNFrames.p, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ns, d.dNSamples.p, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(mx, d.dMax.p, V * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t i = 0; i < V; i++) {
+        const uint32_t v = caller(i);
+        if (nf && nf[i] != wantFrames[v]) return fail(TRM_EHIP, "generator wrote %u frames for voice %u, %u expected", nf[i], v, wantFrames[v]);
+        number_samples[v] = ns[i];
+        max_sample[v] = mx[i];
+    }
+    return TRM_OK;
+}
+
 struct trm_tube {
     trm_batch *b = nullptr;
     std::vector<float> samples;
@@ -581,16 +647,6 @@ SplitPlan plan_split(const trm_batch *b0, const SplitAsk &ask)
 
 }  // extern "C++"
 
-// A hint holds for the one launch that follows it, whether that launch runs or fails: an entry drops it on every return
-// (a hint left by a failed call would plan the next launch by lengths that are not its own)
-struct HintDrop {
-    trm_batch *b;
-    ~HintDrop()
-    {
-        b->hintFrames.clear();
-    }
-};
-
 int trm_batch_hint_frames(trm_batch *b, const uint32_t *nframes, size_t nvoices)
 {
     if (!b) return fail(TRM_EINVAL, "null batch");
@@ -649,7 +705,7 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
                                 void *stream_)
 {
     if (!b) return fail(TRM_EINVAL, "null batch");
-    const HintDrop hintDrop{b};
+    const HintDrop hintDrop{b->hintFrames};
     if (nvoices == 0) return TRM_OK;
     if (!d_frames || !d_frame_offset || !d_nframes || !d_out || !d_out_offset || !d_number_samples || !d_max_sample)
         return fail(TRM_EINVAL, "null device pointer");
@@ -828,120 +884,58 @@ int trm_batch_noise_table(trm_batch *b, float *host_out, size_t n)
     return TRM_OK;
 }
 
-// host-buffer entry: fp32 PCM (out) or the containers' int16 (out16, mono or interleaved stereo), not both
-static int synthesize_host_impl(trm_batch *b, size_t nvoices, const float *frames, const uint64_t *frame_offset,
-                                const uint32_t *nframes, float *out, int16_t *out16, int for_wav_data,
-                                const uint64_t *out_offset, uint32_t *number_samples, float *max_sample)
+// host-buffer entry: fp32 PCM (out) or the containers' int16 (out16, mono or interleaved stereo), not both (trm_host.h: host staging)
+static int synthesize_host_impl(trm_batch *b, size_t nvoices, const float *frames, const uint64_t *frame_offset, const uint32_t *nframes, float *out,
+                                int16_t *out16, int for_wav_data, const uint64_t *out_offset, uint32_t *number_samples, float *max_sample)
 {
     if (!b) return fail(TRM_EINVAL, "null batch");
-    const HintDrop hintDrop{b};
+    const HintDrop hintDrop{b->hintFrames};
     if (nvoices == 0) return TRM_OK;
     if (!frames || !frame_offset || !nframes || (!out && !out16) || !out_offset || !number_samples || !max_sample)
         return fail(TRM_EINVAL, "null pointer");
     HIP_TRY(hipSetDevice(b->device));
-    uint64_t frameRows = 0, outEnd = 0, outBegin = ~0ull, outSum = 0;
+    const size_t ch = b->params.channels == 2 ? 2 : 1, perSample = out16 ? ch : 1;
+    uint64_t frameRows = 1, outEnd = 0, outBegin = ~0ull, outSum = 0;
     uint32_t maxFrames = 0;
+    std::vector<HostSpan> spans(nvoices);
     for (size_t v = 0; v < nvoices; v++) {
-        uint64_t fe = frame_offset[v] + nframes[v];
-        if (fe > frameRows) frameRows = fe;
         const uint64_t ns = trm_batch_samples_for_frames(b, nframes[v]);
-        uint64_t oe = out_offset[v] + ns;
-        if (oe > outEnd) outEnd = oe;
-        if (ns > 0 && out_offset[v] < outBegin) outBegin = out_offset[v];
+        frameRows = std::max<uint64_t>(frameRows, frame_offset[v] + nframes[v]);
+        outEnd = std::max(outEnd, out_offset[v] + ns);
+        if (ns > 0) outBegin = std::min(outBegin, out_offset[v]);
         outSum += ns;
-        if (nframes[v] > maxFrames) maxFrames = nframes[v];
+        maxFrames = std::max(maxFrames, nframes[v]);
+        spans[v] = {out_offset[v] * perSample, out_offset[v] * perSample, ns * perSample};
     }
     if (outBegin > outEnd) outBegin = outEnd;
-    // The header promises writes at out + out_offset[v] only.  Dense spans (the usual case: the voices tile
-    // [outBegin, outEnd) exactly) come back in one copy; a span with gaps is copied voice by voice, so that what
-    // lies between the voices in the caller's buffer is left alone.
+    // The header promises writes at out + out_offset[v] only.  Dense: the voices tile [outBegin, outEnd) exactly (the usual case).
     const bool dense = outSum == outEnd - outBegin;
-    if (frameRows == 0) frameRows = 1;
-    const size_t ch = b->params.channels == 2 ? 2 : 1;
-    int rc;
-    if ((rc = b->dFrames.reserve(frameRows * 16)) || (rc = b->dOut.reserve(outEnd + 1)) ||
-        (rc = b->dFrameOff.reserve(nvoices)) || (rc = b->dOutOff.reserve(nvoices)) ||
-        (rc = b->dNFrames.reserve(nvoices)) || (rc = b->dNSamples.reserve(nvoices)) || (rc = b->dMax.reserve(nvoices)))
-        return rc;
-    if (out16 && (rc = b->dOut16.reserve(outEnd * ch + 1))) return rc;
+    HostStaging &d = b->stage;
+    int rc = d.reserve(frameRows * 16, outEnd + 1, nvoices);
+    if (rc || (out16 && (rc = d.dOut16.reserve(outEnd * ch + 1)))) return rc;
     hipStream_t s = b->stream;
-    // Ragged batches: the kernels' voice index is put in order of decreasing length, so that the voices of a workgroup
-    // (16 or 64 consecutive indices) end together instead of every workgroup lasting as long as the longest voice of
-    // the batch: a workgroup that ends early frees its CU for the next one.  Only the three index arrays are permuted
-    // (frames and PCM stay where the caller's offsets put them); the per-voice results are put back in caller order.
-    std::vector<uint32_t> perm;
-    std::vector<uint64_t> pFrameOff, pOutOff;
-    std::vector<uint32_t> pNFrames, pNs;
-    std::vector<float> pMx;
-    {
-        bool sorted = true;
-        for (size_t v = 1; v < nvoices && sorted; v++) sorted = nframes[v] <= nframes[v - 1];
-        if (!sorted && nvoices > 16) {
-            perm.resize(nvoices);
-            for (size_t v = 0; v < nvoices; v++) perm[v] = (uint32_t)v;
-            std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return nframes[x] > nframes[y]; });
-            pFrameOff.resize(nvoices); pOutOff.resize(nvoices); pNFrames.resize(nvoices); pNs.resize(nvoices); pMx.resize(nvoices);
-            for (size_t i = 0; i < nvoices; i++) {
-                pFrameOff[i] = frame_offset[perm[i]];
-                pOutOff[i] = out_offset[perm[i]];
-                pNFrames[i] = nframes[perm[i]];
-            }
-        }
-    }
-    const bool permuted = !perm.empty();
-    HIP_TRY(hipMemcpyAsync(b->dFrames.p, frames, frameRows * 16 * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b->dFrameOff.p, permuted ? pFrameOff.data() : frame_offset, nvoices * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b->dOutOff.p, permuted ? pOutOff.data() : out_offset, nvoices * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b->dNFrames.p, permuted ? pNFrames.data() : nframes, nvoices * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    {
-        // what the time-split planner may know about a ragged batch: every voice's length, in the kernels' voice order
-        const uint32_t *order = permuted ? pNFrames.data() : nframes;
-        b->hintFrames.assign(order, order + nvoices);
-    }
-    rc = trm_batch_synthesize_device(b, nvoices, b->dFrames.p, b->dFrameOff.p, b->dNFrames.p, maxFrames, b->dOut.p,
-                                     b->dOutOff.p, b->dNSamples.p, b->dMax.p, s);
+    const size_t range[2] = {0, nvoices};
+    HostCall call(nvoices, range, 1, nframes, true);
+    if ((rc = call.upload(d, frames, frameRows, frame_offset, out_offset, nframes, b->hintFrames, s))) return rc;
+    rc = trm_batch_synthesize_device(b, nvoices, d.dFrames.p, d.dFrameOff.p, d.dNFrames.p, maxFrames, d.dOut.p, d.dOutOff.p, d.dNSamples.p, d.dMax.p, s);
     if (rc) return rc;
-    if (out16) {
-        rc = trm_batch_scale_to_int16_device(b, nvoices, b->dOut.p, b->dOutOff.p, b->dNSamples.p, b->dMax.p, b->dOut16.p,
-                                             for_wav_data, s);
-        if (rc) return rc;
-        if (dense && outEnd > outBegin)
-            HIP_TRY(hipMemcpyAsync(out16 + outBegin * ch, b->dOut16.p + outBegin * ch, (outEnd - outBegin) * ch * sizeof(int16_t), hipMemcpyDeviceToHost, s));
-        for (size_t v = 0; !dense && v < nvoices; v++)
-            if (const uint64_t ns = trm_batch_samples_for_frames(b, nframes[v]))
-                HIP_TRY(hipMemcpyAsync(out16 + out_offset[v] * ch, b->dOut16.p + out_offset[v] * ch, ns * ch * sizeof(int16_t), hipMemcpyDeviceToHost, s));
-    } else {
-        if (dense && outEnd > outBegin)
-            HIP_TRY(hipMemcpyAsync(out + outBegin, b->dOut.p + outBegin, (outEnd - outBegin) * sizeof(float), hipMemcpyDeviceToHost, s));
-        for (size_t v = 0; !dense && v < nvoices; v++)
-            if (const uint64_t ns = trm_batch_samples_for_frames(b, nframes[v]))
-                HIP_TRY(hipMemcpyAsync(out + out_offset[v], b->dOut.p + out_offset[v], ns * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipMemcpyAsync(permuted ? pNs.data() : number_samples, b->dNSamples.p, nvoices * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(permuted ? pMx.data() : max_sample, b->dMax.p, nvoices * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; permuted && i < nvoices; i++) {
-        number_samples[perm[i]] = pNs[i];
-        max_sample[perm[i]] = pMx[i];
-    }
-    return TRM_OK;
+    if (out16 && (rc = trm_batch_scale_to_int16_device(b, nvoices, d.dOut.p, d.dOutOff.p, d.dNSamples.p, d.dMax.p, d.dOut16.p, for_wav_data, s))) return rc;
+    if ((rc = out16 ? copy_back(out16, d.dOut16.p, sizeof(int16_t), spans, dense, s) : copy_back(out, d.dOut.p, sizeof(float), spans, dense, s))) return rc;
+    return call.results(d, s, number_samples, max_sample, nullptr);
 }
 
-int trm_batch_synthesize_host(trm_batch *b, size_t nvoices, const float *frames, const uint64_t *frame_offset,
-                              const uint32_t *nframes, float *out, const uint64_t *out_offset,
-                              uint32_t *number_samples, float *max_sample)
+int trm_batch_synthesize_host(trm_batch *b, size_t nvoices, const float *frames, const uint64_t *frame_offset, const uint32_t *nframes,
+                              float *out, const uint64_t *out_offset, uint32_t *number_samples, float *max_sample)
 {
     if (!out) return fail(TRM_EINVAL, "null pointer");
     return synthesize_host_impl(b, nvoices, frames, frame_offset, nframes, out, nullptr, 0, out_offset, number_samples, max_sample);
 }
 
-int trm_batch_synthesize_host_int16(trm_batch *b, size_t nvoices, const float *frames, const uint64_t *frame_offset,
-                                    const uint32_t *nframes, int16_t *out16, const uint64_t *out_offset,
-                                    uint32_t *number_samples, float *max_sample, int for_wav_data)
+int trm_batch_synthesize_host_int16(trm_batch *b, size_t nvoices, const float *frames, const uint64_t *frame_offset, const uint32_t *nframes,
+                                    int16_t *out16, const uint64_t *out_offset, uint32_t *number_samples, float *max_sample, int for_wav_data)
 {
     if (!out16) return fail(TRM_EINVAL, "null pointer");
-    return synthesize_host_impl(b, nvoices, frames, frame_offset, nframes, nullptr, out16, for_wav_data, out_offset, number_samples,
-                                max_sample);
+    return synthesize_host_impl(b, nvoices, frames, frame_offset, nframes, nullptr, out16, for_wav_data, out_offset, number_samples, max_sample);
 }
 
 // ------------------------------------------------------------------ several devices from one process

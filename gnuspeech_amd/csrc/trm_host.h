@@ -1,12 +1,12 @@
 // trm_host.h -- what the host translation units of libtrm_hip share (private; the public interface is include/trm_c_api.h).
 //   trm_capi.cc    errors and info, trm_batch (with the time-split planner of every one-shot launch and the host entries), trm_tube and the data list,
-//                  trm_multi, the uniform tracks, int16 and file entries; defines the launch set-up helpers declared here
+//                  trm_multi, the uniform tracks, int16 and file entries; defines the launch set-up, planning and host-staging helpers declared here
 //   trm_stream.cc  trm_stream and trm_mixed_stream, one chunk engine over parameter sets, in three files over
 //                  trm_stream_engine.h and one translation unit (this one carries the other two with an #include):
 //                  create (stream_init), the lock-step chunk, the trm_stream_* and the lock-step trm_mixed_stream_* entries
 //   trm_stream_step.cc    a grouped stream's step: the plan, the step's tables, the launches, the four step entries
 //   trm_stream_groups.cc  what a grouped stream is given between steps: event lists, bindings, parameters, the conversion path
-//   trm_mixed.cc   trm_mixed with its tracks, output and events-to-files entries; SetBatches and the block map
+//   trm_mixed.cc   trm_mixed: its device entry (the plan, the shape, the launches), its host, tracks, output and events-to-files entries; SetBatches, the block map
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -56,6 +57,15 @@ struct DevBuf {
     void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }
 };
 
+// The device buffers of a one-shot host entry's launch (below: host staging): a member of trm_batch and of trm_mixed
+struct HostStaging {
+    DevBuf<float> dFrames, dOut, dMax;
+    DevBuf<int16_t> dOut16;
+    DevBuf<uint64_t> dFrameOff, dOutOff, dRelOff;     // (dRelOff: the mixed int16 entry's offsets within a set)
+    DevBuf<uint32_t> dNFrames, dNSamples;
+    int reserve(size_t frameFloats, size_t outFloats, size_t nvoices);       // all but dOut16 and dRelOff (the int16 entries')
+};
+
 struct trm_batch {
     trm_input_params params;
     trm::Const c;
@@ -73,16 +83,12 @@ struct trm_batch {
     DevBuf<float> dNoise;
     double *dNoiseState = nullptr;
     uint32_t noiseLen = 0;
-    // host-form staging
-    DevBuf<float> dFrames, dOut, dMax;
-    DevBuf<int16_t> dOut16;
+    HostStaging stage;                   // the host-buffer entries'
     // trm_batch_generate_frames_host staging
     DevBuf<uint32_t> evT, evN;
     DevBuf<double> evV;
     DevBuf<uint64_t> evOff;
     DevBuf<float> evF;
-    DevBuf<uint64_t> dFrameOff, dOutOff;
-    DevBuf<uint32_t> dNFrames, dNSamples;
     // kernel timing (hipEvents on the launch stream)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;      // launches not yet folded into the sums below
     double timedMs = 0.0;
@@ -189,6 +195,54 @@ SplitPlan plan_split(const trm_batch *b0, const SplitAsk &ask);
 // max_nframes), in control periods
 void hinted_blocks(const size_t *set_begin, size_t nsets, size_t perWg, const std::vector<uint32_t> &hint, uint32_t max_nframes,
                    std::vector<SplitBlock> &blocks);
+
+// ------------------------------------------------------------------ host staging, stated once (trm_capi.cc)
+// What trm_batch_synthesize_host[_int16] (with trm_tube_synthesize and every shard of trm_multi_*, a thread each: nothing here
+// is static or shared), trm_mixed_synthesize_host[_int16] and trm_mixed_events_to_files_host share.  Their device layouts of
+// the PCM: a trm_batch keeps the CALLER's out_offset (int16: times the channels); a trm_mixed PACKS -- voice after voice in
+// caller order (fp32), set by set with the set's channels applied (int16), image after image (files).
+
+// A hint holds for the one launch that follows it, whether that launch runs or fails: an entry drops it on every return
+struct HintDrop {
+    std::vector<uint32_t> &hint;
+    ~HintDrop() { hint.clear(); }
+};
+
+// A voice's stretch of a copy back, in elements of `elem` bytes.  dense (the entry's rule: the spans tile one range, the same
+// on either side): one copy from the lowest span that has something; else one per such span -- the gaps are left alone.
+struct HostSpan { uint64_t host, dev, count; };
+int copy_back(void *host, const void *dev, size_t elem, const std::vector<HostSpan> &spans, bool dense, hipStream_t st);
+
+// One call of a host entry: its voices' launch order and every host array its asynchronous copies use (kept past the synchronise)
+struct HostCall {
+    const size_t V;
+    std::vector<uint32_t> perm;              // launch index -> caller's index; empty: the identity
+    // The kernels' voice index runs from the longest voice down within each range of set_begin (a stable sort): the voices of a
+    // workgroup end together, and one that ends early frees its CU.  batchRule (trm_batch's; the mixed entries always permute):
+    // the identity when the voices are sorted already or at most 16 -- the caller's arrays then go up as they are, uncopied.
+    HostCall(size_t nvoices, const size_t *set_begin, size_t nsets, const uint32_t *nframes, bool batchRule);
+    uint32_t caller(size_t i) const { return perm.empty() ? (uint32_t)i : perm[i]; }
+    template <class T> T *keep()             // V elements that live as long as the call
+    {
+        kept.emplace_back(new char[V * sizeof(T)]);
+        return reinterpret_cast<T *>(kept.back().get());
+    }
+    template <class T> const T *in_launch_order(const T *x)      // x (caller order); x itself under the identity
+    {
+        if (perm.empty()) return x;
+        T *p = keep<T>();
+        for (size_t i = 0; i < V; i++) p[i] = x[perm[i]];
+        return p;
+    }
+    // frames as they are, the three index arrays (out_offset: the device layout) and `hint`, the planner's, in launch order
+    int upload(HostStaging &d, const float *frames, uint64_t frameRows, const uint64_t *frame_offset, const uint64_t *out_offset,
+               const uint32_t *nframes, std::vector<uint32_t> &hint, hipStream_t st);
+    // number_samples and max_sample fetched, the stream synchronised, each put at its caller's index.  wantFrames (caller
+    // order; null: not looked at): the frame counts the generator must have written to d.dNFrames.
+    int results(HostStaging &d, hipStream_t st, uint32_t *number_samples, float *max_sample, const uint32_t *wantFrames);
+private:
+    std::vector<std::unique_ptr<char[]>> kept;
+};
 
 // ------------------------------------------------------------------ parameter sets (trm_mixed.cc)
 // One trm_batch per parameter set -- that set's constants, derived values and down-sampling rows (the read-only device tables

@@ -104,11 +104,7 @@ struct trm_mixed {
     // the device), then uploads in stream order
     hipEvent_t lastUse = nullptr;
     bool lastUseRecorded = false;
-    // host-entry staging
-    DevBuf<float> dFrames, dOut, dMax;
-    DevBuf<int16_t> dOut16;
-    DevBuf<uint64_t> dFrameOff, dOutOff, dRelOff;
-    DevBuf<uint32_t> dNFrames, dNSamples;
+    HostStaging stage;                       // the host entries'
     // the output entries (trm_mixed_scale_to_int16_device, trm_mixed_sound_files_device): every set's scaling and header
     // template (built at create), and the device copy of set_begin their workgroups look their set up in -- uploaded when
     // set_begin changes, under the block map's rule (hSetBegin outlives the upload; a change waits for outLastUse alone)
@@ -231,7 +227,10 @@ int trm_mixed_hint_frames(trm_mixed *m, const uint32_t *nframes, size_t nvoices)
     return TRM_OK;
 }
 
-static int mixed_check_sets(const trm_mixed *m, const size_t *set_begin) { return check_set_begin(m->sets.size(), set_begin); }
+static int mixed_check_sets(const trm_mixed *m, const size_t *set_begin)
+{
+    return m ? check_set_begin(m->sets.size(), set_begin) : fail(TRM_EINVAL, "null handle");
+}
 
 // The kernel form of a mixed launch: what a trm_batch of the same voice count -- every set padded to the form's workgroup --
 // runs with the time split off (trm_batch_synthesize_device), and the one-voice-per-lane form when a non-empty set forbids
@@ -265,187 +264,161 @@ static bool mixed_split_quad_ok(const trm_mixed *m, const size_t *set_begin, int
     return true;
 }
 
-int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const float *d_frames, const uint64_t *d_frame_offset,
-                                const uint32_t *d_nframes, uint32_t max_nframes, float *d_out, const uint64_t *d_out_offset,
-                                uint32_t *d_number_samples, float *d_max_sample, void *stream_)
-{
-    if (!m) return fail(TRM_EINVAL, "null handle");
-    // a hint holds for the one launch that follows it, whether that launch runs or fails (as trm_batch_hint_frames')
-    struct HintDrop {
-        trm_mixed *m;
-        ~HintDrop() { m->hintFrames.clear(); }
-    } const hintDrop{m};
-    int rc = mixed_check_sets(m, set_begin);
-    if (rc) return rc;
-    const size_t S = m->sets.size(), nvoices = set_begin[S];
-    if (nvoices == 0) return TRM_OK;
-    if (!d_frames || !d_frame_offset || !d_nframes || !d_out || !d_out_offset || !d_number_samples || !d_max_sample)
-        return fail(TRM_EINVAL, "null device pointer");
-    hipStream_t stream = (hipStream_t)stream_;
-    trm_batch *b0 = m->sets[0];
-    HIP_TRY(hipSetDevice(b0->device));
-    // the noise sequence for the longest voice of any set
-    uint64_t need = 0;
-    const trm_batch *cb = nullptr;        // the set with the shortest control period: the launchers' checks see it
-    for (size_t s = 0; s < S; s++) {
-        if (set_begin[s + 1] == set_begin[s]) continue;
-        const trm_batch *b = m->sets[s];
-        const uint64_t needs = noise_need(b, max_nframes);
-        if (!needs) return fail(TRM_ERANGE, "utterance too long (parameter set %zu)", s);
-        need = std::max(need, needs);
-        if (!cb || b->c.controlPeriod < cb->c.controlPeriod) cb = b;
-    }
-    if ((rc = ensure_noise(b0, (uint32_t)need, stream))) return rc;
-    int which = mixed_form(m, set_begin);
-    // The time split: one segment length S (control periods) for all sets, every set's own warm-up by the batch's rule, planned
-    // (plan_split) over the 64-voice cut (the one-voice-per-lane segments', and every split launch's whole-utterance fallback)
-    // and, where the four-lane segment form is admissible, the 16-voice cut; block by block where a hint told the lengths.
-    uint32_t split = 0;
-    int segForm = TRM_KERNEL_WIDE;
-    std::vector<uint32_t> warm(S, 0);
+// trm_mixed_synthesize_device in three parts: the plan, the shape, the launches.  The plan of the time split: one segment length
+// S (control periods) for all sets, every set's own warm-up by the batch's rule, planned (plan_split) over the 64-voice cut (the
+// one-voice-per-lane segments', and every split launch's whole-utterance fallback) and, where the four-lane segment form is
+// admissible, the 16-voice cut; block by block where a hint told the lengths.  `which`: the whole-utterance launch's form.
+struct MixedPlan {
+    uint32_t split = 0;                   // S; 0: whole utterances
+    int segForm = TRM_KERNEL_WIDE;        // the segments' form
+    std::vector<uint32_t> warm;           // every set's warm-up
     std::vector<SplitBlock> blocks;       // a split launch under a hint: per entry of the segments' map its longest voice
-    const bool hinted = m->hintFrames.size() == nvoices;
-    if (m->splitSetting != TRM_TIME_SPLIT_OFF && max_nframes >= 2) {
-        std::vector<SplitSet> sets(S);
-        bool forgets = true;          // every set with voices does: else a split asked for by name fails, AUTO runs whole utterances
-        for (size_t s = 0; s < S; s++) {
-            const size_t n = set_begin[s + 1] - set_begin[s];
-            warm[s] = trm::split_warm_periods(m->sets[s]->c, m->splitWarmup);
-            sets[s] = {(uint32_t)m->sets[s]->c.controlPeriod, warm[s], (n + 63) / 64, (n + 15) / 16};
-            if (n == 0 || warm[s] != 0) continue;
-            if (m->splitSetting > 0)
-                return fail(TRM_ERANGE, "time split: the tube of parameter set %zu never forgets (loss factor %g %%)", s, m->sets[s]->params.lossFactor);
-            forgets = false;
+    bool hinted = false;
+};
+
+static int mixed_plan(const trm_mixed *m, const size_t *set_begin, uint32_t max_nframes, int which, MixedPlan &pl)
+{
+    const size_t S = m->sets.size(), nvoices = set_begin[S];
+    pl.warm.assign(S, 0);
+    pl.hinted = m->hintFrames.size() == nvoices;
+    if (m->splitSetting == TRM_TIME_SPLIT_OFF || max_nframes < 2) return TRM_OK;
+    std::vector<SplitSet> sets(S);
+    bool forgets = true;          // every set with voices does: else a split asked for by name fails, AUTO runs whole utterances
+    for (size_t s = 0; s < S; s++) {
+        const size_t n = set_begin[s + 1] - set_begin[s];
+        pl.warm[s] = trm::split_warm_periods(m->sets[s]->c, m->splitWarmup);
+        sets[s] = {(uint32_t)m->sets[s]->c.controlPeriod, pl.warm[s], (n + 63) / 64, (n + 15) / 16};
+        if (n == 0 || pl.warm[s] != 0) continue;
+        if (m->splitSetting > 0)
+            return fail(TRM_ERANGE, "time split: the tube of parameter set %zu never forgets (loss factor %g %%)", s, m->sets[s]->params.lossFactor);
+        forgets = false;
+    }
+    if (!forgets) return TRM_OK;
+    SplitAsk ask = {sets.data(), S, nvoices, max_nframes - 1, m->splitSetting, which, m->kernel, mixed_split_quad_ok(m, set_begin, which), nullptr, nullptr};
+    std::vector<SplitBlock> blocks16;
+    if (pl.hinted) {
+        hinted_blocks(set_begin, S, 64, m->hintFrames, max_nframes, pl.blocks);
+        ask.cut64 = &pl.blocks;
+        if (ask.quadOk) {
+            hinted_blocks(set_begin, S, 16, m->hintFrames, max_nframes, blocks16);
+            ask.cut16 = &blocks16;
         }
-        if (forgets) {
-            SplitAsk ask = {sets.data(), S, nvoices, max_nframes - 1, m->splitSetting, which, m->kernel, mixed_split_quad_ok(m, set_begin, which), nullptr, nullptr};
-            std::vector<SplitBlock> blocks16;
-            if (hinted) {
-                hinted_blocks(set_begin, S, 64, m->hintFrames, max_nframes, blocks);
-                ask.cut64 = &blocks;
-                if (ask.quadOk) {
-                    hinted_blocks(set_begin, S, 16, m->hintFrames, max_nframes, blocks16);
-                    ask.cut16 = &blocks16;
+    }
+    const SplitPlan sp = plan_split(m->sets[0], ask);
+    pl.split = sp.periods;
+    pl.segForm = sp.form;
+    if (pl.split && pl.segForm == TRM_KERNEL_QUAD) pl.blocks.swap(blocks16);       // (the launch order: per entry of the segments' map)
+    return TRM_OK;
+}
+
+// The shape: the block map(s), a split launch's order and the down-sampling sets' row offsets, rebuilt and uploaded when the
+// shape changes (a split launch's includes its segment length and the lengths its launch order was built from)
+static int mixed_shape(trm_mixed *m, const size_t *set_begin, uint32_t max_nframes, const MixedPlan &pl, int form, uint32_t perWg, hipStream_t stream)
+{
+    const size_t S = m->sets.size(), nvoices = set_begin[S];
+    const uint32_t split = pl.split;
+    if (m->haveShape && m->shapeForm == form && m->shapeMaxFrames == max_nframes && std::equal(set_begin, set_begin + S + 1, m->shapeBegin.begin()) &&
+        m->shapeSplit == split && !(split && (pl.hinted ? m->shapeHint != m->hintFrames : !m->shapeHint.empty())))
+        return TRM_OK;
+    // (an earlier launch, on whichever stream, may still read the arrays and their host copies' uploads)
+    if (m->lastUseRecorded) HIP_TRY(hipEventSynchronize(m->lastUse));
+    m->haveShape = false;
+    int rc;
+    std::vector<uint4> &map = m->hMap;
+    std::vector<uint64_t> &toff = m->hTubeOff;
+    build_block_map(set_begin, S, perWg, map);
+    m->hSegMap.clear();
+    m->segRows = 0;
+    if (split) {
+        // The launch order: every (segment, map entry) pair up to the segments max_nframes allows -- a wrong hint changes
+        // the order, never the set of pairs -- those with work by the lengths we know first, in (segment, entry) order: a
+        // workgroup that exits at once does not free its place.
+        uint32_t nsegMax = 0;
+        for (size_t e = 0; e < map.size(); e++) {
+            map[e].w = pl.warm[map[e].x];
+            nsegMax = std::max(nsegMax, trm::seg_count(max_nframes - 1, split, map[e].w));
+        }
+        if ((uint64_t)nsegMax * map.size() > 0x7FFFFFFFull / 64) return fail(TRM_ERANGE, "time split: too many segments");
+        for (int pass = 0; pass < 2; pass++)
+            for (uint32_t sgm = 0; sgm < nsegMax; sgm++)
+                for (size_t e = 0; e < map.size(); e++) {
+                    if (sgm >= trm::seg_count(max_nframes - 1, split, map[e].w)) continue;
+                    const bool work = trm::seg_has_work(sgm, pl.hinted ? pl.blocks[e].longest : max_nframes - 1, trm::seg_first(split, map[e].w), split);
+                    if (work == (pass == 0)) m->hSegMap.push_back(make_uint2(sgm, (uint32_t)e));
                 }
-            }
-            const SplitPlan pl = plan_split(b0, ask);
-            split = pl.periods;
-            segForm = pl.form;
-            if (split && segForm == TRM_KERNEL_QUAD) blocks.swap(blocks16);       // (the launch order below: per entry of the segments' map)
+        m->segRows = nsegMax;
+    }
+    toff.assign(nvoices, 0);
+    uint64_t rows = 0;
+    for (size_t s = 0; s < S; s++) {
+        const size_t lo = set_begin[s], hi = set_begin[s + 1];
+        const trm_batch *b = m->sets[s];
+        if (!b->c.upsample && hi > lo) {
+            // fixed-pitch rows of (max_nframes-1)*controlPeriod + 2*pad floats per voice, 16-byte aligned (as a trm_batch lays them out)
+            const uint64_t ntube = max_nframes > 0 ? (uint64_t)(max_nframes - 1) * (uint64_t)b->d.controlPeriod : 0;
+            const uint64_t pitch = tube_row_pitch(b, ntube);
+            for (size_t v = lo; v < hi; v++) { toff[v] = rows; rows += pitch; }
         }
     }
-    m->lastSplitPeriods = split;
-    m->lastWarm.assign(S, 0);
-    // `form`: of the launch that is meant to run (a split launch: its segments); `which`: of the whole-utterance launch -- a
-    // split launch's fallback is the one-voice-per-lane kernel over the 64-voice map, whatever the segments' form (trm_batch's)
-    const int form = split ? segForm : which;
+    if (map.size() > 0x7FFFFFFFull) return fail(TRM_ERANGE, "too many workgroups");
+    m->hMap64.clear();
+    if (split && pl.segForm == TRM_KERNEL_QUAD) {
+        build_block_map(set_begin, S, 64, m->hMap64);
+        if ((rc = m->dMap64.reserve(m->hMap64.size()))) return rc;
+        HIP_TRY(hipMemcpyAsync(m->dMap64.p, m->hMap64.data(), m->hMap64.size() * sizeof(uint4), hipMemcpyHostToDevice, stream));
+    }
+    if ((rc = m->dMap.reserve(map.size())) || (rc = m->dTubeOff.reserve(nvoices)) || (rc = m->dTube.reserve(rows + 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(m->dMap.p, map.data(), map.size() * sizeof(uint4), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(m->dTubeOff.p, toff.data(), nvoices * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
     if (split) {
-        m->lastWarm = warm;
-        which = TRM_KERNEL_WIDE;
+        if ((rc = m->dSegMap.reserve(m->hSegMap.size())) || (rc = m->dSegPhase.reserve((size_t)m->segRows * map.size() * perWg)) ||
+            (rc = m->dPeriodAdv.reserve(nvoices * (size_t)max_nframes)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(m->dSegMap.p, m->hSegMap.data(), m->hSegMap.size() * sizeof(uint2), hipMemcpyHostToDevice, stream));
     }
-    const bool quadSplit = split && segForm == TRM_KERNEL_QUAD;
-    const uint32_t perWg = form == TRM_KERNEL_WIDE ? 64u : form == TRM_KERNEL_QUAD ? 16u : 8u;
-    // the block map and the down-sampling sets' row offsets: rebuilt when the shape changes (a split launch's shape includes its
-    // segment length and the lengths its launch order was built from)
-    if (!m->haveShape || m->shapeForm != form || m->shapeMaxFrames != max_nframes || !std::equal(set_begin, set_begin + S + 1, m->shapeBegin.begin()) ||
-        m->shapeSplit != split || (split && (hinted ? m->shapeHint != m->hintFrames : !m->shapeHint.empty()))) {
-        // (an earlier launch, on whichever stream, may still read the arrays and their host copies' uploads)
-        if (m->lastUseRecorded) HIP_TRY(hipEventSynchronize(m->lastUse));
-        m->haveShape = false;
-        std::vector<uint4> &map = m->hMap;
-        std::vector<uint64_t> &toff = m->hTubeOff;
-        build_block_map(set_begin, S, perWg, map);
-        m->hSegMap.clear();
-        m->segRows = 0;
-        if (split) {
-            // The launch order: every (segment, map entry) pair up to the segments max_nframes allows -- a wrong hint changes
-            // the order, never the set of pairs -- those with work by the lengths we know first, in (segment, entry) order: a
-            // workgroup that exits at once does not free its place.
-            uint32_t nsegMax = 0;
-            for (size_t e = 0; e < map.size(); e++) {
-                map[e].w = warm[map[e].x];
-                nsegMax = std::max(nsegMax, trm::seg_count(max_nframes - 1, split, map[e].w));
-            }
-            if ((uint64_t)nsegMax * map.size() > 0x7FFFFFFFull / 64) return fail(TRM_ERANGE, "time split: too many segments");
-            for (int pass = 0; pass < 2; pass++)
-                for (uint32_t sgm = 0; sgm < nsegMax; sgm++)
-                    for (size_t e = 0; e < map.size(); e++) {
-                        if (sgm >= trm::seg_count(max_nframes - 1, split, map[e].w)) continue;
-                        const bool work = trm::seg_has_work(sgm, hinted ? blocks[e].longest : max_nframes - 1, trm::seg_first(split, map[e].w), split);
-                        if (work == (pass == 0)) m->hSegMap.push_back(make_uint2(sgm, (uint32_t)e));
-                    }
-            m->segRows = nsegMax;
-        }
-        toff.assign(nvoices, 0);
-        uint64_t rows = 0;
-        for (size_t s = 0; s < S; s++) {
-            const size_t lo = set_begin[s], hi = set_begin[s + 1];
-            const trm_batch *b = m->sets[s];
-            if (!b->c.upsample && hi > lo) {
-                // fixed-pitch rows of (max_nframes-1)*controlPeriod + 2*pad floats per voice, 16-byte aligned (as a trm_batch lays them out)
-                const uint64_t ntube = max_nframes > 0 ? (uint64_t)(max_nframes - 1) * (uint64_t)b->d.controlPeriod : 0;
-                const uint64_t pitch = tube_row_pitch(b, ntube);
-                for (size_t v = lo; v < hi; v++) { toff[v] = rows; rows += pitch; }
-            }
-        }
-        if (map.size() > 0x7FFFFFFFull) return fail(TRM_ERANGE, "too many workgroups");
-        m->hMap64.clear();
-        if (quadSplit) {
-            build_block_map(set_begin, S, 64, m->hMap64);
-            if ((rc = m->dMap64.reserve(m->hMap64.size()))) return rc;
-            HIP_TRY(hipMemcpyAsync(m->dMap64.p, m->hMap64.data(), m->hMap64.size() * sizeof(uint4), hipMemcpyHostToDevice, stream));
-        }
-        if ((rc = m->dMap.reserve(map.size())) || (rc = m->dTubeOff.reserve(nvoices)) || (rc = m->dTube.reserve(rows + 1))) return rc;
-        HIP_TRY(hipMemcpyAsync(m->dMap.p, map.data(), map.size() * sizeof(uint4), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(m->dTubeOff.p, toff.data(), nvoices * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        if (split) {
-            if ((rc = m->dSegMap.reserve(m->hSegMap.size())) || (rc = m->dSegPhase.reserve((size_t)m->segRows * map.size() * perWg)) ||
-                (rc = m->dPeriodAdv.reserve(nvoices * (size_t)max_nframes)))
-                return rc;
-            HIP_TRY(hipMemcpyAsync(m->dSegMap.p, m->hSegMap.data(), m->hSegMap.size() * sizeof(uint2), hipMemcpyHostToDevice, stream));
-        }
-        m->shapeSplit = split;
-        m->segGrid = (uint32_t)m->hSegMap.size();
-        if (split && hinted) m->shapeHint = m->hintFrames;
-        else m->shapeHint.clear();
-        m->shapeBegin.assign(set_begin, set_begin + S + 1);
-        m->shapeForm = form;
-        m->shapeMaxFrames = max_nframes;
-        m->mapEntries = (uint32_t)map.size();
-        m->map64Entries = (uint32_t)m->hMap64.size();
-        m->haveShape = true;
-    }
-    trm::TubeArgs a = tube_args(b0, d_frames, d_frame_offset, d_nframes, d_out, d_out_offset, d_number_samples, d_max_sample, nvoices, max_nframes);
-    a.tube_out = m->dTube.p;
-    a.tube_offset = m->dTubeOff.p;
-    a.mix_map = m->dMap.p;
-    a.set_const = (trm::ConstTable)m->sets.dConst;
-    a.mix_grid = m->mapEntries;
-    m->lastKernel = form;
-    if (split) {
+    m->shapeSplit = split;
+    m->segGrid = (uint32_t)m->hSegMap.size();
+    if (split && pl.hinted) m->shapeHint = m->hintFrames;
+    else m->shapeHint.clear();
+    m->shapeBegin.assign(set_begin, set_begin + S + 1);
+    m->shapeForm = form;
+    m->shapeMaxFrames = max_nframes;
+    m->mapEntries = (uint32_t)map.size();
+    m->map64Entries = (uint32_t)m->hMap64.size();
+    m->haveShape = true;
+    return TRM_OK;
+}
+
+// The launches.  a: the arguments with the shape's arrays set; which: the whole-utterance launch's form
+static int mixed_launches(trm_mixed *m, const size_t *set_begin, trm::TubeArgs a, const MixedPlan &pl, int which, uint32_t perWg, const trm_batch *cb,
+                          hipStream_t stream)
+{
+    const size_t S = m->sets.size(), nvoices = set_begin[S];
+    const trm_batch *b0 = m->sets[0];
+    if (pl.split) {
         // The pre-pass, set by set over its voice range (the oscillator's advance per period and the guard's floor are the
         // set's): its rows of seg_phase start at the set's first map entry, every set ORs into one gate word.  Then both
         // launches, of which the device runs one (TubeArgs::gate): the segments, or -- a frame of any voice below its set's
         // floor -- whole utterances, over the same map or (four-lane segments) over the 64-voice one.
         uint32_t *gate = b0->dGate;
-        HIP_TRY(trm::launch_split_clear(d_max_sample, (uint32_t)nvoices, gate, stream));
+        HIP_TRY(trm::launch_split_clear(a.max_sample, (uint32_t)nvoices, gate, stream));
         size_t entry = 0;
         for (size_t s = 0; s < S; s++) {
             const size_t lo = set_begin[s], n = set_begin[s + 1] - lo;
             if (n == 0) continue;
             const trm_batch *b = m->sets[s];
-            const trm::PhaseArgs ph = phase_args(b, a, lo, n, split, warm[s], m->mapEntries, perWg, m->dSegPhase.p + entry * perWg,
-                                                 m->dPeriodAdv.p + lo * (size_t)max_nframes, gate);
+            const trm::PhaseArgs ph = phase_args(b, a, lo, n, pl.split, pl.warm[s], m->mapEntries, perWg, m->dSegPhase.p + entry * perWg,
+                                                 m->dPeriodAdv.p + lo * (size_t)a.max_nframes, gate);
             HIP_TRY(trm::launch_phase(b->c, ph, stream));
             entry += (n + perWg - 1) / perWg;
         }
         trm::TubeArgs sa = a;
-        sa.seg_periods = split; sa.seg_wg_per_seg = m->mapEntries; sa.seg_grid = m->segGrid;
+        sa.seg_periods = pl.split; sa.seg_wg_per_seg = m->mapEntries; sa.seg_grid = m->segGrid;
         sa.seg_phase = m->dSegPhase.p;
         sa.seg_map = m->dSegMap.p;
         sa.gate = gate; sa.gate_want = 0;
-        HIP_TRY(launch_form(segForm, b0, cb->c, sa, stream));
-        if (quadSplit) {
+        HIP_TRY(launch_form(pl.segForm, b0, cb->c, sa, stream));
+        if (pl.segForm == TRM_KERNEL_QUAD) {
             a.mix_map = m->dMap64.p;
             a.mix_grid = m->map64Entries;
         }
@@ -468,103 +441,109 @@ int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const flo
     return TRM_OK;
 }
 
-// host-buffer entries: fp32 PCM (out) or int16 (out16, mono or interleaved stereo per set), not both.  On the device voice v's
-// PCM is packed in voice order (fp32: after the voices before it; int16: set by set, channels applied); the results go back to
-// the caller's offsets in one copy where those are the same packing, voice by voice otherwise.
-static int mixed_host_impl(trm_mixed *m, const size_t *set_begin, const float *frames, const uint64_t *frame_offset, const uint32_t *nframes,
-                           float *out, int16_t *out16, int for_wav_data, const uint64_t *out_offset, uint32_t *number_samples,
-                           float *max_sample)
+int trm_mixed_synthesize_device(trm_mixed *m, const size_t *set_begin, const float *d_frames, const uint64_t *d_frame_offset,
+                                const uint32_t *d_nframes, uint32_t max_nframes, float *d_out, const uint64_t *d_out_offset,
+                                uint32_t *d_number_samples, float *d_max_sample, void *stream_)
 {
     if (!m) return fail(TRM_EINVAL, "null handle");
+    const HintDrop hintDrop{m->hintFrames};
+    int rc = mixed_check_sets(m, set_begin);
+    if (rc) return rc;
+    const size_t S = m->sets.size(), nvoices = set_begin[S];
+    if (nvoices == 0) return TRM_OK;
+    if (!d_frames || !d_frame_offset || !d_nframes || !d_out || !d_out_offset || !d_number_samples || !d_max_sample)
+        return fail(TRM_EINVAL, "null device pointer");
+    hipStream_t stream = (hipStream_t)stream_;
+    trm_batch *b0 = m->sets[0];
+    HIP_TRY(hipSetDevice(b0->device));
+    // the noise sequence for the longest voice of any set
+    uint64_t need = 0;
+    const trm_batch *cb = nullptr;        // the set with the shortest control period: the launchers' checks see it
+    for (size_t s = 0; s < S; s++) {
+        if (set_begin[s + 1] == set_begin[s]) continue;
+        const trm_batch *b = m->sets[s];
+        const uint64_t needs = noise_need(b, max_nframes);
+        if (!needs) return fail(TRM_ERANGE, "utterance too long (parameter set %zu)", s);
+        need = std::max(need, needs);
+        if (!cb || b->c.controlPeriod < cb->c.controlPeriod) cb = b;
+    }
+    if ((rc = ensure_noise(b0, (uint32_t)need, stream))) return rc;
+    int which = mixed_form(m, set_begin);
+    MixedPlan pl;
+    if ((rc = mixed_plan(m, set_begin, max_nframes, which, pl))) return rc;
+    m->lastSplitPeriods = pl.split;
+    m->lastWarm.assign(S, 0);
+    // `form`: of the launch that is meant to run (a split launch: its segments); `which`: of the whole-utterance launch -- a
+    // split launch's fallback is the one-voice-per-lane kernel over the 64-voice map, whatever the segments' form (trm_batch's)
+    const int form = pl.split ? pl.segForm : which;
+    if (pl.split) {
+        m->lastWarm = pl.warm;
+        which = TRM_KERNEL_WIDE;
+    }
+    const uint32_t perWg = form == TRM_KERNEL_WIDE ? 64u : form == TRM_KERNEL_QUAD ? 16u : 8u;
+    if ((rc = mixed_shape(m, set_begin, max_nframes, pl, form, perWg, stream))) return rc;
+    trm::TubeArgs a = tube_args(b0, d_frames, d_frame_offset, d_nframes, d_out, d_out_offset, d_number_samples, d_max_sample, nvoices, max_nframes);
+    a.tube_out = m->dTube.p;
+    a.tube_offset = m->dTubeOff.p;
+    a.mix_map = m->dMap.p;
+    a.set_const = (trm::ConstTable)m->sets.dConst;
+    a.mix_grid = m->mapEntries;
+    m->lastKernel = form;
+    return mixed_launches(m, set_begin, a, pl, which, perWg, cb, stream);
+}
+
+// host-buffer entries: fp32 PCM (out) or int16 (out16, mono or interleaved stereo per set), not both (trm_host.h: host staging)
+static int mixed_host_impl(trm_mixed *m, const size_t *set_begin, const float *frames, const uint64_t *frame_offset, const uint32_t *nframes, float *out,
+                           int16_t *out16, int for_wav_data, const uint64_t *out_offset, uint32_t *number_samples, float *max_sample)
+{
     int rc = mixed_check_sets(m, set_begin);
     if (rc) return rc;
     const size_t S = m->sets.size(), V = set_begin[S];
     if (V == 0) return TRM_OK;
     if (!frames || !frame_offset || !nframes || (!out && !out16) || !out_offset || !number_samples || !max_sample)
         return fail(TRM_EINVAL, "null pointer");
-    trm_batch *b0 = m->sets[0];
-    HIP_TRY(hipSetDevice(b0->device));
-    hipStream_t st = b0->stream;
-    std::vector<uint64_t> dev32(V), dev16(V), base32(S + 1), base16(S + 1);
-    std::vector<uint64_t> ns(V);
+    const HintDrop hintDrop{m->hintFrames};       // (the upload leaves the hint: no return between it and the device entry keeps it)
+    HIP_TRY(hipSetDevice(m->sets[0]->device));
+    hipStream_t st = m->sets[0]->stream;
+    HostStaging &d = m->stage;
+    // the packing: fp32 (dev32; rel: within the voice's set, the int16 launch's) and int16 (the copy back's spans)
+    std::vector<uint64_t> dev32(V), rel(V), base32(S + 1), base16(S + 1);
+    std::vector<HostSpan> spans(V);
     uint64_t frameRows = 1, o32 = 0, o16 = 0;
-    uint32_t maxFrames = 0;
     for (size_t s = 0; s < S; s++) {
         const uint64_t ch = m->sets[s]->params.channels == 2 ? 2 : 1;
         base32[s] = o32;
         base16[s] = o16;
         for (size_t v = set_begin[s]; v < set_begin[s + 1]; v++) {
-            ns[v] = trm_batch_samples_for_frames(m->sets[s], nframes[v]);
+            const uint64_t ns = trm_batch_samples_for_frames(m->sets[s], nframes[v]);
             dev32[v] = o32;
-            dev16[v] = o16;
-            o32 += ns[v];
-            o16 += ns[v] * ch;
+            rel[v] = o32 - base32[s];
+            spans[v] = out16 ? HostSpan{out_offset[v], o16, ns * ch} : HostSpan{out_offset[v], o32, ns};
+            o32 += ns;
+            o16 += ns * ch;
             frameRows = std::max<uint64_t>(frameRows, frame_offset[v] + nframes[v]);
-            maxFrames = std::max(maxFrames, nframes[v]);
         }
     }
-    base32[S] = o32;
-    base16[S] = o16;
-    const std::vector<uint64_t> &packed = out16 ? dev16 : dev32;
-    bool dense = true;
-    for (size_t v = 0; v < V && dense; v++) dense = out_offset[v] == out_offset[0] + packed[v];
-    // within a set, the kernels' voice index runs from the longest voice down (as trm_batch's host entry orders a ragged batch):
-    // a workgroup's voices end together
-    std::vector<uint32_t> perm(V);
-    for (size_t v = 0; v < V; v++) perm[v] = (uint32_t)v;
-    for (size_t s = 0; s < S; s++)
-        std::stable_sort(perm.begin() + set_begin[s], perm.begin() + set_begin[s + 1], [&](uint32_t x, uint32_t y) { return nframes[x] > nframes[y]; });
-    std::vector<uint64_t> pFrameOff(V), pOutOff(V), pRel(V);
-    std::vector<uint32_t> pNFrames(V), pNs(V);
-    std::vector<float> pMx(V);
-    for (size_t s = 0; s < S; s++)
-        for (size_t i = set_begin[s]; i < set_begin[s + 1]; i++) {
-            pFrameOff[i] = frame_offset[perm[i]];
-            pNFrames[i] = nframes[perm[i]];
-            pOutOff[i] = dev32[perm[i]];
-            pRel[i] = dev32[perm[i]] - base32[s];
-        }
-    if ((rc = m->dFrames.reserve(frameRows * 16)) || (rc = m->dOut.reserve(o32 + 1)) || (rc = m->dFrameOff.reserve(V)) ||
-        (rc = m->dOutOff.reserve(V)) || (rc = m->dNFrames.reserve(V)) || (rc = m->dNSamples.reserve(V)) || (rc = m->dMax.reserve(V)))
-        return rc;
-    if (out16 && ((rc = m->dOut16.reserve(o16 + 1)) || (rc = m->dRelOff.reserve(V)))) return rc;
-    HIP_TRY(hipMemcpyAsync(m->dFrames.p, frames, frameRows * 16 * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m->dFrameOff.p, pFrameOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m->dOutOff.p, pOutOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m->dNFrames.p, pNFrames.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (out16) HIP_TRY(hipMemcpyAsync(m->dRelOff.p, pRel.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    m->hintFrames = pNFrames;       // (the lengths in launch order: the time split's plan and launch order)
-    rc = trm_mixed_synthesize_device(m, set_begin, m->dFrames.p, m->dFrameOff.p, m->dNFrames.p, maxFrames, m->dOut.p, m->dOutOff.p,
-                                     m->dNSamples.p, m->dMax.p, st);
+    bool dense = true;      // the caller's offsets are the packing, shifted by out_offset[0]
+    for (size_t v = 0; v < V && dense; v++) dense = out_offset[v] == out_offset[0] + spans[v].dev;
+    if ((rc = d.reserve(frameRows * 16, o32 + 1, V)) || (out16 && ((rc = d.dOut16.reserve(o16 + 1)) || (rc = d.dRelOff.reserve(V))))) return rc;
+    HostCall call(V, set_begin, S, nframes, false);
+    if ((rc = call.upload(d, frames, frameRows, frame_offset, dev32.data(), nframes, m->hintFrames, st))) return rc;
+    if (out16) HIP_TRY(hipMemcpyAsync(d.dRelOff.p, call.in_launch_order(rel.data()), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    rc = trm_mixed_synthesize_device(m, set_begin, d.dFrames.p, d.dFrameOff.p, d.dNFrames.p, *std::max_element(nframes, nframes + V), d.dOut.p, d.dOutOff.p,
+                                     d.dNSamples.p, d.dMax.p, st);
     if (rc) return rc;
-    if (out16) {
-        // each set scaled with its own volume, balance and channels (trm_batch_scale_to_int16_device per set)
-        for (size_t s = 0; s < S; s++) {
-            const size_t lo = set_begin[s], n = set_begin[s + 1] - lo;
-            if (n == 0) continue;
-            const trm::ScaleArgs sc = scale_args(m->sets[s], m->dOut.p + base32[s], m->dRelOff.p + lo, m->dNSamples.p + lo, m->dMax.p + lo,
-                                                 m->dOut16.p + base16[s], for_wav_data);
-            HIP_TRY(trm::launch_int16(sc, (uint32_t)n, st));
-        }
-        if (dense && o16 > 0) HIP_TRY(hipMemcpyAsync(out16 + out_offset[0], m->dOut16.p, o16 * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-        for (size_t s = 0; !dense && s < S; s++) {
-            const uint64_t ch = m->sets[s]->params.channels == 2 ? 2 : 1;
-            for (size_t v = set_begin[s]; v < set_begin[s + 1]; v++)
-                if (ns[v]) HIP_TRY(hipMemcpyAsync(out16 + out_offset[v], m->dOut16.p + dev16[v], ns[v] * ch * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-        }
-    } else {
-        if (dense && o32 > 0) HIP_TRY(hipMemcpyAsync(out + out_offset[0], m->dOut.p, o32 * sizeof(float), hipMemcpyDeviceToHost, st));
-        for (size_t v = 0; !dense && v < V; v++)
-            if (ns[v]) HIP_TRY(hipMemcpyAsync(out + out_offset[v], m->dOut.p + dev32[v], ns[v] * sizeof(float), hipMemcpyDeviceToHost, st));
+    // each set scaled with its own volume, balance and channels (trm_batch_scale_to_int16_device per set)
+    for (size_t s = 0; out16 && s < S; s++) {
+        const size_t lo = set_begin[s], n = set_begin[s + 1] - lo;
+        if (n == 0) continue;
+        const trm::ScaleArgs sc = scale_args(m->sets[s], d.dOut.p + base32[s], d.dRelOff.p + lo, d.dNSamples.p + lo, d.dMax.p + lo,
+                                             d.dOut16.p + base16[s], for_wav_data);
+        HIP_TRY(trm::launch_int16(sc, (uint32_t)n, st));
     }
-    HIP_TRY(hipMemcpyAsync(pNs.data(), m->dNSamples.p, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(pMx.data(), m->dMax.p, V * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (size_t i = 0; i < V; i++) {
-        number_samples[perm[i]] = pNs[i];
-        max_sample[perm[i]] = pMx[i];
-    }
-    return TRM_OK;
+    if ((rc = out16 ? copy_back(out16, d.dOut16.p, sizeof(int16_t), spans, dense, st) : copy_back(out, d.dOut.p, sizeof(float), spans, dense, st)))
+        return rc;
+    return call.results(d, st, number_samples, max_sample, nullptr);
 }
 
 int trm_mixed_synthesize_host(trm_mixed *m, const size_t *set_begin, const float *frames, const uint64_t *frame_offset,
@@ -670,7 +649,6 @@ int trm_mixed_scale_to_int16_device(trm_mixed *m, const size_t *set_begin, const
                                     const uint32_t *d_number_samples, const float *d_max_sample, int16_t *d_int16,
                                     const uint64_t *d_int16_offset, int for_wav_data, void *stream_)
 {
-    if (!m) return fail(TRM_EINVAL, "null handle");
     int rc = mixed_check_sets(m, set_begin);
     if (rc) return rc;
     const size_t V = set_begin[m->sets.size()];
@@ -686,7 +664,6 @@ int trm_mixed_sound_files_device(trm_mixed *m, const size_t *set_begin, const fl
                                  const uint32_t *d_number_samples, const float *d_max_sample, uint8_t *d_files,
                                  const uint64_t *d_file_offset, void *stream_)
 {
-    if (!m) return fail(TRM_EINVAL, "null handle");
     int rc = mixed_check_sets(m, set_begin);
     if (rc) return rc;
     const size_t V = set_begin[m->sets.size()];
@@ -703,7 +680,6 @@ int trm_mixed_events_to_files_host(trm_mixed *m, const size_t *set_begin, const 
                                    const uint64_t *event_offset, const uint32_t *nevents, const trm_intonation *settings,
                                    uint8_t *files, const uint64_t *file_offset, uint32_t *number_samples, float *max_sample)
 {
-    if (!m) return fail(TRM_EINVAL, "null handle");
     int rc = mixed_check_sets(m, set_begin);
     if (rc) return rc;
     const size_t S = m->sets.size(), V = set_begin[S];
@@ -714,88 +690,63 @@ int trm_mixed_events_to_files_host(trm_mixed *m, const size_t *set_begin, const 
     uint64_t E = 0;
     for (size_t v = 0; v < V; v++) E = std::max<uint64_t>(E, event_offset[v] + nevents[v]);
     if (E && (!event_times || !event_values)) return fail(TRM_EINVAL, "null pointer");
-    // every voice's frame count with its own settings, its sample count and file size with its own set's
+    // every voice's frame count with its own settings, its file size with its own set's; the images packed in caller order
     std::vector<uint32_t> nfr(V);
-    std::vector<uint64_t> fsize(V), devFile(V);
+    std::vector<uint64_t> devFile(V);
+    std::vector<HostSpan> spans(V);
     uint64_t fileBytes = 0;
-    uint32_t maxFrames = 0;
     for (size_t s = 0; s < S; s++)
         for (size_t v = set_begin[s]; v < set_begin[s + 1]; v++) {
             size_t n = 0;
             if ((rc = trm_events_count_frames(event_times ? event_times + event_offset[v] : nullptr, nevents[v], &settings[v], &n))) return rc;
             if (n > 0xFFFFFFFFull) return fail(TRM_ERANGE, "voice %zu: %zu frames", v, n);
             nfr[v] = (uint32_t)n;
-            maxFrames = std::max(maxFrames, nfr[v]);
-            fsize[v] = trm_sound_file_size(&m->sets[s]->params, trm_batch_samples_for_frames(m->sets[s], n));
             devFile[v] = fileBytes;
-            fileBytes += fsize[v];
+            spans[v] = {file_offset[v], fileBytes, trm_sound_file_size(&m->sets[s]->params, trm_batch_samples_for_frames(m->sets[s], n))};
+            fileBytes += spans[v].count;
         }
     bool dense = true;
     for (size_t v = 0; v < V && dense; v++) dense = file_offset[v] == file_offset[0] + devFile[v];
-    // within a set, the longest voice first (as mixed_host_impl orders it): a workgroup's voices end together
-    std::vector<uint32_t> perm(V);
-    for (size_t v = 0; v < V; v++) perm[v] = (uint32_t)v;
-    for (size_t s = 0; s < S; s++)
-        std::stable_sort(perm.begin() + set_begin[s], perm.begin() + set_begin[s + 1], [&](uint32_t x, uint32_t y) { return nfr[x] > nfr[y]; });
-    std::vector<uint64_t> pEvOff(V), pFrameOff(V), pOutOff(V), pFileOff(V);
-    std::vector<uint32_t> pNev(V), pNs(V), pNf(V);
-    std::vector<trm_intonation> pSet(V);
-    std::vector<float> pMx(V);
+    HostCall call(V, set_begin, S, nfr.data(), false);
+    // frames and fp32 PCM in launch order, every voice's PCM from a multiple of 32 samples
+    uint64_t *pFrameOff = call.keep<uint64_t>(), *pOutOff = call.keep<uint64_t>();
     uint64_t frameRows = 0, outs = 0;
     for (size_t s = 0; s < S; s++)
         for (size_t i = set_begin[s]; i < set_begin[s + 1]; i++) {
-            const uint32_t v = perm[i];
-            pEvOff[i] = event_offset[v];
-            pNev[i] = nevents[v];
-            pSet[i] = settings[v];
             pFrameOff[i] = frameRows;
-            frameRows += nfr[v];
+            frameRows += nfr[call.caller(i)];
             pOutOff[i] = outs;
-            outs += (trm_batch_samples_for_frames(m->sets[s], nfr[v]) + 31) / 32 * 32;
-            pFileOff[i] = devFile[v];
+            outs += (trm_batch_samples_for_frames(m->sets[s], nfr[call.caller(i)]) + 31) / 32 * 32;
         }
     trm_batch *b0 = m->sets[0];
     HIP_TRY(hipSetDevice(b0->device));
     hipStream_t st = b0->stream;
+    HostStaging &d = m->stage;
     if ((rc = m->evT.reserve(E + 1)) || (rc = m->evV.reserve((E + 1) * TRM_EVENT_VALUES)) || (rc = m->evOff.reserve(V)) || (rc = m->evN.reserve(V)) ||
-        (rc = m->dSettings.reserve(V)) || (rc = m->dFrames.reserve((frameRows + 1) * 16)) || (rc = m->dFrameOff.reserve(V)) ||
-        (rc = m->dNFrames.reserve(V)) || (rc = m->dOut.reserve(outs + 1)) || (rc = m->dOutOff.reserve(V)) || (rc = m->dNSamples.reserve(V)) ||
-        (rc = m->dMax.reserve(V)) || (rc = m->dFiles.reserve(fileBytes + 1)) || (rc = m->dFileOff.reserve(V)))
+        (rc = m->dSettings.reserve(V)) || (rc = d.reserve((frameRows + 1) * 16, outs + 1, V)) || (rc = m->dFiles.reserve(fileBytes + 1)) ||
+        (rc = m->dFileOff.reserve(V)))
         return rc;
     if (E) {
         HIP_TRY(hipMemcpyAsync(m->evT.p, event_times, E * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(m->evV.p, event_values, E * TRM_EVENT_VALUES * sizeof(double), hipMemcpyHostToDevice, st));
     }
-    HIP_TRY(hipMemcpyAsync(m->evOff.p, pEvOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m->evN.p, pNev.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m->dSettings.p, pSet.data(), V * sizeof(trm_intonation), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m->dFrameOff.p, pFrameOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m->dOutOff.p, pOutOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(m->dFileOff.p, pFileOff.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->evOff.p, call.in_launch_order(event_offset), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->evN.p, call.in_launch_order(nevents), V * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->dSettings.p, call.in_launch_order(settings), V * sizeof(trm_intonation), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.dFrameOff.p, pFrameOff, V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.dOutOff.p, pOutOff, V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m->dFileOff.p, call.in_launch_order(devFile.data()), V * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     // three launches; the generator writes the frame counts the tube kernel reads
-    if ((rc = trm_mixed_generate_frames_device(m, V, m->evT.p, m->evV.p, m->evOff.p, m->evN.p, m->dSettings.p, m->dFrames.p, m->dFrameOff.p,
-                                               m->dNFrames.p, st)))
+    if ((rc = trm_mixed_generate_frames_device(m, V, m->evT.p, m->evV.p, m->evOff.p, m->evN.p, m->dSettings.p, d.dFrames.p, d.dFrameOff.p, d.dNFrames.p, st)))
         return rc;
-    m->hintFrames.resize(V);
-    for (size_t i = 0; i < V; i++) m->hintFrames[i] = nfr[perm[i]];
-    if ((rc = trm_mixed_synthesize_device(m, set_begin, m->dFrames.p, m->dFrameOff.p, m->dNFrames.p, maxFrames, m->dOut.p, m->dOutOff.p,
-                                          m->dNSamples.p, m->dMax.p, st)))
-        return rc;
-    if ((rc = trm_mixed_sound_files_device(m, set_begin, m->dOut.p, m->dOutOff.p, m->dNSamples.p, m->dMax.p, m->dFiles.p, m->dFileOff.p, st)))
-        return rc;
-    if (dense && fileBytes > 0) HIP_TRY(hipMemcpyAsync(files + file_offset[0], m->dFiles.p, fileBytes, hipMemcpyDeviceToHost, st));
-    for (size_t v = 0; !dense && v < V; v++)
-        if (fsize[v]) HIP_TRY(hipMemcpyAsync(files + file_offset[v], m->dFiles.p + devFile[v], fsize[v], hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(pNf.data(), m->dNFrames.p, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(pNs.data(), m->dNSamples.p, V * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(pMx.data(), m->dMax.p, V * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (size_t i = 0; i < V; i++) {
-        if (pNf[i] != nfr[perm[i]]) return fail(TRM_EHIP, "generator wrote %u frames for voice %u, %u expected", pNf[i], perm[i], nfr[perm[i]]);
-        number_samples[perm[i]] = pNs[i];
-        max_sample[perm[i]] = pMx[i];
-    }
-    return TRM_OK;
+    const uint32_t *launchFrames = call.in_launch_order(nfr.data());
+    m->hintFrames.assign(launchFrames, launchFrames + V);
+    rc = trm_mixed_synthesize_device(m, set_begin, d.dFrames.p, d.dFrameOff.p, d.dNFrames.p, *std::max_element(nfr.begin(), nfr.end()), d.dOut.p, d.dOutOff.p,
+                                     d.dNSamples.p, d.dMax.p, st);
+    if (rc) return rc;
+    if ((rc = trm_mixed_sound_files_device(m, set_begin, d.dOut.p, d.dOutOff.p, d.dNSamples.p, d.dMax.p, m->dFiles.p, m->dFileOff.p, st))) return rc;
+    if ((rc = copy_back(files, m->dFiles.p, 1, spans, dense, st))) return rc;
+    return call.results(d, st, number_samples, max_sample, nfr.data());
 }
 
 }  // extern "C"

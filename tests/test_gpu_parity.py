@@ -977,6 +977,40 @@ def test_host_entry_leaves_gaps_between_voices_alone(g, form):
         assert np.all(out[mask] == 12345)
 
 
+def test_host_entry_permutes_and_leaves_gaps_alone(g, form):
+    """The same with 17 voices of 3 .. 12 frames in no order: more than 16 and unsorted, so the entry launches them from the
+    longest down and, the offsets being padded, copies back voice by voice.  fp32 bits equal to the dense call's, number_samples
+    and max_sample at the caller's indices, the sentinel between the voices intact, fp32 and int16."""
+    pd = cases.monet_default_params(44100.0)
+    b = g.TRMBatch(g.TRMInputParameters.from_dict(pd))
+    lens = [3 + (7 * v) % 10 for v in range(17)]
+    assert lens != sorted(lens, reverse=True) and min(lens) == 3 and max(lens) == 12 and len(set(lens)) > 5
+    voices = [np.asarray(v, dtype=np.float32)[:n] for v, n in zip(cases.config3_frames(17, nframes=12), lens)]
+    ref, ns_ref, mx_ref = b.synthesize(voices)
+    nfr = np.array(lens, dtype=np.uint32)
+    foff = np.concatenate([[0], np.cumsum(nfr[:-1])]).astype(np.uint64)
+    frames = np.ascontiguousarray(np.concatenate(voices), dtype=np.float32)
+    nout = np.array([b.samples_for_frames(int(n)) for n in nfr], dtype=np.uint64)
+    assert len(set(int(x) for x in ns_ref)) > 5                 # (a result at another voice's index shows)
+    pad = 1000
+    ooff = (np.concatenate([[0], np.cumsum(nout[:-1] + pad)]) + pad).astype(np.uint64)
+    total = int(ooff[-1] + nout[-1] + pad)
+    L = g.lib()
+    for dtype, entry, extra in ((np.float32, L.trm_batch_synthesize_host, ()), (np.int16, L.trm_batch_synthesize_host_int16, (0,))):
+        out = np.full(total, 12345, dtype=dtype)
+        ns = np.zeros(17, dtype=np.uint32)
+        mx = np.zeros(17, dtype=np.float32)
+        rc = entry(b._h, 17, frames.ctypes.data, foff.ctypes.data, nfr.ctypes.data, out.ctypes.data, ooff.ctypes.data,
+                   ns.ctypes.data, mx.ctypes.data, *extra)
+        assert rc == 0 and np.array_equal(ns, ns_ref) and np.array_equal(mx, mx_ref)
+        mask = np.ones(total, dtype=bool)
+        for v in range(17):
+            mask[int(ooff[v]):int(ooff[v] + nout[v])] = False
+            if dtype is np.float32:
+                assert np.array_equal(out[int(ooff[v]):int(ooff[v] + nout[v])], ref[v]), v
+        assert np.all(out[mask] == 12345)
+
+
 
 @pytest.mark.parametrize("split", ["auto", "off"])
 def test_full_size_configs4_per_gpu_batch(g, split):

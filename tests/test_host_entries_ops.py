@@ -1,0 +1,461 @@
+"""The one-shot host-buffer entries without a GPU (gnuspeech_amd/csrc/trm_capi.cc: trm_batch_synthesize_host[_int16],
+trm_multi_synthesize_host; trm_mixed.cc: trm_mixed_synthesize_host[_int16], trm_mixed_events_to_files_host): the library's host
+translation units linked with the CPU stand-in of the HIP runtime (tests/_emul/hip_host_mock.cc, with its checking heap) and the
+recorder tests/_emul/hip_op_trace_host.cc.  The recorder writes down every operation an entry enqueues -- what
+hip_op_trace_split.cc writes down, and every copy back to the host with its byte count, its destination's offset in the caller's
+output buffer and its source's offset in its device block, and every stream synchronise -- and gives the launches per-voice
+results by the kernels' voice index, so that a result at the wrong caller's index shows.
+
+Every case of CASES is held against tests/golden/host_entries_parent.json: the return code, the trm_last_error text of a failure,
+what trm_*_last_time_split and trm_*_last_kernel report, the recorded operations, and a hash of number_samples and max_sample as
+the caller gets them.  The golden was recorded ONCE from the commit before the three entries shared one staging path (6b4aea4),
+never from the code under test: that commit's gnuspeech_amd/csrc and include/ were checked out into a scratch directory and
+`python tests/test_host_entries_ops.py record <that csrc>` built them with this module's stand-in and recorder and ran record().
+Runs of more than 24 copies back (a gapped launch of many voices) are kept as their count and a hash."""
+import ctypes as C
+import gc
+import hashlib
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cases                                 # noqa: E402
+import host_mock as M                        # noqa: E402
+import split_warmup_common as S              # noqa: E402
+
+CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
+MOCKS = ["hip_host_mock.cc", "hip_op_trace_host.cc"]
+WRAPPED = sorted(set(re.findall(r"^hipError_t __wrap_(\w+)\(", open(os.path.join(ROOT, "tests", "_emul", "hip_op_trace_host.cc")).read(), re.M)))
+assert len(WRAPPED) == 18 and "hipStreamSynchronize" in WRAPPED and any("launch_tracks_mixed" in w for w in WRAPPED)
+GOLDEN = os.path.join(ROOT, "tests", "golden", "host_entries_parent.json")
+AUTO, OFF = -1, 0                            # TRM_TIME_SPLIT_*
+SENTINEL = {"f32": 12345.0, "i16": 12345, "files": 0x5A}
+DTYPE = {"f32": np.float32, "i16": np.int16, "files": np.uint8}
+
+PDS = {
+    "monet": cases.monet_default_params(44100.0),
+    "verdict": S.VERDICT_PD,
+    "m22k": cases.monet_default_params(22050.0),
+    "short22k": S.SHORT_22K_PD,              # the 15 cm tube at 22.05 kHz: down-sampling
+    "tract": cases.tract_default_params(),
+    "stereo": dict(cases.monet_default_params(44100.0), channels=2, balance=0.25, outputFileFormat=2),
+    "badfmt": dict(cases.monet_default_params(44100.0), outputFileFormat=99),
+    # one control period of 19 750 tube samples: 2^31 tube samples are 108 737 frames, and at 1 kHz few output samples
+    "slow": dict(cases.monet_default_params(1000.0), controlRate=1.0),
+}
+MIXED_SETS = {
+    "pair": ["monet", "verdict"],
+    "triple": ["monet", "verdict", "short22k"],
+    "triple_st": ["monet", "stereo", "short22k"],
+    "five": ["monet", "verdict", "m22k", "short22k", "tract"],             # (m22k gets no voices)
+    "badfmt": ["monet", "badfmt"],
+    "slow": ["monet", "slow"],
+}
+SEVEN = [12, 7, 12, 3, 1, 9, 12]
+DRAW_SEED = 20250119
+
+
+def lengths_of(kind, V):
+    """a launch's frame counts: `uns` 3 .. 12 in no order, `sort` the same descending, `edge` with a voice of no frames and one
+    of a single frame, `rag` the seeded ragged draw (cut down: the stand-in's PCM is real memory), `seven` the mixed entries' own"""
+    if kind == "seven":
+        return np.array((SEVEN * (V // 7 + 1))[:V], dtype=np.uint32)
+    if kind == "rag":
+        d = np.random.default_rng(DRAW_SEED).integers(150, 1501, size=V)
+        return np.maximum(d // (4 if V <= 64 else 10), 2).astype(np.uint32)
+    n = (3 + (np.arange(V) * 7) % 10).astype(np.uint32)
+    if kind == "sort":
+        n = np.sort(n)[::-1].copy()
+    if kind == "edge":
+        n[V // 2], n[V // 3] = 0, 1
+    return n
+
+
+def set_begin_of(sets, V):
+    live = [s for s in range(len(sets)) if not (len(sets) == 5 and s == 2)]
+    counts = [0] * len(sets)
+    for i, s in enumerate(live):
+        counts[s] = V // len(live) + (1 if i < V % len(live) else 0)
+    return np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+
+
+# ------------------------------------------------------------------------------------------------ the cases
+def all_cases():
+    out = []
+
+    def b(pd="monet", V=17, lens="uns", lay="dense", fmt="f32", setting=AUTO, bad="-"):
+        out.append(dict(kind="b", pd=pd, V=V, lens=lens, lay=lay, fmt=fmt, setting=setting, bad=bad))
+
+    def m(sets="pair", V=7, lay="dense", fmt="f32", setting=OFF, calls=1, bad="-", kind="m", lens=None):
+        out.append(dict(kind=kind, sets=sets, V=V, lens=lens or ("seven" if V == 7 else "rag"), lay=lay, fmt=fmt, setting=setting, calls=calls, bad=bad))
+    for fmt in ("f32", "i16"):
+        for V, lens in ((5, "sort"), (5, "uns"), (16, "uns"), (17, "uns"), (17, "sort"), (64, "rag"), (1024, "rag")):
+            for lay in ("dense", "gap"):
+                b(V=V, lens=lens, lay=lay, fmt=fmt)
+        b(lens="edge", lay="gap", fmt=fmt)
+    b(lens="edge")
+    b(pd="stereo", lay="gap"), b(pd="stereo", fmt="i16"), b(pd="stereo", lay="gap", fmt="i16")
+    b(pd="short22k", lay="gap"), b(pd="short22k", fmt="i16")
+    b(V=64, lens="rag", setting=OFF), b(V=64, lens="rag", setting=20)
+    for fmt in ("f32", "i16"):
+        for sets in ("pair", "triple", "triple_st", "five"):
+            m(sets, 7, "gap", fmt)
+        m("pair", 64, "dense", fmt, AUTO), m("triple_st", 64, "shift", fmt), m("five", 64, "gap", fmt, AUTO), m("triple", 64, "dense", fmt)
+    m("triple_st", 7, "shift", "i16", AUTO)
+    m("triple", 64, "dense", "f32", AUTO, calls=2)                         # the second call of one shape uploads no map
+    for sets, V, lay in (("pair", 7, "dense"), ("triple_st", 7, "gap"), ("five", 64, "gap"), ("triple", 64, "dense")):
+        m(sets, V, lay, "files", kind="e")
+    m("pair", 7, "gap", "files", kind="e", lens="edge")                    # (a voice without events among them)
+    out.append(dict(kind="x", V=40, lens="uns", lay="dense", fmt="f32", bad="-"))          # trm_multi: two shards on device 0
+    # refusals
+    for bad in ("frames", "out", "out_offset", "long"):
+        b(bad=bad, pd="slow" if bad == "long" else "monet", V=2 if bad == "long" else 17)
+    for bad in ("frames", "out", "number_samples", "begin0", "decreasing"):
+        m(bad=bad)
+    m("slow", 2, bad="long", lens="uns")
+    for bad in ("settings", "files", "times", "decreasing"):
+        m(fmt="files", kind="e", bad=bad)
+    m("badfmt", fmt="files", kind="e", bad="format")
+    m("slow", 2, fmt="files", kind="e", bad="long", lens="uns")
+    out.append(dict(kind="x", V=40, lens="uns", lay="dense", fmt="f32", bad="interleave"))
+    out.append(dict(kind="x", V=40, lens="uns", lay="dense", fmt="f32", bad="frames"))
+    return out
+
+
+def key_of(c):
+    st = {AUTO: "A", OFF: "off"}.get(c.get("setting"), str(c.get("setting")))
+    return " ".join(str(x) for x in (c["kind"], c.get("pd", c.get("sets", "multi")), "V%d" % c["V"], c["lens"], c["lay"], c["fmt"], "S" + st,
+                                     "x%d" % c.get("calls", 1), c["bad"]))
+
+
+CASES = {key_of(c): c for c in all_cases()}
+
+
+# ------------------------------------------------------------------------------------------------ the library on the stand-in
+def build(out, csrc=CSRC):
+    """the host units of `csrc` with the stand-in and the recorder in front of it"""
+    srcs = [os.path.join(csrc, u + ".cc") for u in M.host_units(csrc)]
+    mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in MOCKS]
+    wrap = ["-Wl,--wrap=" + w for w in WRAPPED]
+    subprocess.check_call(["hipcc", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-o", out] + wrap + mocks + srcs + ["-lpthread", "-lm"])
+
+
+def bind(path):
+    from gnuspeech_amd import _capi
+    saved = (_capi._lib, _capi.LIB_PATH)
+    _capi._lib, _capi.LIB_PATH = None, path
+    try:
+        L = _capi.lib()
+    finally:
+        _capi._lib, _capi.LIB_PATH = saved
+    assert L.trm_device_count() == 1
+    L.trace_take.argtypes, L.trace_take.restype = [C.c_char_p, C.c_size_t], C.c_size_t
+    L.trace_out_buffer.argtypes, L.trace_out_buffer.restype = [C.c_void_p, C.c_size_t], None
+    return M.bind(L)
+
+
+def trace_take(L):
+    n = L.trace_take(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    L.trace_take(buf, n + 1)
+    return buf.value.decode().splitlines()
+
+
+def compact(ops):
+    """runs of more than 24 copies back as their count and a hash"""
+    out, i = [], 0
+    while i < len(ops):
+        j = i
+        while j < len(ops) and ops[j].startswith("dh ") and ops[i].startswith("dh "):
+            j += 1
+        if j - i > 24:
+            out.append("dh*%d %s" % (j - i, hashlib.sha1("|".join(ops[i:j]).encode()).hexdigest()[:16]))
+        else:
+            out.extend(ops[i:max(j, i + 1)])
+        i = max(j, i + 1)
+    return out
+
+
+def params_of(name):
+    from gnuspeech_amd import TRMInputParameters
+    return TRMInputParameters.from_dict(PDS[name]).c
+
+
+def warm_noise(L):
+    """the process-wide noise sequence, generated once for the longest launch of any case: not an entry's business"""
+    h = C.c_void_p()
+    p = params_of("tract")
+    assert L.trm_batch_create(C.byref(p), 0, C.byref(h)) == 0
+    buf = np.zeros(1 << 20, dtype=np.float32)
+    assert L.trm_batch_noise_table(h, buf.ctypes.data, len(buf)) == 0
+    L.trm_batch_destroy(h)
+
+
+class Launch:
+    """a case's host arrays: frames row after row in caller order, the output laid out by `lay` (dense: packed from 0; shift: packed
+    from 100; gap: 40 elements in front of every voice) from the per-voice element counts `sizes`"""
+
+    def __init__(self, c, nfr, sizes, ch=1):
+        V = len(nfr)
+        self.ch = ch                                 # elements per unit of `sizes` and of the offsets (a uniform stereo batch's int16: 2)
+        self.nfr = nfr
+        self.foff = np.concatenate([[0], np.cumsum(nfr[:-1])]).astype(np.uint64)
+        rows = max(int(nfr.sum()), 1)
+        self.frames = (np.arange(rows * 16, dtype=np.float32) % 97.0).reshape(rows, 16)
+        pad = 40 if c["lay"] == "gap" else 0
+        sizes = np.asarray(sizes, dtype=np.uint64)
+        self.sizes = sizes
+        self.ooff = (np.concatenate([[0], np.cumsum(sizes[:-1] + pad)]) + pad + (100 if c["lay"] == "shift" else 0)).astype(np.uint64)
+        self.out = np.full((int(self.ooff[-1] + sizes[-1]) + 40) * ch, SENTINEL[c["fmt"]], dtype=DTYPE[c["fmt"]])
+        self.ns, self.mx = np.zeros(V, dtype=np.uint32), np.zeros(V, dtype=np.float32)
+
+    def check(self, c, rc, permuted_results=True):
+        """what no golden is needed for: the sentinel between the voices is intact; the per-voice results are at the caller's
+        indices (the recorder's rule: 3 * nframes + 1, the voice's own frame offset)"""
+        if rc:
+            return
+        mask = np.ones(len(self.out), dtype=bool)
+        for o, n in zip(self.ooff, self.sizes):
+            mask[int(o) * self.ch:int(o + n) * self.ch] = False
+        assert np.all(self.out[mask] == SENTINEL[c["fmt"]]), "a copy back wrote between the voices"
+        assert np.array_equal(self.ns, 3 * self.nfr + 1), (self.ns, self.nfr)
+        if c["kind"] != "e":
+            assert np.array_equal(self.mx, (self.foff % 4096).astype(np.float32) + 0.5)
+
+    def results_hash(self):
+        return hashlib.sha1(self.ns.tobytes() + self.mx.tobytes()).hexdigest()[:16]
+
+
+def result(L, rc, split, kernel, ops, res):
+    return {"rc": rc, "err": L.trm_last_error().decode() if rc else "", "split": split, "kernel": kernel, "ops": "|".join(compact(ops)), "res": res}
+
+
+def traced(L, la, call):
+    L.trace_out_buffer(la.out.ctypes.data, la.out.nbytes)
+    L.trace_enable(1)
+    trace_take(L)
+    try:
+        rc = call()
+        return rc, trace_take(L)
+    finally:
+        L.trace_enable(0)
+
+
+def ptr(a, c, name):
+    return None if c["bad"] == name else a.ctypes.data
+
+
+def run_batch(L, c):
+    h = C.c_void_p()
+    p = params_of(c["pd"])
+    assert L.trm_batch_create(C.byref(p), 0, C.byref(h)) == 0, L.trm_last_error()
+    try:
+        assert L.trm_batch_set_time_split(h, c["setting"]) == 0
+        V = c["V"]
+        nfr = lengths_of(c["lens"], V)
+        if c["bad"] == "long":
+            nfr[0] = 108800
+        ch = 2 if (PDS[c["pd"]]["channels"] == 2 and c["fmt"] == "i16") else 1
+        nout = np.array([L.trm_batch_samples_for_frames(h, int(n)) for n in nfr], dtype=np.uint64)
+        la = Launch(c, nfr, nout if c["bad"] != "long" else np.ones(V), ch)
+        ooff = la.ooff
+        args = [h, V, ptr(la.frames, c, "frames"), la.foff.ctypes.data, nfr.ctypes.data, ptr(la.out, c, "out"), ptr(ooff, c, "out_offset"),
+                la.ns.ctypes.data, la.mx.ctypes.data]
+        entry = L.trm_batch_synthesize_host if c["fmt"] == "f32" else L.trm_batch_synthesize_host_int16
+        rc, ops = traced(L, la, lambda: entry(*(args + ([0] if c["fmt"] == "i16" else []))))
+        la.check(c, rc)
+        s, w = C.c_uint32(), C.c_uint32()
+        assert L.trm_batch_last_time_split(h, C.byref(s), C.byref(w)) == 0
+        return result(L, rc, [s.value, w.value], L.trm_batch_last_kernel(h), ops, la.results_hash())
+    finally:
+        L.trm_batch_destroy(h)
+
+
+def run_mixed(L, c):
+    from gnuspeech_amd import MMIntonation, intonation_struct
+    from gnuspeech_amd._capi import TrmInputParams, TrmIntonation
+    names = MIXED_SETS[c["sets"]]
+    arr = (TrmInputParams * len(names))(*[params_of(n) for n in names])
+    h = C.c_void_p()
+    assert L.trm_mixed_create(arr, len(names), 0, C.byref(h)) == 0, L.trm_last_error()
+    try:
+        V = c["V"]
+        sb = set_begin_of(names, V)
+        set_of = np.searchsorted(sb, np.arange(V), side="right") - 1
+        if c["bad"] == "begin0":
+            sb = sb + 1
+        if c["bad"] == "decreasing":
+            sb[1] = sb[2] + 1
+        sbc = (C.c_size_t * len(sb))(*[int(x) for x in sb])
+        assert L.trm_mixed_set_time_split(h, c["setting"]) == 0
+        nfr = lengths_of(c["lens"], V)
+        if c["bad"] == "long":
+            nfr[V - 1] = 108800
+        nout = np.array([L.trm_mixed_samples_for_frames(h, int(set_of[v]), int(nfr[v])) for v in range(V)], dtype=np.uint64)
+        chans = np.array([2 if PDS[names[s]]["channels"] == 2 else 1 for s in set_of], dtype=np.uint64)
+        if c["kind"] == "e":
+            sizes = np.array([L.trm_mixed_sound_file_size(h, int(set_of[v]), int(nout[v])) for v in range(V)], dtype=np.uint64)
+        else:
+            sizes = nout * chans if c["fmt"] == "i16" else nout
+        la = Launch(c, nfr, sizes if c["bad"] != "long" else np.ones(V))
+        res = []
+        for _ in range(c["calls"]):
+            if c["kind"] == "e":
+                # two events per voice, 4 ms per frame; a voice of no frames has no events
+                nev = np.where(nfr > 0, 2, 0).astype(np.uint32)
+                eoff = np.concatenate([[0], np.cumsum(nev[:-1])]).astype(np.uint64)
+                times = np.concatenate([[0, 4 * int(n)] for n in nfr if n > 0] or [[]]).astype(np.uint32)
+                values = np.zeros((len(times), 36), dtype=np.float64) + 1.0
+                st = (TrmIntonation * V)(*[intonation_struct(MMIntonation(), -12.0) for _ in range(V)])
+                args = [h, sbc, ptr(times, c, "times"), values.ctypes.data, eoff.ctypes.data, nev.ctypes.data, None if c["bad"] == "settings" else C.addressof(st),
+                        ptr(la.out, c, "files"), la.ooff.ctypes.data, la.ns.ctypes.data, la.mx.ctypes.data]
+                rc, ops = traced(L, la, lambda: L.trm_mixed_events_to_files_host(*args))
+            else:
+                args = [h, sbc, ptr(la.frames, c, "frames"), la.foff.ctypes.data, nfr.ctypes.data, ptr(la.out, c, "out"), la.ooff.ctypes.data,
+                        ptr(la.ns, c, "number_samples"), la.mx.ctypes.data]
+                entry = L.trm_mixed_synthesize_host if c["fmt"] == "f32" else L.trm_mixed_synthesize_host_int16
+                rc, ops = traced(L, la, lambda: entry(*(args + ([0] if c["fmt"] == "i16" else []))))
+            la.check(c, rc)
+            s, w = C.c_uint32(), (C.c_uint32 * len(names))()
+            assert L.trm_mixed_last_time_split(h, C.byref(s), w, len(names)) == 0
+            res.append(result(L, rc, [s.value] + list(w), L.trm_mixed_last_kernel(h), ops, la.results_hash()))
+        return res
+    finally:
+        L.trm_mixed_destroy(h)
+
+
+def run_multi(L, c):
+    """two shards on device 0, a thread each: their operations interleave as they please, so the record is kept sorted"""
+    h = C.c_void_p()
+    p = params_of("monet")
+    dev = (C.c_int * 2)(0, 0)
+    assert L.trm_multi_create(C.byref(p), dev, 2, C.byref(h)) == 0, L.trm_last_error()
+    try:
+        V = c["V"]
+        nfr = lengths_of(c["lens"], V)
+        b = C.c_void_p()
+        assert L.trm_batch_create(C.byref(p), 0, C.byref(b)) == 0
+        nout = np.array([L.trm_batch_samples_for_frames(b, int(n)) for n in nfr], dtype=np.uint64)
+        L.trm_batch_destroy(b)
+        la = Launch(c, nfr, nout)
+        if c["bad"] == "interleave":
+            la.ooff = la.ooff[::-1].copy()                   # the first shard's voices lie behind AND in front of the second's
+            la.ooff[0], la.ooff[V - 1] = la.ooff[V - 1], la.ooff[0]
+        args = [h, V, ptr(la.frames, c, "frames"), la.foff.ctypes.data, nfr.ctypes.data, la.out.ctypes.data, la.ooff.ctypes.data, la.ns.ctypes.data, la.mx.ctypes.data]
+        rc, ops = traced(L, la, lambda: L.trm_multi_synthesize_host(*args))
+        if rc == 0:
+            assert np.array_equal(la.ns, 3 * nfr + 1)
+        return result(L, rc, [], 0, sorted(ops), la.results_hash())
+    finally:
+        L.trm_multi_destroy(h)
+
+
+def run_case(L, c):
+    """(the library reads its environment at create: a case runs with none of it set)"""
+    saved = {k: os.environ.pop(k, None) for k in ("TRM_TUBE_KERNEL", "TRM_QUAD_CUS", "TRM_TIME_SPLIT", "TRM_DOWNSAMPLE_GENERIC")}
+    try:
+        return {"b": run_batch, "m": run_mixed, "e": run_mixed, "x": run_multi}[c["kind"]](L, c)
+    finally:
+        os.environ.update({k: v for k, v in saved.items() if v is not None})
+
+
+def first(r):
+    return r[0] if isinstance(r, list) else r
+
+
+def copies_back(ops):
+    return sum(int(o.split()[0][3:]) if o.startswith("dh*") else 1 for o in ops.split("|") if o.startswith("dh"))
+
+
+def assert_covers(out):
+    """the record holds what the cases are there for: both sides of the batch's permutation rule, one copy and many, split
+    launches, a second call without a map, every refusal"""
+    ops = lambda k: first(out[k])["ops"]
+    up = lambda k: [o for o in ops(k).split("|") if o.startswith("up")]
+    assert up(key_of(dict(kind="b", pd="monet", V=16, lens="uns", lay="dense", fmt="f32", setting=AUTO, bad="-")))[3].split()[2] != \
+        up(key_of(dict(kind="b", pd="monet", V=17, lens="uns", lay="dense", fmt="f32", setting=AUTO, bad="-")))[3].split()[2]
+    for k, r in out.items():
+        c, r0 = CASES[k], first(r)
+        assert (r0["rc"] != 0) == (c["bad"] != "-"), (k, r0)
+        if c["bad"] == "-" and c["kind"] != "x":
+            assert copies_back(r0["ops"]) >= (c["V"] // 2 if c["lay"] == "gap" else 3) and r0["ops"].endswith("|ssync"), (k, r0)
+            if c["lay"] != "gap":
+                assert copies_back(r0["ops"]) == 3 + (c["kind"] == "e"), (k, r0["ops"])
+    assert any(first(r)["split"] and first(r)["split"][0] for r in out.values())
+    two = [r for k, r in out.items() if CASES[k].get("calls") == 2][0]
+    assert two[0]["ops"].count("upa") > two[1]["ops"].count("upa") and copies_back(two[0]["ops"]) == copies_back(two[1]["ops"])
+    errs = " ".join(first(r)["err"] for r in out.values())
+    for text in ("null pointer", "set_begin[0]", "set_begin decreases", "parameter set 1: unknown sound file format 99", "interleave", "utterance too long",
+                 "utterance too long (parameter set 1)"):
+        assert text in errs, text
+
+
+def record(lib_path):
+    """every case's result from the library at `lib_path` (the PARENT's host units on this module's stand-in and recorder)"""
+    L = bind(lib_path)
+    warm_noise(L)
+    out = {k: run_case(L, c) for k, c in CASES.items()}
+    gc.collect()
+    M.assert_clean(L)
+    assert_covers(out)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the tests
+@pytest.fixture(scope="module")
+def L(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("hostmock_entries") / "libtrm_hostmock_entries.so")
+    build(out)
+    lib = bind(out)
+    warm_noise(lib)
+    yield lib
+    gc.collect()
+    M.assert_clean(lib)
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return json.load(open(GOLDEN))
+
+
+def test_the_golden_holds_every_case_and_is_the_smaller_file(golden):
+    assert sorted(golden) == sorted(CASES) and 55 <= len(CASES) <= 90
+    assert_covers(golden)
+    assert os.path.getsize(GOLDEN) < os.path.getsize(os.path.join(ROOT, "tests", "golden", "split_plan_parent.json"))
+
+
+def _groups():
+    groups = {}
+    for k, c in CASES.items():
+        groups.setdefault(("refusals" if c["bad"] != "-" else "%s-%s" % (c["kind"], c["fmt"])), []).append(k)
+    return groups
+
+
+@pytest.mark.parametrize("group", sorted(_groups()))
+def test_entries_do_what_the_parents_did(L, golden, group):
+    """return code, error text, last_time_split, last_kernel, every enqueued operation and the results as the caller gets them,
+    case by case, as the commit before the entries shared their staging; the stand-in's heap saw no copy leave its block"""
+    M.violations(L)
+    bad = []
+    for k in _groups()[group]:
+        got = run_case(L, CASES[k])
+        if got != golden[k]:
+            bad.append((k, got, golden[k]))
+    M.assert_clean(L)
+    assert not bad, "%d of %d cases differ; first: %r" % (len(bad), len(_groups()[group]), bad[0])
+
+
+if __name__ == "__main__":
+    # python tests/test_host_entries_ops.py record <csrc of the parent commit> [out.json]
+    assert sys.argv[1] == "record"
+    sys.path.insert(0, ROOT)
+    lib_path = os.path.join(os.path.dirname(os.path.abspath(sys.argv[2])), "libtrm_hostmock_entries_parent.so")
+    build(lib_path, sys.argv[2])
+    json.dump(record(lib_path), open(sys.argv[3] if len(sys.argv) > 3 else GOLDEN, "w"), indent=0, sort_keys=True)

@@ -223,3 +223,53 @@ def test_large_grid_crosses_slice_boundary(g, monkeypatch):
         assert np.array_equal(ns[idx], uns)
         got = np.concatenate([pcm[i] for i in idx])
         assert got.tobytes() == np.concatenate(upcm).tobytes(), s
+
+
+@pytest.mark.parametrize("int16", [False, True])
+def test_host_entry_permutes_and_leaves_gaps_alone(g, int16, monkeypatch):
+    """trm_mixed_synthesize_host[_int16] called with padded offsets: Monet's 44.1 kHz mono voice, a stereo set and the 22.05 kHz
+    down-sampling tube; 7 voices of 12, 7, 12, 3, 1, 9 and 12 frames dealt so that no set's voices are in launch order, so the
+    entry permutes within every set and copies back voice by voice.  Every voice bit-equal to a TRMBatch of its own set (split
+    off, same form), the sentinel between the voices intact, number_samples and max_sample at the caller's indices."""
+    import ctypes as C
+    _env(monkeypatch, "auto")
+    plist = [_ip(g, length=17.5), _ip(g, length=15.0, channels=2, balance=-0.3), _ip(g, outputRate=22050.0, length=15.0)]
+    lens, sets = [7, 12, 3, 1, 12, 9, 12], [0, 0, 0, 1, 1, 2, 2]
+    set_begin = np.array([0, 3, 5, 7], dtype=np.uint64)
+    assert sorted(lens) == sorted([12, 7, 12, 3, 1, 9, 12])
+    for s in range(3):
+        own = [n for n, x in zip(lens, sets) if x == s]
+        assert own != sorted(own, reverse=True)
+    voices = [np.asarray(v, dtype=np.float32)[:n] for v, n in zip(cases.config4_frames(7, seed=23, lo=12, hi=12), lens)]
+    m = g.TRMMixedBatch(plist, device=0)
+    m.synthesize(voices, sets)
+    form = m.last_kernel
+    monkeypatch.setenv("TRM_TUBE_KERNEL", form)
+    m = g.TRMMixedBatch(plist, device=0)
+    ref = [None] * 7
+    for s, (idx, (upcm, uns, umx), uk) in _uniform(g, plist, voices, sets, form, int16=0 if int16 else None).items():
+        assert uk == form
+        for k, i in enumerate(idx):
+            ref[i] = (np.ascontiguousarray(upcm[k]).reshape(-1), int(uns[k]), umx[k])
+    nfr = np.array(lens, dtype=np.uint32)
+    foff = np.concatenate([[0], np.cumsum(nfr[:-1])]).astype(np.uint64)
+    frames = np.ascontiguousarray(np.concatenate(voices), dtype=np.float32)
+    width = np.array([m.samples_for_frames(s, n) * (m.channels(s) if int16 else 1) for s, n in zip(sets, lens)], dtype=np.uint64)
+    assert [int(w) for w in width] == [len(r[0]) for r in ref] and len(set(r[1] for r in ref)) >= 5
+    pad = 1000
+    ooff = (np.concatenate([[0], np.cumsum(width[:-1] + pad)]) + pad).astype(np.uint64)
+    total = int(ooff[-1] + width[-1] + pad)
+    out = np.full(total, 12345, dtype=np.int16 if int16 else np.float32)
+    ns, mx = np.zeros(7, dtype=np.uint32), np.zeros(7, dtype=np.float32)
+    assert set_begin.itemsize == C.sizeof(C.c_size_t)
+    L = g.lib()
+    args = [m._h, set_begin.ctypes.data, frames.ctypes.data, foff.ctypes.data, nfr.ctypes.data, out.ctypes.data, ooff.ctypes.data, ns.ctypes.data, mx.ctypes.data]
+    rc = L.trm_mixed_synthesize_host_int16(*args, 0) if int16 else L.trm_mixed_synthesize_host(*args)
+    assert rc == 0, L.trm_last_error()
+    mask = np.ones(total, dtype=bool)
+    for v, (rp, rn, rm) in enumerate(ref):
+        lo, hi = int(ooff[v]), int(ooff[v] + width[v])
+        mask[lo:hi] = False
+        assert out[lo:hi].tobytes() == rp.tobytes(), v
+        assert int(ns[v]) == rn and mx[v].tobytes() == rm.tobytes(), v
+    assert np.all(out[mask] == 12345)

@@ -331,3 +331,48 @@ def test_refusals_name_the_set(g):
     # the int16 entry does not read the container: the set with the unknown format still scales
     pcm16, off = m.scale_to_int16_device(st)
     assert pcm16.numel() >= 1
+
+
+def test_host_entry_with_gapped_file_offsets_leaves_the_gaps_alone(g):
+    """trm_mixed_events_to_files_host with padded file_offset: Monet's 44.1 kHz mono voice, a stereo set and the 22.05 kHz
+    down-sampling tube, no set's voices in launch order, so the images come back one by one and from a permuted launch: every
+    image byte-equal to the dense call's, the sentinel between the images intact, the results at the caller's indices."""
+    rng = np.random.default_rng(29)
+    plist = [_ip(g, outputFileFormat=0, length=17.5), _ip(g, outputFileFormat=2, length=15.0, channels=2, balance=-0.3),
+             _ip(g, outputFileFormat=1, length=15.0, outputRate=22050.0)]
+    sets = [0, 0, 0, 1, 1, 2, 2]
+    set_begin = np.array([0, 3, 5, 7], dtype=np.uint64)
+    lists = _event_voices(7, 31, counts=(5, 12, 3, 2, 9, 4, 12))
+    raw = [_settings(g, k, rng, ranges=False) for k in range(7)]
+    ranges = [(0, 0)] * 7
+    m = g.TRMMixedBatch(plist, device=0)
+    dense = m.synthesize_event_lists(_event_lists(g, lists, raw, ranges), sets)
+    els = _event_lists(g, lists, raw, ranges)
+    nframes = [el.count_frames() for el in els]
+    for s in range(3):
+        own = [n for n, x in zip(nframes, sets) if x == s]
+        assert own != sorted(own, reverse=True), (s, own)
+    arrays = [el.arrays() for el in els]
+    settings = (g._capi.TrmIntonation * 7)(*[el.settings(0, 0) for el in els])
+    nev = np.array([len(t) for t, _ in arrays], dtype=np.uint32)
+    eoff = np.concatenate([[0], np.cumsum(nev[:-1])]).astype(np.uint64)
+    times = np.ascontiguousarray(np.concatenate([t for t, _ in arrays]), dtype=np.uint32)
+    values = np.ascontiguousarray(np.concatenate([v for _, v in arrays]), dtype=np.float64)
+    sizes = np.array([len(x) for x in dense], dtype=np.uint64)
+    pad = 777
+    foff = (np.concatenate([[0], np.cumsum(sizes[:-1] + pad)]) + pad).astype(np.uint64)
+    total = int(foff[-1] + sizes[-1] + pad)
+    files = np.full(total, 0x5A, dtype=np.uint8)
+    ns, mx = np.zeros(7, dtype=np.uint32), np.zeros(7, dtype=np.float32)
+    L = g.lib()
+    rc = L.trm_mixed_events_to_files_host(m._h, set_begin.ctypes.data, times.ctypes.data, values.ctypes.data, eoff.ctypes.data, nev.ctypes.data,
+                                          C.addressof(settings), files.ctypes.data, foff.ctypes.data, ns.ctypes.data, mx.ctypes.data)
+    assert rc == 0, L.trm_last_error()
+    mask = np.ones(total, dtype=bool)
+    for v in range(7):
+        lo, hi = int(foff[v]), int(foff[v] + sizes[v])
+        mask[lo:hi] = False
+        assert files[lo:hi].tobytes() == dense[v], v
+        assert int(ns[v]) == m.samples_for_frames(sets[v], nframes[v]), v
+    assert np.all(files[mask] == 0x5A)
+    assert len(set(int(x) for x in ns)) >= 5
