@@ -85,6 +85,8 @@ EXPORTS = [
     "trm_mixed_stream_step", "trm_mixed_stream_step_device",
     "trm_mixed_stream_group_set_events", "trm_mixed_stream_group_frames_left", "trm_mixed_stream_last_frames",
     "trm_mixed_stream_step_int16", "trm_mixed_stream_step_device_int16",
+    "trm_mixed_stream_step_counts", "trm_mixed_stream_step_counts_device", "trm_mixed_stream_step_counts_int16",
+    "trm_mixed_stream_step_counts_device_int16",
     "trm_mixed_stream_group_bind", "trm_mixed_stream_group_bound_set", "trm_mixed_stream_set_params",
     "trm_mixed_stream_set_group_convert", "trm_mixed_stream_group_convert",
     "trm_mixed_stream_set_mode_of", "trm_mixed_stream_mode_of", "trm_mixed_stream_set_slice", "trm_mixed_stream_slice",
@@ -241,6 +243,10 @@ def lib():
     L.trm_mixed_stream_last_frames.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.trm_mixed_stream_step_int16.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp, vp, vp]
     L.trm_mixed_stream_step_device_int16.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp, vp, vp, vp]
+    L.trm_mixed_stream_step_counts.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+    L.trm_mixed_stream_step_counts_device.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
+    L.trm_mixed_stream_step_counts_int16.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp, vp, vp]
+    L.trm_mixed_stream_step_counts_device_int16.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp, vp, vp, vp]
     L.trm_mixed_stream_group_bind.argtypes = [vp, C.c_size_t, C.c_size_t]
     L.trm_mixed_stream_group_bound_set.argtypes = [vp, C.c_size_t]
     L.trm_mixed_stream_group_bound_set.restype = C.c_size_t

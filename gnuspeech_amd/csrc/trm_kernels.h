@@ -175,6 +175,24 @@ struct GrpPrepArgs {
     uint32_t nvoices, rows;           // rows = frames per push + 1
 };
 hipError_t launch_grp_prep(const GrpPrepArgs &p, hipStream_t stream);
+// ... and the same with a frame count per group (trm_grp_prep.hip: trm_grp_prep_counts_kernel; trm_mixed_stream_step_counts): a voice
+// whose group pushes n = group_count[g] frames has its lead row, rows 1 .. n from the first n pushed rows and its last frame
+// from pushed row n - 1; nothing is read or written at the rows above n.  group_count is the counts stretch of the step's tables
+// (StepLayout::counts), typed in the constant address space (ConstTable's reason), read for pushing groups alone; a pushing
+// group's count is 1 .. min(pitch, rows - 1).
+struct GrpPrepCountsArgs {
+    float *frames;                    // [nvoices][rows][16]: row 0 = the lead row
+    float *last;                      // [nvoices][16]
+    const float *pushed;              // [nvoices][pitch][16], the caller's: voice v's first group_count[g] rows are read
+    const uint32_t *voice_group;      // [nvoices]
+    const uint32_t *group_step;       // [groups]: kGrp* bits
+    float *max_sample;
+    uint32_t nvoices, rows;           // rows = the step's frame pitch + 1
+    uint64_t pitch;                   // rows between two voices of `pushed`
+    const __attribute__((address_space(4))) uint32_t *group_count;       // [groups]
+};
+// (installed by trm_grp_prep.hip when the library is loaded, like grp_gain_launcher; null: the entries with counts are refused)
+extern hipError_t (*grp_prep_counts_launcher)(const GrpPrepCountsArgs &a, hipStream_t stream);
 // small-batch form (trm_quad.hip): 16 voices per workgroup, four lanes per voice
 constexpr int kStreamFloats = 192;   // oscillator position, filter memories, 32 samples of FIR / converter history, 4 x 20 tube values
 // `cus` = the device's compute units: more workgroups than that run the instance that fits two per CU

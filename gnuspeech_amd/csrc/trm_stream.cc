@@ -56,7 +56,7 @@ static int groups_tables(trm_stream_engine *s)
     for (size_t g = 0; g < G; g++)
         for (size_t v = s->gbegin[g]; v < s->gbegin[g + 1]; v++) vg[v] = (uint32_t)g;
     int rc;
-    if ((rc = s->dVoiceGroup.reserve(V)) || (rc = s->dStep.reserve(step_words_room(s, false, false))) || (rc = s->dOutSets.reserve(S))) return rc;
+    if ((rc = s->dVoiceGroup.reserve(V)) || (rc = s->dStep.reserve(step_words_room(s, false, false, false))) || (rc = s->dOutSets.reserve(S))) return rc;
     hipError_t e = hipMemcpy(s->dVoiceGroup.p, vg.data(), V * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(TRM_EHIP, "group table: %s", hipGetErrorString(e));
     std::vector<trm::GrpOutSet> os(S);

@@ -19,6 +19,8 @@
 // (trm_tracks_run.hip) generates in place in front of the tube launch, and as the flush once they have run out.
 // A step may also leave as int16 PCM (trm_mixed_stream_step_int16): the same step into fp32 rows of the engine's, then one launch
 // (trm_grp_out.hip) that scales the rows of the voices that received samples against their group's level.
+// A step may give every group a frame count of its own (trm_mixed_stream_step_counts): the step's shape is then the caller's row
+// pitch, every group's plan follows its count, and the prep kernel with counts (trm_grp_prep.hip) lays the rows out per group.
 // A closed group may be bound to another of the stream's sets (trm_mixed_stream_group_bind) and a set that no open group runs
 // may be given other parameters (trm_mixed_stream_set_params): both make the storage that depends on the binding current
 // themselves -- the group's map entries, the history rows, the tube-rate offsets (rebind_plan, rebind_commit) -- so a step finds
@@ -136,6 +138,9 @@ struct trm_stream_engine {
     size_t downBlocks = 0;                   // blocks of kGrpDownVoices voices over all groups
     std::vector<trm::GrpDownSet> hDownSets;  // per set (an up-sampling set: zeros)
     DevBuf<trm::GrpDownSet> dDownSets;
+    // ---- frame counts per group (trm_mixed_stream_step_counts): the first such step gives the step's tables room for the counts
+    // stretch, as the first per-set setter does for the gain stretch
+    bool countsRoom = false;
     void free_step_copies()
     {
         for (StepCopy &c : stepCopies) {
@@ -208,8 +213,11 @@ static inline void set_control_period(trm_batch *b, uint32_t cp)
 //   what    kGrp* per group (GrpPrepArgs)                      run     {voice, frames | opening} per voice whose frames are generated
 //   int16   an int16 step's part (GrpInt16Args::step)          down    the groups that convert in one launch (GrpDownArgs::step)
 //   gain    {map entry, samples per voice} per entry of a TRAcT-order group that received samples (GrpGainArgs::step)
-struct StepLayout { size_t clock = 0, active = 0, what = 0, run = 0, int16 = 0, down = 0, gain = 0, words = 0; };
-static inline StepLayout step_layout(size_t E, size_t G, size_t nrun, bool int16, size_t nentries, size_t downGroups, size_t downBlocks, size_t gainEntries)
+//   counts  the frames every group pushes in a step with counts per group (GrpPrepCountsArgs::group_count); there only once the
+//           stream has taken such a step
+struct StepLayout { size_t clock = 0, active = 0, what = 0, run = 0, int16 = 0, down = 0, gain = 0, counts = 0, words = 0; };
+static inline StepLayout step_layout(size_t E, size_t G, size_t nrun, bool int16, size_t nentries, size_t downGroups, size_t downBlocks, size_t gainEntries,
+                                     bool counts)
 {
     StepLayout l;
     l.active = l.clock + 4 * E;
@@ -218,14 +226,16 @@ static inline StepLayout step_layout(size_t E, size_t G, size_t nrun, bool int16
     l.int16 = l.run + 2 * nrun;
     l.down = l.int16 + (int16 ? 2 * G + 1 + nentries : 0);
     l.gain = l.down + trm::kGrpDownWords * downGroups + 2 * downBlocks;
-    l.words = l.gain + 2 * gainEntries;
+    l.counts = l.gain + 2 * gainEntries;
+    l.words = l.counts + (counts ? G : 0);
     return l;
 }
 // the words the step's tables have room for, on the device and in every pinned copy: the layout at its maxima
-static inline size_t step_words_room(const trm_stream_engine *s, bool downRoom, bool gainRoom)
+static inline size_t step_words_room(const trm_stream_engine *s, bool downRoom, bool gainRoom, bool countsRoom)
 {
     const size_t G = s->gbegin.size() - 1;
-    return step_layout(s->mapEntries, G, s->nvoices, true, s->mapEntries, downRoom ? G : 0, downRoom ? s->downBlocks : 0, gainRoom ? s->mapEntries : 0).words;
+    return step_layout(s->mapEntries, G, s->nvoices, true, s->mapEntries, downRoom ? G : 0, downRoom ? s->downBlocks : 0, gainRoom ? s->mapEntries : 0,
+                       countsRoom).words;
 }
 
 // ------------------------------------------------------------------ ranges and shapes
@@ -397,17 +407,30 @@ static inline int maxima_out(trm_stream_engine *s, const StreamOut &o)
     return TRM_OK;
 }
 
-// a host entry's frames to dPushed: those of the units that push (null: all), runs of neighbouring ones in one copy
-static inline int frames_in(trm_stream_engine *s, const std::vector<size_t> &begin, const uint8_t *pushes, const float *frames, size_t nframes, hipStream_t st)
+// a host entry's frames to dPushed: those of the units that push (null: all), runs of neighbouring ones in one copy.  rowsOf
+// (null: every unit pushes nframes rows): unit u pushes the first rowsOf[u] <= nframes rows of each of its voices, which lie
+// nframes rows apart -- a unit with fewer rows than that goes in a 2-D copy of its own, and no row beyond a unit's is read.
+static inline int frames_in(trm_stream_engine *s, const std::vector<size_t> &begin, const uint8_t *pushes, const float *frames, size_t nframes, hipStream_t st,
+                            const uint32_t *rowsOf = nullptr)
 {
     const size_t U = begin.size() - 1;
     if (nframes == 0) return TRM_OK;
     if (int rc = s->dPushed.reserve(s->nvoices * nframes * 16)) return rc;
+    auto whole = [&](size_t u) { return !rowsOf || rowsOf[u] == nframes; };
     for (size_t u = 0; u < U;) {
         if (pushes && !pushes[u]) { u++; continue; }
+        const size_t at = begin[u] * nframes * 16;
+        if (!whole(u)) {
+            const size_t n = begin[u + 1] - begin[u];
+            if (n > 0)
+                HIP_TRY(hipMemcpy2DAsync(s->dPushed.p + at, nframes * 16 * sizeof(float), frames + at, nframes * 16 * sizeof(float),
+                                         (size_t)rowsOf[u] * 16 * sizeof(float), n, hipMemcpyHostToDevice, st));
+            u++;
+            continue;
+        }
         size_t e = u;
-        while (e < U && (!pushes || pushes[e])) e++;
-        const size_t lo = begin[u] * nframes * 16, hi = begin[e] * nframes * 16;
+        while (e < U && (!pushes || pushes[e]) && whole(e)) e++;
+        const size_t lo = at, hi = begin[e] * nframes * 16;
         if (hi > lo) HIP_TRY(hipMemcpyAsync(s->dPushed.p + lo, frames + lo, (hi - lo) * sizeof(float), hipMemcpyHostToDevice, st));
         u = e;
     }

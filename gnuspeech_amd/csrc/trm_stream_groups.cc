@@ -366,7 +366,7 @@ int trm_mixed_stream_set_group_convert(trm_mixed_stream *s, int mode)
         DevBuf<uint32_t> step;
         DevBuf<trm::GrpDownSet> sets;
         int rc;
-        if ((rc = step.reserve(step_words_room(s, true, s->perSet))) || (rc = sets.reserve(S))) return rc;
+        if ((rc = step.reserve(step_words_room(s, true, s->perSet, s->countsRoom))) || (rc = sets.reserve(S))) return rc;
         std::vector<trm::GrpDownSet> h(S);
         for (size_t k = 0; k < S; k++) h[k] = grp_down_set(s->sets[k]);
         HIP_TRY(hipMemcpy(sets.p, h.data(), S * sizeof(trm::GrpDownSet), hipMemcpyHostToDevice));
@@ -406,7 +406,7 @@ static int per_set_commit(trm_mixed_stream *s, size_t set, int mode, uint32_t cp
     HIP_TRY(hipSetDevice(s->sets[0]->device));
     DevBuf<uint32_t> step;
     if (!s->perSet)
-        if (int rc = step.reserve(step_words_room(s, s->downRoom, true))) return rc;
+        if (int rc = step.reserve(step_words_room(s, s->downRoom, true, s->countsRoom))) return rc;
     if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
     trm_batch *b = s->sets[set];
     const trm::Const c = b->c;

@@ -1,4 +1,4 @@
-// trm_stream_step.cc -- a grouped stream's step (trm_mixed_stream_step and its device and int16 forms): what every group does in
+// trm_stream_step.cc -- a grouped stream's step (trm_mixed_stream_step[_counts] and their device and int16 forms): what every group does in
 // it, the step's tables, the launches, the entries (the engine and its account: trm_stream_engine.h).
 #include "trm_stream_engine.h"
 
@@ -8,6 +8,7 @@ hipError_t (*grp_int16_launcher)(const GrpInt16Args &a, hipStream_t stream) = nu
 hipError_t (*grp_hist_in_launcher)(const GrpDownArgs &a, hipStream_t stream) = nullptr;       // (trm_kernels.h; both set by trm_grp_down.hip)
 hipError_t (*grp_convert_launcher)(const GrpDownArgs &a, hipStream_t stream) = nullptr;
 hipError_t (*grp_gain_launcher)(const GrpGainArgs &a, hipStream_t stream) = nullptr;          // (trm_kernels.h; set by trm_grp_gain.hip)
+hipError_t (*grp_prep_counts_launcher)(const GrpPrepCountsArgs &a, hipStream_t stream) = nullptr;      // (trm_kernels.h; set by trm_grp_prep.hip)
 }
 
 // ------------------------------------------------------------------ grouped streams: a step
@@ -19,7 +20,7 @@ struct GroupPlan {
     bool lead = false;                       // a pushing group: its rows begin with a lead row
     bool gen = false;                        // a pushing group whose frames come from its event lists (TRM_GROUP_RUN)
     bool drop = false;                       // the group's event lists end with this step: run to their end, or dropped by a finish
-    uint64_t frames = 0;                     // a pushing group: the frames it pushes (the step's; a running group's last stretch: fewer)
+    uint64_t frames = 0;                     // a pushing group: the frames it pushes (the step's or its own count; a running group's last stretch: fewer)
     uint64_t Q = 0, kBase = 0, kEnd = 0, nHi = 0;    // control periods of the step; converter outputs kBase <= k < kEnd; last tube sample + 1
 };
 
@@ -34,9 +35,19 @@ void run_means(const trm_stream_engine *s, size_t g, size_t nframes, bool *push,
     *flush = ev.state == trm_stream_engine::kEvPending && left == 0 && s->gopen[g];
 }
 
-// `frames`: the caller's frames, looked at for null alone
-static int step_plan(const trm_stream_engine *s, const uint8_t *action, const float *frames, size_t nframes, std::vector<GroupPlan> &plan)
+// The frames of a step as the caller gave them.  An entry with counts (counted): group g pushes or runs count[g] frames and
+// voice v's rows lie at rows + v * pitch * 16; the entries without: every group pushes `pitch` frames (count: null).
+struct StepFrames {
+    const float *rows;
+    size_t pitch;
+    const uint32_t *count;
+    bool counted;
+};
+
+// `f.rows`: the caller's frames, looked at for null alone
+static int step_plan(const trm_stream_engine *s, const uint8_t *action, const StepFrames &f, std::vector<GroupPlan> &plan)
 {
+    const float *frames = f.rows;
     const size_t G = s->gbegin.size() - 1;
     plan.assign(G, GroupPlan());
     bool anyRun = false, anyPushed = false;
@@ -46,6 +57,15 @@ static int step_plan(const trm_stream_engine *s, const uint8_t *action, const fl
         const int ev = s->gev[g].state;
         p.push = action[g] == TRM_GROUP_PUSH;
         p.flush = action[g] == TRM_GROUP_FINISH && s->gopen[g];
+        // the frames the step has for the group: its own count where the entry takes counts
+        size_t nframes = f.pitch;
+        if (f.counted && (action[g] == TRM_GROUP_PUSH || action[g] == TRM_GROUP_RUN)) {
+            if (!f.count) return fail(TRM_EINVAL, "null count, and group %zu %s", g, action[g] == TRM_GROUP_PUSH ? "pushes" : "runs");
+            if (f.count[g] == 0) return fail(TRM_EINVAL, "group %zu %s, but its count is 0", g, action[g] == TRM_GROUP_PUSH ? "pushes" : "runs");
+            if (f.count[g] > f.pitch)
+                return fail(TRM_EINVAL, "group %zu: count %u > frame_pitch %zu", g, (unsigned)f.count[g], f.pitch);
+            nframes = f.count[g];
+        }
         p.frames = nframes;
         // (a finish aborts a group that runs, and drops lists that have not begun)
         p.drop = action[g] == TRM_GROUP_FINISH && ev == trm_stream_engine::kEvPending;
@@ -80,7 +100,8 @@ static int step_plan(const trm_stream_engine *s, const uint8_t *action, const fl
             return fail(TRM_ERANGE, "utterance too long (group %zu)", g);
     }
     // (frames may stay away where every frame of the step is generated)
-    if (nframes > 0 && !frames && (anyPushed || !anyRun)) return fail(TRM_EINVAL, "null frames");
+    // (an entry with counts reads frames for the groups that push alone)
+    if (!frames && (f.counted ? anyPushed : f.pitch > 0 && (anyPushed || !anyRun))) return fail(TRM_EINVAL, "null frames");
     return TRM_OK;
 }
 
@@ -170,7 +191,8 @@ static void tables_down(const trm_stream_engine *s, const std::vector<GroupPlan>
 }
 
 // The tables of a step, to the host buffer h (room: step_words_room): the stretches are counted, laid out (step_layout) and filled
-static StepTables step_tables(const trm_stream_engine *s, const std::vector<GroupPlan> &plan, const StepInt16 *o16, bool oneLaunch, uint32_t *h)
+// (counted: a step with frame counts per group, whose counts stretch the prep kernel reads)
+static StepTables step_tables(const trm_stream_engine *s, const std::vector<GroupPlan> &plan, const StepInt16 *o16, bool oneLaunch, bool counted, uint32_t *h)
 {
     const size_t G = plan.size();
     size_t nrun = 0, nentries = 0, ngroups = 0, nblocks = 0, ngain = 0;
@@ -184,7 +206,7 @@ static StepTables step_tables(const trm_stream_engine *s, const std::vector<Grou
         nblocks += (group_voices(s, g) + trm::kGrpDownVoices - 1) / trm::kGrpDownVoices;
     }
     StepTables t;
-    t.at = step_layout(s->mapEntries, G, nrun, o16 != nullptr, nentries, ngroups, nblocks, ngain);
+    t.at = step_layout(s->mapEntries, G, nrun, o16 != nullptr, nentries, ngroups, nblocks, ngain, counted);
     memset(h, 0, t.at.int16 * sizeof(uint32_t));
     uint32_t *clock = h + t.at.clock, *active = h + t.at.active, *what = h + t.at.what, *run = h + t.at.run;
     // an int16 step: [level bits | samples per voice | for_wav_data | the entries that receive samples] (a group that receives nothing: 0, 0)
@@ -218,6 +240,8 @@ static StepTables step_tables(const trm_stream_engine *s, const std::vector<Grou
         }
     }
     if (o16) cnt[G] = o16->forWav ? 1u : 0u;
+    // (a group that does not push frames of the caller's: 0, which nothing reads)
+    for (size_t g = 0; counted && g < G; g++) h[t.at.counts + g] = plan[g].push && !plan[g].gen ? (uint32_t)plan[g].frames : 0u;
     if (oneLaunch) tables_down(s, plan, ngroups, h, t);
     return t;
 }
@@ -270,8 +294,9 @@ static int step_synthesize(trm_stream_engine *s, const StepTables &t, const std:
 
 // One step on the device (plan: step_plan's): the tables of the step, the frame rows, ONE tube launch over the map entries of the
 // groups that synthesize with what surrounds it (step_synthesize); an int16 step (o16; d_out then the engine's fp32 rows) ends with
-// the launch that scales them.  The host waits only on a shape change (frames per push, out_pitch) or when the noise has to grow.
-static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &plan, const float *d_pushed, size_t nframes, float *d_out,
+// the launch that scales them.  The host waits only on a shape change (frames per push or frame pitch, out_pitch) or when the noise has to grow.
+// A step with counts (counted) has `nframes` = the frame pitch: the shape's, whatever the groups' counts are.
+static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &plan, const float *d_pushed, size_t nframes, bool counted, float *d_out,
                             size_t out_pitch, uint32_t *nout, hipStream_t st, const StepInt16 *o16)
 {
     const size_t G = plan.size(), V = s->nvoices;
@@ -292,18 +317,34 @@ static int stream_step_impl(trm_stream_engine *s, const std::vector<GroupPlan> &
     // Rows per voice on the device: the lead row and the pushed frames; a step without frames (finishes, idle) takes any
     // shape, so it keeps the one it finds.  Tube-rate rows are sized for a continuing push, the longest a group can run.
     const size_t rows = nframes == 0 && s->shapeRows > 0 && s->shapePitch == out_pitch ? s->shapeRows : nframes + 1;
+    if (counted && !s->countsRoom) {
+        // Room for the counts stretch in the step's tables, once (as the first per-set setter makes room for the gain stretch):
+        // the steps so far may still read the tables and their uploads the pinned copies, so the host waits for them here.
+        DevBuf<uint32_t> step;
+        if ((rc = step.reserve(step_words_room(s, s->downRoom, s->perSet, true)))) return rc;
+        if (s->haveChunk) HIP_TRY(hipEventSynchronize(s->chunkDone));
+        s->dStep.swap(step);
+        s->free_step_copies();
+        s->countsRoom = true;
+    }
     if ((rc = s->dFrames.reserve(V * rows * 16))) return rc;
     if ((rc = stream_shape(s, rows, out_pitch, rows - 1, s->anyDown, st))) return rc;
     uint32_t *h = nullptr;
-    if ((rc = step_copy(s, step_words_room(s, s->downRoom, s->perSet), &h))) return rc;
+    if ((rc = step_copy(s, step_words_room(s, s->downRoom, s->perSet, s->countsRoom), &h))) return rc;
     const bool oneLaunch = s->convert == TRM_GROUP_CONVERT_ONE_LAUNCH && downRuns;
-    const StepTables t = step_tables(s, plan, o16, oneLaunch, h);
+    const StepTables t = step_tables(s, plan, o16, oneLaunch, counted, h);
     if (t.down.tiles >= 65535u) return fail(TRM_ERANGE, "%u outputs per voice in one step: too many for the one-launch converter", t.maxOut);
     HIP_TRY(hipMemcpyAsync(s->dStep.p, h, t.at.words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(s->stepCopies.back().uploaded, st));
     typedef const __attribute__((address_space(4))) uint32_t *Words;
-    trm::GrpPrepArgs prep{s->dFrames.p, s->dLast.p, d_pushed, s->dVoiceGroup.p, s->dStep.p + t.at.what, s->dMax.p, (uint32_t)V, (uint32_t)rows};
-    HIP_TRY(trm::launch_grp_prep(prep, st));
+    if (counted) {
+        trm::GrpPrepCountsArgs prep{s->dFrames.p, s->dLast.p, d_pushed, s->dVoiceGroup.p, s->dStep.p + t.at.what, s->dMax.p, (uint32_t)V, (uint32_t)rows,
+                                    (uint64_t)nframes, (Words)(s->dStep.p + t.at.counts)};
+        HIP_TRY(trm::grp_prep_counts_launcher(prep, st));
+    } else {
+        trm::GrpPrepArgs prep{s->dFrames.p, s->dLast.p, d_pushed, s->dVoiceGroup.p, s->dStep.p + t.at.what, s->dMax.p, (uint32_t)V, (uint32_t)rows};
+        HIP_TRY(trm::launch_grp_prep(prep, st));
+    }
     if (t.nRun > 0) {
         // the frames of the groups that run: generated in place, with their lead rows and last frames
         trm::TrackRunArgs r{(Words)s->dEvTimes.p, s->dEvValues.p, (const __attribute__((address_space(4))) uint64_t *)s->dEvOff.p, (Words)s->dEvN.p,
@@ -362,14 +403,19 @@ static size_t int16_row_pitch(size_t out_pitch16) { return (out_pitch16 + 3) & ~
 
 // A step to the outputs `o` (q: as int16 PCM, o.rows then int16 rows).  A device entry's maxima leave inside the ordered work:
 // the next step, on whichever stream, clears and writes them again.
-static int stream_step(trm_stream_engine *s, const uint8_t *action, const float *frames, size_t nframes, StreamOut o, StepInt16 *q)
+// One path under all eight entries: those without counts give every group f.pitch frames.
+static int stream_step(trm_stream_engine *s, const uint8_t *action, const StepFrames &f, StreamOut o, StepInt16 *q)
 {
+    const float *frames = f.rows;
+    const size_t nframes = f.pitch;
     int rc = step_check(s, action, nframes);
     if (rc) return rc;
+    if (f.counted && !trm::grp_prep_counts_launcher)
+        return fail(TRM_EHIP, "this build of the library holds no prep kernel for frame counts per group (trm_grp_prep.hip)");
     if (q && !trm::grp_int16_launcher) return fail(TRM_EHIP, "this build of the library holds no int16 output kernel (trm_grp_out.hip)");
     std::vector<GroupPlan> plan;
     size_t packed = 0;
-    if ((rc = step_plan(s, action, frames, nframes, plan)) || (q && (rc = step_check_int16(s, plan, q->level, (const int16_t *)o.rows, o.pitch, &packed))))
+    if ((rc = step_plan(s, action, f, plan)) || (q && (rc = step_check_int16(s, plan, q->level, (const int16_t *)o.rows, o.pitch, &packed))))
         return rc;
     const size_t G = plan.size(), V = s->nvoices;
     trm_batch *b0 = s->sets[0];
@@ -377,11 +423,13 @@ static int stream_step(trm_stream_engine *s, const uint8_t *action, const float 
     if (o.host) {
         o.st = b0->stream;
         std::vector<uint8_t> pushes(G);
+        std::vector<uint32_t> pushed(f.counted ? G : 0);      // (the rows every pushing group uploads)
         for (size_t g = 0; g < G; g++) {
             pushes[g] = plan[g].push && !plan[g].gen;
+            if (f.counted) pushed[g] = pushes[g] ? (uint32_t)plan[g].frames : 0u;
             if (!q && plan[g].runs && group_voices(s, g) > 0) packed = std::max<size_t>(packed, plan[g].kEnd - plan[g].kBase);
         }
-        if ((!q && (rc = refuse_pitch(s, o.rows, o.pitch, packed))) || (rc = frames_in(s, s->gbegin, pushes.data(), frames, nframes, o.st)))
+        if ((!q && (rc = refuse_pitch(s, o.rows, o.pitch, packed))) || (rc = frames_in(s, s->gbegin, pushes.data(), frames, nframes, o.st, f.counted ? pushed.data() : nullptr)))
             return rc;
         frames = s->dPushed.p;
     }
@@ -402,7 +450,7 @@ static int stream_step(trm_stream_engine *s, const uint8_t *action, const float 
     std::vector<uint32_t> counts(G);
     uint32_t *nout = o.host ? counts.data() : o.nout;
     auto work = [&]() -> int {
-        if (int r = stream_step_impl(s, plan, frames, nframes, rows, pitch, nout, o.st, q)) return r;
+        if (int r = stream_step_impl(s, plan, frames, nframes, f.counted, rows, pitch, nout, o.st, q)) return r;
         return o.host ? TRM_OK : maxima_out(s, o);
     };
     if ((rc = stream_ordered(s, o.st, work))) return rc;
@@ -421,20 +469,20 @@ extern "C" {
 int trm_mixed_stream_step(trm_mixed_stream *s, const uint8_t *action, const float *frames, size_t nframes, float *out, size_t out_pitch,
                           uint32_t *nout, float *max_out)
 {
-    return stream_step(s, action, frames, nframes, StreamOut{true, out, out_pitch, nout, max_out}, nullptr);
+    return stream_step(s, action, StepFrames{frames, nframes, nullptr, false}, StreamOut{true, out, out_pitch, nout, max_out}, nullptr);
 }
 
 int trm_mixed_stream_step_device(trm_mixed_stream *s, const uint8_t *action, const float *d_frames, size_t nframes, float *d_out,
                                  size_t out_pitch, uint32_t *nout, float *d_max_out, void *hip_stream)
 {
-    return stream_step(s, action, d_frames, nframes, StreamOut{false, d_out, out_pitch, nout, d_max_out, nullptr, (hipStream_t)hip_stream}, nullptr);
+    return stream_step(s, action, StepFrames{d_frames, nframes, nullptr, false}, StreamOut{false, d_out, out_pitch, nout, d_max_out, nullptr, (hipStream_t)hip_stream}, nullptr);
 }
 
 int trm_mixed_stream_step_int16(trm_mixed_stream *s, const uint8_t *action, const float *frames, size_t nframes, const float *level,
                                 int for_wav_data, int16_t *out16, size_t out_pitch16, uint32_t *nout, float *max_out, uint32_t *clipped)
 {
     StepInt16 q{level, for_wav_data};
-    return stream_step(s, action, frames, nframes, StreamOut{true, out16, out_pitch16, nout, max_out, clipped}, &q);
+    return stream_step(s, action, StepFrames{frames, nframes, nullptr, false}, StreamOut{true, out16, out_pitch16, nout, max_out, clipped}, &q);
 }
 
 int trm_mixed_stream_step_device_int16(trm_mixed_stream *s, const uint8_t *action, const float *d_frames, size_t nframes, const float *level,
@@ -442,7 +490,38 @@ int trm_mixed_stream_step_device_int16(trm_mixed_stream *s, const uint8_t *actio
                                        uint32_t *d_clipped, void *hip_stream)
 {
     StepInt16 q{level, for_wav_data};
-    return stream_step(s, action, d_frames, nframes, StreamOut{false, d_out16, out_pitch16, nout, d_max_out, d_clipped, (hipStream_t)hip_stream}, &q);
+    return stream_step(s, action, StepFrames{d_frames, nframes, nullptr, false}, StreamOut{false, d_out16, out_pitch16, nout, d_max_out, d_clipped, (hipStream_t)hip_stream}, &q);
+}
+
+// the four with a frame count per group and a row pitch in place of nframes (include/trm_c_api.h)
+int trm_mixed_stream_step_counts(trm_mixed_stream *s, const uint8_t *action, const uint32_t *count, const float *frames, size_t frame_pitch,
+                                 float *out, size_t out_pitch, uint32_t *nout, float *max_out)
+{
+    return stream_step(s, action, StepFrames{frames, frame_pitch, count, true}, StreamOut{true, out, out_pitch, nout, max_out}, nullptr);
+}
+
+int trm_mixed_stream_step_counts_device(trm_mixed_stream *s, const uint8_t *action, const uint32_t *count, const float *d_frames,
+                                        size_t frame_pitch, float *d_out, size_t out_pitch, uint32_t *nout, float *d_max_out, void *hip_stream)
+{
+    return stream_step(s, action, StepFrames{d_frames, frame_pitch, count, true},
+                       StreamOut{false, d_out, out_pitch, nout, d_max_out, nullptr, (hipStream_t)hip_stream}, nullptr);
+}
+
+int trm_mixed_stream_step_counts_int16(trm_mixed_stream *s, const uint8_t *action, const uint32_t *count, const float *frames,
+                                       size_t frame_pitch, const float *level, int for_wav_data, int16_t *out16, size_t out_pitch16,
+                                       uint32_t *nout, float *max_out, uint32_t *clipped)
+{
+    StepInt16 q{level, for_wav_data};
+    return stream_step(s, action, StepFrames{frames, frame_pitch, count, true}, StreamOut{true, out16, out_pitch16, nout, max_out, clipped}, &q);
+}
+
+int trm_mixed_stream_step_counts_device_int16(trm_mixed_stream *s, const uint8_t *action, const uint32_t *count, const float *d_frames,
+                                              size_t frame_pitch, const float *level, int for_wav_data, int16_t *d_out16, size_t out_pitch16,
+                                              uint32_t *nout, float *d_max_out, uint32_t *d_clipped, void *hip_stream)
+{
+    StepInt16 q{level, for_wav_data};
+    return stream_step(s, action, StepFrames{d_frames, frame_pitch, count, true},
+                       StreamOut{false, d_out16, out_pitch16, nout, d_max_out, d_clipped, (hipStream_t)hip_stream}, &q);
 }
 
 }  // extern "C"

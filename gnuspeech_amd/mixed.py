@@ -792,9 +792,36 @@ class TRMGroupedStream:
             a[self._gindex[int(g)]] = self._ACTIONS[act]
         return a
 
-    def _counts(self, a, nframes):
-        """samples per voice of every group (the library's order) for the step, asked before it"""
-        return np.array([lib().trm_mixed_stream_group_samples_for(self._h, g, int(a[g]), nframes) for g in range(self.ngroups)], dtype=np.int64)
+    def _counts(self, a, nframes, c=None):
+        """samples per voice of every group (the library's order) for the step, asked before it (c: the groups' own frame counts)"""
+        return np.array([lib().trm_mixed_stream_group_samples_for(self._h, g, int(a[g]), nframes if c is None else int(c[g]))
+                         for g in range(self.ngroups)], dtype=np.int64)
+
+    def _group_counts(self, a, counts):
+        """the library's count array (its group order) of a step with frame counts per group, from a sequence of ngroups counts
+        or a dict {group: n}; entries may be missing (None, or absent from the dict) only for groups that neither push nor run"""
+        c = np.zeros(self.ngroups, dtype=np.uint32)
+        given = np.zeros(self.ngroups, dtype=bool)
+        if isinstance(counts, dict):
+            items = counts.items()
+        else:
+            counts = list(counts)
+            if len(counts) != self.ngroups:
+                raise ValueError("%d counts for %d groups" % (len(counts), self.ngroups))
+            items = enumerate(counts)
+        for g, n in items:
+            if not 0 <= int(g) < self.ngroups:
+                raise ValueError("group %r outside 0 .. %d" % (g, self.ngroups - 1))
+            if n is None:
+                continue
+            if not 0 <= int(n) <= 0xFFFFFFFF:
+                raise ValueError("group %r: count %r" % (g, n))
+            c[self._gindex[int(g)]] = int(n)
+            given[self._gindex[int(g)]] = True
+        needs = (a == TRM_GROUP_PUSH) | (a == TRM_GROUP_RUN)
+        if np.any(needs & ~given):
+            raise ValueError("a group pushes or runs without a count")
+        return c
 
     def _width(self, counts):
         nonempty = np.diff(self.group_begin.astype(np.int64)) > 0
@@ -840,21 +867,30 @@ class TRMGroupedStream:
         return n, pushed
 
     # -------------------------------------------------------------- host buffers (caller's voice order)
-    def step(self, actions, frames=None, nframes=None):
+    def step(self, actions, frames=None, nframes=None, counts=None):
         """actions: ngroups entries ("push" | "finish" | "idle" / None | "run"), or a dict {group: action} (the others idle).
         frames: [nvoices, n, 16] in the caller's order, needed when a group pushes; only the rows of pushing groups are read.
         nframes: the frames of the step where no group pushes and groups "run" (with frames given it must be their count).
         Returns (pcm [nvoices, max_m] float32, samples per voice uint32[nvoices], max |sample| per voice float32[nvoices]);
-        voice i's samples are pcm[i, :count[i]]."""
+        voice i's samples are pcm[i, :count[i]].
+        counts (include/trm_c_api.h: trm_mixed_stream_step_counts): a frame count per group, ngroups entries or a dict {group: n} in
+        the caller's group indices, needed for every group that pushes or runs.  frames is then [nvoices, pitch, 16] and group g
+        reads frames[v, :counts[g]] of its voices -- rows beyond are not read -- and nframes names the pitch where no frames are
+        given.  The same holds for step_device; the int16 steps with counts are step_counts_int16 and step_counts_device_int16."""
         a = self._actions(actions)
+        c = self._group_counts(a, counts) if counts is not None else None
         n, f = self._host_frames(a, frames, nframes)
-        counts = self._counts(a, n)
+        counts = self._counts(a, n, c)
         m = self._width(counts)
         out = np.zeros((self.nvoices, max(m, 1)), dtype=np.float32)
         mx = np.zeros(self.nvoices, dtype=np.float32)
         nout = np.zeros(self.ngroups, dtype=np.uint32)
-        check(lib().trm_mixed_stream_step(self._h, a.ctypes.data, f.ctypes.data if f is not None else None, n, out.ctypes.data, max(m, 1),
-                                          nout.ctypes.data, mx.ctypes.data))
+        fp = f.ctypes.data if f is not None else None
+        if c is None:
+            check(lib().trm_mixed_stream_step(self._h, a.ctypes.data, fp, n, out.ctypes.data, max(m, 1), nout.ctypes.data, mx.ctypes.data))
+        else:
+            check(lib().trm_mixed_stream_step_counts(self._h, a.ctypes.data, c.ctypes.data, fp, n, out.ctypes.data, max(m, 1), nout.ctypes.data,
+                                                     mx.ctypes.data))
         assert np.array_equal(nout.astype(np.int64), counts)
         per_voice = nout[self._vgroup]
         return out[self.inverse, :m], per_voice[self.inverse], mx[self.inverse]
@@ -895,20 +931,34 @@ class TRMGroupedStream:
         normalised against -- as -saveOutputToFile: (for_wav_data: -generateWAVData) scales it, saturated where the level is too
         low.  levels: ngroups entries or a dict {group: level}, needed for the groups that synthesize.
         Returns (pcm16 [nvoices, max values] int16, values per voice uint32[nvoices], max |sample| per voice float32[nvoices] of
-        the fp32 samples, clipped values per voice uint32[nvoices]); a stereo voice has two interleaved values per sample."""
+        the fp32 samples, clipped values per voice uint32[nvoices]); a stereo voice has two interleaved values per sample.
+        With a frame count per group: step_counts_int16()."""
+        return self._step_int16(actions, frames, nframes, levels, for_wav_data, None)
+
+    def step_counts_int16(self, actions, counts, frames=None, nframes=None, levels=None, for_wav_data=False):
+        """step_int16() with a frame count per group (step()'s `counts`; trm_mixed_stream_step_counts_int16): frames is
+        [nvoices, pitch, 16] and group g reads frames[v, :counts[g]]; the widths are count x channels per group."""
+        return self._step_int16(actions, frames, nframes, levels, for_wav_data, counts)
+
+    def _step_int16(self, actions, frames, nframes, levels, for_wav_data, counts):
         a = self._actions(actions)
         lv = self._levels(levels)
+        c = self._group_counts(a, counts) if counts is not None else None
         n, f = self._host_frames(a, frames, nframes)
-        counts = self._counts(a, n)
+        counts = self._counts(a, n, c)
         values = self._values(counts)
         m = self._width(values)
         out = np.zeros((self.nvoices, max(m, 1)), dtype=np.int16)
         mx = np.zeros(self.nvoices, dtype=np.float32)
         cl = np.zeros(self.nvoices, dtype=np.uint32)
         nout = np.zeros(self.ngroups, dtype=np.uint32)
-        check(lib().trm_mixed_stream_step_int16(self._h, a.ctypes.data, f.ctypes.data if f is not None else None, n,
-                                                lv.ctypes.data if lv is not None else None, int(bool(for_wav_data)), out.ctypes.data, max(m, 1),
-                                                nout.ctypes.data, mx.ctypes.data, cl.ctypes.data))
+        tail = (lv.ctypes.data if lv is not None else None, int(bool(for_wav_data)), out.ctypes.data, max(m, 1), nout.ctypes.data, mx.ctypes.data,
+                cl.ctypes.data)
+        fp = f.ctypes.data if f is not None else None
+        if c is None:
+            check(lib().trm_mixed_stream_step_int16(self._h, a.ctypes.data, fp, n, *tail))
+        else:
+            check(lib().trm_mixed_stream_step_counts_int16(self._h, a.ctypes.data, c.ctypes.data, fp, n, *tail))
         assert np.array_equal(nout.astype(np.int64), counts)
         per_voice = values.astype(np.uint32)[self._vgroup]
         return out[self.inverse, :m], per_voice[self.inverse], mx[self.inverse], cl[self.inverse]
@@ -918,14 +968,24 @@ class TRMGroupedStream:
         """As step_device(), the PCM as int16 (step_int16): everything in GROUPED order, asynchronous on torch's current stream.
         Returns (pcm16 [nvoices, max values] view of `out`, values per voice uint32[nvoices]).  `out` (optional): int16 CUDA tensor
         [nvoices, pitch >= max values], any pitch, odd ones too; `max_out` (optional): float32 CUDA tensor [nvoices];
-        `clipped` (optional): int32 CUDA tensor [nvoices] (the counts, which stay far below 2^31)."""
+        `clipped` (optional): int32 CUDA tensor [nvoices] (the counts, which stay far below 2^31).
+        With a frame count per group: step_counts_device_int16()."""
+        return self._step_device_int16(actions, frames, out, max_out, clipped, device, nframes, levels, for_wav_data, None)
+
+    def step_counts_device_int16(self, actions, counts, frames=None, out=None, max_out=None, clipped=None, device=None, nframes=None, levels=None,
+                                 for_wav_data=False):
+        """step_device_int16() with a frame count per group (step()'s `counts`; trm_mixed_stream_step_counts_device_int16)."""
+        return self._step_device_int16(actions, frames, out, max_out, clipped, device, nframes, levels, for_wav_data, counts)
+
+    def _step_device_int16(self, actions, frames, out, max_out, clipped, device, nframes, levels, for_wav_data, counts):
         import torch
         a = self._actions(actions)
         lv = self._levels(levels)
+        c = self._group_counts(a, counts) if counts is not None else None
         n, pushed = self._device_frames(a, frames, nframes)
         dev = frames.device if pushed else out.device if out is not None else device if device is not None \
             else torch.device("cuda", torch.cuda.current_device())
-        counts = self._counts(a, n)
+        counts = self._counts(a, n, c)
         values = self._values(counts)
         m = self._width(values)
         if out is None:
@@ -939,25 +999,29 @@ class TRMGroupedStream:
             raise ValueError("clipped must be a contiguous int32 CUDA tensor of %d values" % self.nvoices)
         nout = np.zeros(self.ngroups, dtype=np.uint32)
         st = torch.cuda.current_stream(dev).cuda_stream
-        check(lib().trm_mixed_stream_step_device_int16(self._h, a.ctypes.data, frames.data_ptr() if pushed else None, n,
-                                                       lv.ctypes.data if lv is not None else None, int(bool(for_wav_data)), out.data_ptr(),
-                                                       out.stride(0), nout.ctypes.data, max_out.data_ptr() if max_out is not None else None,
-                                                       clipped.data_ptr() if clipped is not None else None, st))
+        tail = (lv.ctypes.data if lv is not None else None, int(bool(for_wav_data)), out.data_ptr(), out.stride(0), nout.ctypes.data,
+                max_out.data_ptr() if max_out is not None else None, clipped.data_ptr() if clipped is not None else None, st)
+        fp = frames.data_ptr() if pushed else None
+        if c is None:
+            check(lib().trm_mixed_stream_step_device_int16(self._h, a.ctypes.data, fp, n, *tail))
+        else:
+            check(lib().trm_mixed_stream_step_counts_device_int16(self._h, a.ctypes.data, c.ctypes.data, fp, n, *tail))
         assert np.array_equal(nout.astype(np.int64), counts)
         return out[:, :m], values.astype(np.uint32)[self._vgroup]
 
     # -------------------------------------------------------------- device buffers (torch tensors, grouped order)
-    def step_device(self, actions, frames=None, out=None, max_out=None, device=None, nframes=None):
+    def step_device(self, actions, frames=None, out=None, max_out=None, device=None, nframes=None, counts=None):
         """As step(), on the device: frames a float32 CUDA tensor [nvoices, n, 16] in GROUPED order (frames[order] of the caller's).
         Asynchronous on torch's current stream; nothing but the step's small tables crosses PCIe.  Returns (pcm [nvoices, max_m]
         view of `out`, samples per voice uint32[nvoices]), both in grouped order.  `out` (optional): float32 CUDA tensor
         [nvoices, pitch >= max_m]; `max_out` (optional): float32 CUDA tensor [nvoices]."""
         import torch
         a = self._actions(actions)
+        c = self._group_counts(a, counts) if counts is not None else None
         n, pushed = self._device_frames(a, frames, nframes)
         dev = frames.device if pushed else out.device if out is not None else device if device is not None \
             else torch.device("cuda", torch.cuda.current_device())
-        counts = self._counts(a, n)
+        counts = self._counts(a, n, c)
         m = self._width(counts)
         if out is None:
             out = torch.empty((self.nvoices, max(m, 1)), dtype=torch.float32, device=dev)
@@ -968,7 +1032,11 @@ class TRMGroupedStream:
             raise ValueError("max_out must be a float32 CUDA tensor of %d values" % self.nvoices)
         nout = np.zeros(self.ngroups, dtype=np.uint32)
         st = torch.cuda.current_stream(dev).cuda_stream
-        check(lib().trm_mixed_stream_step_device(self._h, a.ctypes.data, frames.data_ptr() if pushed else None, n, out.data_ptr(), out.stride(0),
-                                                 nout.ctypes.data, max_out.data_ptr() if max_out is not None else None, st))
+        tail = (out.data_ptr(), out.stride(0), nout.ctypes.data, max_out.data_ptr() if max_out is not None else None, st)
+        fp = frames.data_ptr() if pushed else None
+        if c is None:
+            check(lib().trm_mixed_stream_step_device(self._h, a.ctypes.data, fp, n, *tail))
+        else:
+            check(lib().trm_mixed_stream_step_counts_device(self._h, a.ctypes.data, c.ctypes.data, fp, n, *tail))
         assert np.array_equal(nout.astype(np.int64), counts)
         return out[:, :m], nout[self._vgroup]

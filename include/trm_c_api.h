@@ -653,7 +653,8 @@ int    trm_mixed_stream_finish_device(trm_mixed_stream *s, float *d_out, size_t 
  *                         -- tube at rest, converter pre-roll, as the first trm_stream_push -- otherwise it continues one.
  *       TRM_GROUP_FINISH  the converter's flush; the group is closed afterwards.  On a closed group: nothing, nout[g] = 0.
  *       TRM_GROUP_IDLE    nothing changes for the group, open (its utterance pauses) or closed.
- *     All pushing groups push the same number of frames; the rows of voices that do not push are not read.  nframes may be 0
+ *     All pushing groups push the same number of frames (a count per group: "Frame counts per group", below); the rows of
+ *     voices that do not push are not read.  nframes may be 0
  *     (and frames null) when no group pushes.  nout[g] (optional, ngroups entries) = the samples every voice of group g
  *     received = trm_mixed_stream_group_samples_for(s, g, action[g], nframes) asked before the step; max_out[v] = 0 for voices
  *     that received nothing.  out_pitch >= the largest count of a non-empty group in this step (TRM_EINVAL otherwise).  A step
@@ -672,6 +673,7 @@ int    trm_mixed_stream_create_groups(const trm_input_params *params, size_t nse
                                       const size_t *group_begin, size_t ngroups, int device, trm_mixed_stream **out);
 size_t trm_mixed_stream_groups(const trm_mixed_stream *s);            /* 0: not a grouped stream */
 int    trm_mixed_stream_group_open(const trm_mixed_stream *s, size_t group);      /* 1 while an utterance is open */
+/* (nframes: the frames the group itself would push or run -- a step with counts per group asks with count[g]) */
 size_t trm_mixed_stream_group_samples_for(const trm_mixed_stream *s, size_t group, int action, size_t nframes);
 int    trm_mixed_stream_step(trm_mixed_stream *s, const uint8_t *action, const float *frames, size_t nframes, float *out,
                              size_t out_pitch, uint32_t *nout, float *max_out);
@@ -690,7 +692,7 @@ int    trm_mixed_stream_step_device(trm_mixed_stream *s, const uint8_t *action, 
  *     entries gain no host wait).  Calling it again on a closed group replaces the lists.
  *   - action TRM_GROUP_RUN, with left = F - frames emitted so far:
  *       left > 0           as TRM_GROUP_PUSH of min(nframes, left) generated frames (nframes == 0: TRM_EINVAL, as for a push); it
- *                          opens the utterance if the group is closed.  PUSH groups of the same step still push nframes each.
+ *                          opens the utterance if the group is closed.  PUSH groups of the same step push nframes each (trm_mixed_stream_step_counts: each its own count).
  *       left == 0, open    as TRM_GROUP_FINISH: the group closes and its events are consumed.
  *       closed, consumed   nothing, nout[g] = 0.
  *       never had events   TRM_EINVAL (so is RUN on a group whose utterance was opened by TRM_GROUP_PUSH).
@@ -841,13 +843,58 @@ int    trm_mixed_stream_group_convert(const trm_mixed_stream *s);
  *     grows the step's tables by the stretch that lists those groups' map entries, as the first
  *     trm_mixed_stream_set_group_convert(ONE_LAUNCH) does.  A stream on which neither is called enqueues exactly what it did
  *     without them.
- *   - NOT OFFERED.  All pushing groups of a step still push the same number of frames: a session with 1 ms slices steps more
- *     often than the sentence groups need, and those sit idle (TRM_GROUP_IDLE) in the steps between. */
+ *   - A session with 1 ms slices has more frames per tick than the sentence groups: "Frame counts per group", below, lets them
+ *     share a step. */
 enum { TRM_STREAM_MODE_MIXED = -1 };      /* returned only: the sets' orders differ */
 int      trm_mixed_stream_set_mode_of(trm_mixed_stream *s, size_t set, int mode);
 int      trm_mixed_stream_mode_of(const trm_mixed_stream *s, size_t set);
 int      trm_mixed_stream_set_slice(trm_mixed_stream *s, size_t set, uint32_t tube_samples);   /* 0: the set's control period */
 uint32_t trm_mixed_stream_slice(const trm_mixed_stream *s, size_t set);
+
+/* Frame counts per group: the four step entries with a COUNT per group and a row PITCH in place of nframes, so that groups of
+ * one step push different numbers of frames -- in a 100 ms tick an interactive tube in TRAcT order with a 1 ms slice has 100
+ * frames and a sentence voice in Framework order 25, and both are one step and one tube launch.
+ *   - THE RULE does not change.  Every voice receives, bit for bit, what a trm_stream of its group alone returns for that
+ *     group's own pushes and finishes, in the same kernel form, under the group's set's parameters, order and slice: samples,
+ *     counts, maxima, int16 values and clip counts.
+ *   - count: a HOST array of ngroups entries, like action; count[g] is read only where action[g] is TRM_GROUP_PUSH or
+ *     TRM_GROUP_RUN.  On PUSH the group's voices take count[g] frames; on RUN the group generates min(count[g], frames left),
+ *     as it does with nframes.  A PUSH or RUN with count[g] == 0 or count[g] > frame_pitch: TRM_EINVAL naming the group; so is
+ *     a null count with such a group.
+ *   - frames is [nvoices][frame_pitch][16]: voice v's rows are at frames + v * frame_pitch * 16 and the first count[g] of them
+ *     are its frames.  Rows beyond count[g], and the rows of voices that do not PUSH, are not read (the host entry does not
+ *     upload them).  frame_pitch may be 0 and frames null when no group PUSHes or RUNs; frames may be null when groups RUN and
+ *     none PUSHes.  frame_pitch < 0x7FFFFFFF, as nframes.
+ *   - nout[g] = trm_mixed_stream_group_samples_for(s, g, action[g], count[g]) asked before the step.  out_pitch (out_pitch16) >=
+ *     the largest count (x channels) of a non-empty group that synthesizes, the counts now being per group.
+ *     trm_mixed_stream_last_frames returns the count[g] rows a voice consumed (fewer for a RUN near its end), and
+ *     trm_mixed_stream_group_frames_left counts down by what was generated.
+ *   - The step's SHAPE is (frame_pitch, out_pitch) -- an int16 step's (frame_pitch, out_pitch16 rounded up to a multiple of 4) --
+ *     and the device entries make the host wait only when that pair changes or the noise sequence has to grow: counts that vary
+ *     from step to step under one pitch cost no wait, no allocation and no re-upload of the index arrays.  Tube-rate rows of
+ *     down-sampling sets are sized for frame_pitch periods.  A step with frame_pitch 0 keeps the shape it finds.
+ *   - Every refusal comes before any device work and leaves the stream as it was.
+ *   - The entries with and without counts may alternate on one stream: trm_mixed_stream_step(.., nframes, ..) is
+ *     trm_mixed_stream_step_counts with every count equal to nframes and frame_pitch = nframes, and returns the same bits.  Loop
+ *     orders and slices per set, bind / set_params, both conversion modes, TRAcT order's x100, the refusal of RUN on a sliced
+ *     set and of a stream without groups are those of the entries without counts.
+ *   - The first step with counts grows the step's tables by the stretch that holds the counts (it may wait for the device
+ *     once, where a first step's shape waits anyway); a stream on which these entries are never called enqueues exactly what it
+ *     did without them.
+ *   - A library built without the kernel that lays the rows out per count (the host units alone) refuses these entries with
+ *     TRM_EHIP; all else works. */
+int    trm_mixed_stream_step_counts(trm_mixed_stream *s, const uint8_t *action, const uint32_t *count, const float *frames,
+                                    size_t frame_pitch, float *out, size_t out_pitch, uint32_t *nout, float *max_out);
+int    trm_mixed_stream_step_counts_device(trm_mixed_stream *s, const uint8_t *action, const uint32_t *count, const float *d_frames,
+                                           size_t frame_pitch, float *d_out, size_t out_pitch, uint32_t *nout, float *d_max_out,
+                                           void *hip_stream);
+int    trm_mixed_stream_step_counts_int16(trm_mixed_stream *s, const uint8_t *action, const uint32_t *count, const float *frames,
+                                          size_t frame_pitch, const float *level, int for_wav_data, int16_t *out16,
+                                          size_t out_pitch16, uint32_t *nout, float *max_out, uint32_t *clipped);
+int    trm_mixed_stream_step_counts_device_int16(trm_mixed_stream *s, const uint8_t *action, const uint32_t *count,
+                                                 const float *d_frames, size_t frame_pitch, const float *level, int for_wav_data,
+                                                 int16_t *d_out16, size_t out_pitch16, uint32_t *nout, float *d_max_out,
+                                                 uint32_t *d_clipped, void *hip_stream);
 
 /* Library / device identification. */
 int  trm_device_count(void);
