@@ -250,6 +250,12 @@ class TRMBatch:
     def last_kernel(self):
         return {0: "auto", 1: "wide", 2: "quad", 3: "oct"}[lib().trm_batch_last_kernel(self._h)]
 
+    @property
+    def last_downsample(self):
+        """'none' | 'tiled' | 'generic': the converter kernel the last launch ran behind the tube (include/trm_c_api.h:
+        trm_batch_last_downsample)."""
+        return {0: "none", 1: "tiled", 2: "generic"}[lib().trm_batch_last_downsample(self._h)]
+
     def kernel_time_ms(self):
         t = C.c_double()
         n = C.c_uint32()
@@ -307,4 +313,4 @@ class TRMMultiBatch(TRMBatch):
     prepare_device = synthesize_device = scale_to_int16_device = prepare_events_device = generate_frames_device = _device_only
     sound_files_device = _device_only
     noise_table = set_kernel = kernel_time_ms = set_timing = set_time_split = set_split_warmup = _device_only
-    last_kernel = last_time_split = split_warmup = property(_device_only)
+    last_kernel = last_downsample = last_time_split = split_warmup = property(_device_only)

@@ -817,8 +817,11 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
     }
     b->lastKernel = pl.periods ? b->lastSplitForm : which;
     HIP_TRY(launch_form(which, b, b->c, a, stream));
+    b->lastDown = TRM_DOWN_NONE;
     if (!b->c.upsample) {
-        HIP_TRY(trm::launch_downsample(b->c, down_args(b, a, b->dTubeOff.p, 0, nvoices, nullptr), stream));
+        const trm::DownArgs da = down_args(b, a, b->dTubeOff.p, 0, nvoices, nullptr);
+        b->lastDown = trm::downsample_runs_tiled(b->c, da) ? TRM_DOWN_TILED : TRM_DOWN_GENERIC;
+        HIP_TRY(trm::launch_downsample(b->c, da, stream));
     }
     if (b->timing) {
         hipError_t e = hipEventRecord(e1, stream);
@@ -841,6 +844,8 @@ int trm_batch_set_kernel(trm_batch *b, int kernel)
 }
 
 int trm_batch_last_kernel(const trm_batch *b) { return b ? b->lastKernel : TRM_KERNEL_AUTO; }
+
+int trm_batch_last_downsample(const trm_batch *b) { return b ? b->lastDown : TRM_DOWN_NONE; }
 
 int trm_batch_set_timing(trm_batch *b, int on)
 {

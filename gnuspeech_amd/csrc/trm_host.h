@@ -97,6 +97,7 @@ struct trm_batch {
     int kernel = TRM_KERNEL_AUTO;        // trm_batch_set_kernel
     uint32_t wideThreshold = 4097;       // voices from which the one-voice-per-lane kernel is the faster form (set at create)
     int lastKernel = TRM_KERNEL_AUTO;    // what the last launch ran
+    int lastDown = TRM_DOWN_NONE;        // ... and which down-sampling kernel behind it (trm_batch_last_downsample)
     int cus = 0;                         // compute units of the device (set at create)
     int envKernel = TRM_KERNEL_AUTO;     // TRM_TUBE_KERNEL, read once at create (steers launches left on AUTO; tests)
     bool envDownGeneric = false;         // TRM_DOWNSAMPLE_GENERIC, read once at create (tests: the generic down-sampling kernel)

@@ -228,6 +228,8 @@ struct DownArgs {
 hipError_t launch_downsample(const Const &c, const DownArgs &a, hipStream_t stream);
 // whether the tiled kernel (the only one that converts stream chunks) can run a converter of lmax + rmax taps
 bool downsample_tiled_fits(const Const &c, uint32_t lmax, uint32_t rmax);
+// which of the two kernels launch_downsample runs for `a`: the one statement of the choice (trm_batch_last_downsample reports it)
+inline bool downsample_runs_tiled(const Const &c, const DownArgs &a) { return a.rows && downsample_tiled_fits(c, a.lmax, a.rmax); }
 hipError_t launch_int16(const ScaleArgs &s, uint32_t nvoices, hipStream_t stream);
 // sound-file images (header + int16 payload in the container's byte order) per voice, on the device
 struct FileArgs {

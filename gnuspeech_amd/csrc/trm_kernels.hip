@@ -1219,7 +1219,7 @@ hipError_t launch_downsample(const Const &c, const DownArgs &a, hipStream_t stre
     // the tiled kernel where its rows and windows fit LDS (any ratio a stream accepts does), else the generic walk
     uint32_t xlen = 0;
     const size_t lds = down_tile_lds(c, a.lmax, a.rmax, &xlen);
-    if (a.rows && downsample_tiled_fits(c, a.lmax, a.rmax)) {
+    if (downsample_runs_tiled(c, a)) {
         if (lds > 48 * 1024) {
             static DynamicLdsAllowance allowance;
             hipError_t ea = allowance.ensure(reinterpret_cast<const void *>(trm_downsample_rows_kernel), (int)kDownLdsMax);

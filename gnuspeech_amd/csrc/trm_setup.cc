@@ -147,6 +147,12 @@ int build_const(const trm_input_params &p, Const &c, trm_derived &d)
     } else {
         d.phaseIncrement = (uint32_t)rint(d.sampleRateRatio * 65536.0);  // :92
         d.padSize = (int32_t)((float)13 / rounded) + 1;                  // :96
+        // The ratio limit.  Between two runs of the converter the ring takes in kSrcRing - 2 * padSize tube samples
+        // (TRMRingBuffer.m:85-93), and src_count_outputs (trm_lane.h) follows the reference's count as long as that fill is at
+        // least the timeRegisterIncrement / 2^16 samples one output advances by.  Below it (padSize 494 and up, output under
+        // 1/37.9 of the tube rate) a run can end without an output and the reference's count leaves the rule; at padSize 512
+        // the fill is 0, above it the ring's window wraps over itself.  Refused here, so by every create path.
+        if (((int64_t)kSrcRing - 2 * (int64_t)d.padSize) * 65536 < (int64_t)d.timeRegisterIncrement) return TRM_ERANGE;
     }
     d.firTaps = kFirTaps;                                                // TRMFIRFilter.h:7-9: always the same 49
 

@@ -165,7 +165,11 @@ int  trm_batch_derived(const trm_batch *batch, trm_derived *out);
 
 /* Output samples a voice of `nframes` frames produces (exact, integer-only). */
 size_t trm_batch_samples_for_frames(const trm_batch *batch, size_t nframes);
-/* Same, and the derived constants, without a device (sizing / sharding on hosts that only plan). */
+/* Same, and the derived constants, without a device (sizing / sharding on hosts that only plan).  trm_derive -- and with it
+ * every create -- refuses with TRM_ERANGE an output rate so far below the tube rate that the converter's ring, filled between
+ * two runs with 1024 - 2 * padSize tube samples, holds less than the timeRegisterIncrement / 65536 samples one output advances
+ * by (padSize 494 and up, output below about 1/37.9 of the tube rate): from there the reference's own sample count stops
+ * following its rule, and at padSize 512 the fill is 0.  trm_samples_for_frames returns 0 for refused parameters. */
 int    trm_derive(const trm_input_params *params, trm_derived *out);
 size_t trm_samples_for_frames(const trm_input_params *params, size_t nframes);
 
@@ -393,6 +397,13 @@ int  trm_stream_finish_device(trm_stream *stream, float *d_out, size_t out_pitch
 enum { TRM_KERNEL_AUTO = 0, TRM_KERNEL_WIDE = 1, TRM_KERNEL_QUAD = 2, TRM_KERNEL_OCT = 3 };
 int  trm_batch_set_kernel(trm_batch *batch, int kernel);
 int  trm_batch_last_kernel(const trm_batch *batch);
+/* Which converter kernel the last launch ran behind the tube (host bookkeeping; nothing is enqueued): none when the
+ * parameters up-sample; the tiled kernel (per-phase coefficient rows and the voices' windows in LDS) where rows were built --
+ * at most 160 taps a wing -- and a tile fits 96 KB of LDS, output rates down to about 1/5.3 of the tube rate; the generic
+ * kernel (the reference's two wing loops over the fine table, TRMSampleRateConverter.m:234-297) below that and when the
+ * environment variable TRM_DOWNSAMPLE_GENERIC was set as the batch was created (tests).  Both compute the same bits. */
+enum { TRM_DOWN_NONE = 0, TRM_DOWN_TILED = 1, TRM_DOWN_GENERIC = 2 };
+int  trm_batch_last_downsample(const trm_batch *batch);
 
 /* Time split.  -[TRMTubeModel synthesize] (TRMTubeModel.m:272-361) is a serial recurrence per voice, so a batch of a few
  * long utterances (GnuTTSServer's one tube per sentence, PhoneToSpeech.m:66-88) lasts as long as its longest voice

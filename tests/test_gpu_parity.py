@@ -164,11 +164,15 @@ def test_downsampling_speech_rates(g, form, rate, monkeypatch):
     pd = cases.monet_default_params(rate)
     rows = cases.load_gnuspeech_rows()
     voices = cases.config4_frames(11, lo=3, hi=70) + [np.zeros((0, 16)), rows[5:6].copy(), rows[100:102].copy(), rows[0:130].copy()]
+    monkeypatch.delenv("TRM_DOWNSAMPLE_GENERIC", raising=False)
     worst = _batch_vs_oracle(g, pd, voices)
     b = g.TRMBatch(g.TRMInputParameters.from_dict(pd))
     pcm, ns, mx = b.synthesize(voices)
-    monkeypatch.setenv("TRM_DOWNSAMPLE_GENERIC", "1")
-    pcm2, ns2, mx2 = b.synthesize(voices)
+    assert b.last_downsample == "tiled"
+    monkeypatch.setenv("TRM_DOWNSAMPLE_GENERIC", "1")                 # read when a batch object is created
+    b2 = g.TRMBatch(g.TRMInputParameters.from_dict(pd))
+    pcm2, ns2, mx2 = b2.synthesize(voices)
+    assert b2.last_downsample == "generic"
     assert np.array_equal(ns, ns2) and np.array_equal(mx, mx2)
     for a, c in zip(pcm, pcm2):
         assert np.array_equal(a, c)
@@ -188,12 +192,17 @@ def test_downsampling_reference_extra_lap(g, form, monkeypatch):
     rows = cases.load_gnuspeech_rows()
     long_rows = np.concatenate([rows] * 4)
     voices = [long_rows[:1137].copy(), long_rows[100:1236].copy(), long_rows[7:1144].copy()]
+    monkeypatch.delenv("TRM_DOWNSAMPLE_GENERIC", raising=False)
     _batch_vs_oracle(g, pd, voices)                                   # counts exact, RMS within tolerance, incl. the extra lap
     b = g.TRMBatch(ip)
     pcm, ns, mx = b.synthesize(voices)
+    assert b.last_downsample == "tiled"
     assert [int(x) for x in ns] == [plain(1137) + 572, plain(1136), plain(1137) + 572]
-    monkeypatch.setenv("TRM_DOWNSAMPLE_GENERIC", "1")                 # the generic kernel: the same bits
-    pcm2, ns2, mx2 = b.synthesize(voices)
+    monkeypatch.setenv("TRM_DOWNSAMPLE_GENERIC", "1")                 # the generic kernel (a batch created under it): the same bits
+    b2 = g.TRMBatch(ip)
+    pcm2, ns2, mx2 = b2.synthesize(voices)
+    assert b2.last_downsample == "generic"
+    assert [int(x) for x in ns2] == [plain(1137) + 572, plain(1136), plain(1137) + 572]
     assert np.array_equal(ns, ns2) and np.array_equal(mx, mx2) and all(np.array_equal(a, c) for a, c in zip(pcm, pcm2))
 
 
