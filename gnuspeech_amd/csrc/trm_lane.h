@@ -279,8 +279,10 @@ TRM_HD void osc_read(const Const &C, double axd, double pos1, double pos2, SineL
 // The oscillator's advance per half tube sample, f0/2 * 512/sampleRate table entries (TRMWavetable.m:178-181), rounded
 // to a multiple of 2^-30 entries.  Every phase the kernels form is a sum of such increments below 2^11, hence EXACT in
 // fp64: the four-lane kernel's prefix sums, the one-lane kernel's running sum and a stream cut anywhere arrive at the
-// same positions bit for bit, whatever the order of the additions.  (2^-31 entries of rounding per sample: a random
-// walk of 1e-6 entries over a million samples, far inside the tolerance.)
+// same positions bit for bit, whatever the order of the additions.  (At most 2^-31 entries of rounding per increment, two
+// increments per sample: a random walk of 1e-6 entries over a million samples while the pitch moves; a HELD pitch rounds
+// the same way every sample and drifts linearly, at most 2^-30 entries per sample -- 1e-3 entries over a million samples,
+// still far inside the tolerance: tests/stage_probe_common.py check_phase.)
 TRM_HD double osc_increment(double f0, const Const &C)
 {
     return rint_d(((f0 * 0.5) * C.basicIncrement) * 1073741824.0) * (1.0 / 1073741824.0);

@@ -1,6 +1,8 @@
 // trm_oct.h -- the tube stage with EIGHT lanes per voice (trm_quad.hip's "oct" instance): the same junction
 // arithmetic as trm_lane.h's tube_step / trm_quad.h's tube_quad_core (same operations in the same order, so the
-// three agree bit for bit), spread over eight "parts" of two junction slots each instead of four parts of four.
+// three agree bit for bit -- as written: where the compiler fuses an a * b + c of its own choice, per kernel, the device
+// builds differ in the last bit; tests/_probe builds its lane-form probes without that licence), spread over eight "parts"
+// of two junction slots each instead of four parts of four.
 //
 // Why: a wave issues one instruction per ~4.85 cycles whatever its width (profiles/valu_ceiling_r02.txt), so the tube
 // wave's cost per sample is its instruction COUNT.  With four parts a lane carries two packed pairs, the ends as a third

@@ -197,6 +197,7 @@ typedef struct {
     int32_t numberSamples;
     double *out; size_t out_cap;
     double *tube; size_t tube_cap; int32_t ntube; int keep_tube;
+    int32_t ntube_run;                          /* tube samples run so far (kept or not) */
     int oom;
 } tube_t;
 
@@ -475,6 +476,16 @@ static void frication_taps(tube_t *t, int tract)
     }
 }
 
+/* band-pass coefficients (:300, TRMFilters.m:9-17) */
+static void bandpass_coefficients(tube_t *t)
+{
+    double tanv = tan((M_PI * t->current[F_FRICBW]) / t->sampleRate);
+    double cosv = cos((2.0 * M_PI * t->current[F_FRICCF]) / t->sampleRate);
+    t->bpBeta = (1.0 - tanv) / (2.0 * (1.0 + tanv));
+    t->bpGamma = (0.5 + t->bpBeta) * cosv;
+    t->bpAlpha = (0.5 - t->bpBeta) / 2.0;
+}
+
 /* TRMWavetable -update: (TRMWavetable.m:117-162); scalar form (:143-149) == vDSP form */
 static void wavetable_update(tube_t *t, double amp)
 {
@@ -614,8 +625,21 @@ static void tube_push(tube_t *t, double v)
 /* slice: TRAcT's loop order only -- the tube samples every frame is held for (0: a control period).  tube.c reads `current`
  * every sample (tube.c:1121-1136), so parameters may change at any sample; a frame per `slice` samples is that loop with
  * the changes on a grid of `slice` samples (trm_stream_set_slice). */
+/* The stage values a tube holds after tube_coefficients / frication_taps / bandpass_coefficients (trm_oracle.h:
+ * TRM_ORACLE_STAGE_COEFS doubles): what the stage exports hand out and what the sample loop can be asked to show. */
+static void stage_copy(const tube_t *t, double *o)
+{
+    for (int i = 0; i < 8; i++) o[i] = t->oro_k[i];
+    for (int i = 0; i < N_NASAL; i++) o[8 + i] = t->nas_k[i];
+    for (int i = 0; i < 3; i++) o[14 + i] = t->alpha[i];
+    for (int i = 0; i < N_TAPS_FRIC; i++) o[17 + i] = t->fricTap[i];
+    o[25] = t->bpAlpha; o[26] = t->bpBeta; o[27] = t->bpGamma;
+}
+
+typedef struct { int32_t sample; int seen; double *coefs, *table; } stage_tap;
+
 static int synthesize_impl(const trm_input_params *p, const double *frames, size_t nframes,
-                           int keep_tube_samples, trm_oracle_result *out, int tract, int32_t slice)
+                           int keep_tube_samples, trm_oracle_result *out, int tract, int32_t slice, stage_tap *tap)
 {
     if (!p || !out || (nframes && !frames)) return TRM_EINVAL;
     memset(out, 0, sizeof *out);
@@ -635,13 +659,7 @@ static int synthesize_impl(const trm_input_params *p, const double *frames, size
                 double ah1 = trm_oracle_amplitude(t->current[F_ASPVOL]);
                 tube_coefficients(t);                                           /* :298 */
                 frication_taps(t, tract);                                       /* :299 */
-                {                                                               /* :300, TRMFilters.m:9-17 */
-                    double tanv = tan((M_PI * t->current[F_FRICBW]) / t->sampleRate);
-                    double cosv = cos((2.0 * M_PI * t->current[F_FRICCF]) / t->sampleRate);
-                    t->bpBeta = (1.0 - tanv) / (2.0 * (1.0 + tanv));
-                    t->bpGamma = (0.5 + t->bpBeta) * cosv;
-                    t->bpAlpha = (0.5 - t->bpBeta) / 2.0;
-                }
+                bandpass_coefficients(t);                                       /* :300 */
                 double lp_noise;                                                /* :305 */
                 {
                     double product = t->seed * 377.0;
@@ -651,6 +669,12 @@ static int synthesize_impl(const trm_input_params *p, const double *frames, size
                     t->noiseX = nz;
                 }
                 if (p->waveform == TRM_WAVEFORM_PULSE) wavetable_update(t, ax); /* :308-309 */
+                if (tap && !tap->seen && t->ntube_run == tap->sample) {         /* (the stage values this sample uses) */
+                    stage_copy(t, tap->coefs);
+                    memcpy(tap->table, t->wavetable, sizeof t->wavetable);
+                    tap->seen = 1;
+                }
+                t->ntube_run++;
                 double pulse = oscillator(t, f0);                               /* :312 */
                 double pulsed_noise = lp_noise * pulse;                         /* :315 */
                 pulse = ax * ((pulse * (1.0 - t->breathinessFactor)) + (pulsed_noise * t->breathinessFactor)); /* :318 */
@@ -695,20 +719,75 @@ static int synthesize_impl(const trm_input_params *p, const double *frames, size
 int trm_oracle_synthesize(const trm_input_params *p, const double *frames, size_t nframes,
                           int keep_tube_samples, trm_oracle_result *out)
 {
-    return synthesize_impl(p, frames, nframes, keep_tube_samples, out, 0, 0);
+    return synthesize_impl(p, frames, nframes, keep_tube_samples, out, 0, 0, NULL);
 }
 
 int trm_oracle_synthesize_tract(const trm_input_params *p, const double *frames, size_t nframes,
                                 int keep_tube_samples, trm_oracle_result *out)
 {
-    return synthesize_impl(p, frames, nframes, keep_tube_samples, out, 1, 0);
+    return synthesize_impl(p, frames, nframes, keep_tube_samples, out, 1, 0, NULL);
 }
 
 int trm_oracle_synthesize_tract_slices(const trm_input_params *p, const double *frames, size_t nframes, int32_t slice,
                                        int keep_tube_samples, trm_oracle_result *out)
 {
     if (slice < 1) return TRM_EINVAL;
-    return synthesize_impl(p, frames, nframes, keep_tube_samples, out, 1, slice);
+    return synthesize_impl(p, frames, nframes, keep_tube_samples, out, 1, slice, NULL);
+}
+
+/* ---------------------------------------------------------------- stage exports (trm_oracle.h)
+ * Each fills a tube_t and calls the statics the sample loop calls; no formula is stated here. */
+int trm_oracle_stage_wavetables(const trm_input_params *p, const double *amplitudes, size_t n, double *out)
+{
+    if (!p || (n && (!amplitudes || !out))) return TRM_EINVAL;
+    tube_t *t = (tube_t *)malloc(sizeof *t);
+    if (!t) return TRM_ENOMEM;
+    trm_derived d;
+    int rc = tube_init(t, p, &d);
+    for (size_t i = 0; i < n && !rc; i++) {
+        if (p->waveform == TRM_WAVEFORM_PULSE) wavetable_update(t, amplitudes[i]);
+        memcpy(out + i * WT_LEN, t->wavetable, sizeof t->wavetable);
+    }
+    free(t);
+    return rc;
+}
+
+int trm_oracle_stage_wavetable(const trm_input_params *p, double amplitude, double *out)
+{
+    return trm_oracle_stage_wavetables(p, &amplitude, 1, out);
+}
+
+int trm_oracle_stage_coefficients_n(const trm_input_params *p, const double *frames, size_t n, int tract, double *out)
+{
+    if (!p || (n && (!frames || !out))) return TRM_EINVAL;
+    tube_t *t = (tube_t *)malloc(sizeof *t);
+    if (!t) return TRM_ENOMEM;
+    trm_derived d;
+    int rc = tube_init(t, p, &d);
+    for (size_t i = 0; i < n && !rc; i++) {
+        set_control_rate(t, frames + 16 * i, frames + 16 * i);      /* current = the frame, delta 0 */
+        tube_coefficients(t);
+        frication_taps(t, tract);
+        bandpass_coefficients(t);
+        stage_copy(t, out + i * TRM_ORACLE_STAGE_COEFS);
+    }
+    free(t);
+    return rc;
+}
+
+int trm_oracle_stage_coefficients(const trm_input_params *p, const double *frame, int tract, double *out)
+{
+    return trm_oracle_stage_coefficients_n(p, frame, 1, tract, out);
+}
+
+int trm_oracle_synthesize_tapped(const trm_input_params *p, const double *frames, size_t nframes, int32_t sample,
+                                 double *coefs, double *table, trm_oracle_result *out)
+{
+    if (!coefs || !table || sample < 0) return TRM_EINVAL;
+    stage_tap tap = {sample, 0, coefs, table};
+    int rc = synthesize_impl(p, frames, nframes, 1, out, 0, 0, &tap);
+    if (!rc && !tap.seen) { trm_oracle_result_free(out); return TRM_EINVAL; }
+    return rc;
 }
 
 /* bench.py's cpu_baseline leg: `count` voices of `nframes` frames each (frames = [voices][nframes][16] doubles),

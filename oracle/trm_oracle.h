@@ -67,6 +67,24 @@ void trm_oracle_lp_noise(double *lp, size_t count);
 double trm_oracle_amplitude(double decibelLevel);
 double trm_oracle_frequency(double pitch);
 
+/* Stage exports: one tube stage's values for given inputs, from the statics the sample loop itself runs (the probes of
+ * tests/test_stage_probe_*.py compare the kernels' stage functions with them).
+ *   wavetable     the 512-entry glottal table after -update: for `amplitude` (TRMWavetable.m:79-101, :117-162); the sine
+ *                 table for the sine waveform
+ *   coefficients  for one set of current values `frame` (16 columns): TRM_ORACLE_STAGE_COEFS doubles
+ *                 C1..C8 | NC1..NC6 | alpha0..2 | FC1..FC8 | band-pass alpha, beta, gamma
+ *                 (TRMTubeModel.m:712-773, TRMFilters.m:9-17); tract: frication taps x10 (tube.c:1371)
+ * The plural / _n forms run `n` inputs on one tube (out: n x 512, n x TRM_ORACLE_STAGE_COEFS). */
+#define TRM_ORACLE_STAGE_COEFS 28
+int trm_oracle_stage_wavetable(const trm_input_params *params, double amplitude, double *out);
+int trm_oracle_stage_wavetables(const trm_input_params *params, const double *amplitudes, size_t n, double *out);
+int trm_oracle_stage_coefficients(const trm_input_params *params, const double *frame, int tract, double *out);
+int trm_oracle_stage_coefficients_n(const trm_input_params *params, const double *frames, size_t n, int tract, double *out);
+/* trm_oracle_synthesize keeping the tube samples, which also hands out the stage values (as above) and the glottal table
+ * that tube sample `sample` was computed from. */
+int trm_oracle_synthesize_tapped(const trm_input_params *params, const double *frames, size_t nframes, int32_t sample,
+                                 double *coefs, double *table, trm_oracle_result *out);
+
 /* Output scaling (TRMTubeModel.m:370-389 file path, :515-533 WAV-data path):
  * interleaved int16 (host byte order) for `channels` channels. */
 void trm_oracle_scale_int16(const trm_input_params *params, const double *samples, int32_t n,

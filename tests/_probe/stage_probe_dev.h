@@ -1,0 +1,64 @@
+// stage_probe_dev.h -- TEST INFRASTRUCTURE.  What the device launchers of stage_probe*.hip share: device buffers that are
+// freed on every path with the result of hipFree reported, and the one launch-and-fetch sequence.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "stage_probe.h"
+
+namespace trm_probe {
+
+struct DevBufs {
+    void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int n = 0;
+    template <class T>
+    hipError_t get(T **out, size_t count)
+    {
+        *out = nullptr;
+        if (n >= 6) return hipErrorOutOfMemory;
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, count * sizeof(T));
+        if (e != hipSuccess) return e;
+        p[n++] = q;
+        *out = static_cast<T *>(q);
+        return hipSuccess;
+    }
+    // a buffer filled from host memory
+    template <class T>
+    hipError_t put(T **out, const T *host, size_t count)
+    {
+        hipError_t e = get(out, count);
+        return e != hipSuccess ? e : hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice);
+    }
+    hipError_t release()
+    {
+        hipError_t r = hipSuccess;
+        for (int i = 0; i < n; i++) {
+            hipError_t e = hipFree(p[i]);
+            if (r == hipSuccess) r = e;
+        }
+        n = 0;
+        return r;
+    }
+};
+
+// after the launch: its own error, the device's, then the results back to the host
+template <class T>
+inline hipError_t finish(T *host, const T *dev, size_t count)
+{
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost);
+    return e;
+}
+
+inline int result(hipError_t e, DevBufs &B)
+{
+    const hipError_t f = B.release();
+    return (int)(e != hipSuccess ? e : f);
+}
+
+constexpr int kBlock = 256;
+inline unsigned blocks_for(int n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+}  // namespace trm_probe

@@ -172,6 +172,67 @@ def corner_cases():
     return out
 
 
+MONET_VOWEL_FRAME = [-12.0, 60.0, 0.0, 0.0, 5.5, 2500.0, 500.0, 0.8, 0.89, 0.99, 0.81, 0.76, 1.05, 1.23, 0.01, 0.1]   # golden_cases' mv
+FRIC_ONLY_POSITIONS = (0, 0.5, 3, 6.999, 7, 7.5)
+
+
+def isolated_path_cases():
+    """name -> (params dict, frames): voices in which ONE of the tube's quiet paths is the only source (or the path under
+    test the only thing that moves), so that the parity bar -- normalised by the voice's own maximum -- applies to that path
+    itself and not to a vowel 20-40 dB above it: frication alone at a tap, between taps, at the last tap and past it;
+    aspiration alone; the nasal branch with the mouth closed; the throat alone; the pitch extremes (an oscillator increment
+    below one table entry, and 4x the default); voicing from 0.5 dB; a glottal pulse that fills its table and a short one;
+    and a closure point that steps through every tie of rint(amplitude * tnDelta).  41 frames each, closure_sweep 81."""
+    out = {}
+    monet = monet_default_params(44100.0)
+
+    def base(n=41):
+        return static_frames(MONET_VOWEL_FRAME, n)
+
+    def tract(n=41):
+        return static_frames(TRACT_VOWEL_FRAME, n)
+    for pos in FRIC_ONLY_POSITIONS:
+        fr = base()
+        fr[:, 1] = 0.0; fr[:, 2] = 0.0; fr[:, 3] = 54.0; fr[:, 14] = 1.0; fr[:, 4] = pos
+        out["fric_only_pos%g" % pos] = (monet, fr)
+    fr = base()
+    fr[:, 1] = 0.0; fr[:, 2] = 0.0
+    fr[:, 3] = np.linspace(20.0, 60.0, 41)
+    fr[:, 4] = np.linspace(0.0, 7.9, 41)
+    fr[:, 5] = np.linspace(200.0, 9000.0, 41)
+    fr[:, 6] = np.linspace(250.0, 6000.0, 41)
+    out["fric_only_sweep"] = (monet, fr)
+    fr = base()
+    fr[:, 1] = 0.0; fr[:, 2] = np.linspace(5.0, 40.0, 41); fr[:, 14] = 1.0
+    out["asp_only"] = (monet, fr)
+    fr = base()
+    fr[:, 13] = 0.01; fr[:, 14] = 0.01; fr[:, 15] = 1.5
+    out["nasal_only"] = (monet, fr)
+    p = monet_default_params(44100.0); p["throatVol"] = 24.0; p["throatCutoff"] = 300.0
+    fr = base()
+    fr[:, 14] = 0.001; fr[:, 15] = 0.0
+    out["throat_only"] = (p, fr)
+    for pitch in (-24, 24):
+        fr = tract()
+        fr[:, 0] = float(pitch)
+        out["pitch_%d" % pitch] = (tract_default_params(), fr)
+    fr = tract()
+    fr[:, 1] = np.linspace(0.5, 12.0, 41)
+    out["quiet_voicing"] = (tract_default_params(), fr)
+    for name, t in (("pulse_full_table", 50.0), ("pulse_short", 5.0)):
+        p = tract_default_params(); p["tp"] = p["tnMin"] = p["tnMax"] = t
+        out[name] = (p, tract())
+    fr = tract(81)
+    fr[:, 1] = np.linspace(30.0, 60.0, 81)
+    out["closure_sweep"] = (tract_default_params(), fr)
+    return out
+
+
+ISOLATED_PATH_NAMES = ["fric_only_pos%g" % p for p in FRIC_ONLY_POSITIONS] + [
+    "fric_only_sweep", "asp_only", "nasal_only", "throat_only", "pitch_-24", "pitch_24", "quiet_voicing", "pulse_full_table",
+    "pulse_short", "closure_sweep"]
+
+
 # ---------------------------------------------------------------- TRAcT's own loop (SURVEY 8f N4)
 def tract_shim_params():
     """shim/tract_tube.c's utterance-rate globals = Applications/TRAcT/tube.c:326-352 (what the program starts with)."""

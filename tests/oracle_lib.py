@@ -107,6 +107,15 @@ def lib():
         L.trm_oracle_parse_file.argtypes = [C.c_char_p, C.POINTER(InputParams),
                                             C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_size_t)]
         L.trm_oracle_parse_file.restype = C.c_int
+        dp = C.POINTER(C.c_double)
+        L.trm_oracle_stage_wavetable.argtypes = [C.POINTER(InputParams), C.c_double, dp]
+        L.trm_oracle_stage_wavetables.argtypes = [C.POINTER(InputParams), dp, C.c_size_t, dp]
+        L.trm_oracle_stage_coefficients.argtypes = [C.POINTER(InputParams), dp, C.c_int, dp]
+        L.trm_oracle_stage_coefficients_n.argtypes = [C.POINTER(InputParams), dp, C.c_size_t, C.c_int, dp]
+        L.trm_oracle_synthesize_tapped.argtypes = [C.POINTER(InputParams), dp, C.c_size_t, C.c_int32, dp, dp, C.POINTER(_Result)]
+        for f in (L.trm_oracle_stage_wavetable, L.trm_oracle_stage_wavetables, L.trm_oracle_stage_coefficients,
+                  L.trm_oracle_stage_coefficients_n, L.trm_oracle_synthesize_tapped):
+            f.restype = C.c_int
         _lib = L
     return _lib
 
@@ -139,6 +148,58 @@ def synthesize(params, frames, keep_tube=False, tract=False, slice=0):
     out["tubeSamples"] = np.ctypeslib.as_array(res.tubeSamples, shape=(nt,)).copy() if nt else np.zeros(0)
     lib().trm_oracle_result_free(C.byref(res))
     return out
+
+
+STAGE_COEFS = 28        # TRM_ORACLE_STAGE_COEFS: C1..C8 | NC1..NC6 | alpha0..2 | FC1..FC8 | band-pass alpha, beta, gamma
+ST_C, ST_NC, ST_ALPHA, ST_FC, ST_BP = slice(0, 8), slice(8, 14), slice(14, 17), slice(17, 25), slice(25, 28)
+
+
+def stage_wavetables(params, amplitudes):
+    """The glottal table after -update: for every amplitude (oracle/trm_oracle.h stage exports): [n, 512] float64."""
+    a = np.ascontiguousarray(np.atleast_1d(amplitudes), dtype=np.float64)
+    out = np.zeros((len(a), 512))
+    rc = lib().trm_oracle_stage_wavetables(C.byref(params), _dptr(a), len(a), _dptr(out))
+    if rc != 0:
+        raise RuntimeError("trm_oracle_stage_wavetables rc=%d" % rc)
+    return out
+
+
+def stage_wavetable(params, amplitude):
+    out = np.zeros(512)
+    rc = lib().trm_oracle_stage_wavetable(C.byref(params), float(amplitude), _dptr(out))
+    if rc != 0:
+        raise RuntimeError("trm_oracle_stage_wavetable rc=%d" % rc)
+    return out
+
+
+def stage_coefficients(params, frames, tract=False):
+    """The stage values for every row of current values (frames [n,16] or [16]): [n, STAGE_COEFS] float64 (or [STAGE_COEFS])."""
+    fr = np.ascontiguousarray(frames, dtype=np.float64)
+    one = fr.ndim == 1
+    fr = fr.reshape(-1, 16)
+    out = np.zeros((len(fr), STAGE_COEFS))
+    if one:
+        rc = lib().trm_oracle_stage_coefficients(C.byref(params), _dptr(fr), int(tract), _dptr(out))
+    else:
+        rc = lib().trm_oracle_stage_coefficients_n(C.byref(params), _dptr(fr), len(fr), int(tract), _dptr(out))
+    if rc != 0:
+        raise RuntimeError("trm_oracle_stage_coefficients rc=%d" % rc)
+    return out[0] if one else out
+
+
+def synthesize_tapped(params, frames, sample):
+    """synthesize(keep_tube=True) plus the stage values and the glottal table tube sample `sample` was computed from."""
+    frames = np.ascontiguousarray(frames, dtype=np.float64).reshape(-1, 16)
+    res = _Result()
+    coefs, table = np.zeros(STAGE_COEFS), np.zeros(512)
+    rc = lib().trm_oracle_synthesize_tapped(C.byref(params), _dptr(frames), frames.shape[0], int(sample), _dptr(coefs), _dptr(table),
+                                            C.byref(res))
+    if rc != 0:
+        raise RuntimeError("trm_oracle_synthesize_tapped rc=%d" % rc)
+    nt = res.numberTubeSamples
+    tube = np.ctypeslib.as_array(res.tubeSamples, shape=(nt,)).copy()
+    lib().trm_oracle_result_free(C.byref(res))
+    return coefs, table, tube
 
 
 def derive(params):

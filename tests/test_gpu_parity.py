@@ -116,6 +116,16 @@ def test_corner_cases(g, form, name):
     _batch_vs_oracle(g, pd, [frames, frames[:7].copy()])
 
 
+@pytest.mark.parametrize("name", cases.ISOLATED_PATH_NAMES)
+def test_isolated_paths(g, form, name):
+    """tests/cases.py isolated_path_cases in every kernel form: frication, aspiration, the nasal branch or the throat as the
+    voice's ONLY source, the pitch extremes, quiet voicing, the glottal table's extremes -- the one bar, normalised by what
+    that path alone produces.  (The host model of the same arithmetic passes them: tests/test_quad_model.py; a failure
+    here that the model does not show is a device primitive, and tests/test_stage_probe_gpu.py says which.)"""
+    pd, frames = cases.isolated_path_cases()[name]
+    _batch_vs_oracle(g, pd, [frames, frames[:7].copy()])
+
+
 def test_batch_static_vowels_config2(g, form):
     """BASELINE config 2 shape at a size the oracle finishes in seconds: 96 voices x 0.2 s."""
     fr = cases.config2_frames(96, nframes=51)

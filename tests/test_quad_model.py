@@ -116,3 +116,33 @@ def test_product_fir_table_equals_reference_taps(emul):
         ref = golden_io.load(name)["firCoef"]
         assert len(ref) == 49
         assert np.array_equal(half, ref[:25]) and np.array_equal(half[:24], ref[:24:-1])
+
+
+@pytest.fixture(scope="module")
+def isolated():
+    import cases
+    return cases.isolated_path_cases()
+
+
+@pytest.mark.parametrize("name", __import__("cases").ISOLATED_PATH_NAMES)
+def test_isolated_paths_against_oracle(emul, isolated, name):
+    """tests/cases.py isolated_path_cases: voices whose only source is frication, aspiration, the nasal branch or the
+    throat, and the oscillator's and the glottal table's extremes -- the project's bar (exact count, 1e-5 per voice and
+    per control period, normalised by the voice's own maximum) then applies to that path itself.  Both host-model entries."""
+    import parity
+    pd, frames = isolated[name]
+    assert len(frames) == (81 if name == "closure_sweep" else 41)
+    p = O.InputParams.from_dict(pd)
+    fr = np.ascontiguousarray(frames, dtype=np.float32)
+    o = O.synthesize(p, fr.astype(np.float64))
+    assert o["maximumSampleValue"] > 1e-6          # audible on its own: the bar is about this path, not a floor
+    for what, fn in (("lane", emul.trm_emul_synthesize), ("quad", emul.trm_emul_synthesize_quad)):
+        cap = len(fr) * 700 + 2000
+        out = np.zeros(cap, dtype=np.float32)
+        n, m = C.c_uint32(), C.c_float()
+        assert fn(C.byref(p), fr.ctypes.data_as(C.POINTER(C.c_float)), len(fr), out.ctypes.data_as(C.POINTER(C.c_float)), cap,
+                  C.byref(n), C.byref(m), None) == 0
+        assert n.value == o["numberSamples"]
+        r = parity.check_oracle(out[:n.value], o, parity.window_length_of(pd), what="%s (%s)" % (name, what))
+        print("%s %s: max %.3e, normalised RMS %.2e, worst control period %.2e" % (name, what, o["maximumSampleValue"], r["nrms"],
+                                                                                   r["worst_window_nrms"]))

@@ -1,0 +1,68 @@
+"""The stage probes on the device: every stage function of gnuspeech_amd/csrc/trm_lane.h / trm_quad.h / trm_oct.h run by itself
+in a kernel of tests/_probe/libtrm_probe.so -- the real v_rcp_f32, v_exp_f32, fmed3, v_fma_f32 and DPP moves, where every model
+test under tests/_emul runs the headers' host stand-ins -- over the grids of tests/stage_probe_common.py, against the oracle's
+stage exports at bars derived there, with the headers' exact promises asserted bit for bit.  The host build of the same probe
+bodies runs beside it where a claim reads "device == host build".  Each probe is one launch of at most 2^20 threads."""
+import pytest
+
+import stage_probe_common as S
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def P():
+    return S.device_probe()
+
+
+@pytest.fixture(scope="module")
+def H():
+    return S.host_probe()
+
+
+def test_amplitude(P, H):
+    S.check_amplitude(P, host=H)
+
+
+def test_amplitude_is_continuous_below_2_to_minus_100(P, H):
+    S.check_amplitude_continuity(P, host=H)
+
+
+def test_sine_table(P):
+    S.check_sine(P)
+
+
+def test_polynomials(P):
+    S.check_polynomials(P)
+
+
+def test_pulse_table(P):
+    S.check_pulse(P)
+
+
+def test_area_coefficients(P):
+    S.check_area(P)
+
+
+def test_frication_coefficients(P):
+    S.check_fric(P)
+
+
+def test_frication_positions_below_zero_are_continuous(P, H):
+    S.check_fric_below_zero(P, host=H)
+
+
+def test_held_periods(P):
+    S.check_held(P)
+
+
+@pytest.mark.parametrize("which", ["quad", "oct"])
+def test_lane_forms_equal_tube_step(P, which):
+    """tube_quad_step / tube_quad_core (DPP row rotations by banks of four lanes) and tube_oct_core (row rotations by single
+    lanes) beside tube_step in the same kernel: 16 resp. 8 voices per wave, 2 000 steps, seeds 1..3, once with every voice
+    under test and once with every other voice carrying NaN."""
+    S.check_lanes(P, which)
+
+
+def test_oscillator_phase(P):
+    S.check_phase(P)

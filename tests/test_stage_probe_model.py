@@ -1,0 +1,57 @@
+"""The stage probes on the CPU: the probe bodies of tests/_probe/stage_probe.h built for the host (stage_probe_host.cc over the
+kernel headers' host stand-ins, DPP as tests/_emul/trm_emul.cc emulates it) run over the grids of tests/stage_probe_common.py
+against the oracle's stage exports.  This validates the grids, the references and the derived bars without a GPU;
+tests/test_stage_probe_gpu.py runs the same checks on the device build."""
+import pytest
+
+import stage_probe_common as S
+
+
+@pytest.fixture(scope="module")
+def P():
+    return S.host_probe()
+
+
+def test_amplitude(P):
+    S.check_amplitude(P)
+
+
+def test_amplitude_is_continuous_below_2_to_minus_100(P):
+    S.check_amplitude_continuity(P)
+
+
+def test_sine_table(P):
+    S.check_sine(P)
+
+
+def test_polynomials(P):
+    S.check_polynomials(P)
+
+
+def test_pulse_table(P):
+    S.check_pulse(P)
+
+
+def test_area_coefficients(P):
+    S.check_area(P)
+
+
+def test_frication_coefficients(P):
+    S.check_fric(P)
+
+
+def test_frication_positions_below_zero_are_continuous(P):
+    S.check_fric_below_zero(P)
+
+
+def test_held_periods(P):
+    S.check_held(P)
+
+
+@pytest.mark.parametrize("which", ["quad", "oct"])
+def test_lane_forms_equal_tube_step(P, which):
+    S.check_lanes(P, which)
+
+
+def test_oscillator_phase(P):
+    S.check_phase(P)
