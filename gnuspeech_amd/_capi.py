@@ -72,6 +72,7 @@ EXPORTS = [
     "trm_batch_set_kernel", "trm_batch_last_kernel", "trm_batch_last_downsample", "trm_batch_set_time_split", "trm_batch_last_time_split", "trm_batch_hint_frames",
     "trm_batch_set_split_warmup", "trm_batch_split_warmup", "trm_split_warm_periods", "trm_tube_set_split_warmup",
     "trm_mixed_set_split_warmup", "trm_mixed_split_warmup",
+    "trm_batch_set_split_form", "trm_batch_split_form", "trm_tube_set_split_form",
     "trm_batch_kernel_time_ms", "trm_batch_set_timing", "trm_batch_noise_table", "trm_device_count", "trm_build_info", "trm_kernel_blocks_per_cu", "trm_kernel_blocks_per_cu_form",
     "trm_mixed_create", "trm_mixed_destroy", "trm_mixed_derived", "trm_mixed_samples_for_frames", "trm_mixed_synthesize_device",
     "trm_mixed_synthesize_host", "trm_mixed_synthesize_host_int16", "trm_mixed_set_kernel", "trm_mixed_last_kernel",
@@ -195,6 +196,9 @@ def lib():
     L.trm_split_warm_periods.argtypes = [C.POINTER(TrmInputParams), C.c_int]
     L.trm_split_warm_periods.restype = C.c_uint32
     L.trm_tube_set_split_warmup.argtypes = [vp, C.c_int]
+    L.trm_batch_set_split_form.argtypes = [vp, C.c_int]
+    L.trm_batch_split_form.argtypes = [vp]
+    L.trm_tube_set_split_form.argtypes = [vp, C.c_int]
     L.trm_mixed_set_split_warmup.argtypes = [vp, C.c_int]
     L.trm_mixed_split_warmup.argtypes = [vp]
     L.trm_batch_noise_table.argtypes = [vp, vp, C.c_size_t]
@@ -282,6 +286,14 @@ def split_warmup_code(warmup, periods_ok=True):
 
 def split_warmup_name(code):
     return {TRM_SPLIT_WARMUP_DEFAULT: "default", TRM_SPLIT_WARMUP_COUPLED: "coupled"}.get(code, code)
+
+
+def split_form_code(form):
+    """'auto' | 'oct' -> TRM_KERNEL_AUTO | TRM_KERNEL_OCT (trm_batch_set_split_form); anything else is refused here."""
+    codes = {"auto": TRM_KERNEL_AUTO, "oct": 3}
+    if not isinstance(form, str) or form not in codes:
+        raise ValueError("split form %r: 'auto' or 'oct'" % (form,))
+    return codes[form]
 
 
 def split_warm_periods(inputParameters, rule="default"):

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import TrmDerived, check, lib, split_warmup_code, split_warmup_name
+from ._capi import TrmDerived, check, lib, split_form_code, split_warmup_code, split_warmup_name
 
 
 class TRMBatch:
@@ -242,6 +242,17 @@ class TRMBatch:
         """'default' | 'coupled' | control periods, as set."""
         return split_warmup_name(lib().trm_batch_split_warmup(self._h))
 
+    def set_split_form(self, form):
+        """'auto' | 'oct': the form of a time split's segments (include/trm_c_api.h: trm_batch_set_split_form).  'oct' runs
+        eight-lane segments -- 8 voices x one segment per workgroup, the lowest-latency form for a single utterance -- where the
+        parameters admit them; where not, and under 'auto' (the default), launches are planned as ever."""
+        check(lib().trm_batch_set_split_form(self._h, split_form_code(form)))
+
+    @property
+    def split_form(self):
+        """'auto' | 'oct', as set."""
+        return {0: "auto", 3: "oct"}[lib().trm_batch_split_form(self._h)]
+
     def set_timing(self, on):
         """Launch timing on / off; off, synthesize_device is pure stream work and can be captured into a HIP graph."""
         check(lib().trm_batch_set_timing(self._h, int(bool(on))))
@@ -312,5 +323,5 @@ class TRMMultiBatch(TRMBatch):
 
     prepare_device = synthesize_device = scale_to_int16_device = prepare_events_device = generate_frames_device = _device_only
     sound_files_device = _device_only
-    noise_table = set_kernel = kernel_time_ms = set_timing = set_time_split = set_split_warmup = _device_only
-    last_kernel = last_downsample = last_time_split = split_warmup = property(_device_only)
+    noise_table = set_kernel = kernel_time_ms = set_timing = set_time_split = set_split_warmup = set_split_form = _device_only
+    last_kernel = last_downsample = last_time_split = split_warmup = split_form = property(_device_only)

@@ -550,6 +550,18 @@ double unsplit_cost(const trm_batch *b, size_t nvoices, int which)
     if (which == TRM_KERNEL_QUAD) return vpc <= 16 ? 3.1 : vpc <= 32 ? 4.1 : 4.1 * vpc / 32.0;
     return wide_cost(b, (nvoices + 63) / 64);
 }
+// The eight-lane SEGMENT form (trm_oct_seg.hip), by busy workgroups of 8 voices per CU: ms per second of speech of the launch's
+// longest workgroup.  Fitted from the named-S rows of profiles/bench_split_oct.txt (256 CUs; 1 .. 256 voices x 1 s, S = 15, 23, 40),
+// rate = (t - 0.03) / ((S + W) CP / 19750): up to half a workgroup per CU 2.12 .. 2.32 (nine rows), at 0.75 per CU 2.24 (one
+// row), at 1.25 and 1.875 per CU 2.54 and 2.63.  Each class holds the largest rate measured in it, rounded up to a hundredth, and
+// never less than the class below: the model promises no more than was seen.  (A segment workgroup so runs 3 - 11 % slower than
+// unsplit_cost's whole utterances at the same workgroups per CU: the prologue and the flush are paid per segment.)  Beyond two per
+// CU the launch runs in rounds (4.6 at three per CU) and is not priced: plan_split asks for at most two.
+static double oct_seg_cost(const trm_batch *b, uint64_t busy)
+{
+    const double cus = b->cus > 0 ? b->cus : 256, x = (double)busy / cus;
+    return x <= 1.0 ? 2.32 : 2.64;
+}
 
 // the frication band-pass (TRMFilters.m:9-29) has poles of radius sqrt(2 beta), 2 beta = (1 - t) / (1 + t),
 // t = tan(pi BW / SR): the bandwidth at which a warm-up of `warm` control periods leaves 1e-5 of its memory
@@ -575,13 +587,16 @@ void hinted_blocks(const size_t *set_begin, size_t nsets, size_t perWg, const st
 
 // workgroups of a time-split launch that have work: block by block (its longest voice) the segments it reaches -- what
 // trm_seg_map_kernel counts on the device -- or, where no lengths were told, every block of every set in all of the set's segments
-static uint64_t busy_workgroups(const SplitAsk &ask, bool quad, uint32_t sp)
+// (form: the segments' -- the 64-voice cut, the 16-voice cut of four lanes per voice, the 8-voice cut of eight)
+static uint64_t busy_workgroups(const SplitAsk &ask, int form, uint32_t sp)
 {
+    const bool quad = form == TRM_KERNEL_QUAD, oct = form == TRM_KERNEL_OCT;
     uint64_t n = 0;
-    if (const std::vector<SplitBlock> *cut = quad ? ask.cut16 : ask.cut64) {
+    if (const std::vector<SplitBlock> *cut = oct ? ask.cut8 : quad ? ask.cut16 : ask.cut64) {
         for (const SplitBlock &blk : *cut) n += trm::seg_count(blk.longest, sp, ask.sets[blk.set].warm);
     } else {
-        for (size_t s = 0; s < ask.nsets; s++) n += (quad ? ask.sets[s].blocks16 : ask.sets[s].blocks64) * trm::seg_count(ask.P, sp, ask.sets[s].warm);
+        for (size_t s = 0; s < ask.nsets; s++)
+            n += (oct ? ask.sets[s].blocks8 : quad ? ask.sets[s].blocks16 : ask.sets[s].blocks64) * trm::seg_count(ask.P, sp, ask.sets[s].warm);
     }
     return n;
 }
@@ -610,9 +625,11 @@ SplitPlan plan_split(const trm_batch *b0, const SplitAsk &ask)
         return x;
     };
     if (ask.setting > 0) {
-        // a split asked for by name: in the form asked for by name (four lanes, or one voice per lane), else by size
+        // a split asked for by name: in the segment form asked for by name (eight lanes: trm_batch_set_split_form), else in the
+        // form asked for by name (four lanes, or one voice per lane), else by size
         pl.periods = (uint32_t)ask.setting;
-        if (ask.quadOk && (ask.byName == TRM_KERNEL_QUAD || (ask.byName == TRM_KERNEL_AUTO && busy_workgroups(ask, true, pl.periods) <= cus)))
+        if (ask.octOk) pl.form = TRM_KERNEL_OCT;
+        else if (ask.quadOk && (ask.byName == TRM_KERNEL_QUAD || (ask.byName == TRM_KERNEL_AUTO && busy_workgroups(ask, TRM_KERNEL_QUAD, pl.periods) <= cus)))
             pl.form = TRM_KERNEL_QUAD;
     } else {
         // AUTO.  A time-split launch pays when its workgroups -- one per segment and block of 64 voices, the longest of them
@@ -627,13 +644,22 @@ SplitPlan plan_split(const trm_batch *b0, const SplitAsk &ask)
             const uint32_t sp = (P - warmMax + nseg - 1) / nseg;       // the shortest segments that make `nseg` of them
             if (sp < minPeriods) break;
             // (sp >= 4 and nseg >= 2: P > sp + warmMax, every candidate has a second segment)
-            const double t = 0.03 + wide_cost(b0, busy_workgroups(ask, false, sp)) * seg_samples(sp) / 19750.0;
+            const double t = 0.03 + wide_cost(b0, busy_workgroups(ask, TRM_KERNEL_WIDE, sp)) * seg_samples(sp) / 19750.0;
             if (t < best) { best = t; pl.periods = sp; pl.form = TRM_KERNEL_WIDE; }
             // ... or in the four-lane form (16 voices x one segment per workgroup, one workgroup per CU at 3.1 ms per second of
             // speech -- measured for uniform batches at the default warm-up): a handful of voices, a single utterance
-            if (ask.quadOk && busy_workgroups(ask, true, sp) <= cus) {
+            if (ask.quadOk && busy_workgroups(ask, TRM_KERNEL_QUAD, sp) <= cus) {
                 const double tq = 0.03 + 3.1 * seg_samples(sp) / 19750.0;
                 if (tq < best) { best = tq; pl.periods = sp; pl.form = TRM_KERNEL_QUAD; }
+            }
+            // ... or, where the caller asked for it, in the eight-lane form (8 voices x one segment per workgroup, two workgroups
+            // per CU: oct_seg_cost)
+            if (ask.octOk && ask.byName == TRM_KERNEL_AUTO) {
+                const uint64_t busy8 = busy_workgroups(ask, TRM_KERNEL_OCT, sp);
+                if (busy8 <= 2 * cus) {
+                    const double to = 0.03 + oct_seg_cost(b0, busy8) * seg_samples(sp) / 19750.0;
+                    if (to < best) { best = to; pl.periods = sp; pl.form = TRM_KERNEL_OCT; }
+                }
             }
         }
     }
@@ -641,7 +667,7 @@ SplitPlan plan_split(const trm_batch *b0, const SplitAsk &ask)
     bool any = false;
     for (size_t s = 0; pl.periods && s < ask.nsets; s++) any = any || (ask.sets[s].blocks64 && trm::seg_count(P, pl.periods, ask.sets[s].warm) >= 2);
     if (!any) return SplitPlan();
-    pl.busy = busy_workgroups(ask, pl.form == TRM_KERNEL_QUAD, pl.periods);
+    pl.busy = busy_workgroups(ask, pl.form, pl.periods);
     return pl;
 }
 
@@ -682,6 +708,16 @@ int trm_batch_set_split_warmup(trm_batch *b, int rule_or_periods)
 }
 
 int trm_batch_split_warmup(const trm_batch *b) { return b ? b->splitWarmup : TRM_SPLIT_WARMUP_DEFAULT; }
+
+int trm_batch_set_split_form(trm_batch *b, int form)
+{
+    if (!b) return fail(TRM_EINVAL, "null batch");
+    if (form != TRM_KERNEL_AUTO && form != TRM_KERNEL_OCT) return fail(TRM_EINVAL, "split form: %d is neither TRM_KERNEL_AUTO nor TRM_KERNEL_OCT", form);
+    b->splitForm = form;
+    return TRM_OK;
+}
+
+int trm_batch_split_form(const trm_batch *b) { return b ? b->splitForm : TRM_KERNEL_AUTO; }
 
 uint32_t trm_split_warm_periods(const trm_input_params *params, int rule)
 {
@@ -768,12 +804,15 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
         if ((warm = batch_split_warm(b)) == 0) {
             if (setting > 0) return fail(TRM_ERANGE, "time split: the tube never forgets (loss factor %g %%)", b->params.lossFactor);
         } else {
-            const SplitSet set = {(uint32_t)b->c.controlPeriod, warm, (nvoices + 63) / 64, (nvoices + 15) / 16};
+            const SplitSet set = {(uint32_t)b->c.controlPeriod, warm, (nvoices + 63) / 64, (nvoices + 15) / 16, (nvoices + 7) / 8};
             SplitAsk ask = {&set, 1, nvoices, max_nframes - 1, setting, which, byName, false, nullptr, nullptr};
+            // the eight-lane segment instance, where the caller asked for it (trm_batch_set_split_form): up-sampling sets within the
+            // same converter ratio, control periods of at least two of its steps (launch_tube_oct)
+            ask.octOk = b->splitForm == TRM_KERNEL_OCT && b->c.upsample && !quad_ratio_too_high(b->c) && b->c.controlPeriod >= 16;
             // the four-lane segment instance: up-sampling batches whose converter makes at most four outputs per tube sample
             ask.quadOk = b->c.upsample && !quad_ratio_too_high(b->c) && which != TRM_KERNEL_WIDE;
             // the longest voice of every block of 64 / 16 voices, where the caller told the lengths: AUTO prices the work there is
-            std::vector<SplitBlock> cut64, cut16;
+            std::vector<SplitBlock> cut64, cut16, cut8;
             const size_t range[2] = {0, nvoices};
             if (b->hintFrames.size() == nvoices && setting <= 0) {
                 hinted_blocks(range, 1, 64, b->hintFrames, max_nframes, cut64);
@@ -782,17 +821,22 @@ int trm_batch_synthesize_device(trm_batch *b, size_t nvoices, const float *d_fra
                     hinted_blocks(range, 1, 16, b->hintFrames, max_nframes, cut16);
                     ask.cut16 = &cut16;
                 }
+                if (ask.octOk) {
+                    hinted_blocks(range, 1, 8, b->hintFrames, max_nframes, cut8);
+                    ask.cut8 = &cut8;
+                }
             }
             pl = plan_split(b, ask);
             allBusy = pl.periods && ask.cut64 &&
-                      pl.busy == (uint64_t)trm::seg_count(max_nframes - 1, pl.periods, warm) * (pl.form == TRM_KERNEL_QUAD ? set.blocks16 : set.blocks64);
+                      pl.busy == (uint64_t)trm::seg_count(max_nframes - 1, pl.periods, warm) *
+                                     (pl.form == TRM_KERNEL_OCT ? set.blocks8 : pl.form == TRM_KERNEL_QUAD ? set.blocks16 : set.blocks64);
         }
     }
     b->lastSplitPeriods = pl.periods;
     b->lastSplitWarm = pl.periods ? warm : 0;
     if (pl.periods) {
         const uint32_t nseg = trm::seg_count(max_nframes - 1, pl.periods, warm);
-        const uint32_t perWg = pl.form == TRM_KERNEL_QUAD ? 16u : 64u;
+        const uint32_t perWg = pl.form == TRM_KERNEL_OCT ? 8u : pl.form == TRM_KERNEL_QUAD ? 16u : 64u;
         const uint32_t wgPerSeg = (uint32_t)((nvoices + perWg - 1) / perWg);
         if ((uint64_t)nseg * wgPerSeg > 0x7FFFFFFFull / 64) return fail(TRM_ERANGE, "time split: too many segments");
         if ((rc = b->dSegPhase.reserve((size_t)nseg * wgPerSeg * perWg)) || (rc = b->dPeriodAdv.reserve(nvoices * (size_t)max_nframes)) ||
@@ -1253,6 +1297,12 @@ int trm_tube_set_split_warmup(trm_tube *t, int rule_or_periods)
 {
     if (!t) return fail(TRM_EINVAL, "null tube");
     return trm_batch_set_split_warmup(t->b, rule_or_periods);
+}
+
+int trm_tube_set_split_form(trm_tube *t, int form)
+{
+    if (!t) return fail(TRM_EINVAL, "null tube");
+    return trm_batch_set_split_form(t->b, form);
 }
 
 size_t trm_tube_number_samples(const trm_tube *t) { return t ? t->numberSamples : 0; }

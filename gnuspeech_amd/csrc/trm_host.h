@@ -108,6 +108,7 @@ struct trm_batch {
     uint32_t lastSplitPeriods = 0, lastSplitWarm = 0;      // what the last launch did (0: whole utterances)
     int lastSplitForm = TRM_KERNEL_WIDE;
     int splitWarmup = TRM_SPLIT_WARMUP_DEFAULT;  // trm_batch_set_split_warmup: a rule, or (> 0) a warm-up in control periods
+    int splitForm = TRM_KERNEL_AUTO;             // trm_batch_set_split_form: AUTO, or OCT = eight-lane segments where admissible
     DevBuf<double> dSegPhase, dPeriodAdv;
     DevBuf<uint2> dSegMap;               // a time-split grid's launch order (trm_seg_map_kernel)
     DevBuf<uint32_t> dBlockFrames;
@@ -174,7 +175,7 @@ float split_bw_floor(const trm_batch *b, uint32_t warm);
 
 // The planner of uniform and mixed batches alike: one segment length S for the launch, every parameter set's own warm-up.
 // A trm_batch is the one-set case.  What the callers differ in arrives as data:
-struct SplitSet { uint32_t cp, warm; uint64_t blocks64, blocks16; };    // control period, warm-up (the caller's choice, > 0), workgroups of 64 / 16 voices (0, 0: no voices)
+struct SplitSet { uint32_t cp, warm; uint64_t blocks64, blocks16, blocks8; };    // control period, warm-up (the caller's choice, > 0), workgroups of 64 / 16 / 8 voices (0: no voices; blocks8 only where octOk)
 struct SplitBlock { uint32_t set, longest; };                            // a workgroup's set and its longest voice in control periods
 struct SplitAsk {
     const SplitSet *sets;
@@ -185,10 +186,14 @@ struct SplitAsk {
     bool quadOk;                              // the four-lane segment form is admissible (the caller's policy)
     // the 64-voice and the 16-voice cut block by block where a hint told the lengths; null: every block of SplitSet's counts is P long
     const std::vector<SplitBlock> *cut64, *cut16;
+    // the eight-lane segment form was asked for (trm_batch_set_split_form) and is admissible: a named S runs in it; AUTO, where no
+    // form is named, prices every candidate in it too.  cut8: the 8-voice cut, as the other two.  (A mixed batch: false, null.)
+    bool octOk = false;
+    const std::vector<SplitBlock> *cut8 = nullptr;
 };
 struct SplitPlan {
     uint32_t periods = 0;                     // S; 0 = whole utterances
-    int form = TRM_KERNEL_WIDE;               // the segments' form: one voice per lane (the 64-voice cut) or four lanes per voice (the 16-voice cut)
+    int form = TRM_KERNEL_WIDE;               // the segments' form: one voice per lane (the 64-voice cut), four lanes per voice (the 16-voice cut) or eight (the 8-voice cut)
     uint64_t busy = 0;                        // workgroups of that cut with work
 };
 SplitPlan plan_split(const trm_batch *b0, const SplitAsk &ask);

@@ -62,7 +62,8 @@ struct TubeArgs {
     // trm_capi.cc plan_time_split), and emits the converter outputs whose read position lies in the segment proper.  What a
     // segment cannot reconstruct from the frames is the oscillator position: seg_phase[q * 64 * seg_wg_per_seg + v] is the
     // (wrapped) advance of voice v's oscillator between the warm-up starts of segments q - 1 and q (trm_phase_segment_kernel);
-    // (seg_phase's row pitch is seg_wg_per_seg x the voices of a workgroup: 64 here, 16 in trm_tube_kernel_q's segment instance)
+    // (seg_phase's row pitch is seg_wg_per_seg x the voices of a workgroup: 64 here, 16 in trm_tube_kernel_q's segment instance,
+    // 8 in the eight-lane form's, trm_octseg_kernel)
     // the kernel sums q = 1 .. its own segment (exact sums: osc_increment).  max_sample is folded with an atomic max
     // (zeroed by the launcher), number_samples written by segment 0.
     uint32_t seg_periods = 0, seg_warm = 0, seg_wg_per_seg = 0;
@@ -120,7 +121,7 @@ struct PhaseArgs {
     uint32_t *gate;
     float bw_floor;
     uint32_t nvoices, max_nframes, nseg, seg_periods, seg_warm, seg_wg_per_seg, seg_first;
-    uint32_t voices_per_wg;       // of the tube kernel that follows: 64 (trm_tube_kernel) or 16 (trm_tube_kernel_q)
+    uint32_t voices_per_wg;       // of the tube kernel that follows: 64 (trm_tube_kernel), 16 (trm_tube_kernel_q) or 8 (trm_octseg_kernel)
     // the launch order of the (segment, block of voices) pairs: those with work first (null: none is built)
     uint2 *seg_map = nullptr;
     uint32_t *block_frames = nullptr;     // scratch, seg_wg_per_seg entries: the longest voice of every block
@@ -156,6 +157,9 @@ hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream
 // indexed by map entry * 16 + the voice within the entry)
 hipError_t launch_mix_seg_quad(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);
 hipError_t launch_mix_oct(const Const &c, const TubeArgs &a, hipStream_t stream);
+// The eight-lane form's time-split instance (trm_oct_seg.hip: trm_octseg_kernel; a.seg_periods set, no mix_map, an up-sampling
+// set): a.seg_grid workgroups of 8 voices x one segment, seg_phase rows of 8 * seg_wg_per_seg entries.  launch_tube_oct calls it.
+hipError_t launch_seg_oct(const Const &c, const TubeArgs &a, hipStream_t stream);
 // Grouped streams (TubeArgs::grp_*): trm_grp_stream.hip and trm_grp_stream_q.hip compile the two streaming forms' mixed instances
 // once more with a clock per map entry (trm_grpstream_kernel, trm_grpstream_kernel_q); launch_tube / launch_tube_quad call these
 // for a launch with a grp_clock.  `grid` workgroups from a.wg_base / a.mix_grid workgroups: of the list grp_active.
@@ -197,7 +201,8 @@ extern hipError_t (*grp_prep_counts_launcher)(const GrpPrepCountsArgs &a, hipStr
 constexpr int kStreamFloats = 192;   // oscillator position, filter memories, 32 samples of FIR / converter history, 4 x 20 tube values
 // `cus` = the device's compute units: more workgroups than that run the instance that fits two per CU
 hipError_t launch_tube_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int cus);
-// eight lanes per voice, 8 voices per workgroup (trm_oct.hip): one-shot batches of at most two workgroups per CU
+// eight lanes per voice, 8 voices per workgroup (trm_oct.hip): one-shot batches of at most two workgroups per CU; with
+// a.seg_periods set, the time-split instance (launch_seg_oct)
 hipError_t launch_tube_oct(const Const &c, const TubeArgs &a, hipStream_t stream);
 int tube_oct_kernel_blocks_per_cu();
 int tube_quad_kernel_blocks_per_cu(int sub);     // sub = blocks per pipeline step of the instance asked about (1 or 2)

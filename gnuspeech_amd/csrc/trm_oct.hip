@@ -12,7 +12,8 @@
 //   tube                   lanes = 8 parts of the tube (trm_oct.h): ~35 instructions per sample instead of 50
 //   convert                lane = output time (rows of 32 outputs x 2 voices), two row pairs per block
 // One barrier per step of 8 tube samples.  At step i osc works on block i, mix on i-1, the coefficient waves and the two
-// scans on i-2, tube on i-4, convert on whatever is complete, metered.  No streaming instance (trm_quad.hip carries streams).
+// scans on i-2, tube on i-4, convert on whatever is complete, metered.  No streaming instance (trm_quad.hip carries streams);
+// trm_oct_seg.hip builds the time-split instance (kSeg below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -97,11 +98,34 @@ __device__ __forceinline__ HalfPair across_halves(float x)
     return HalfPair{__builtin_bit_cast(float, r.lo), __builtin_bit_cast(float, r.hi)};
 }
 
+// The launch's output k: the tube sample its window ends at, counted from the launch's first (src_position: trm_lane.h), and its
+// converter phase.  In the segment instance (kSeg, below) the output's index in the utterance is kBase + k and the launch's
+// first tube sample is nBase; otherwise both are 0 and the arguments unused.
+template <bool kSeg>
+__device__ __forceinline__ uint32_t seg_out_position(uint32_t inc, uint32_t kBase, uint32_t nBase, uint32_t k)
+{
+    if constexpr (kSeg) return src_position(kBase + k, inc) - nBase;
+    else return src_position(k, inc);
+}
+template <bool kSeg>
+__device__ __forceinline__ uint32_t seg_out_phase(uint32_t inc, uint32_t kBase, uint32_t k)
+{
+    if constexpr (kSeg) return src_phase(kBase + k, inc);
+    else return src_phase(k, inc);
+}
+
 // kMix: a launch whose workgroups may belong to different parameter sets (trm_kernels.h, TubeArgs::mix_map): the
 // workgroup's constants come from set_const, its voices are the map entry's range.
-template <bool kMix = false>
+// kSeg (trm_oct_seg.hip: trm_octseg_kernel): a TIME-SPLIT launch (trm_kernels.h, TubeArgs::seg_*) -- workgroup w runs one
+// segment of 8 voices from rest, a warm-up ahead, with the time bases of trm_quad.hip's segment instance: tube samples count
+// from the warm-up's first (nBase), converter outputs from the segment's first (kBase).  Up-sampling sets only (no tube_out).
+template <bool kMix = false, bool kSeg = false>
 __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Const Carg, const TubeArgs A)
 {
+    static_assert(!kSeg || !kMix, "the segment instance is a uniform launch's");
+    if constexpr (kSeg) {
+        if (A.gate && ((*A.gate != 0u) ? 1u : 0u) != A.gate_want) return;      // (two launches, the device runs one: TubeArgs::gate)
+    }
     typedef OctLds L;
     extern __shared__ __attribute__((aligned(16))) unsigned char sLds[];
     float2 *const sO = reinterpret_cast<float2 *>(sLds + L::oO);           // osc -> mix: oscillator reads
@@ -143,16 +167,41 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     // mixed launch: the workgroup's parameter set (C read in place: a reference into the table) and voice range
     const uint4 mix = kMix ? A.mix_map[blockIdx.x] : make_uint4(0u, 0u, 0u, 0u);
     const Const &C = kMix ? *(const Const *)(A.set_const + mix.x) : Carg;
-    const uint32_t vFirst = kMix ? mix.y : blockIdx.x * kOV, vEnd = kMix ? mix.z : A.nvoices;
+    // time split: workgroup -> (segment, block of 8 voices)
+    uint32_t seg = 0, vblock = blockIdx.x;
+    if constexpr (kSeg) {
+        if (A.seg_map) {                     // (the pairs with work first: trm_kernels.hip, trm_seg_map_kernel)
+            const uint2 m = A.seg_map[blockIdx.x];
+            seg = m.x;
+            vblock = m.y;
+        } else {
+            seg = blockIdx.x / A.seg_wg_per_seg;
+            vblock = blockIdx.x - seg * A.seg_wg_per_seg;
+        }
+    }
+    const uint32_t vFirst = kMix ? mix.y : vblock * kOV, vEnd = kMix ? mix.z : A.nvoices;
     const uint32_t vRaw = vFirst + vq;
     const bool laneValid = vRaw < vEnd;
     const uint32_t v = laneValid ? vRaw : vEnd - 1;
 
-    const uint32_t nfr = min(A.nframes[v], A.max_nframes);
-    const uint32_t nfrMax = wave_max_u32(nfr);
+    // the frames this launch runs for this lane: the utterance's -- or, below, those of the workgroup's segment with its warm-up
+    const uint32_t nfrAll = min(A.nframes[v], A.max_nframes);
+    const uint32_t nfrMaxAll = kSeg ? 0u : wave_max_u32(nfrAll);
     const uint32_t CP = (uint32_t)C.controlPeriod;
     const uint32_t inc = C.timeRegisterIncrement;
     auto outputs_with_flush = [&](uint64_t ntube) { return (uint32_t)trm::outputs_with_flush(ntube, (uint32_t)C.padSize, inc); };      // (trm_span.h)
+    uint32_t nfr = nfrAll, nfrMax = nfrMaxAll, segFrame0 = 0, nBase = 0, kBase = 0, noutSeg = 0;
+    if constexpr (kSeg) {     // (trm_span.h; as trm_quad.hip's segment instance has them)
+        const SegStretch st = seg_stretch(nfrAll, seg, A.seg_first, A.seg_periods, A.seg_warm, CP, inc);
+        nfr = st.nfr;
+        nfrMax = wave_max_u32(nfr);
+        segFrame0 = st.segFrame0;                                                                            // (uniform)
+        nBase = segFrame0 * CP;
+        kBase = (uint32_t)outputs_before((uint64_t)seg_begin(seg, A.seg_first, A.seg_periods) * CP, inc);   // (uniform)
+        // outputs of this launch for this lane's voice: its own stretch; the voice's last segment runs to the utterance's end
+        const uint32_t noutAll = nfrAll > 0 ? outputs_with_flush((uint64_t)(nfrAll - 1) * CP) : 0u;
+        noutSeg = (nfr > 0 && laneValid) ? (st.segLast ? noutAll : st.segOutEnd) - kBase : 0u;
+    }
     const uint32_t ntubeMax = nfrMax > 0 ? (nfrMax - 1) * CP : 0;
     // tube samples the tube stage produces: the utterance, then the converter's 2*pad zero flush (TRMRingBuffer.m:85-93)
     const uint32_t nTotal = nfrMax > 0 ? ntubeMax + 2u * (uint32_t)C.padSize : 0;
@@ -177,7 +226,10 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     if (role == 2) {
         const uint32_t sv = min(vFirst + ((uint32_t)lane >> 2 & 7u), vEnd - 1);
         stageNfr = min(A.nframes[sv], A.max_nframes);
-        stageSrc = A.frames + (stageNfr > 0 ? A.frame_offset[sv] * 16 : 0) + (lane & 3) * 4;
+        // (the segment instance: its own voice's stretch of the segment, from the warm-up's first frame)
+        if constexpr (kSeg) stageNfr = seg_stretch(stageNfr, seg, A.seg_first, A.seg_periods, A.seg_warm, CP, inc).nfr;
+        if constexpr (kSeg) stageSrc = A.frames + (stageNfr > 0 ? (A.frame_offset[sv] + segFrame0) * 16 : 0) + (lane & 3) * 4;
+        else stageSrc = A.frames + (stageNfr > 0 ? A.frame_offset[sv] * 16 : 0) + (lane & 3) * 4;
     }
     auto stage_frame = [&](uint32_t f) {
         const uint32_t fi = stageNfr > 0 ? (f < stageNfr ? f : stageNfr - 1) : 0u;
@@ -286,6 +338,15 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         // evaluated in one of a voice's four slots of the block and handed to the other three.
         OscSlotTrack T, Tn;
         double P = 0.0;                                 // oscillator position at the start of the step
+        if constexpr (kSeg) {
+            // the position at the warm-up start: the advances between the warm-up starts of the segments so far
+            // (trm_phase_segment_kernel: written for the batch's voices only), summed and wrapped in order -- exact
+            if (laneValid) {
+                const double *ph = A.seg_phase + vRaw;
+                const size_t pitch = (size_t)A.seg_wg_per_seg * kOV;
+                for (uint32_t q = 1; q <= seg; q++) P = osc_wrap(P + ph[q * pitch]);
+            }
+        }
         uint32_t perN = 1, bnd = CP;                    // the period after the one last set up runs between frames perN, perN + 1; bnd: its first sample
         uint32_t j = (uint32_t)slot;                    // position of this lane's sample in its control period
         auto setup_track = [&](OscSlotTrack &D, const float *fa, const float *fb, int jEntry) {
@@ -374,7 +435,9 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
 #endif
         // ------------------------------------------------------------ mix: block i-1 at step i, lane = (voice, slot)
         auto fill_noise_half = [&](uint32_t nFirst, int half) {
-            dma4(A.lp_noise + nFirst + lane, &sNoise[half * kNoiseHalf]);
+            // (the noise sequence is addressed by the utterance's sample index)
+            if constexpr (kSeg) dma4(A.lp_noise + nBase + nFirst + lane, &sNoise[half * kNoiseHalf]);
+            else dma4(A.lp_noise + nFirst + lane, &sNoise[half * kNoiseHalf]);
         };
         // window taps of this lane's parity (m & 1 == slot & 1: steps start on multiples of 8), as (a, b) pairs
         const int o = slot & 1;
@@ -394,7 +457,10 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         uint32_t rowBlk = 0;
         bool rowsInFlight = false;
         float4 rq[4];
-        const uint32_t cvtOutputs = wave_max_u32(laneValid && nfr > 0 ? outputs_with_flush(ntubeLane) : 0u);
+        uint32_t cvtOutputsOf;
+        if constexpr (kSeg) cvtOutputsOf = wave_max_u32(noutSeg);
+        else cvtOutputsOf = wave_max_u32(laneValid && nfr > 0 ? outputs_with_flush(ntubeLane) : 0u);
+        const uint32_t cvtOutputs = cvtOutputsOf;
         const uint32_t cvtBlocks = C.upsample ? (cvtOutputs + kCvtCols - 1) / kCvtCols : 0;
         STAMP_DECL
         for (uint32_t step = 0; step < nSteps; step++) {
@@ -407,12 +473,12 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
             };
             if (rowsInFlight) rows_to_lds();
             for (int r = 0; r < 2; r++) {
-                if (rowBlk < cvtBlocks && src_position(rowBlk * kCvtCols, inc) <= step * kOB + 4u &&
+                if (rowBlk < cvtBlocks && seg_out_position<kSeg>(inc, kBase, nBase, rowBlk * kCvtCols) <= step * kOB + 4u &&
                     rowBlk < lds_flag_consume(&sRowSync[0]) + kRowBufs) {
                     if (rowsInFlight) rows_to_lds();            // (a second block in the same step: its predecessor's loads are waited for here)
                     const uint32_t k = rowBlk * kCvtCols + ((uint32_t)lane >> 1);
-                    const uint32_t off = (src_position(k, inc) + (kQLead - (kSrcWindow - 1))) & 3u;
-                    const float *pc = A.src_rows + (size_t)src_phase(k, inc) * kSrcRowC - off + (lane & 1) * 16;
+                    const uint32_t off = (seg_out_position<kSeg>(inc, kBase, nBase, k) + (kQLead - (kSrcWindow - 1))) & 3u;
+                    const float *pc = A.src_rows + (size_t)seg_out_phase<kSeg>(inc, kBase, k) * kSrcRowC - off + (lane & 1) * 16;
                     for (int q = 0; q < 4; q++) rq[q] = make_float4(pc[4 * q], pc[4 * q + 1], pc[4 * q + 2], pc[4 * q + 3]);
                     rowsInFlight = true;
                     rowBlk++;
@@ -534,7 +600,9 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         OctState<float> S;
         oct_reset(S);
         float4 *const ring = reinterpret_cast<float4 *>(&sY[vq * kYStride]);
-        float *const tubeOut = (A.tube_out && (!kMix || !C.upsample)) ? A.tube_out + A.tube_offset[v] : nullptr;
+        float *tubeOutOf = nullptr;       // (the segment instance: up-sampling sets alone)
+        if constexpr (!kSeg) tubeOutOf = (A.tube_out && (!kMix || !C.upsample)) ? A.tube_out + A.tube_offset[v] : nullptr;
+        float *const tubeOut = tubeOutOf;
         // one sample's inputs: this part's record {k | injections} and the ONE per-voice value this part uses (part 0: the
         // glottal input, part 1: the three-way junction's alpha, part 4: the throat output)
         struct In { float4 r; float xs; };
@@ -616,9 +684,13 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         __builtin_amdgcn_s_setprio(TRM_OCT_PRIO_CVT);
         // ------------------------------------------------------------ convert (lane = output time), 8 voices
         uint32_t noutLane = 0;
-        if (nfr > 0) noutLane = outputs_with_flush(ntubeLane);
+        if constexpr (kSeg) noutLane = noutSeg;
+        else if (nfr > 0) noutLane = outputs_with_flush(ntubeLane);
         if (!laneValid) noutLane = 0;
-        const uintptr_t myOut = reinterpret_cast<uintptr_t>(A.out + A.out_offset[v]);
+        uintptr_t myOutOf;
+        if constexpr (kSeg) myOutOf = reinterpret_cast<uintptr_t>(A.out + A.out_offset[v] + kBase);
+        else myOutOf = reinterpret_cast<uintptr_t>(A.out + A.out_offset[v]);
+        const uintptr_t myOut = myOutOf;
         const uint32_t noutMax = wave_max_u32(noutLane);
         const uint32_t nBlocks = C.upsample ? (noutMax + kCvtCols - 1) / kCvtCols : 0;
         const int col = lane & (kCvtCols - 1);
@@ -627,16 +699,17 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         for (int r = 0; r < 4; r++) sMx[r * kWave + lane] = 0.0f;
 
         // output k reads tube samples e-25 .. e, e = src_position(k): ring slots e + kRingShift .. + 25
+        // (kLane = this lane's output within the launch, ring positions are relative to the launch's first tube sample: seg_out_position)
         constexpr uint32_t kRingShift = kQLead - (kSrcWindow - 1);
         v2f cc[16];
         uint32_t blk = 0, pr = 0;       // next work item: row pair `pr` (0..1) of block `blk`: voices 4*pr .. 4*pr+3
         uint32_t winBase = 0, kLane = 0, needLast = 0, needNext = 0;
         auto begin_block = [&]() {
             kLane = blk * kCvtCols + col;
-            winBase = (src_position(kLane, inc) + kRingShift) & (kYRing - 1) & ~3u;
-            needLast = src_position(blk * kCvtCols + (kCvtCols - 1), inc);
+            winBase = (seg_out_position<kSeg>(inc, kBase, nBase, kLane) + kRingShift) & (kYRing - 1) & ~3u;
+            needLast = seg_out_position<kSeg>(inc, kBase, nBase, blk * kCvtCols + (kCvtCols - 1));
             needLast = needLast < nTotal - 1 ? needLast : nTotal - 1;
-            needNext = src_position((blk + 1) * kCvtCols + (kCvtCols - 1), inc);   // (past the end: never "behind")
+            needNext = seg_out_position<kSeg>(inc, kBase, nBase, (blk + 1) * kCvtCols + (kCvtCols - 1));   // (past the end: never "behind")
             const float4 *row = reinterpret_cast<const float4 *>(&sRows[(blk % kRowBufs) * (kCvtCols * kRowPitch) + col * kRowPitch]);
             for (int q = 0; q < 8; q++) {
                 const float4 x = row[q];
@@ -646,10 +719,10 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         };
         auto begin_block_from_global = [&]() {
             kLane = blk * kCvtCols + col;
-            winBase = (src_position(kLane, inc) + kRingShift) & (kYRing - 1) & ~3u;
+            winBase = (seg_out_position<kSeg>(inc, kBase, nBase, kLane) + kRingShift) & (kYRing - 1) & ~3u;
             needLast = nTotal - 1;
-            const uint32_t off = (src_position(kLane, inc) + kRingShift) & 3u;
-            const float *pc = A.src_rows + (size_t)src_phase(kLane, inc) * kSrcRowC - off;
+            const uint32_t off = (seg_out_position<kSeg>(inc, kBase, nBase, kLane) + kRingShift) & 3u;
+            const float *pc = A.src_rows + (size_t)seg_out_phase<kSeg>(inc, kBase, kLane) * kSrcRowC - off;
             for (int q = 0; q < 16; q++) cc[q] = v2f{pc[2 * q], pc[2 * q + 1]};
         };
         bool needBegin = nBlocks > 0;
@@ -731,8 +804,14 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
             const uint32_t nf = min(A.nframes[ov], A.max_nframes);
             uint32_t nov = 0;
             if (nf > 0) nov = outputs_with_flush((uint64_t)(nf - 1) * CP);
-            A.number_samples[ov] = nov;
-            A.max_sample[ov] = myMax;
+            if constexpr (kSeg) {
+                // (max_sample was zeroed by the launcher; non-negative floats order like their bit patterns)
+                if (seg == 0) A.number_samples[ov] = nov;
+                if (myMax > 0.0f) atomicMax(reinterpret_cast<unsigned int *>(&A.max_sample[ov]), __float_as_uint(myMax));
+            } else {
+                A.number_samples[ov] = nov;
+                A.max_sample[ov] = myMax;
+            }
         }
         return;
     }
@@ -746,6 +825,8 @@ hipError_t launch_tube_oct(const Const &c, const TubeArgs &a, hipStream_t stream
 {
     if (a.nvoices == 0) return hipSuccess;
     if (a.stream_state || c.controlPeriod < 2 * kOB) return hipErrorInvalidValue;     // (the caller picks trm_quad.hip's kernel for these)
+    // time split: 8 voices x one segment per workgroup (trm_oct_seg.hip); a uniform up-sampling launch's alone
+    if (a.seg_periods) return a.mix_map || a.tube_out ? hipErrorInvalidValue : a.seg_grid ? launch_seg_oct(c, a, stream) : hipSuccess;
     if (a.mix_map) {      // (a mixed launch: every set's control period; the host demotes the launch otherwise)
         return a.mix_grid == 0 ? hipSuccess : launch_mix_oct(c, a, stream);
     }

@@ -1,0 +1,22 @@
+// trm_oct_seg.hip -- the time-split instance of trm_oct.hip's eight-lane tube kernel (TubeArgs::seg_periods: one segment of 8
+// voices per workgroup, from rest, a warm-up ahead), compiled from the same source under a name of its own: trm_octseg_kernel.
+// The file's other pieces are not built here (TRM_MIX_TU).
+#define TRM_MIX_TU
+#define trm_tube_kernel_o trm_octseg_kernel
+#include "trm_oct.hip"
+#undef trm_tube_kernel_o
+
+namespace trm {
+
+// OctLds as the whole-utterance instance has it: two workgroups share a CU.  a.seg_grid workgroups; max_sample is folded with an
+// atomic max, so the caller zeroes it in front (trm_kernels.h).
+hipError_t launch_seg_oct(const Const &c, const TubeArgs &a, hipStream_t stream)
+{
+    static DynamicLdsAllowance lds;
+    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_octseg_kernel<false, true>), (int)OctLds::kBytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((trm_octseg_kernel<false, true>), dim3(a.seg_grid), dim3(kWave * kORoles), OctLds::kBytes, stream, c, a);
+    return hipGetLastError();
+}
+
+}  // namespace trm

@@ -168,6 +168,16 @@ class TRMTubeModel:
     def split_warmup(self):
         return getattr(self, "_split_warmup", "default")
 
+    def set_split_form(self, form):
+        """No reference counterpart.  'auto' | 'oct': the form of the segments of the time split a long utterance runs as
+        (include/trm_c_api.h: trm_tube_set_split_form; TRMBatch.set_split_form)."""
+        check(lib().trm_tube_set_split_form(self._h, _capi.split_form_code(form)))
+        self._split_form = "oct" if _capi.split_form_code(form) == 3 else "auto"
+
+    @property
+    def split_form(self):
+        return getattr(self, "_split_form", "auto")
+
     @property
     def numberSamples(self):
         return lib().trm_tube_number_samples(self._h)

@@ -138,6 +138,9 @@ int  trm_tube_synthesize(trm_tube *tube, const trm_parameters *frames, size_t nf
  * tube parameters arrive, so the split's warm-up can be chosen here: forwards to trm_batch_set_split_warmup of the batch
  * inside the tube (TRM_SPLIT_WARMUP_DEFAULT, TRM_SPLIT_WARMUP_COUPLED or control periods; the same refusals). */
 int  trm_tube_set_split_warmup(trm_tube *tube, int rule_or_periods);
+/* ... and the form of its segments: forwards to trm_batch_set_split_form of the batch inside the tube (TRM_KERNEL_AUTO or
+ * TRM_KERNEL_OCT: a single utterance in eight-lane segments; the same refusals). */
+int  trm_tube_set_split_form(trm_tube *tube, int form);
 
 /* TRMSampleRateConverter numberSamples / maximumSampleValue / resampledData
  * (TRMSampleRateConverter.m:206-214,312-315).  The pointer stays valid until the next
@@ -460,6 +463,24 @@ enum { TRM_SPLIT_WARMUP_DEFAULT = 0, TRM_SPLIT_WARMUP_COUPLED = -1 };
 int  trm_batch_set_split_warmup(trm_batch *batch, int rule_or_periods);
 int  trm_batch_split_warmup(const trm_batch *batch);
 uint32_t trm_split_warm_periods(const trm_input_params *params, int rule);
+/* The form of a time split's segments, opt-in (no default changes; no environment variable).
+ *   TRM_KERNEL_AUTO (default)  today's rule, exactly: one voice per lane, or four lanes per voice for small launches;
+ *   TRM_KERNEL_OCT             eight lanes per voice where admissible: a workgroup is one segment of 8 voices, two workgroups
+ *                              share a CU (the lowest-latency form: a single utterance, a handful of voices).
+ * Anything else: TRM_EINVAL, the setting stays.  Eight-lane segments are ADMISSIBLE when the parameters up-sample (tube rate at
+ * or below the output rate), make at most four outputs per tube sample, and their control period holds at least 16 tube
+ * samples -- a 1 kHz control rate on Monet's tube (20 samples) qualifies, which the four-lane forms (24) do not run.  Where they
+ * are not admissible the launch is planned and enqueued exactly as if this setter had never been called (the demotion rule).
+ * Where they are: a segment length set by name (trm_batch_set_time_split(periods)) runs eight-lane segments of that length,
+ * whatever trm_batch_set_kernel says; TRM_TIME_SPLIT_AUTO with no form named (trm_batch_set_kernel / TRM_TUBE_KERNEL) prices
+ * every candidate length in the eight-lane form too, while its workgroups with work are at most two per CU, and takes the
+ * shortest predicted launch; with a form named and AUTO the launch runs whole utterances as ever.  The warm-up rules, the
+ * guard on narrow frication bands (whole utterances in the one-voice-per-lane form then), the hint and trm_batch_last_time_split
+ * apply unchanged; trm_batch_last_kernel reports TRM_KERNEL_OCT for such a launch.
+ * trm_batch_set_kernel(TRM_KERNEL_OCT) is unchanged: it names the form of WHOLE utterances, and with a segment length by name
+ * it still runs one-voice-per-lane segments.  Mixed batches and streams have no such setting. */
+int  trm_batch_set_split_form(trm_batch *batch, int form);
+int  trm_batch_split_form(const trm_batch *batch);
 /* A ragged batch through the device-buffer entry: the library sees the lengths (d_nframes) only on the device, and AUTO then
  * sizes the segments as if every voice were as long as the longest.  trm_batch_hint_frames hands it a host copy of the
  * nframes array (in the launch's voice order) for the NEXT trm_batch_synthesize_device call: AUTO then counts the workgroups

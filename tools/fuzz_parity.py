@@ -11,6 +11,7 @@ first, last = int(sys.argv[1]), int(sys.argv[2])
 maxframes = int(sys.argv[3]) if len(sys.argv) > 3 else 300
 broad = len(sys.argv) > 4 and sys.argv[4] == "broad"        # wider (still legal) parameter and track ranges
 bad = 0; unstable = 0; floor = 0; worst = 0.0; worstBy = {}; allr = []
+split8 = [0, 0]             # launches of the split8 leg; those that really ran eight-lane segments
 for seed in range(first, last):
     rng = np.random.default_rng(5000 + seed)
     pd = cases.monet_default_params(float(rng.choice([22050.0, 44100.0, 16000.0, 8000.0, 11025.0, 48000.0, 32000.0, 12000.0, 96000.0])))
@@ -48,18 +49,27 @@ for seed in range(first, last):
             pass
         continue
     if os.environ.get("FUZZ_ORACLE_ONLY"): continue
-    for form in ("wide", "quad", "oct", "split"):
+    for form in ("wide", "quad", "oct", "split", "split8"):
         try:
             b = g.TRMBatch(g.TRMInputParameters.from_dict(pd))
             if form == "split":
                 # time-split launch (round 4): segments of a random length, warm-up by the library's rule; a tube that never
                 # forgets (lossFactor ~ 0 in the broad set) is refused by name -- expected, not a finding
-                b.set_time_split(int(rng.integers(3, 40)))
+                seg = int(rng.integers(3, 40))
+                b.set_time_split(seg)
+            elif form == "split8":
+                # the same draw and segment length in eight-lane segments (trm_batch_set_split_form); a set the form does not
+                # admit runs as the split leg did
+                b.set_time_split(seg)
+                b.set_split_form("oct")
             else:
                 b.set_kernel(form)
             pcm, ns, mx = b.synthesize(voices)
+            if form == "split8":
+                split8[0] += 1
+                split8[1] += 1 if b.last_kernel == "oct" and b.last_time_split[0] > 0 else 0
         except g.TrmError as e:
-            if form == "split" and e.code == 10: continue           # TRM_ERANGE
+            if form in ("split", "split8") and e.code == 10: continue           # TRM_ERANGE
             print("seed %d %s: %s" % (seed, form, e)); bad += 1; continue
         except Exception as e:
             print("seed %d %s: %s" % (seed, form, e)); bad += 1; continue
@@ -77,6 +87,7 @@ for seed in range(first, last):
                 print("seed %d %s voice %d (%d frames, length %.1f, rate %.0f/%.0f): rms %.3e" % (seed, form, v, len(voices[v]), pd["length"], pd["outputRate"], pd["controlRate"], r)); bad += 1
 print("done: seeds %d..%d, %d findings; worst normalised RMS %.3e; %d voice-runs outside the band-pass's domain (BW >= SR/2), %d nearly silent ones matched on the absolute floor %.0e"
       % (first, last, bad, worst, unstable, floor, cases.ABS_FLOOR))
+print("split8: %d launches, %d of them ran eight-lane segments" % tuple(split8))
 print("worst per form: " + "; ".join("%s %.3e (seed %d voice %d)" % ((f,) + worstBy[f]) for f in sorted(worstBy)))
 allr.sort(reverse=True)
 print("the ten largest: " + "; ".join("%.2e (seed %d %s voice %d: %d frames, %d samples, %.0f Hz)" % t for t in allr[:10]))

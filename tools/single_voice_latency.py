@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Latency of the reference-shaped single-utterance path (TRMTubeModel -synthesize through the C ABI): what a
-TRMSynthesizer caller sees per utterance."""
+TRMSynthesizer caller sees per utterance.   usage: single_voice_latency.py [auto | oct]   (the time split's form:
+trm_tube_set_split_form; default auto)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -8,12 +9,15 @@ import numpy as np
 import cases
 import gnuspeech_amd as g
 rows = cases.load_gnuspeech_rows()
+split_form = sys.argv[1] if len(sys.argv) > 1 else "auto"
+print("split form %s" % split_form)
 for nfr in (26, 251, 1001):
     dl = g.TRMDataList()
     dl.inputParameters = g.TRMInputParameters.from_dict(cases.monet_default_params(44100.0))
     fr = np.tile(rows, (nfr // len(rows) + 1, 1))[:nfr]
     dl.values = [g.TRMParameters(r) for r in fr]
     tube = g.TRMTubeModel.initWithInputData(dl)
+    tube.set_split_form(split_form)
     tube.synthesize()
     t = []
     for _ in range(10):
@@ -26,7 +30,7 @@ for rate in (44100.0, 16000.0):
     dl.values = [g.TRMParameters(r) for r in rows[:251]]
     t_init, t_syn = [], []
     for _ in range(6):
-        t0 = time.perf_counter(); tube = g.TRMTubeModel.initWithInputData(dl); t1 = time.perf_counter()
+        t0 = time.perf_counter(); tube = g.TRMTubeModel.initWithInputData(dl); tube.set_split_form(split_form); t1 = time.perf_counter()
         tube.synthesize(); t2 = time.perf_counter()
         t_init.append(t1 - t0); t_syn.append(t2 - t1)
         del tube
