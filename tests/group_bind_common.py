@@ -16,6 +16,7 @@ import pytest
 import cases
 import group_events_common as EV
 import group_int16_common as I16
+import support
 
 # 0: 17.5 cm at 44.1 kHz, mono; 1: 15 cm at 16 kHz, which down-samples; 2: 16 cm, sine, no modulation, stereo at balance 0.3;
 # 3: 15 cm at 32 kHz, without voices at create; 4: a spare set, without voices at create, whose parameters are replaced
@@ -100,15 +101,10 @@ def _upsamples(pd):
     return pd["outputRate"] >= pd["controlRate"] * period
 
 
-def sets(g, pds=PDS):
-    return [g.TRMInputParameters.from_dict(p) for p in pds]
+sets = support.sets_of(PDS)
 
 
-def layout(seed=5, sizes=GROUP_SIZE, gset=GROUP_SET):
-    """(sets, groups) of the caller's voices, dealt in a shuffled order"""
-    groups = np.concatenate([np.full(n, gr, dtype=np.int64) for gr, n in enumerate(sizes)])
-    groups = np.random.default_rng(seed).permutation(groups)
-    return np.asarray(gset, dtype=np.int64)[groups], groups
+layout = support.layout_of(5, GROUP_SIZE, GROUP_SET)
 
 
 _REF = {}

@@ -12,6 +12,7 @@ import pytest
 
 import cases
 import oracle_lib as O
+import support
 from test_events import random_events
 
 # 17.5 cm and 15 cm at 44.1 kHz; 15 cm at 16 kHz (down-sampling)
@@ -27,15 +28,8 @@ STEPS = [7, 25, 7, 7, 25, 7, 7, 7, 25, 7, 7, 25, 7, 7, 7, 7, 25, 7, 7, 7]
 assert all(f % 7 and f % 25 and 75 <= f <= 150 for f in GROUP_F)
 
 
-def sets(g):
-    return [g.TRMInputParameters.from_dict(p) for p in PDS]
-
-
-def layout(seed=11):
-    """(sets, groups) of the caller's voices, dealt in a shuffled order"""
-    groups = np.concatenate([np.full(n, gr, dtype=np.int64) for gr, n in enumerate(GROUP_SIZE)])
-    groups = np.random.default_rng(seed).permutation(groups)
-    return np.asarray(GROUP_SET, dtype=np.int64)[groups], groups
+sets = support.sets_of(PDS)
+layout = support.layout_of(11, GROUP_SIZE, GROUP_SET)
 
 
 def speechlike(t, v, offsets=False):

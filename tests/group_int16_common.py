@@ -13,6 +13,7 @@ import numpy as np
 
 import cases
 import oracle_lib as O
+import support
 from group_events_common import Lists, eq, intonation, make_list
 
 # 17.5 cm mono; 15 cm stereo, balance 0.3, volume 48; 15 cm at 16 kHz (down-sampling) mono; 12.5 cm stereo, balance -0.6
@@ -33,15 +34,8 @@ assert all(60 <= f <= 110 and f % 7 and f % 25 for fs in UTT_F for f in fs)
 assert sum(RUNS) in (G // 2, G - G // 2)
 
 
-def sets(g):
-    return [g.TRMInputParameters.from_dict(p) for p in PDS]
-
-
-def layout(seed=11):
-    """(sets, groups) of the caller's voices, dealt in a shuffled order"""
-    groups = np.concatenate([np.full(n, gr, dtype=np.int64) for gr, n in enumerate(GROUP_SIZE)])
-    groups = np.random.default_rng(seed).permutation(groups)
-    return np.asarray(GROUP_SET, dtype=np.int64)[groups], groups
+sets = support.sets_of(PDS)
+layout = support.layout_of(11, GROUP_SIZE, GROUP_SET)
 
 
 def channels(gr):

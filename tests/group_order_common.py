@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 import cases
+import support
 
 P, F, I = "push", "finish", "idle"
 FW, TR = "framework", "tract"
@@ -38,8 +39,7 @@ SCHEDULE = [
 NFRAMES = sum(n for n, _ in SCHEDULE)
 
 
-def sets(g, pds=PDS):
-    return [g.TRMInputParameters.from_dict(p) for p in pds]
+sets = support.sets_of(PDS)
 
 
 def tube_rate(g, pd):
@@ -59,11 +59,7 @@ def plan(g, which="mixed"):
     return [TR] * 5, [4, 20, None, 33, None]
 
 
-def layout(seed=7, sizes=GROUP_SIZE, gset=GROUP_SET):
-    """(sets, groups) of the caller's voices, dealt in a shuffled order"""
-    groups = np.concatenate([np.full(n, gr, dtype=np.int64) for gr, n in enumerate(sizes)])
-    groups = np.random.default_rng(seed).permutation(groups)
-    return np.asarray(gset, dtype=np.int64)[groups], groups
+layout = support.layout_of(7, GROUP_SIZE, GROUP_SET)
 
 
 def frames_of(V, n=NFRAMES, seed=20261020):

@@ -16,6 +16,12 @@ import cases
 RMS_TOL = 1e-5
 
 
+def nrms(x, ref, mx):
+    """RMS of x - ref over mx, in float64.  NaN for empty input or mx == 0, which no `<= tol` admits."""
+    e = (np.asarray(x, dtype=np.float64) - np.asarray(ref, dtype=np.float64)) / mx
+    return float(np.sqrt(np.mean(e * e)))
+
+
 def window_length(output_rate, control_rate):
     """Outputs per control period (rounded; at least one)."""
     return max(1, int(round(float(output_rate) / float(control_rate))))

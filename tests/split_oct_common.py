@@ -5,13 +5,14 @@ import functools
 import os
 import tempfile
 
+import host_mock as M
 import test_split_plan_host as P
 
 
 @functools.lru_cache(maxsize=None)
 def mock_library():
     out = os.path.join(tempfile.mkdtemp(prefix="hostmock_split_oct_"), "libtrm_hostmock_split_oct.so")
-    P.build(out)
-    L = P.bind(out)
+    M.build(out, P.MOCKS, P.WRAPPED)
+    L = M.load(out)
     P.warm_noise(L)
     return L

@@ -243,31 +243,15 @@ def test_bench_dump_outputs_is_a_fixed_sample_under_the_budget(tmp_path, monkeyp
     assert np.array_equal(np.load(tmp_path / "a" / "maximum_sample_value.npy"), st["max_sample"].numpy())
 
 
-def test_no_kernel_spills_or_outgrows_its_register_budget(tmp_path):
-    """The code objects inside the built libtrm_hip.so: no kernel has a private (scratch) segment or spilled registers -- a
-    228-byte spill in the streaming instance of the one-voice-per-lane kernel cost 13 % of its throughput in round 3 (a kernel
-    with scratch pays for it on every dispatch) -- and the pipeline kernels stay within 128 VGPRs: four waves per SIMD is what
-    puts two workgroups on a CU."""
-    import re, shutil, subprocess
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip("ROCm LLVM tools not installed")
-    lib = shutil.copy(os.path.join(ROOT, "gnuspeech_amd", "libtrm_hip.so"), tmp_path / "lib.so")
-    subprocess.run([objdump, "--offloading", str(lib)], check=True, capture_output=True, cwd=tmp_path)
-    cos = [f for f in os.listdir(tmp_path) if "gfx950" in f]
-    assert cos, "no gfx950 code object in libtrm_hip.so"
-    kernels = {}
-    for f in cos:
-        notes = subprocess.run([readelf, "--notes", str(tmp_path / f)], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split("- .agpr_count:")[1:]:              # one metadata entry per kernel (its first key)
-            name = re.search(r"\.name:\s+(_Z\S+)", blk)
-            if not name:
-                continue
-            get = lambda key: int(re.search(key + r":\s+(\d+)", blk).group(1))
-            kernels[name.group(1)] = (get(r"\.private_segment_fixed_size"), get(r"\.sgpr_spill_count"), get(r"\.vgpr_spill_count"), get(r"\.vgpr_count"))
-    tube = [k for k in kernels if "trm_tube_kernel" in k]
-    assert len(tube) == 8, sorted(kernels)           # wide x3 (one-shot, stream, time-split), quad x4 (+ its time-split instance), oct
-    for k, (scratch, sspill, vspill, vgprs) in kernels.items():
-        assert scratch == 0 and sspill == 0 and vspill == 0, (k, scratch, sspill, vspill)
-    for k in tube:
-        assert kernels[k][3] <= 128, (k, kernels[k][3])
+def test_no_kernel_spills_or_outgrows_its_register_budget():
+    """The code objects inside the built libtrm_hip.so hold exactly the kernels of tests/kernel_manifest.py, each built once.  No
+    kernel has a private (scratch) segment or spilled registers -- a 228-byte spill in the streaming instance of the
+    one-voice-per-lane kernel cost 13 % of its throughput in round 3 (a kernel with scratch pays for it on every dispatch) -- and
+    every kernel stays within 128 VGPRs: four waves per SIMD is what puts two workgroups on a CU."""
+    import kernel_manifest
+    import kernel_notes
+    kernels = kernel_notes.read_kernels()
+    assert sorted(kernels) == sorted(kernel_manifest.KERNELS), sorted(set(kernels) ^ set(kernel_manifest.KERNELS))
+    kernel_manifest.check(kernels, *kernel_manifest.KERNELS)
+    # wide x3 (one-shot, stream, time-split), quad x4 (+ its time-split instance), oct
+    assert len(kernel_manifest.named("trm_tube_kernel")) == 8

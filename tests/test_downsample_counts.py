@@ -11,6 +11,7 @@ import pytest
 import cases
 import downsample_paths_common as P
 import oracle_lib as O
+import support
 
 TRM_ERANGE = 10
 
@@ -20,12 +21,7 @@ COUNT_SETS = [P.PATH_SETS[k][:2] for k in P.PATH_SETS] + [(17.5, 19550.0), (17.5
                                                          (10.0, 916.5)]
 COUNT_FRAMES = list(range(1, 61)) + list(range(71, 301, 11))
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    return gnuspeech_amd
+g = support.product(gpu=False)
 
 
 def _ip(g, length, rate):

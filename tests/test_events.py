@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import support
 
 NV = 36
 
@@ -147,11 +148,7 @@ def test_frame_count_functions_agree():
 
 
 # ---------------------------------------------------------------- GPU == oracle, bit for bit
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
+g = support.product(gpu=True)
 
 
 def _to_g(gm, s):

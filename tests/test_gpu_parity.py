@@ -16,39 +16,18 @@ import cases
 import golden_io
 import oracle_lib as O
 import parity
+from parity import nrms
+import support
 
 pytestmark = pytest.mark.gpu
 
 RMS_TOL = 1e-5      # ONE tolerance for every fixture, both kernel forms and the randomized voices (north_star)
 ALL_CASES = list(golden_io.CASE_NAMES)      # incl. short_tube_downsample: the converter's down-sampling branch
 
-
-def nrms(x, ref, mx):
-    e = (np.asarray(x, dtype=np.float64) - ref) / mx
-    return float(np.sqrt(np.mean(e * e)))
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
-
-
-@pytest.fixture(params=["wide", "quad", "quad1", "oct"])
-def form(request, monkeypatch):
-    """Every kernel form must meet the same bar (include/trm_c_api.h): one voice per lane, four lanes per voice, eight lanes
-    per voice, and the four-lane form's second instance ("quad1": one block per pipeline step, the one that lets two
-    workgroups share a CU and that batches of more than 16 voices x CUs run; TRM_QUAD_CUS=1 makes every batch take it).
-    TRM_TUBE_KERNEL steers every launch that is left on TRM_KERNEL_AUTO; both variables are read when a batch object is
-    created."""
-    monkeypatch.setenv("TRM_TUBE_KERNEL", "quad" if request.param == "quad1" else request.param)
-    if request.param == "quad1":
-        monkeypatch.setenv("TRM_QUAD_CUS", "1")
-    else:
-        monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
+g = support.product(gpu=True)
+# Every kernel form must meet the same bar (include/trm_c_api.h): one voice per lane, four lanes per voice, eight lanes per voice,
+# and the four-lane form's second instance ("quad1", support.kernel_form).
+form = support.kernel_form(["wide", "quad", "quad1", "oct"])
 
 
 @pytest.mark.parametrize("name", ALL_CASES)

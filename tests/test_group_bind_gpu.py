@@ -16,28 +16,13 @@ import numpy as np
 import pytest
 
 import group_bind_common as B
+import support
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    yield gnuspeech_amd
-    B._REF.clear()
-    _BATCHES.clear()
-
-
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    """Both streaming forms, forced by TRM_TUBE_KERNEL (read when a stream is created) as tests/test_group_stream_gpu.py does."""
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
-
-
 _BATCHES = {}
+g = support.product(gpu=True, after=lambda: (B._REF.clear(), _BATCHES.clear()))
+form = support.kernel_form(["quad", "wide"])
 
 
 def batch_scaler(g):

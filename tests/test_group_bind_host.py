@@ -10,14 +10,14 @@ import gc
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import group_bind_common as B
 import host_mock as M
-from test_group_events_host import CSRC, ROOT
+import support
+from test_group_events_host import ROOT
 
 MOCKS = ["hip_host_mock.cc", "hip_host_mock_events.cc", "hip_host_mock_out.cc", "hip_op_trace.cc"]
 # what hip_op_trace.cc stands in front of (-Wl,--wrap): every __wrap_<symbol> it defines, read from the file itself
@@ -27,53 +27,20 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "group_bind_unchanged_ops.json")
 P, F, I, R = B.P, B.F, B.I, B.R
 
 
-def build(out, csrc=CSRC):
-    """the host units of `csrc` with the stand-ins and the recorder in front of them"""
-    srcs = [os.path.join(csrc, u + ".cc") for u in M.host_units(csrc)]
-    oracle = os.path.join(ROOT, "oracle")
-    if not os.path.exists(os.path.join(oracle, "libtrm_oracle.so")):
-        subprocess.check_call(["make", "-s", "-C", oracle, "libtrm_oracle.so"])
-    mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in MOCKS]
-    wrap = ["-Wl,--wrap=" + w for w in WRAPPED]
-    # (-Bsymbolic: the library's calls into the runtime bind to the stand-in, whatever else the process has loaded)
-    subprocess.check_call(["hipcc", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-o", out] + wrap + mocks + srcs +
-                          ["-L" + oracle, "-l:libtrm_oracle.so", "-Wl,-rpath," + oracle, "-lpthread", "-lm"])
-
-
 @pytest.fixture(scope="module")
 def g(tmp_path_factory):
     """gnuspeech_amd bound to the host-mock library for the tests of this module, and back to the product afterwards"""
-    import gnuspeech_amd
-    from gnuspeech_amd import _capi
     out = str(tmp_path_factory.mktemp("hostmock_bind") / "libtrm_hostmock_bind.so")
-    build(out)
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, out
-    try:
-        assert _capi.lib().trm_device_count() == 1
-        yield gnuspeech_amd
-    finally:
-        B._REF.clear()
-        gc.collect()             # (streams of the stand-in are destroyed by the stand-in)
-        _capi._lib, _capi.LIB_PATH = saved
+    M.build(out, MOCKS, WRAPPED, oracle=True)
+    with M.product_on(out) as pkg:
+        try:
+            yield pkg
+        finally:
+            B._REF.clear()
 
 
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
-
-
-@pytest.fixture(autouse=True)
-def heap_stays_clean(g):
-    """every test of this module is a bounds test too: the stand-in's checking heap (tests/_emul/hip_host_mock.cc) saw no copy,
-    memset or kernel span leave its block, and no guard zone was written"""
-    M.violations(g.lib())
-    yield
-    M.bind(g.lib()).mock_fail_malloc(0, 0)
-    gc.collect()
-    M.assert_clean(g.lib())
+form = support.kernel_form(["quad", "wide"])
+heap_stays_clean = M.heap_clean(M.allow_malloc)
 
 
 def test_schedule_contains_every_event():
@@ -179,9 +146,9 @@ def test_bind_between_device_steps_of_one_shape(g, form):
         nout = np.zeros(3, dtype=np.uint32)
         d_out.a[...] = 7.0
         L.trace_enable(1)
-        trace_take(L)
+        M.trace_take(L)
         rc = L.trm_mixed_stream_step_device(a._h, act.ctypes.data, d_f.ptr if n else None, n, d_out.ptr, pitch, nout.ctypes.data, d_mx.ptr, None)
-        ops = trace_take(L)
+        ops = M.trace_take(L)
         L.trace_enable(0)
         assert rc == 0, L.trm_last_error()
         if n:
@@ -264,14 +231,6 @@ def test_failed_allocation_leaves_the_stream_under_its_old_binding(g, form, call
 
 
 # ------------------------------------------------------------------------------------------------ the unchanged stream
-def trace_take(L):
-    L.trace_take.argtypes, L.trace_take.restype = [C.c_char_p, C.c_size_t], C.c_size_t
-    n = L.trace_take(None, 0)
-    buf = C.create_string_buffer(n + 1)
-    L.trace_take(buf, n + 1)
-    return buf.value.decode().splitlines()
-
-
 def record_unchanged(g, form):
     """{"create": [...], "steps": [[...], ...]}: the operations of a grouped stream that never binds -- create, then the pushes and
     finishes of the common schedule through the host entries, two of them as int16 steps"""
@@ -282,9 +241,9 @@ def record_unchanged(g, form):
     warm = new()                             # (the process-wide noise sequence, generated once: not the stream's business)
     gc.collect()                             # (nothing of an earlier test is freed while the record runs)
     L.trace_enable(1)
-    trace_take(L)
+    M.trace_take(L)
     s = new()
-    out = {"create": trace_take(L), "steps": []}
+    out = {"create": M.trace_take(L), "steps": []}
     at = 0
     for st in B.SCHEDULE:
         acts = [a if a != R else I for a in st["acts"]]
@@ -293,7 +252,7 @@ def record_unchanged(g, form):
             s.step_int16(acts, frames, nframes=st["n"], levels=[1.0] * B.G)
         else:
             s.step(acts, frames, nframes=st["n"])
-        out["steps"].append(trace_take(L))
+        out["steps"].append(M.trace_take(L))
         at += st["n"]
     L.trace_enable(0)
     s.step([F] * B.G)

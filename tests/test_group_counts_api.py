@@ -4,22 +4,18 @@ step's tables covers the counts stretch, and the kernel that lays the rows out p
 import inspect
 import os
 import re
-import shutil
 import subprocess
 
-import pytest
+import kernel_manifest
+import kernel_notes
+import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
 NEW = ["trm_mixed_stream_step_counts", "trm_mixed_stream_step_counts_device", "trm_mixed_stream_step_counts_int16",
        "trm_mixed_stream_step_counts_device_int16"]
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    return gnuspeech_amd
+g = support.product(gpu=False)
 
 
 def test_the_four_entries_are_exported_and_declared(g):
@@ -74,23 +70,11 @@ def test_the_room_of_the_steps_tables_covers_the_counts_stretch(tmp_path):
     assert "step_words_room(s, false, false, false)" in open(os.path.join(CSRC, "trm_stream.cc")).read()
 
 
-def test_the_kernel_is_in_the_library(tmp_path):
+def test_the_kernel_is_in_the_library():
     """trm_grp_prep_counts_kernel once in the gfx950 code objects of libtrm_hip.so, beside trm_grp_prep_kernel, without scratch or
     spills (tests/test_capi_exports.py holds that for every kernel; here the new one is looked at by name)"""
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    assert os.path.exists(objdump) and os.path.exists(readelf), "ROCm LLVM tools are needed to look into the library's code objects"
+    assert kernel_notes.tools_installed(), "ROCm LLVM tools are needed to look into the library's code objects"
     assert "trm_grp_prep.hip" in open(os.path.join(CSRC, "Makefile")).read()
-    lib = shutil.copy(os.path.join(ROOT, "gnuspeech_amd", "libtrm_hip.so"), tmp_path / "lib.so")
-    subprocess.run([objdump, "--offloading", str(lib)], check=True, capture_output=True, cwd=tmp_path)
-    cos = [f for f in os.listdir(tmp_path) if "gfx950" in f]
-    assert cos, "no gfx950 code object in libtrm_hip.so"
-    found = []
-    for f in cos:
-        notes = subprocess.run([readelf, "--notes", str(tmp_path / f)], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split("- .agpr_count:")[1:]:              # one metadata entry per kernel (its first key)
-            name = re.search(r"\.name:\s+(_Z\S+)", blk)
-            if name and "trm_grp_prep" in name.group(1):
-                get = lambda key: int(re.search(key + r":\s+(\d+)", blk).group(1))
-                found.append((name.group(1), get(r"\.private_segment_fixed_size"), get(r"\.sgpr_spill_count"), get(r"\.vgpr_spill_count")))
-    assert sorted("counts" in n for n, _, _, _ in found) == [False, True], found
-    assert all(scratch == 0 and ss == 0 and vs == 0 for _, scratch, ss, vs in found), found
+    found = kernel_manifest.named("trm_grp_prep")
+    assert sorted("counts" in n for n in found) == [False, True], found
+    kernel_manifest.check(kernel_notes.read_kernels(), *found)

@@ -11,7 +11,6 @@ import ctypes as C
 import gc
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -22,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import group_counts_common as K               # noqa: E402
 import group_order_common as B                # noqa: E402
 import host_mock as M                         # noqa: E402
+import support                                # noqa: E402
 import test_stream_ops_host as SO             # noqa: E402
 
 P, F, I, R = K.P, K.F, K.I, K.R
@@ -29,16 +29,9 @@ COUNTS = "hip_host_mock_counts.cc"
 GOLDEN = os.path.join(ROOT, "tests", "golden", "group_counts_unchanged_ops.json")
 
 
-def build(out, csrc=M.CSRC, counts=True):
-    """the host units of `csrc` with the stand-ins (counts: the prep stand-in with counts among them) behind the recorder"""
-    srcs = [os.path.join(csrc, u + ".cc") for u in M.host_units(csrc)]
-    oracle = os.path.join(ROOT, "oracle")
-    if not os.path.exists(os.path.join(oracle, "libtrm_oracle.so")):
-        subprocess.check_call(["make", "-s", "-C", oracle, "libtrm_oracle.so"])
-    mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in SO.MOCKS + ([COUNTS] if counts else [])]
-    wrap = ["-Wl,--wrap=" + w for w in SO.WRAPPED]
-    subprocess.check_call(["hipcc", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-o", out] + wrap + mocks + srcs +
-                          ["-L" + oracle, "-l:libtrm_oracle.so", "-Wl,-rpath," + oracle, "-lpthread", "-lm"])
+def build(out, counts=True):
+    """the host units with the stand-ins (counts: the prep stand-in with counts among them) behind the recorder"""
+    M.build(out, SO.MOCKS + ([COUNTS] if counts else []), SO.WRAPPED, oracle=True)
 
 
 def bound(out):
@@ -66,22 +59,8 @@ def g(tmp_path_factory):
         _capi._lib, _capi.LIB_PATH = saved
 
 
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
-
-
-@pytest.fixture(autouse=True)
-def heap_stays_clean(g):
-    """every test of this module is a bounds test too (tests/_emul/hip_host_mock.cc)"""
-    M.violations(g.lib())
-    yield
-    g.lib().mock_counts_install(1)
-    g.lib().trace_enable(0)
-    gc.collect()
-    M.assert_clean(g.lib())
+form = support.kernel_form(["quad", "wide"])
+heap_stays_clean = M.heap_clean(lambda L: (L.mock_counts_install(1), L.trace_enable(0)))
 
 
 class MockArray:
@@ -99,7 +78,7 @@ class MockArray:
 
 
 def take(L):
-    return SO.trace_take(L).splitlines()
+    return M.trace_take(L)
 
 
 def tract_stream(g, form, convert="per_group"):

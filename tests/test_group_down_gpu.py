@@ -14,25 +14,13 @@ import pytest
 import group_bind_common as B
 import group_down_common as D
 import group_events_common as EV
+import support
 
 pytestmark = pytest.mark.gpu
 P, F, I, R = D.P, D.F, D.I, D.R
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    yield gnuspeech_amd
-    B._REF.clear()
-
-
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    """Both streaming forms, forced by TRM_TUBE_KERNEL (read when a stream is created)."""
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
+g = support.product(gpu=True, after=B._REF.clear)
+form = support.kernel_form(["quad", "wide"])
 
 
 @pytest.mark.parametrize("mode", ["framework", "tract"])

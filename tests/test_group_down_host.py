@@ -6,11 +6,9 @@ hip_op_trace.cc, which writes down every operation the host units enqueue.  The 
 its history head, the row's origin and the output index, as the stand-in launch_downsample does, so the two paths return the
 same bits only if the step's tables name the right groups, origins, ranges and history rows.  The kernels' arithmetic is the GPU
 test's business (tests/test_group_down_gpu.py)."""
-import ctypes as C
 import gc
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +16,7 @@ import pytest
 import group_bind_common as B
 import group_down_common as D
 import host_mock as M
+import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
@@ -28,33 +27,14 @@ WRAPPED = sorted(set(re.findall(r"^hipError_t __wrap_(\w+)\(", open(os.path.join
 P, F, I, R = D.P, D.F, D.I, D.R
 
 
-def build(out, mocks):
-    """the host units with the stand-ins `mocks` and the recorder in front of them"""
-    srcs = [os.path.join(CSRC, u + ".cc") for u in M.host_units()]
-    oracle = os.path.join(ROOT, "oracle")
-    if not os.path.exists(os.path.join(oracle, "libtrm_oracle.so")):
-        subprocess.check_call(["make", "-s", "-C", oracle, "libtrm_oracle.so"])
-    mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in mocks]
-    wrap = ["-Wl,--wrap=" + w for w in WRAPPED]
-    # (-Bsymbolic: the library's calls into the runtime bind to the stand-in, whatever else the process has loaded)
-    subprocess.check_call(["hipcc", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-o", out] + wrap + mocks + srcs +
-                          ["-L" + oracle, "-l:libtrm_oracle.so", "-Wl,-rpath," + oracle, "-lpthread", "-lm"])
-
-
 def _bound(tmp_path_factory, name, mocks):
-    import gnuspeech_amd
-    from gnuspeech_amd import _capi
     out = str(tmp_path_factory.mktemp(name) / ("libtrm_%s.so" % name))
-    build(out, mocks)
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, out
-    try:
-        assert _capi.lib().trm_device_count() == 1
-        yield gnuspeech_amd
-    finally:
-        B._REF.clear()
-        gc.collect()             # (streams of the stand-in are destroyed by the stand-in)
-        _capi._lib, _capi.LIB_PATH = saved
+    M.build(out, mocks, WRAPPED, oracle=True)
+    with M.product_on(out) as pkg:
+        try:
+            yield pkg
+        finally:
+            B._REF.clear()
 
 
 @pytest.fixture(scope="module")
@@ -63,30 +43,8 @@ def g(tmp_path_factory):
     yield from _bound(tmp_path_factory, "hostmock_down", MOCKS + [DOWN])
 
 
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
-
-
-@pytest.fixture(autouse=True)
-def heap_stays_clean(g):
-    """every test of this module is a bounds test too: the stand-in's checking heap saw no copy, memset or kernel span leave its
-    block, and no guard zone was written"""
-    M.violations(g.lib())
-    yield
-    M.bind(g.lib()).mock_fail_malloc(0, 0)
-    gc.collect()
-    M.assert_clean(g.lib())
-
-
-def trace_take(L):
-    L.trace_take.argtypes, L.trace_take.restype = [C.c_char_p, C.c_size_t], C.c_size_t
-    n = L.trace_take(None, 0)
-    buf = C.create_string_buffer(n + 1)
-    L.trace_take(buf, n + 1)
-    return buf.value.decode().splitlines()
+form = support.kernel_form(["quad", "wide"])
+heap_stays_clean = M.heap_clean(M.allow_malloc)
 
 
 def test_schedule_contains_every_event():
@@ -122,13 +80,13 @@ def record(g, s, convert_before=None):
     fr = D.frames_of(s.nvoices)
     out, at = [], 0
     L.trace_enable(1)
-    trace_take(L)
+    M.trace_take(L)
     left = D.RUN_F
     for st in D.SCHEDULE:
         acts = [(P if left > 0 else F) if a == R else a for a in st["acts"]]
         left -= st["n"] if R in st["acts"] else 0
         s.step(acts, fr[:, at:at + st["n"]] if st["n"] else None, nframes=st["n"])
-        out.append(trace_take(L))
+        out.append(M.trace_take(L))
         at += st["n"]
     L.trace_enable(0)
     assert not any(s.is_open(gr) for gr in range(D.G))
@@ -165,9 +123,9 @@ def test_operations_of_a_step_do_not_grow_with_the_groups(g, form):
         ops = []
         for acts in ({0: P}, {gr: P for gr in range(6)}):
             L.trace_enable(1)
-            trace_take(L)
+            M.trace_take(L)
             s.step(acts, fr[:, 7:14])
-            ops.append(trace_take(L))
+            ops.append(M.trace_take(L))
             L.trace_enable(0)
             s.step([F] * 6)
         counts[convert] = [len(o) for o in ops]

@@ -9,23 +9,12 @@ import numpy as np
 import pytest
 
 import group_events_common as T
+import support
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
-
-
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    """Both streaming forms, forced by TRM_TUBE_KERNEL (read when a stream is created)."""
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
+g = support.product(gpu=True)
+form = support.kernel_form(["quad", "wide"])
 
 
 def test_frames_equal_the_oracle_step_by_step(g, form):

@@ -7,72 +7,34 @@ driven by "push" and "finish" (tests/group_events_common.py).  The kernels' arit
 import ctypes as C
 import gc
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import group_events_common as T
 import host_mock as M
+import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
 
 
 def _build(out, mocks):
-    srcs = [os.path.join(CSRC, u + ".cc") for u in M.host_units()]
-    oracle = os.path.join(ROOT, "oracle")
-    if not os.path.exists(os.path.join(oracle, "libtrm_oracle.so")):
-        subprocess.check_call(["make", "-s", "-C", oracle, "libtrm_oracle.so"])
-    link = ["-L" + oracle, "-l:libtrm_oracle.so", "-Wl,-rpath," + oracle] if len(mocks) > 1 else []
-    objs = [os.path.join(CSRC, "build", u + ".o") for u in M.host_units()]
-    hdrs = M.unit_dependencies()
-    fresh = all(os.path.exists(o) and all(os.path.getmtime(o) >= os.path.getmtime(d) for d in [s] + hdrs) for o, s in zip(objs, srcs))
-    flags = ["-O1", "-std=c++17", "-fPIC"]
-    mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in mocks]
-    # (-Bsymbolic: the library's calls into the runtime bind to the stand-in, whatever else the process has loaded)
-    if fresh:        # the product build's host objects: only the stand-ins are compiled
-        mos = []
-        for i, m in enumerate(mocks):
-            mos.append("%s.%d.o" % (out[:-3], i))
-            subprocess.check_call(["hipcc"] + flags + ["-c", m, "-o", mos[-1]])
-        subprocess.check_call(["g++", "-shared", "-Wl,-Bsymbolic", "-o", out] + mos + objs + link + ["-lpthread", "-lm"])
-    else:
-        subprocess.check_call(["hipcc"] + flags + ["-shared", "-Wl,-Bsymbolic", "-o", out] + mocks + srcs + link + ["-lpthread", "-lm"])
+    """the product build's host objects, where fresh, over `mocks`; the oracle's library for every stand-in but the runtime's"""
+    M.build(out, mocks, oracle=len(mocks) > 1, reuse_objects=True)
 
 
 @pytest.fixture(scope="module")
 def g(tmp_path_factory):
     """gnuspeech_amd bound to the host-mock library for the tests of this module, and back to the product afterwards"""
-    import gnuspeech_amd
-    from gnuspeech_amd import _capi
     out = str(tmp_path_factory.mktemp("hostmock_events") / "libtrm_hostmock_events.so")
     _build(out, ["hip_host_mock.cc", "hip_host_mock_events.cc"])
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, out
-    try:
-        assert _capi.lib().trm_device_count() == 1
-        yield gnuspeech_amd
-    finally:
-        gc.collect()             # (streams of the stand-in are destroyed by the stand-in)
-        _capi._lib, _capi.LIB_PATH = saved
+    with M.product_on(out) as pkg:
+        yield pkg
 
 
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
-
-
-@pytest.fixture(autouse=True)
-def heap_stays_clean(g):
-    """every test of this module is a bounds test too: the stand-in's checking heap (tests/_emul/hip_host_mock.cc) saw no copy,
-    memset or kernel span leave its block, and no guard zone was written"""
-    M.violations(g.lib())
-    yield
-    gc.collect()
-    M.assert_clean(g.lib())
+form = support.kernel_form(["quad", "wide"])
+heap_stays_clean = M.heap_clean()
 
 
 def test_host_engine_frames_step_by_step(g, form):

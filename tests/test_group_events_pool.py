@@ -6,47 +6,27 @@ never the library's own bookkeeping; and every test ends with no violation of th
 
 First the stand-in itself: the net has no hole."""
 import ctypes as C
-import gc
 
 import numpy as np
 import pytest
 
 import group_events_common as T
 import host_mock as M
+import support
 from test_group_events_host import _build
 
 
 @pytest.fixture(scope="module")
 def g(tmp_path_factory):
     """gnuspeech_amd bound to the host-mock library for the tests of this module, and back to the product afterwards"""
-    import gnuspeech_amd
-    from gnuspeech_amd import _capi
     out = str(tmp_path_factory.mktemp("hostmock_pool") / "libtrm_hostmock_pool.so")
     _build(out, ["hip_host_mock.cc", "hip_host_mock_events.cc"])
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, out
-    try:
-        assert _capi.lib().trm_device_count() == 1
-        yield gnuspeech_amd
-    finally:
-        gc.collect()             # (streams of the stand-in are destroyed by the stand-in)
-        _capi._lib, _capi.LIB_PATH = saved
+    with M.product_on(out) as pkg:
+        yield pkg
 
 
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
-
-
-@pytest.fixture(autouse=True)
-def heap_stays_clean(g):
-    """no copy, memset or kernel span left its block during the test, and no guard zone was written"""
-    M.violations(g.lib())
-    yield
-    gc.collect()
-    M.assert_clean(g.lib())
+form = support.kernel_form(["quad", "wide"])
+heap_stays_clean = M.heap_clean()
 
 
 def same(a, b):

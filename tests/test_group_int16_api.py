@@ -1,15 +1,16 @@
 """CPU-side checks of the int16 steps of grouped streams (include/trm_c_api.h: trm_mixed_stream_step_int16,
 trm_mixed_stream_step_device_int16): the header declares them, the binding lists them, the library exports them, the Python
 mirror exists and checks its arguments before it reaches the library, and the new kernel is in the library's code object under a
-name that the tests which count tube kernels do not count.  No GPU compute here."""
+name of its own, built once.  No GPU compute here."""
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+import kernel_manifest
+import kernel_notes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("trm_mixed_stream_step_int16", "trm_mixed_stream_step_device_int16")
@@ -65,19 +66,9 @@ def test_python_mirror_exists_and_checks_its_arguments(monkeypatch):
     assert vals[s._gindex[0]] == 20 and vals[s._gindex[1]] == 7
 
 
-def test_the_kernel_is_in_the_library_under_a_name_of_its_own(tmp_path):
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip("ROCm LLVM tools not installed")
-    lib = shutil.copy(os.path.join(ROOT, "gnuspeech_amd", "libtrm_hip.so"), tmp_path / "lib.so")
-    subprocess.run([objdump, "--offloading", str(lib)], check=True, capture_output=True, cwd=tmp_path)
-    names = []
-    for f in os.listdir(tmp_path):
-        if "gfx950" in f:
-            notes = subprocess.run([readelf, "--notes", str(tmp_path / f)], check=True, capture_output=True, text=True).stdout
-            names += re.findall(r"\.name:\s+(_Z\S+)", notes)
-    mine = [n for n in names if "trm_grp_int16_kernel" in n]
-    assert len(mine) == 1, sorted(names)
-    assert "trm_tube_kernel" not in mine[0] and "trm_mix_kernel" not in mine[0]
+def test_the_kernel_is_in_the_library_under_a_name_of_its_own():
+    mine = kernel_manifest.named("trm_grp_int16_kernel")
+    assert mine == ["_ZN3trm20trm_grp_int16_kernelENS_12GrpInt16ArgsE"]
+    kernel_manifest.check(kernel_notes.read_kernels(), *mine)
     srcs = open(os.path.join(ROOT, "gnuspeech_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRCS\s*:=.*\btrm_grp_out\.hip\b", srcs, re.M)

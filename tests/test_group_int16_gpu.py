@@ -21,24 +21,12 @@ import pytest
 
 import group_int16_common as T
 import oracle_lib as O
+import support
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    yield gnuspeech_amd
-    T._TWIN.clear()
-
-
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    """Both streaming forms, forced by TRM_TUBE_KERNEL (read when a stream is created)."""
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
+g = support.product(gpu=True, after=T._TWIN.clear)
+form = support.kernel_form(["quad", "wide"])
 
 
 def device_entry(pitch=None):

@@ -14,6 +14,7 @@ import pytest
 import group_int16_common as T
 import host_mock as M
 import oracle_lib as O
+import support
 from test_group_events_host import _build
 
 MOCKS = ["hip_host_mock.cc", "hip_host_mock_events.cc", "hip_host_mock_out.cc"]
@@ -22,36 +23,17 @@ MOCKS = ["hip_host_mock.cc", "hip_host_mock_events.cc", "hip_host_mock_out.cc"]
 @pytest.fixture(scope="module")
 def g(tmp_path_factory):
     """gnuspeech_amd bound to the host-mock library for the tests of this module, and back to the product afterwards"""
-    import gnuspeech_amd
-    from gnuspeech_amd import _capi
     out = str(tmp_path_factory.mktemp("hostmock_out") / "libtrm_hostmock_out.so")
     _build(out, MOCKS)
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, out
-    try:
-        assert _capi.lib().trm_device_count() == 1
-        yield gnuspeech_amd
-    finally:
-        T._TWIN.clear()
-        gc.collect()             # (streams of the stand-in are destroyed by the stand-in)
-        _capi._lib, _capi.LIB_PATH = saved
+    with M.product_on(out) as pkg:
+        try:
+            yield pkg
+        finally:
+            T._TWIN.clear()
 
 
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
-
-
-@pytest.fixture(autouse=True)
-def heap_stays_clean(g):
-    """every test of this module is a bounds test too: the stand-in's checking heap (tests/_emul/hip_host_mock.cc) saw no copy,
-    memset or kernel span leave its block, and no guard zone was written"""
-    M.violations(g.lib())
-    yield
-    gc.collect()
-    M.assert_clean(g.lib())
+form = support.kernel_form(["quad", "wide"])
+heap_stays_clean = M.heap_clean()
 
 
 def test_the_header_alone_against_the_oracle_scaler(g):

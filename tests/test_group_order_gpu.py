@@ -12,28 +12,15 @@ import pytest
 import cases
 import golden_io
 import group_order_common as B
+import support
 
 pytestmark = pytest.mark.gpu
 P, F, I, FW, TR = B.P, B.F, B.I, B.FW, B.TR
 
 
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    yield gnuspeech_amd
-    _RUN.clear()
-
-
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    """Both streaming forms, forced by TRM_TUBE_KERNEL (read when a stream is created)."""
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
-
-
 _RUN = {}
+g = support.product(gpu=True, after=_RUN.clear)
+form = support.kernel_form(["quad", "wide"])
 
 
 def common_run(g, form):

@@ -14,17 +14,14 @@ import pytest
 
 import group_order_common as B
 import host_mock as M
+import support
 from test_group_stream_host import g, heap_stays_clean      # noqa: F401  (the stand-in library and its checking heap, per test)
 
 P, F, I, FW, TR = B.P, B.F, B.I, B.FW, B.TR
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "group_order_unchanged_ops.json")
 
 
-@pytest.fixture(params=["quad", "wide"])
-def form(request, monkeypatch):
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    return request.param
+form = support.kernel_form(["quad", "wide"])
 
 
 class MockArray:
@@ -212,22 +209,15 @@ def test_a_stream_that_never_calls_the_new_entries_enqueues_what_it_did_before(f
     this feature did (tests/golden/group_order_unchanged_ops.json, recorded once from that commit's host units with
     record_unchanged() behind the recorder of tests/test_group_bind_host.py): in TRAcT order a launch_gain per group and step.  A
     stream on which set_mode_of has been called -- even one that changes nothing -- may differ, and nothing else is asked of it here."""
-    import gnuspeech_amd
-    from gnuspeech_amd import _capi
     import test_group_bind_host as TB
     out = str(tmp_path_factory.mktemp("hostmock_order") / "libtrm_hostmock_order.so")
-    TB.build(out)
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, out
-    try:
-        L = _capi.lib()
+    M.build(out, TB.MOCKS, TB.WRAPPED, oracle=True)
+    with M.product_on(out) as pkg:
+        L = pkg.lib()
         assert callable(L.trm_mixed_stream_set_mode_of)
-        got = record_unchanged(gnuspeech_amd, form, lambda: TB.trace_take(L))
+        got = record_unchanged(pkg, form, lambda: M.trace_take(L))
         gc.collect()
         M.assert_clean(L)
-    finally:
-        gc.collect()
-        _capi._lib, _capi.LIB_PATH = saved
     want = json.load(open(GOLDEN))[form]
     assert got["create"] == want["create"]
     assert len(got["steps"]) == len(want["steps"]) == len(B.SCHEDULE)

@@ -1,43 +1,31 @@
 """CPU-side checks of grouped streams (include/trm_c_api.h: trm_mixed_stream_create_groups, trm_mixed_stream_step): the symbols are
 exported and declared, the actions have their declared values, the group layout is validated before a device is looked for,
 TRMGroupedStream validates its arguments, and the two grouped-stream instances of the tube kernels are in the library, each once
-under a stem of its own and within the register budget."""
+and within the register budget."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-import cases
+import kernel_manifest
+import kernel_notes
+import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NEW = ["trm_mixed_stream_create_groups", "trm_mixed_stream_groups", "trm_mixed_stream_group_open", "trm_mixed_stream_group_samples_for",
        "trm_mixed_stream_step", "trm_mixed_stream_step_device"]
-STEMS = ["trm_grpstream_kernel_q", "trm_grpstream_kernel"]
-COUNTED_STEMS = ["trm_tube_kernel", "trm_mix_kernel", "trm_mixseg_kernel", "trm_mixqseg_kernel"]
+KERNELS = ["_ZN3trm22trm_grpstream_kernel_qILb1ELi2ELb0ELb1EEEvNS_5ConstENS_8TubeArgsE",      # trm_grpstream_kernel_q<true, 2, false, true>
+           "_ZN3trm20trm_grpstream_kernelILi6EEEvNS_5ConstENS_8TubeArgsE"]                       # trm_grpstream_kernel<6>
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    return gnuspeech_amd
-
-
-def _params(g, **kw):
-    return g.TRMInputParameters.from_dict(dict(cases.monet_default_params(), **kw))
+g = support.product(gpu=False)
+_params = support.input_params
 
 
 def test_new_symbols_are_exported_and_declared(g):
-    header = open(os.path.join(ROOT, "include", "trm_c_api.h")).read()
-    for name in NEW:
-        assert name in g._capi.EXPORTS, name
-        assert name + "(" in header, name
-        getattr(g.lib(), name)
+    support.assert_exported_and_declared(g, NEW)
 
 
 def test_action_values_are_as_declared(g):
@@ -104,33 +92,7 @@ def test_layout_of_a_grouped_stream(g):
     assert inverse[order].tolist() == [0, 1, 2, 3, 4]
 
 
-def test_grouped_stream_instances_are_built_once_each_within_budget(tmp_path):
-    """Exactly one kernel per new stem, whose name holds none of the stems other tests count kernels by; no scratch, no spills,
-    at most 128 VGPRs (the method of tests/test_mixed_split_quad_api.py: the code object's notes)."""
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip("ROCm LLVM tools not installed")
-    lib = shutil.copy(os.path.join(ROOT, "gnuspeech_amd", "libtrm_hip.so"), tmp_path / "lib.so")
-    subprocess.run([objdump, "--offloading", str(lib)], check=True, capture_output=True, cwd=tmp_path)
-    cos = [f for f in os.listdir(tmp_path) if "gfx950" in f]
-    assert cos, "no gfx950 code object in libtrm_hip.so"
-    kernels = {}
-    for f in cos:
-        notes = subprocess.run([readelf, "--notes", str(tmp_path / f)], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split("- .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s+(_Z\S+)", blk)
-            if not name:
-                continue
-            get = lambda key: int(re.search(key + r":\s+(\d+)", blk).group(1))
-            kernels[name.group(1)] = (get(r"\.private_segment_fixed_size"), get(r"\.sgpr_spill_count"), get(r"\.vgpr_spill_count"),
-                                      get(r"\.vgpr_count"))
-    quad = [k for k in kernels if STEMS[0] in k]
-    wide = [k for k in kernels if STEMS[1] in k and STEMS[0] not in k]
-    assert len(quad) == 1 and len(wide) == 1, sorted(kernels)
-    for k in quad + wide:
-        for other in COUNTED_STEMS:
-            assert other not in k, (k, other)
-        scratch, sspill, vspill, vgprs = kernels[k]
-        print("%s: scratch %d, SGPR spills %d, VGPR spills %d, VGPRs %d" % (k, scratch, sspill, vspill, vgprs))
-        assert scratch == 0 and sspill == 0 and vspill == 0, (k, scratch, sspill, vspill)
-        assert vgprs <= 128, (k, vgprs)
+def test_grouped_stream_instances_are_built_once_each_within_budget():
+    """Exactly one kernel per name (lines of tests/kernel_manifest.py); no scratch, no spills, at most 128 VGPRs."""
+    kernel_manifest.check(kernel_notes.read_kernels(), *KERNELS)
+    assert sorted(kernel_manifest.named("trm_grpstream_kernel")) == sorted(KERNELS)

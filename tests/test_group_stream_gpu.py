@@ -10,26 +10,14 @@ import pytest
 
 import cases
 import parity
+import support
 
 pytestmark = pytest.mark.gpu
 
 FORM = {"now": "quad"}
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
-
-
-@pytest.fixture(autouse=True, params=["quad", "wide"])
-def stream_form(request, monkeypatch):
-    """Both streaming forms, forced by TRM_TUBE_KERNEL (read when a stream is created) as tests/test_mixed_stream_gpu.py does."""
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    FORM["now"] = request.param
-    return request.param
+g = support.product(gpu=True)
+stream_form = support.kernel_form(["quad", "wide"], autouse=True, note=FORM)
 
 
 # 17.5 cm at 44.1 kHz; 15 cm at 22.05 kHz; 15 cm at 16 kHz (down-sampling); sine without modulation; an empty set

@@ -5,9 +5,7 @@ history).  Two paths then agree bit for bit only if the host hands the kernels t
 tests/test_group_stream_gpu.py -- a grouped stream against one stream per group, a group's independence of the others, the device
 entry against the host entry, the refusals -- hold here for the tables, the frame rows, the ordering and the sizes.  The kernels'
 arithmetic is the GPU tests' business."""
-import gc
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,31 +20,13 @@ CSRC = os.path.join(ROOT, "gnuspeech_amd", "csrc")
 @pytest.fixture(scope="module")
 def g(tmp_path_factory):
     """gnuspeech_amd bound to the host-mock library for the tests of this module, and back to the product afterwards"""
-    import gnuspeech_amd
-    from gnuspeech_amd import _capi
     out = str(tmp_path_factory.mktemp("hostmock") / "libtrm_hostmock.so")
-    mock = os.path.join(ROOT, "tests", "_emul", "hip_host_mock.cc")
-    objs = [os.path.join(CSRC, "build", u + ".o") for u in M.host_units()]
-    srcs = [os.path.join(CSRC, u + ".cc") for u in M.host_units()]
-    hdrs = M.unit_dependencies()
-    fresh = all(os.path.exists(o) and all(os.path.getmtime(o) >= os.path.getmtime(d) for d in [s] + hdrs) for o, s in zip(objs, srcs))
-    flags = ["-O1", "-std=c++17", "-fPIC"]
-    # (-Bsymbolic: the library's calls into the runtime bind to the stand-in, whatever else the process has loaded)
-    if fresh:        # the product build's host objects: only the stand-in is compiled
-        mo = out[:-3] + ".o"
-        subprocess.check_call(["hipcc"] + flags + ["-c", mock, "-o", mo])
-        subprocess.check_call(["g++", "-shared", "-Wl,-Bsymbolic", "-o", out, mo] + objs + ["-lpthread", "-lm"])
-    else:
-        subprocess.check_call(["hipcc"] + flags + ["-shared", "-Wl,-Bsymbolic", "-o", out, mock] + srcs + ["-lpthread", "-lm"])
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, out
-    try:
-        assert _capi.lib().trm_device_count() == 1
-        yield gnuspeech_amd
-    finally:
-        T._CACHE.clear()
-        gc.collect()             # (streams of the stand-in are destroyed by the stand-in)
-        _capi._lib, _capi.LIB_PATH = saved
+    M.build(out, ["hip_host_mock.cc"], reuse_objects=True)
+    with M.product_on(out) as pkg:
+        try:
+            yield pkg
+        finally:
+            T._CACHE.clear()
 
 
 @pytest.fixture(autouse=True, params=["quad", "wide"])
@@ -59,14 +39,7 @@ def stream_form(request, monkeypatch):
     T._CACHE.clear()
 
 
-@pytest.fixture(autouse=True)
-def heap_stays_clean(g):
-    """every test of this module is a bounds test too: the stand-in's checking heap (tests/_emul/hip_host_mock.cc) saw no copy,
-    memset or kernel span leave its block, and no guard zone was written"""
-    M.violations(g.lib())
-    yield
-    gc.collect()
-    M.assert_clean(g.lib())
+heap_stays_clean = M.heap_clean()
 
 
 @pytest.mark.parametrize("mode", ["framework", "tract"])

@@ -15,6 +15,7 @@ import pytest
 import cases
 import oracle_lib as O
 import parity
+import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PD = cases.monet_default_params(44100.0)
@@ -86,11 +87,7 @@ def test_moving_columns_do_not_hold_and_random_periods_agree(hc):
 
 
 # ---------------------------------------------------------------- GPU: held path == per-sample path, bit for bit
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
+g = support.product(gpu=True)
 
 
 NF = 126                     # 0.5 s of frames at 250 Hz: 125 control periods of 79 tube samples (an odd length: every other

@@ -18,7 +18,6 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -78,14 +77,6 @@ def lengths_of(kind, V):
     return n
 
 
-def set_begin_of(sets, V):
-    live = [s for s in range(len(sets)) if not (len(sets) == 5 and s == 2)]
-    counts = [0] * len(sets)
-    for i, s in enumerate(live):
-        counts[s] = V // len(live) + (1 if i < V % len(live) else 0)
-    return np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
-
-
 # ------------------------------------------------------------------------------------------------ the cases
 def all_cases():
     out = []
@@ -139,33 +130,10 @@ CASES = {key_of(c): c for c in all_cases()}
 
 
 # ------------------------------------------------------------------------------------------------ the library on the stand-in
-def build(out, csrc=CSRC):
-    """the host units of `csrc` with the stand-in and the recorder in front of it"""
-    srcs = [os.path.join(csrc, u + ".cc") for u in M.host_units(csrc)]
-    mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in MOCKS]
-    wrap = ["-Wl,--wrap=" + w for w in WRAPPED]
-    subprocess.check_call(["hipcc", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-o", out] + wrap + mocks + srcs + ["-lpthread", "-lm"])
-
-
 def bind(path):
-    from gnuspeech_amd import _capi
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, path
-    try:
-        L = _capi.lib()
-    finally:
-        _capi._lib, _capi.LIB_PATH = saved
-    assert L.trm_device_count() == 1
-    L.trace_take.argtypes, L.trace_take.restype = [C.c_char_p, C.c_size_t], C.c_size_t
+    L = M.load(path)
     L.trace_out_buffer.argtypes, L.trace_out_buffer.restype = [C.c_void_p, C.c_size_t], None
-    return M.bind(L)
-
-
-def trace_take(L):
-    n = L.trace_take(None, 0)
-    buf = C.create_string_buffer(n + 1)
-    L.trace_take(buf, n + 1)
-    return buf.value.decode().splitlines()
+    return L
 
 
 def compact(ops):
@@ -183,15 +151,10 @@ def compact(ops):
     return out
 
 
-def params_of(name):
-    from gnuspeech_amd import TRMInputParameters
-    return TRMInputParameters.from_dict(PDS[name]).c
-
-
 def warm_noise(L):
     """the process-wide noise sequence, generated once for the longest launch of any case: not an entry's business"""
     h = C.c_void_p()
-    p = params_of("tract")
+    p = M.c_params(PDS["tract"])
     assert L.trm_batch_create(C.byref(p), 0, C.byref(h)) == 0
     buf = np.zeros(1 << 20, dtype=np.float32)
     assert L.trm_batch_noise_table(h, buf.ctypes.data, len(buf)) == 0
@@ -240,10 +203,10 @@ def result(L, rc, split, kernel, ops, res):
 def traced(L, la, call):
     L.trace_out_buffer(la.out.ctypes.data, la.out.nbytes)
     L.trace_enable(1)
-    trace_take(L)
+    M.trace_take(L)
     try:
         rc = call()
-        return rc, trace_take(L)
+        return rc, M.trace_take(L)
     finally:
         L.trace_enable(0)
 
@@ -254,7 +217,7 @@ def ptr(a, c, name):
 
 def run_batch(L, c):
     h = C.c_void_p()
-    p = params_of(c["pd"])
+    p = M.c_params(PDS[c["pd"]])
     assert L.trm_batch_create(C.byref(p), 0, C.byref(h)) == 0, L.trm_last_error()
     try:
         assert L.trm_batch_set_time_split(h, c["setting"]) == 0
@@ -282,12 +245,12 @@ def run_mixed(L, c):
     from gnuspeech_amd import MMIntonation, intonation_struct
     from gnuspeech_amd._capi import TrmInputParams, TrmIntonation
     names = MIXED_SETS[c["sets"]]
-    arr = (TrmInputParams * len(names))(*[params_of(n) for n in names])
+    arr = (TrmInputParams * len(names))(*[M.c_params(PDS[n]) for n in names])
     h = C.c_void_p()
     assert L.trm_mixed_create(arr, len(names), 0, C.byref(h)) == 0, L.trm_last_error()
     try:
         V = c["V"]
-        sb = set_begin_of(names, V)
+        sb = M.set_begin_of(names, V)
         set_of = np.searchsorted(sb, np.arange(V), side="right") - 1
         if c["bad"] == "begin0":
             sb = sb + 1
@@ -334,7 +297,7 @@ def run_mixed(L, c):
 def run_multi(L, c):
     """two shards on device 0, a thread each: their operations interleave as they please, so the record is kept sorted"""
     h = C.c_void_p()
-    p = params_of("monet")
+    p = M.c_params(PDS["monet"])
     dev = (C.c_int * 2)(0, 0)
     assert L.trm_multi_create(C.byref(p), dev, 2, C.byref(h)) == 0, L.trm_last_error()
     try:
@@ -412,7 +375,7 @@ def record(lib_path):
 @pytest.fixture(scope="module")
 def L(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("hostmock_entries") / "libtrm_hostmock_entries.so")
-    build(out)
+    M.build(out, MOCKS, WRAPPED)
     lib = bind(out)
     warm_noise(lib)
     yield lib
@@ -457,5 +420,5 @@ if __name__ == "__main__":
     assert sys.argv[1] == "record"
     sys.path.insert(0, ROOT)
     lib_path = os.path.join(os.path.dirname(os.path.abspath(sys.argv[2])), "libtrm_hostmock_entries_parent.so")
-    build(lib_path, sys.argv[2])
+    M.build(lib_path, MOCKS, WRAPPED, csrc=sys.argv[2])
     json.dump(record(lib_path), open(sys.argv[3] if len(sys.argv) > 3 else GOLDEN, "w"), indent=0, sort_keys=True)

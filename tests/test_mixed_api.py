@@ -5,18 +5,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import cases
+import support
 
-
-def _params(g, **kw):
-    return g.TRMInputParameters.from_dict(dict(cases.monet_default_params(), **kw))
-
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    return gnuspeech_amd
+g = support.product(gpu=False)
+_params = support.input_params
 
 
 def _create(g, plist, device=-1):

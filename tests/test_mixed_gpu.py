@@ -7,17 +7,14 @@ import pytest
 import cases
 import golden_io
 import parity
+import support
 
 pytestmark = pytest.mark.gpu
 
 FORMS = ["wide", "quad", "quad1", "oct"]
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
+g = support.product(gpu=True)
+_ip = support.input_params
 
 
 def _env(monkeypatch, form):
@@ -29,10 +26,6 @@ def _env(monkeypatch, form):
         monkeypatch.setenv("TRM_QUAD_CUS", "1")
     else:
         monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-
-
-def _ip(g, **kw):
-    return g.TRMInputParameters.from_dict(dict(cases.monet_default_params(), **kw))
 
 
 @pytest.mark.parametrize("form", ["auto"] + FORMS)

@@ -3,32 +3,21 @@ trm_mixed_scale_to_int16_device, trm_mixed_sound_file_size, trm_mixed_sound_file
 symbols are declared and exported, null handles and pointers and malformed set layouts are refused, the file sizes follow each
 set's parameters, the Python wrapper checks its settings, and the three new kernels are in the library within budget."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-import cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import support
 
 NEW = ["trm_mixed_generate_frames_device", "trm_mixed_scale_to_int16_device", "trm_mixed_sound_file_size",
        "trm_mixed_sound_files_device", "trm_mixed_events_to_files_host"]
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    return gnuspeech_amd
+g = support.product(gpu=False)
+_params = support.input_params
 
 
 def test_new_symbols_are_exported_and_declared(g):
-    header = open(os.path.join(ROOT, "include", "trm_c_api.h")).read()
-    for name in NEW:
-        assert name in g._capi.EXPORTS, name
-        assert name + "(" in header, name
-        getattr(g.lib(), name)
+    header = support.assert_exported_and_declared(g, NEW)
     assert "device-side sound-file images" not in header
 
 
@@ -51,10 +40,6 @@ def _mixed_or_skip(g, plist):
         if e.code == g._capi.TRM_ENODEVICE:
             pytest.skip("no GPU: a trm_mixed cannot be created")
         raise
-
-
-def _params(g, **kw):
-    return g.TRMInputParameters.from_dict(dict(cases.monet_default_params(), **kw))
 
 
 def test_malformed_set_begin_and_null_device_pointers(g):
@@ -115,28 +100,11 @@ def test_python_wrapper_rejects_a_settings_list_of_the_wrong_length(g):
             m.prepare_events_device([(np.zeros(0, np.uint32), np.zeros((0, 36)))] * 3, sets, bad)
 
 
-def test_pipeline_kernels_are_built_within_budget(tmp_path):
+def test_pipeline_kernels_are_built_within_budget():
     """trm_tracks_mixed_kernel, trm_mixed_int16_kernel and trm_mixed_file_image_kernel are in the gfx950 code object with no
     scratch and no spills; the mixed tube kernels still number six."""
-    import re, shutil, subprocess
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip("ROCm LLVM tools not installed")
-    lib = shutil.copy(os.path.join(ROOT, "gnuspeech_amd", "libtrm_hip.so"), tmp_path / "lib.so")
-    subprocess.run([objdump, "--offloading", str(lib)], check=True, capture_output=True, cwd=tmp_path)
-    cos = [f for f in os.listdir(tmp_path) if "gfx950" in f]
-    assert cos, "no gfx950 code object in libtrm_hip.so"
-    kernels = {}
-    for f in cos:
-        notes = subprocess.run([readelf, "--notes", str(tmp_path / f)], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split("- .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s+(_Z\S+)", blk)
-            if not name:
-                continue
-            get = lambda key: int(re.search(key + r":\s+(\d+)", blk).group(1))
-            kernels[name.group(1)] = (get(r"\.private_segment_fixed_size"), get(r"\.sgpr_spill_count"), get(r"\.vgpr_spill_count"))
-    for k in ("_ZN3trm23trm_tracks_mixed_kernelENS_14MixedTrackArgsE", "_ZN3trm22trm_mixed_int16_kernelENS_10MixOutArgsE",
-              "_ZN3trm27trm_mixed_file_image_kernelENS_10MixOutArgsE"):
-        assert k in kernels, (k, sorted(x for x in kernels if "mixed" in x))
-        assert kernels[k] == (0, 0, 0), (k, kernels[k])
-    assert len([k for k in kernels if "trm_mix_kernel" in k]) == 6
+    import kernel_manifest
+    import kernel_notes
+    kernel_manifest.check(kernel_notes.read_kernels(), "_ZN3trm23trm_tracks_mixed_kernelENS_14MixedTrackArgsE",
+                          "_ZN3trm22trm_mixed_int16_kernelENS_10MixOutArgsE", "_ZN3trm27trm_mixed_file_image_kernelENS_10MixOutArgsE")
+    assert len(kernel_manifest.named("trm_mix_kernel")) == 6

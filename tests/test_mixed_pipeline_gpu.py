@@ -10,20 +10,13 @@ import pytest
 
 import cases
 import oracle_lib as O
+import support
 from test_events import random_events
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
-
-
-def _ip(g, **kw):
-    return g.TRMInputParameters.from_dict(dict(cases.monet_default_params(), **kw))
+g = support.product(gpu=True)
+_ip = support.input_params
 
 
 def _sets(g):

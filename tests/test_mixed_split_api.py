@@ -3,41 +3,32 @@ trm_mixed_last_time_split, trm_mixed_hint_frames): the symbols are exported and 
 instance of the one-voice-per-lane kernel is in the library under a name of its own and within its register budget, and the
 inputs of the GPU parity test (tests/test_mixed_split_gpu.py) are inside the tolerance by the host model of the split alone."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import cases
 import golden_io
+import kernel_manifest
+import kernel_notes
 import oracle_lib as O
 import parity
+import support
 from test_time_split import RMS_TOL, UP_CASES, _emul_split, emul, nrms, warm_periods  # noqa: F401  (emul: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 NEW = ["trm_mixed_set_time_split", "trm_mixed_last_time_split", "trm_mixed_hint_frames"]
-STEM = "trm_mixseg_kernel"
+KERNEL = "_ZN3trm17trm_mixseg_kernelILi5EEEvNS_5ConstENS_8TubeArgsE"            # trm_mixseg_kernel<5>
 
 # what tests/test_mixed_split_gpu.py runs: every up-sampling fixture, with its own parameter set, cut every 9 control periods
 PARITY_SEG = 9
 # ... and the parameter sets of its full-size test: the five distinct ones among those fixtures
 FULL_SIZE_SETS = ["monet_vowel_44k", "monet_vowel_22k", "sine_nomod", "female_15cm_stereo", "tract_vowel_1s"]
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    return gnuspeech_amd
+g = support.product(gpu=False)
 
 
 def test_new_symbols_are_exported_declared_and_refuse_a_null_handle(g):
-    header = open(os.path.join(ROOT, "include", "trm_c_api.h")).read()
-    for name in NEW:
-        assert name in g._capi.EXPORTS, name
-        assert name + "(" in header, name
-        getattr(g.lib(), name)
+    support.assert_exported_and_declared(g, NEW)
     L, E = g.lib(), g._capi.TRM_EINVAL
     p, w = C.c_uint32(), (C.c_uint32 * 4)()
     n = np.array([3, 4], np.uint32)
@@ -49,33 +40,11 @@ def test_new_symbols_are_exported_declared_and_refuse_a_null_handle(g):
         assert hasattr(g.TRMMixedBatch, name), name
 
 
-def test_mixed_segment_instance_is_built_under_its_own_name_within_budget(tmp_path):
-    """Exactly one kernel of the new stem; its name counts neither as a trm_tube_kernel nor as a trm_mix_kernel (the sibling tests
-    count those); no scratch, no spills, at most 128 VGPRs: two workgroups per CU, as the uniform segment instance."""
-    import re, shutil, subprocess
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip("ROCm LLVM tools not installed")
-    lib = shutil.copy(os.path.join(ROOT, "gnuspeech_amd", "libtrm_hip.so"), tmp_path / "lib.so")
-    subprocess.run([objdump, "--offloading", str(lib)], check=True, capture_output=True, cwd=tmp_path)
-    cos = [f for f in os.listdir(tmp_path) if "gfx950" in f]
-    assert cos, "no gfx950 code object in libtrm_hip.so"
-    kernels = {}
-    for f in cos:
-        notes = subprocess.run([readelf, "--notes", str(tmp_path / f)], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split("- .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s+(_Z\S+)", blk)
-            if not name:
-                continue
-            get = lambda key: int(re.search(key + r":\s+(\d+)", blk).group(1))
-            kernels[name.group(1)] = (get(r"\.private_segment_fixed_size"), get(r"\.sgpr_spill_count"), get(r"\.vgpr_spill_count"), get(r"\.vgpr_count"))
-    mine = [k for k in kernels if STEM in k]
-    assert len(mine) == 1, sorted(kernels)
-    k = mine[0]
-    assert "trm_tube_kernel" not in k and "trm_mix_kernel" not in k, k
-    scratch, sspill, vspill, vgprs = kernels[k]
-    assert scratch == 0 and sspill == 0 and vspill == 0, (k, scratch, sspill, vspill)
-    assert vgprs <= 128, (k, vgprs)
+def test_mixed_segment_instance_is_built_under_its_own_name_within_budget():
+    """Exactly one kernel of the name (a line of tests/kernel_manifest.py); no scratch, no spills, at most 128 VGPRs: two
+    workgroups per CU, as the uniform segment instance."""
+    kernel_manifest.check(kernel_notes.read_kernels(), KERNEL)
+    assert kernel_manifest.named("trm_mixseg_kernel") == [KERNEL]
 
 
 @pytest.mark.parametrize("name", UP_CASES)

@@ -12,34 +12,16 @@ import cases
 import golden_io
 import oracle_lib as O
 import parity
+import support
+from test_mixed_gpu import _sets
 from test_mixed_split_api import FULL_SIZE_SETS, PARITY_SEG
 from test_time_split import RMS_TOL, UP_CASES, nrms, warm_periods
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
-
-
-@pytest.fixture(autouse=True)
-def _no_form_by_environment(monkeypatch):
-    monkeypatch.delenv("TRM_TUBE_KERNEL", raising=False)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    monkeypatch.delenv("TRM_TIME_SPLIT", raising=False)
-
-
-def _ip(g, **kw):
-    return g.TRMInputParameters.from_dict(dict(cases.monet_default_params(), **kw))
-
-
-def _sets(g):
-    # male 17.5 cm, female 15 cm stereo, a down-sampling set, an empty set, sine / no modulation (tests/test_mixed_gpu.py)
-    return [_ip(g, length=17.5), _ip(g, length=15.0, channels=2, balance=-0.3), _ip(g, outputRate=22050.0, length=15.0),
-            _ip(g, length=12.5), _ip(g, length=16.0, waveform=1, usesModulation=0)]
+g = support.product(gpu=True)
+_ip = support.input_params
+_no_form_by_environment = support.no_plan_by_environment()
 
 
 def _bench_sets(g):

@@ -14,25 +14,15 @@ import oracle_lib as O
 import parity
 from test_mixed_split_api import PARITY_SEG
 from test_mixed_split_gpu import _assert_matches, _ip, _reference, _voices
+import support
 from test_time_split import RMS_TOL, UP_CASES, nrms, warm_periods
 
 pytestmark = pytest.mark.gpu
 
 COUNTS = [21, 10, 0, 35]
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
-
-
-@pytest.fixture(autouse=True)
-def _no_form_by_environment(monkeypatch):
-    monkeypatch.delenv("TRM_TUBE_KERNEL", raising=False)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    monkeypatch.delenv("TRM_TIME_SPLIT", raising=False)
+g = support.product(gpu=True)
+_no_form_by_environment = support.no_plan_by_environment()
 
 
 def _up_sets(g):

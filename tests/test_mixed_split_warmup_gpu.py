@@ -10,23 +10,13 @@ import pytest
 import parity
 import split_warmup_common as W
 from test_mixed_split_gpu import _assert_matches
+import support
 from test_time_split import RMS_TOL, nrms, warm_periods
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
-
-
-@pytest.fixture(autouse=True)
-def _no_plan_by_environment(monkeypatch):
-    monkeypatch.delenv("TRM_TUBE_KERNEL", raising=False)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    monkeypatch.delenv("TRM_TIME_SPLIT", raising=False)
+g = support.product(gpu=True)
+_no_plan_by_environment = support.no_plan_by_environment()
 
 
 @pytest.fixture(scope="module")

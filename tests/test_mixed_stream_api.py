@@ -2,29 +2,18 @@
 validates the set layout and every parameter set before it looks for a device, TRMMixedStream validates its arguments, and the
 two streaming instances of the mixed kernels are in the library within their register budget."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-import cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import support
 
 NEW = ["trm_mixed_stream_create", "trm_mixed_stream_destroy", "trm_mixed_stream_set_mode", "trm_mixed_stream_mode",
        "trm_mixed_stream_kernel", "trm_mixed_stream_samples_for_push", "trm_mixed_stream_samples_for_finish",
        "trm_mixed_stream_push", "trm_mixed_stream_finish", "trm_mixed_stream_push_device", "trm_mixed_stream_finish_device"]
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    return gnuspeech_amd
-
-
-def _params(g, **kw):
-    return g.TRMInputParameters.from_dict(dict(cases.monet_default_params(), **kw))
+g = support.product(gpu=False)
+_params = support.input_params
 
 
 def _create(g, plist, set_begin, device=-1):
@@ -38,11 +27,7 @@ def _create(g, plist, set_begin, device=-1):
 
 
 def test_new_symbols_are_exported_and_declared(g):
-    header = open(os.path.join(ROOT, "include", "trm_c_api.h")).read()
-    for name in NEW:
-        assert name in g._capi.EXPORTS, name
-        assert name + "(" in header, name
-        getattr(g.lib(), name)
+    support.assert_exported_and_declared(g, NEW)
 
 
 def test_malformed_set_layouts_give_einval(g):
@@ -106,31 +91,12 @@ def test_python_wrapper_validates_its_arguments(g):
         g.TRMMixedStream([p], [0], mode="bogus")
 
 
-def test_streaming_instances_of_the_mixed_kernels_are_built_within_budget(tmp_path):
+def test_streaming_instances_of_the_mixed_kernels_are_built_within_budget():
     """The two new instances -- trm_mix_kernel<kModeMixedStream> (one voice per lane) and trm_mix_kernel_q<true, 2, false, true>
     (four lanes per voice) -- are in the built library with no scratch, no spills and at most 128 VGPRs."""
-    import re, shutil, subprocess
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip("ROCm LLVM tools not installed")
-    lib = shutil.copy(os.path.join(ROOT, "gnuspeech_amd", "libtrm_hip.so"), tmp_path / "lib.so")
-    subprocess.run([objdump, "--offloading", str(lib)], check=True, capture_output=True, cwd=tmp_path)
-    cos = [f for f in os.listdir(tmp_path) if "gfx950" in f]
-    assert cos, "no gfx950 code object in libtrm_hip.so"
-    kernels = {}
-    for f in cos:
-        notes = subprocess.run([readelf, "--notes", str(tmp_path / f)], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split("- .agpr_count:")[1:]:
-            name = re.search(r"\.name:\s+(_Z\S+)", blk)
-            if not name:
-                continue
-            get = lambda key: int(re.search(key + r":\s+(\d+)", blk).group(1))
-            kernels[name.group(1)] = (get(r"\.private_segment_fixed_size"), get(r"\.sgpr_spill_count"), get(r"\.vgpr_spill_count"), get(r"\.vgpr_count"))
+    import kernel_manifest
+    import kernel_notes
     wide = "_ZN3trm14trm_mix_kernelILi4EEEvNS_5ConstENS_8TubeArgsE"           # trm_mix_kernel<4 = kModeMixedStream>
     quad = "_ZN3trm16trm_mix_kernel_qILb1ELi2ELb0ELb1EEEvNS_5ConstENS_8TubeArgsE"  # trm_mix_kernel_q<true, 2, false, true>
-    for k in (wide, quad):
-        assert k in kernels, (k, sorted(x for x in kernels if "mix" in x))
-        scratch, sspill, vspill, vgprs = kernels[k]
-        assert scratch == 0 and sspill == 0 and vspill == 0, (k, scratch, sspill, vspill)
-        assert vgprs <= 128, (k, vgprs)
-    assert len([k for k in kernels if "trm_mix_kernel" in k]) == 6       # one-shot x4 (wide, quad x2, oct) + streaming x2
+    kernel_manifest.check(kernel_notes.read_kernels(), wide, quad)
+    assert len(kernel_manifest.named("trm_mix_kernel")) == 6       # one-shot x4 (wide, quad x2, oct) + streaming x2

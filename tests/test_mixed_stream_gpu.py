@@ -9,30 +9,16 @@ import pytest
 
 import cases
 import parity
+from parity import nrms
+import support
 
 pytestmark = pytest.mark.gpu
 
 FORM = {"now": "quad"}
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
-
-
-@pytest.fixture(autouse=True, params=["quad", "wide"])
-def stream_form(request, monkeypatch):
-    """Both streaming forms, forced by TRM_TUBE_KERNEL (read when a stream is created) as tests/test_stream.py does."""
-    monkeypatch.setenv("TRM_TUBE_KERNEL", request.param)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    FORM["now"] = request.param
-    return request.param
-
-
-def _ip(g, **kw):
-    return g.TRMInputParameters.from_dict(dict(cases.monet_default_params(), **kw))
+g = support.product(gpu=True)
+_ip = support.input_params
+stream_form = support.kernel_form(["quad", "wide"], autouse=True, note=FORM)
 
 
 def _sets(g):
@@ -97,11 +83,6 @@ def _assert_equal_to_per_set(mixed, ref):
 
 def _concat(parts, v):
     return np.concatenate([pcm[v, :int(ns[v])] for pcm, ns, _ in parts])
-
-
-def nrms(x, ref, mx):
-    e = (np.asarray(x, dtype=np.float64) - np.asarray(ref, dtype=np.float64)) / mx
-    return float(np.sqrt(np.mean(e * e)))
 
 
 @pytest.mark.parametrize("mode", ["framework", "tract"])

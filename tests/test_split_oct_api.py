@@ -2,30 +2,20 @@
 trm_tube_set_split_form): the symbols are declared and exported, the raw entries refuse what has no object behind it and every
 form but AUTO and OCT, the getter's default is AUTO, and the Python mirrors check their argument before they ask the library."""
 import ctypes as C
-import os
 
 import pytest
 
 import cases
+import support
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["trm_batch_set_split_form", "trm_batch_split_form", "trm_tube_set_split_form"]
 AUTO, WIDE, QUAD, OCT = 0, 1, 2, 3                # TRM_KERNEL_*
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    return gnuspeech_amd
+g = support.product(gpu=False)
 
 
 def test_new_symbols_are_exported_and_declared(g):
-    header = open(os.path.join(ROOT, "include", "trm_c_api.h")).read()
-    for name in NEW:
-        assert name in g._capi.EXPORTS, name
-        assert name + "(" in header, name
-        getattr(g.lib(), name)
+    header = support.assert_exported_and_declared(g, NEW)
     # admissibility, the demotion rule and the statement on trm_batch_set_kernel stand in the comment
     assert "at least 16 tube" in header and "at most four outputs per tube sample" in header
     assert "exactly as if this setter had never been called" in header

@@ -13,23 +13,13 @@ import golden_io
 import oracle_lib as O
 import parity
 import split_warmup_common as W
+import support
 from test_time_split import MV_CLOSED, RMS_TOL, UP_CASES, _check_voices_against_oracle, _seam_voices, nrms, warm_periods
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
-
-
-@pytest.fixture(autouse=True)
-def _no_plan_by_environment(monkeypatch):
-    monkeypatch.delenv("TRM_TUBE_KERNEL", raising=False)
-    monkeypatch.delenv("TRM_QUAD_CUS", raising=False)
-    monkeypatch.delenv("TRM_TIME_SPLIT", raising=False)
+g = support.product(gpu=True)
+_no_plan_by_environment = support.no_plan_by_environment()
 
 
 def _batch(g, pd, split, form="oct", kernel=None, warmup=None):

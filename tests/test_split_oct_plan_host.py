@@ -39,15 +39,10 @@ def arrays(L):
     a.free()
 
 
-def params_of(name):
-    from gnuspeech_amd import TRMInputParameters
-    return TRMInputParameters.from_dict(PDS[name]).c
-
-
 def run(L, A, pd="monet", V=64, F=251, hint=None, setting=AUTO, form=None, kernel=K_AUTO):
     """one trm_batch_synthesize_device on a fresh batch -> {rc, err, split, kernel, ops}; form None: the setter is never called"""
     h = C.c_void_p()
-    p = params_of(pd)
+    p = M.c_params(PDS[pd])
     assert L.trm_batch_create(C.byref(p), 0, C.byref(h)) == 0, L.trm_last_error()
     try:
         assert L.trm_batch_set_kernel(h, kernel) == 0
@@ -57,11 +52,11 @@ def run(L, A, pd="monet", V=64, F=251, hint=None, setting=AUTO, form=None, kerne
             assert L.trm_batch_split_form(h) == form
         A.nframes.a[:V] = F if hint is None else hint
         L.trace_enable(1)
-        P.trace_take(L)
+        M.trace_take(L)
         if hint is not None:
             assert L.trm_batch_hint_frames(h, hint.ctypes.data, V) == 0
         rc = L.trm_batch_synthesize_device(h, V, A.frames.ptr, A.off.ptr, A.nframes.ptr, F, A.out.ptr, A.off.ptr, A.ns.ptr, A.mx.ptr, None)
-        ops = P.trace_take(L)
+        ops = M.trace_take(L)
         L.trace_enable(0)
         s, w = C.c_uint32(), C.c_uint32()
         assert L.trm_batch_last_time_split(h, C.byref(s), C.byref(w)) == 0

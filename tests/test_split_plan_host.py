@@ -15,7 +15,6 @@ import gc
 import json
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -130,14 +129,6 @@ MIXED_SETS = {
 }
 
 
-def set_begin_of(sets, V):
-    live = [s for s in range(len(sets)) if not (len(sets) == 5 and s == 2)]
-    counts = [0] * len(sets)
-    for i, s in enumerate(live):
-        counts[s] = V // len(live) + (1 if i < V % len(live) else 0)
-    return np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
-
-
 def mixed_cases():
     out = []
 
@@ -182,41 +173,6 @@ for _c in batch_cases() + mixed_cases():
 
 
 # ------------------------------------------------------------------------------------------------ the library on the stand-in
-def build(out, csrc=CSRC):
-    """the host units of `csrc` with the stand-in and the recorder in front of it"""
-    srcs = [os.path.join(csrc, u + ".cc") for u in M.host_units(csrc)]
-    mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in MOCKS]
-    wrap = ["-Wl,--wrap=" + w for w in WRAPPED]
-    # (-Bsymbolic: the library's calls into the runtime bind to the stand-in, whatever else the process has loaded)
-    subprocess.check_call(["hipcc", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-o", out] + wrap + mocks + srcs + ["-lpthread", "-lm"])
-
-
-def bind(path):
-    """gnuspeech_amd's ctypes view of the library at `path` (argument types included), plus the recorder's two entries"""
-    from gnuspeech_amd import _capi
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, path
-    try:
-        L = _capi.lib()
-    finally:
-        _capi._lib, _capi.LIB_PATH = saved
-    assert L.trm_device_count() == 1
-    L.trace_take.argtypes, L.trace_take.restype = [C.c_char_p, C.c_size_t], C.c_size_t
-    return M.bind(L)
-
-
-def trace_take(L):
-    n = L.trace_take(None, 0)
-    buf = C.create_string_buffer(n + 1)
-    L.trace_take(buf, n + 1)
-    return buf.value.decode().splitlines()
-
-
-def params_of(name):
-    from gnuspeech_amd import TRMInputParameters
-    return TRMInputParameters.from_dict(PDS[name]).c
-
-
 class Arrays:
     """the "device" arrays of a launch, shared by all cases (the stand-in's one-shot kernels read and write nothing but
     max_sample's clears): every voice's frames are rows 0 .. of one block, its PCM starts at 0"""
@@ -237,7 +193,7 @@ class Arrays:
 def warm_noise(L):
     """the process-wide noise sequence, generated once for the longest launch of any case: not a launch's business"""
     h = C.c_void_p()
-    p = params_of("tract")
+    p = M.c_params(PDS["tract"])
     assert L.trm_batch_create(C.byref(p), 0, C.byref(h)) == 0
     buf = np.zeros(4, dtype=np.float32)
     assert L.trm_batch_noise_table(h, buf.ctypes.data, 4) == 0
@@ -256,7 +212,7 @@ def run_batch(L, A, c):
     if c["env"] != "-":
         os.environ["TRM_TUBE_KERNEL"] = c["env"]
     h = C.c_void_p()
-    p = params_of(c["pd"])
+    p = M.c_params(PDS[c["pd"]])
     try:
         assert L.trm_batch_create(C.byref(p), 0, C.byref(h)) == 0, L.trm_last_error()
     finally:
@@ -269,7 +225,7 @@ def run_batch(L, A, c):
         hint = hint_of(c["hint"], V, F)
         A.nframes.a[:V] = F if hint is None else hint
         L.trace_enable(1)
-        trace_take(L)
+        M.trace_take(L)
         if c["entry"] == "host":
             nfr = hint.copy()
             zero = np.zeros(V, dtype=np.uint64)
@@ -281,7 +237,7 @@ def run_batch(L, A, c):
             if hint is not None:
                 assert L.trm_batch_hint_frames(h, hint.ctypes.data, V) == 0
             rc = L.trm_batch_synthesize_device(h, V, A.frames.ptr, A.off.ptr, A.nframes.ptr, F, A.out.ptr, A.off.ptr, A.ns.ptr, A.mx.ptr, None)
-        ops = trace_take(L)
+        ops = M.trace_take(L)
         L.trace_enable(0)
         s, w = C.c_uint32(), C.c_uint32()
         assert L.trm_batch_last_time_split(h, C.byref(s), C.byref(w)) == 0
@@ -294,11 +250,11 @@ def run_batch(L, A, c):
 def run_mixed(L, A, c):
     from gnuspeech_amd._capi import TrmInputParams
     names = MIXED_SETS[c["sets"]]
-    arr = (TrmInputParams * len(names))(*[params_of(n) for n in names])
+    arr = (TrmInputParams * len(names))(*[M.c_params(PDS[n]) for n in names])
     h = C.c_void_p()
     assert L.trm_mixed_create(arr, len(names), 0, C.byref(h)) == 0, L.trm_last_error()
     V = c["V"]
-    sb = set_begin_of(names, V)
+    sb = M.set_begin_of(names, V)
     assert int(sb[-1]) == V
     sbc = (C.c_size_t * len(sb))(*[int(x) for x in sb])
     res = []
@@ -312,9 +268,9 @@ def run_mixed(L, A, c):
             if hint is not None:
                 assert L.trm_mixed_hint_frames(h, hint.ctypes.data, V) == 0
             L.trace_enable(1)
-            trace_take(L)
+            M.trace_take(L)
             rc = L.trm_mixed_synthesize_device(h, sbc, A.frames.ptr, A.off.ptr, A.nframes.ptr, F, A.out.ptr, A.off.ptr, A.ns.ptr, A.mx.ptr, None)
-            ops = trace_take(L)
+            ops = M.trace_take(L)
             L.trace_enable(0)
             s, w = C.c_uint32(), (C.c_uint32 * len(names))()
             assert L.trm_mixed_last_time_split(h, C.byref(s), w, len(names)) == 0
@@ -345,7 +301,7 @@ def twins(golden):
 
 def record(lib_path):
     """every case's result from the library at `lib_path` (the PARENT's host units on this module's stand-in and recorder)"""
-    L = bind(lib_path)
+    L = M.load(lib_path)
     warm_noise(L)
     A = Arrays(L)
     out = {k: run_case(L, A, c) for k, c in CASES.items()}
@@ -365,8 +321,8 @@ def record(lib_path):
 @pytest.fixture(scope="module")
 def L(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("hostmock_split") / "libtrm_hostmock_split.so")
-    build(out)
-    lib = bind(out)
+    M.build(out, MOCKS, WRAPPED)
+    lib = M.load(out)
     warm_noise(lib)
     yield lib
     gc.collect()
@@ -417,5 +373,5 @@ if __name__ == "__main__":
     assert sys.argv[1] == "record"
     sys.path.insert(0, ROOT)
     lib_path = os.path.join(os.path.dirname(os.path.abspath(sys.argv[2])), "libtrm_hostmock_split_parent.so")
-    build(lib_path, sys.argv[2])
+    M.build(lib_path, MOCKS, WRAPPED, csrc=sys.argv[2])
     json.dump(record(lib_path), open(sys.argv[3] if len(sys.argv) > 3 else GOLDEN, "w"), indent=0, sort_keys=True)

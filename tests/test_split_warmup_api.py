@@ -12,26 +12,18 @@ import pytest
 import cases
 import golden_io
 import split_warmup_common as W
+import support
 from test_time_split import warm_periods
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["trm_batch_set_split_warmup", "trm_batch_split_warmup", "trm_split_warm_periods", "trm_mixed_set_split_warmup",
        "trm_mixed_split_warmup", "trm_tube_set_split_warmup"]
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    return gnuspeech_amd
+g = support.product(gpu=False)
 
 
 def test_new_symbols_are_exported_and_declared(g):
-    header = open(os.path.join(ROOT, "include", "trm_c_api.h")).read()
-    for name in NEW:
-        assert name in g._capi.EXPORTS, name
-        assert name + "(" in header, name
-        getattr(g.lib(), name)
+    header = support.assert_exported_and_declared(g, NEW)
     # the rule, the refusals and the statement on streams stand in the comment
     assert "rho_c = (c + sqrt(c^2 + 4 d^2 (1 - c))) / 2" in header
     assert "may lengthen the warm-up and" in header and "never shorten it: TRM_ERANGE" in header

@@ -8,15 +8,11 @@ import pytest
 
 import cases
 import parity
+import support
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
+g = support.product(gpu=True)
 
 
 FORM = {"now": "quad"}
@@ -35,8 +31,7 @@ def stream_form(request, monkeypatch):
 def nrms(x, ref, mx):
     if mx == 0.0:                                   # a silent voice: both must be silent
         return 0.0 if not np.any(x) and not np.any(ref) else np.inf
-    e = (np.asarray(x, dtype=np.float64) - np.asarray(ref, dtype=np.float64)) / mx
-    return float(np.sqrt(np.mean(e * e)))
+    return parity.nrms(x, ref, mx)
 
 
 def stream_all(g, pd, fr, chunks):

@@ -17,7 +17,6 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -139,48 +138,9 @@ CASES = {"stream up": stream_schedule("up"), "stream down": stream_schedule("dow
 
 
 # ------------------------------------------------------------------------------------------------ the library on the stand-ins
-def build(out, csrc=M.CSRC):
-    """the host units of `csrc` with the stand-ins and the recorder in front of them"""
-    srcs = [os.path.join(csrc, u + ".cc") for u in M.host_units(csrc)]
-    oracle = os.path.join(ROOT, "oracle")
-    if not os.path.exists(os.path.join(oracle, "libtrm_oracle.so")):
-        subprocess.check_call(["make", "-s", "-C", oracle, "libtrm_oracle.so"])
-    mocks = [os.path.join(ROOT, "tests", "_emul", m) for m in MOCKS]
-    wrap = ["-Wl,--wrap=" + w for w in WRAPPED]
-    # (-Bsymbolic: the library's calls into the runtime bind to the stand-in, whatever else the process has loaded)
-    subprocess.check_call(["hipcc", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wl,-Bsymbolic", "-o", out] + wrap + mocks + srcs +
-                          ["-L" + oracle, "-l:libtrm_oracle.so", "-Wl,-rpath," + oracle, "-lpthread", "-lm"])
-
-
-def bind(path):
-    """gnuspeech_amd's ctypes view of the library at `path` (argument types included), plus the recorder's two entries"""
-    from gnuspeech_amd import _capi
-    saved = (_capi._lib, _capi.LIB_PATH)
-    _capi._lib, _capi.LIB_PATH = None, path
-    try:
-        L = _capi.lib()
-    finally:
-        _capi._lib, _capi.LIB_PATH = saved
-    assert L.trm_device_count() == 1
-    L.trace_take.argtypes, L.trace_take.restype = [C.c_char_p, C.c_size_t], C.c_size_t
-    return M.bind(L)
-
-
-def trace_take(L):
-    n = L.trace_take(None, 0)
-    buf = C.create_string_buffer(n + 1)
-    L.trace_take(buf, n + 1)
-    return buf.value.decode()
-
-
-def params_of(name):
-    from gnuspeech_amd import TRMInputParameters
-    return TRMInputParameters.from_dict(PDS[name]).c
-
-
 def params_array(names):
     from gnuspeech_amd._capi import TrmInputParams
-    return (TrmInputParams * len(names))(*[params_of(n) for n in names])
+    return (TrmInputParams * len(names))(*[M.c_params(PDS[n]) for n in names])
 
 
 def sizes(x):
@@ -239,7 +199,7 @@ class Run:
     # -- the ops
     def create_stream(self, pd, V):
         self.kind, self.V, self.units = "stream", V, 1
-        p = params_of(pd)
+        p = M.c_params(PDS[pd])
         return self.result(self.L.trm_stream_create(C.byref(p), 0, V, C.byref(self.h)))
 
     def create_mixed(self, names, set_begin):
@@ -329,7 +289,7 @@ class Run:
         return self.result(self.L.trm_mixed_stream_group_bind(self.h, group, k), [self.L.trm_mixed_stream_group_bound_set(self.h, min(group, 4))])
 
     def params(self, k, pd):
-        p = params_of(pd) if pd != "null" else None
+        p = M.c_params(PDS[pd]) if pd != "null" else None
         return self.result(self.L.trm_mixed_stream_set_params(self.h, k, C.byref(p) if p is not None else None))
 
     def last(self, voice, cap, how=None):
@@ -339,7 +299,7 @@ class Run:
 
     def null_stream(self, what):
         """the entries' refusals of a null stream (before anything else is looked at)"""
-        L, p = self.L, params_of("up")
+        L, p = self.L, M.c_params(PDS["up"])
         rc = {"bind": lambda: L.trm_mixed_stream_group_bind(None, 0, 0), "convert": lambda: L.trm_mixed_stream_set_group_convert(None, ONE_LAUNCH),
               "events": lambda: L.trm_mixed_stream_group_set_events(None, 0, None, None, None, None, None),
               "params": lambda: L.trm_mixed_stream_set_params(None, 0, C.byref(p)), "last": lambda: L.trm_mixed_stream_last_frames(None, 0, None, 0, None),
@@ -370,9 +330,9 @@ def run_case(L, form, ops):
     try:
         for op in ops:
             L.trace_enable(1)
-            trace_take(L)
+            M.trace_take(L, lines=False)
             res = getattr(r, op[0])(*op[1:])
-            res["ops"] = trace_take(L)
+            res["ops"] = M.trace_take(L, lines=False)
             L.trace_enable(0)
             out.append(res)
     finally:
@@ -386,7 +346,7 @@ def run_case(L, form, ops):
 def record(lib_path):
     """{"traces": [...], "cases": {"<case> <form>": [call, ...]}} from the library at `lib_path` (the PARENT's host units on this
     module's stand-ins and recorder); a call's "ops" is an index into the traces, a trace a list of indices into the lines"""
-    L = bind(lib_path)
+    L = M.load(lib_path)
     warm_noise(L)
     traces, index, out = [], {}, {}
     for name, ops in CASES.items():
@@ -413,8 +373,8 @@ def load_golden():
 @pytest.fixture(scope="module")
 def L(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("hostmock_stream_ops") / "libtrm_hostmock_stream_ops.so")
-    build(out)
-    lib = bind(out)
+    M.build(out, MOCKS, WRAPPED, oracle=True)
+    lib = M.load(out)
     warm_noise(lib)
     yield lib
     gc.collect()
@@ -467,5 +427,5 @@ if __name__ == "__main__":
     assert sys.argv[1] == "record"
     sys.path.insert(0, ROOT)
     lib_path = os.path.join(os.path.dirname(os.path.abspath(sys.argv[2])), "libtrm_hostmock_stream_ops_parent.so")
-    build(lib_path, sys.argv[2])
+    M.build(lib_path, MOCKS, WRAPPED, csrc=sys.argv[2], oracle=True)
     json.dump(record(lib_path), open(sys.argv[3] if len(sys.argv) > 3 else GOLDEN, "w"), separators=(",", ":"), sort_keys=True)

@@ -18,17 +18,14 @@ import cases
 import golden_io
 import oracle_lib as O
 import parity
+from parity import nrms
+import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RMS_TOL = 1e-5
 UP_CASES = [n for n in golden_io.CASE_NAMES if n != "short_tube_downsample"]
 
 MV_CLOSED = [-12.0, 60.0, 0.0, 0.0, 5.5, 2500.0, 500.0, 0.8, 0.89, 0.99, 0.81, 0.76, 1.05, 1.23, 0.01, 0.0]   # mouth AND velum closed
-
-
-def nrms(x, ref, mx):
-    e = (np.asarray(x, dtype=np.float64) - ref) / mx
-    return float(np.sqrt(np.mean(e * e)))
 
 
 # ---------------------------------------------------------------- CPU: the host model of the split arithmetic
@@ -137,12 +134,7 @@ def test_host_model_warm_up_shortfall_is_seen_per_period_first(emul):
 
 
 # ---------------------------------------------------------------- GPU
-@pytest.fixture(scope="module")
-def g():
-    import gnuspeech_amd
-    gnuspeech_amd.lib()
-    assert gnuspeech_amd.lib().trm_device_count() >= 1
-    return gnuspeech_amd
+g = support.product(gpu=True)
 
 
 def _batch(g, pd, split):

@@ -11,6 +11,7 @@ import pytest
 
 import cases
 import golden_io
+from parity import nrms
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,11 +38,6 @@ def run_driver(exe, tmp_path, total, *events, slice_samples=0):
     r = subprocess.run([exe, out, str(total)] + list(events), capture_output=True, text=True, env=env, timeout=120)
     assert r.returncode == 0, r.stderr
     return np.fromfile(out, dtype=np.float32), r
-
-
-def nrms(x, ref, mx):
-    e = (np.asarray(x, dtype=np.float64) - np.asarray(ref, dtype=np.float64)) / mx
-    return float(np.sqrt(np.mean(e * e)))
 
 
 def outputs_after(periods, gold):
