@@ -269,14 +269,65 @@ def lib():
     return L
 
 
+def _names(codes):
+    return {code: name for name, code in codes.items()}
+
+
+# The tables between the names this package takes and returns and the codes of include/trm_c_api.h, each written once and read in
+# both directions.
+KERNELS = {"auto": 0, "wide": 1, "quad": 2, "oct": 3}      # TRM_KERNEL_*: what set_kernel takes
+KERNEL_NAMES = _names(KERNELS)                             # ... and last_kernel returns
+STREAM_KERNEL_NAMES = {1: "wide", 2: "quad"}               # the forms a stream runs in: fixed when it was created
+MODE_NAMES = {0: "framework", 1: "tract"}                  # TRM_STREAM_MODE_*: the loop order of a stream, or of one set
+MODES = _names(MODE_NAMES)
+SHARED_MODE_NAMES = {**MODE_NAMES, TRM_STREAM_MODE_MIXED: "mixed"}         # what trm_mixed_stream_mode may return
+TIME_SPLITS = {"auto": -1, "off": 0}                       # set_time_split: a name, or control periods per segment
+SPLIT_WARMUPS = {"default": TRM_SPLIT_WARMUP_DEFAULT, "coupled": TRM_SPLIT_WARMUP_COUPLED}
+SPLIT_FORMS = {"auto": TRM_KERNEL_AUTO, "oct": KERNELS["oct"]}
+CONVERTS = {"per_group": TRM_GROUP_CONVERT_PER_GROUP, "one_launch": TRM_GROUP_CONVERT_ONE_LAUNCH}
+CONVERT_NAMES = _names(CONVERTS)
+
+
+def mode_code(mode):
+    """'framework' | 'tract' -> TRM_STREAM_MODE_*, for the mixed streams, which refuse anything else here."""
+    if mode not in MODES:
+        raise ValueError("unknown stream mode %r" % (mode,))
+    return MODES[mode]
+
+
+class Handle:
+    """A library object behind `_h`, destroyed with the entry the class names in `_destroy`."""
+    _destroy = None
+
+    def _create(self, entry, *args):
+        """entry(*args, &handle), the library's create call; `_h` exists before it, so that a failed create leaves nothing to destroy"""
+        self._h = C.c_void_p()
+        check(entry(*args, C.byref(self._h)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                getattr(lib(), self._destroy)(h)
+            except Exception:      # interpreter shutdown: the process is going away anyway
+                pass
+            self._h = None
+
+
+def derived(entry, *args):
+    """The TrmDerived that entry(*args, &derived) fills, as a dict."""
+    d = TrmDerived()
+    check(entry(*args, C.byref(d)))
+    return {k: getattr(d, k) for k, _ in TrmDerived._fields_}
+
+
 def split_warmup_code(warmup, periods_ok=True):
     """'default' | 'coupled' | control periods (an int above 0, where periods_ok) -> the C interface's value; anything else is
     refused here, with the names that are accepted."""
-    rules = {"default": TRM_SPLIT_WARMUP_DEFAULT, "coupled": TRM_SPLIT_WARMUP_COUPLED}
     if isinstance(warmup, str):
-        if warmup not in rules:
+        if warmup not in SPLIT_WARMUPS:
             raise ValueError("split warm-up %r: 'default' or 'coupled'%s" % (warmup, ", or control periods" if periods_ok else ""))
-        return rules[warmup]
+        return SPLIT_WARMUPS[warmup]
     if isinstance(warmup, bool) or int(warmup) != warmup or warmup <= 0:
         raise ValueError("split warm-up %r: 'default', 'coupled'%s" % (warmup, " or a whole number of control periods above 0" if periods_ok else ""))
     if not periods_ok:
@@ -285,15 +336,18 @@ def split_warmup_code(warmup, periods_ok=True):
 
 
 def split_warmup_name(code):
-    return {TRM_SPLIT_WARMUP_DEFAULT: "default", TRM_SPLIT_WARMUP_COUPLED: "coupled"}.get(code, code)
+    return _names(SPLIT_WARMUPS).get(code, code)
 
 
 def split_form_code(form):
     """'auto' | 'oct' -> TRM_KERNEL_AUTO | TRM_KERNEL_OCT (trm_batch_set_split_form); anything else is refused here."""
-    codes = {"auto": TRM_KERNEL_AUTO, "oct": 3}
-    if not isinstance(form, str) or form not in codes:
+    if not isinstance(form, str) or form not in SPLIT_FORMS:
         raise ValueError("split form %r: 'auto' or 'oct'" % (form,))
-    return codes[form]
+    return SPLIT_FORMS[form]
+
+
+def split_form_name(code):
+    return _names(SPLIT_FORMS)[code]
 
 
 def split_warm_periods(inputParameters, rule="default"):

@@ -12,6 +12,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import layout
 from ._capi import TrmIntonation, check, lib
 
 MAX_VALUES = 36
@@ -72,11 +73,7 @@ class EventList:
         return intonation_struct(self.intonation, self.pitchMean, self.timeQuantization, start_ms, length_ms, self.driftSeed)
 
     def count_frames(self, start_ms=0, length_ms=0):
-        times, _ = self.arrays()
-        n = C.c_size_t()
-        s = self.settings(start_ms, length_ms)
-        check(lib().trm_events_count_frames(times.ctypes.data, len(times), C.byref(s), C.byref(n)))
-        return n.value
+        return layout.count_frames(self.arrays()[0], self.settings(start_ms, length_ms))
 
     def generateOutputInTimeRange(self, batch, synthesizer=None, start_ms=0, length_ms=0):
         """Returns the [n,16] float32 frames (computed on the GPU through `batch`, a TRMBatch) and, like the

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import TrmDerived, check, lib
+from ._capi import derived, lib
 
 
 def shard_range(nvoices, rank, world):
@@ -26,9 +26,7 @@ def samples_for_frames(inputParameters, nframes):
 
 
 def derive(inputParameters):
-    d = TrmDerived()
-    check(lib().trm_derive(C.byref(inputParameters.c), C.byref(d)))
-    return {k: getattr(d, k) for k, _ in TrmDerived._fields_}
+    return derived(lib().trm_derive, C.byref(inputParameters.c))
 
 
 def max_over_ranks(seconds, device=None):

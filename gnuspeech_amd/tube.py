@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import TrmDerived, TrmInputParams, TrmParameters, check, lib
+from ._capi import Handle, TrmInputParams, TrmParameters, check, lib
 
 TRMSoundFileFormat_AU, TRMSoundFileFormat_AIFF, TRMSoundFileFormat_WAVE = 0, 1, 2
 TRMWaveFormType_Pulse, TRMWaveFormType_Sine = 0, 1
@@ -109,8 +109,9 @@ class TRMDataList:
         return np.ascontiguousarray([p.values() for p in self.values], dtype=np.float64)
 
 
-class TRMTubeModel:
+class TRMTubeModel(Handle):
     """-initWithInputData: / -synthesize / -saveOutputToFile:error: / -generateWAVData."""
+    _destroy = "trm_tube_destroy"
 
     def __init__(self):
         raise TypeError("use TRMTubeModel.initWithInputData(dataList)")
@@ -128,19 +129,8 @@ class TRMTubeModel:
         check(rc)
         return self
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().trm_tube_destroy(h)
-            except Exception:      # interpreter shutdown: the process is going away anyway
-                pass
-            self._h = None
-
     def derived(self):
-        d = TrmDerived()
-        check(lib().trm_tube_derived(self._h, C.byref(d)))
-        return {k: getattr(d, k) for k, _ in TrmDerived._fields_}
+        return _capi.derived(lib().trm_tube_derived, self._h)
 
     def printInputData(self):                    # TRMTubeModel.m:595-605, to stdout like the reference
         import sys
@@ -172,7 +162,7 @@ class TRMTubeModel:
         """No reference counterpart.  'auto' | 'oct': the form of the segments of the time split a long utterance runs as
         (include/trm_c_api.h: trm_tube_set_split_form; TRMBatch.set_split_form)."""
         check(lib().trm_tube_set_split_form(self._h, _capi.split_form_code(form)))
-        self._split_form = "oct" if _capi.split_form_code(form) == 3 else "auto"
+        self._split_form = _capi.split_form_name(_capi.split_form_code(form))
 
     @property
     def split_form(self):

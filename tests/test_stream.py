@@ -398,3 +398,28 @@ def test_stream_corner_calls(g):
     assert np.array_equal(b, o2.cpu().numpy()) and np.array_equal(c, tail)
     o3, n3 = s.finish_device(device=dev)
     assert n3 == 0
+
+
+def test_push_device_refuses_tensors_outside_its_contract(g):
+    """push_device with a CPU tensor, with a float64 tensor and with an `out` one column too narrow raises ValueError -- the mixed
+    streams' refusals, not an assert that python -O drops -- before the library is called: the stream's next correct push, 1 voice
+    of 2 frames, is bit for bit that of a fresh stream."""
+    import torch
+    ip = g.TRMInputParameters.from_dict(cases.monet_default_params(44100.0))
+    fr = cases.config3_frames(1, nframes=2, seed=7).astype(np.float32)
+    dev = torch.device("cuda", 0)
+    frd = torch.from_numpy(fr).to(dev)
+    s, fresh = g.TRMStream(ip, nvoices=1), g.TRMStream(ip, nvoices=1)
+    m = g.lib().trm_stream_samples_for_push(s._h, 2)
+    assert m > 1
+    narrow = torch.empty((1, m - 1), dtype=torch.float32, device=dev)
+    for frames, out, text in ((torch.from_numpy(fr), None, "frames must be a contiguous float32 CUDA tensor"),
+                              (frd.double(), None, "frames must be a contiguous float32 CUDA tensor"),
+                              (frd, narrow, "out must be a float32 CUDA tensor")):
+        with pytest.raises(ValueError, match=text):
+            s.push_device(frames, out=out)
+    a, ma = s.push_device(frd)
+    b, mb = fresh.push_device(frd)
+    torch.cuda.synchronize()
+    assert ma == mb == m and a.shape == (1, m)
+    assert np.array_equal(a.cpu().numpy().view(np.uint32), b.cpu().numpy().view(np.uint32))

@@ -422,6 +422,35 @@ def test_every_call_enqueues_and_returns_what_the_parent_did(L, golden, case, fo
     assert not bad, "%d of %d calls differ; first: %r" % (len(bad), len(got), bad[0])
 
 
+def test_stream_push_refuses_wrong_frames_before_any_library_call(L, monkeypatch):
+    """TRMStream.push checks its frames as the mixed streams do -- a ValueError, where an assert would go with python -O -- for a
+    wrong number of voices and a last dimension other than 16, before it asks the library anything: nothing is enqueued, and the
+    next correct push is that of a fresh stream"""
+    with M.product_on(L._name) as pkg:
+        lib = pkg.lib()
+        ip = pkg.TRMInputParameters.from_dict(PDS["up"])
+        fr = cases.config3_frames(2, nframes=4).astype(np.float32)
+        s, fresh = pkg.TRMStream(ip, nvoices=2, device=0), pkg.TRMStream(ip, nvoices=2, device=0)
+
+        def called(*a):
+            raise AssertionError("the library was called")
+        with monkeypatch.context() as mp:
+            for name in ("trm_stream_samples_for_push", "trm_stream_push"):
+                mp.setattr(lib, name, called, raising=False)
+            lib.trace_enable(1)
+            M.trace_take(lib)
+            for bad in (fr[:1], np.concatenate([fr, fr[:1]]), fr[:, :, :15], np.zeros((2, 4, 17), np.float32)):
+                with pytest.raises(ValueError, match=r"frames must be \[2 voices, n >= 1, 16\], got"):
+                    s.push(bad)
+            assert M.trace_take(lib) == []
+            lib.trace_enable(0)
+        got, want = s.push(fr), fresh.push(fr)
+        assert got[0].shape[1] > 0 and np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32)) and np.array_equal(got[1], want[1])
+        del s, fresh
+    gc.collect()
+    M.assert_clean(L)
+
+
 if __name__ == "__main__":
     # python tests/test_stream_ops_host.py record <csrc of the parent commit> [out.json]
     assert sys.argv[1] == "record"
