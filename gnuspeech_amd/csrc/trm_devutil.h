@@ -10,7 +10,7 @@
 namespace trm {
 
 // More than 64 KB of dynamic LDS has to be allowed once per kernel and device (hipFuncSetAttribute).  One of these per
-// kernel instance (a function-local static of its launcher): handles of different devices launch from different
+// kernel instance (launch_lds's function-local static): handles of different devices launch from different
 // threads, so the bookkeeping is locked, and it grows with the device index instead of capping it.
 struct DynamicLdsAllowance {
     std::mutex m;
@@ -30,6 +30,19 @@ struct DynamicLdsAllowance {
         return hipSuccess;
     }
 };
+
+// The launch of a kernel instance with `ldsBytes` of dynamic LDS: the allowance (this instantiation's function-local static, so
+// one per kKernel), the launch, its error.  The kernel is named ONCE: an allowance for one instance in front of the launch of
+// another cannot be written.
+template <auto kKernel, class... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, size_t ldsBytes, hipStream_t stream, const Args &...args)
+{
+    static DynamicLdsAllowance lds;
+    const hipError_t e = lds.ensure(reinterpret_cast<const void *>(kKernel), (int)ldsBytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kKernel, grid, block, ldsBytes, stream, args...);
+    return hipGetLastError();
+}
 
 constexpr int kWave = 64;
 constexpr int kNoiseRing = 128;      // noise ring: one float per tube sample, refilled by halves of 64

@@ -12,11 +12,7 @@ namespace trm {
 // two blocks per pipeline step and QuadLds<2>, as every streaming instance of the four-lane form
 hipError_t launch_grp_quad(const Const &c, const TubeArgs &a, hipStream_t stream)
 {
-    static DynamicLdsAllowance lds;
-    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_grpstream_kernel_q<true, 2, false, true>), (int)QuadLds<2>::kBytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((trm_grpstream_kernel_q<true, 2, false, true>), dim3(a.mix_grid), dim3(kWave * kQRoles), QuadLds<2>::kBytes, stream, c, a);
-    return hipGetLastError();
+    return launch_quad<true, 2, false, true>(c, a, stream, a.mix_grid);
 }
 
 }  // namespace trm

@@ -109,6 +109,34 @@ struct TubeArgs {
     const __attribute__((address_space(4))) uint4 *grp_clock = nullptr;
 };
 
+// The modes of a tube launch: what trm_tube_kernel is instantiated over, and what the four- and eight-lane kernels spell as
+// <kStream, kSub, kSeg, kMix> / <kMix, kSeg> (and TRM_GRP_INSTANCE).  kModeOneShot: whole utterances.  kModeStream: a chunk of a
+// streamed utterance (TubeArgs::stream_*).  kModeSegments: a time-split launch (TubeArgs::seg_*): the workgroup
+// runs ONE segment of its voices from rest, a warm-up ahead of the segment's first control period; like a stream chunk
+// its tube samples and converter outputs keep their global indices (nBase, kBase -- here per workgroup), unlike one it
+// neither restores nor saves state: only the oscillator position is handed in.  kModeMixed: a one-shot launch whose
+// workgroups may belong to different parameter sets (TubeArgs::mix_map): the workgroup's constants come from set_const, its
+// voices are the map entry's range; otherwise it is the one-shot instance.  kModeMixedStream: both, a chunk of a mixed stream
+// (its time bases are the set's own, derived from a count of control periods); the state block of workgroup
+// wg is the map entry's.  kModeMixedSegments: a time-split launch of a mixed batch: the workgroup runs one segment of one
+// map entry (seg_map lists the pairs), with the set's constants and the set's own warm-up (the map entry's fourth component):
+// its segment boundaries and time bases are those of a kModeSegments launch of that set alone.  kModeGroupStream: a step of a
+// grouped stream (TubeArgs::grp_*): kModeMixedStream with the workgroup's map entry taken from the list of the
+// entries that run, the entry's own clock (periods, first chunk, flush) in place of the launch's, and the entry's frame rows
+// derived from that clock; the state block is the entry's.
+constexpr int kModeOneShot = 0, kModeStream = 1, kModeSegments = 2, kModeMixed = 3, kModeMixedStream = 4, kModeMixedSegments = 5,
+              kModeGroupStream = 6;
+// The mode of a launch, from which of its tables are set: the ONE statement of that rule, which launch_tube, launch_tube_quad and
+// launch_tube_oct switch over.  Seven combinations are built by the host, one per mode; a grp_clock is only ever set together
+// with stream_state and mix_map (its one assignment: trm_stream_step.cc, step_synthesize), and no host path sets seg_periods on a
+// stream.  The other nine fall where the order of the questions puts them (tests/test_tube_mode.py writes them out).
+inline int tube_mode(const TubeArgs &a)
+{
+    if (a.seg_periods) return a.mix_map ? kModeMixedSegments : kModeSegments;
+    if (a.stream_state) return !a.mix_map ? kModeStream : a.grp_clock ? kModeGroupStream : kModeMixedStream;
+    return a.mix_map ? kModeMixed : kModeOneShot;
+}
+
 // trm_phase_*_kernel: the oscillator advances a time-split launch starts from, and the guard that decides whether the batch
 // may be split at all: *gate is set when a frame's frication bandwidth lies below bw_floor (the band-pass then remembers
 // longer than the warm-up; whole-utterance launch instead).  `nseg` = segments of the longest voice.
@@ -143,16 +171,22 @@ struct ScaleArgs {
 int tube_kernel_blocks_per_cu();
 hipError_t launch_noise(float *lp, uint32_t from, uint32_t to, double *state, hipStream_t stream);
 hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream);
-// Mixed-parameter instances (TubeArgs::mix_map) of the three tube kernels: trm_mix.hip, trm_mix_q.hip and trm_mix_o.hip compile
-// each kernel's source once more with the mixed instances alone, under a name of its own (trm_mix_kernel, trm_mix_kernel_q,
-// trm_mix_kernel_o).  The launchers above call these for a launch with a mix_map; with a stream_state too, the first two run
-// their mixed streaming instance.
-hipError_t launch_mix_wide(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);       // `grid` workgroups from a.wg_base
-// ... and of a mixed batch's time-split launch (trm_mix_seg.hip: trm_mixseg_kernel; a.seg_periods and a.mix_map both set)
+// The instance files: each compiles one tube kernel's source once more with the instances of one or two modes alone, under a name
+// of its own, and holds the launcher of those instances -- one or two lines over the including kernel file's launch helper.  The
+// three launchers above decide the mode (tube_mode), keep the early returns and refusals, and call these; none of them looks at
+// the TubeArgs' tables again.
+//   kModeMixed, kModeMixedStream    trm_mix.hip trm_mix_kernel, trm_mix_q.hip trm_mix_kernel_q; kModeMixed also trm_mix_o.hip trm_mix_kernel_o
+//   kModeMixedSegments              trm_mix_seg.hip trm_mixseg_kernel, trm_mix_seg_q.hip trm_mixqseg_kernel
+//   kModeSegments, eight lanes      trm_oct_seg.hip trm_octseg_kernel
+//   kModeGroupStream                trm_grp_stream.hip trm_grpstream_kernel, trm_grp_stream_q.hip trm_grpstream_kernel_q
+// `mode`: kModeMixed or kModeMixedStream, the caller's tube_mode.  `grid` workgroups from a.wg_base.
+hipError_t launch_mix_wide(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream, int mode);
+// (a.seg_periods and a.mix_map both set)
 hipError_t launch_mix_seg(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);
 // max_sample[0 .. n) = 0 and, where gate is not null, *gate = 0, in one launch (trm_mix_seg.hip)
 hipError_t launch_split_clear(float *max_sample, uint32_t n, uint32_t *gate, hipStream_t stream);
-hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int sub);
+// `sub`: blocks per pipeline step of a kModeMixed launch, chosen as for a one-shot batch; a stream chunk always runs with two
+hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int mode, int sub);
 // ... and the four-lane form's (trm_mix_seg_q.hip: trm_mixqseg_kernel; mix_map is then the 16-voice map, seg_phase rows are
 // indexed by map entry * 16 + the voice within the entry)
 hipError_t launch_mix_seg_quad(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);

@@ -75,7 +75,7 @@ constexpr int kRoles = 7;            // waves per workgroup: osc, mix, coef x2, 
 constexpr int kTB = 2;               // tube samples per pipeline step (one barrier per step)
 constexpr int kKQuads = 5;           // coef -> tube: 20 floats per lane per sample
 
-// TRM_MIX_TU: trm_mix*.hip include this file again, for the tube kernel's mixed instance alone.  Outside these guards stays
+// TRM_MIX_TU: the instance files (trm_kernels.h lists them) include this file again, for the tube kernel alone.  Outside these guards stays
 // ONLY what that kernel needs (constants, types, __device__ functions); every other __global__ kernel, __device__/__constant__
 // variable and host function goes inside them, or the second translation unit builds (and exports) another copy of it.
 #ifndef TRM_MIX_TU
@@ -119,21 +119,7 @@ __global__ void trm_noise_kernel(float *lp, uint32_t from, uint32_t to, double *
 //   [58..68] filter memories            [72..103] the last 32 tube samples (the converter's history)
 // stored per workgroup as [field][lane]: field i of the workgroup's lane l at stream_state[(wg * kStreamFloats + i) * 64 + l]
 // (trm_quad.hip's records are voice-major); the buffer holds kStreamFloats floats per voice, voices rounded up to 64.
-// kMode: kModeOneShot | kModeStream (above) | kModeSegments: a time-split launch (trm_kernels.h, TubeArgs::seg_*): the workgroup
-// runs ONE segment of its 64 voices from rest, a warm-up ahead of the segment's first control period; like a stream chunk
-// its tube samples and converter outputs keep their global indices (nBase, kBase -- here per workgroup), unlike one it
-// neither restores nor saves state: only the oscillator position is handed in.  kModeMixed: a one-shot launch whose
-// workgroups may belong to different parameter sets (TubeArgs::mix_map): the workgroup's constants come from set_const, its
-// voices are the map entry's range; otherwise it is the one-shot instance.  kModeMixedStream: both, a chunk of a mixed stream
-// (trm_kernels.h: its time bases are the set's own, derived from a count of control periods); the state block of workgroup
-// wg is the map entry's.  kModeMixedSegments: a time-split launch of a mixed batch: the workgroup runs one segment of one
-// map entry (seg_map lists the pairs), with the set's constants and the set's own warm-up (the map entry's fourth component):
-// its segment boundaries and time bases are those of a kModeSegments launch of that set alone.  kModeGroupStream: a step of a
-// grouped stream (trm_kernels.h, TubeArgs::grp_*): kModeMixedStream with the workgroup's map entry taken from the list of the
-// entries that run, the entry's own clock (periods, first chunk, flush) in place of the launch's, and the entry's frame rows
-// derived from that clock; the state block is the entry's.
-constexpr int kModeOneShot = 0, kModeStream = 1, kModeSegments = 2, kModeMixed = 3, kModeMixedStream = 4, kModeMixedSegments = 5,
-              kModeGroupStream = 6;
+// kMode: one of trm_kernels.h's kMode* (kModeStream: above; a workgroup of a kModeSegments launch runs its 64 voices).
 template <int kMode>
 __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const Carg, const TubeArgs A)
 {
@@ -721,7 +707,7 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
     }
 }
 
-// TRM_MIX_TU: trm_mix*.hip include this file again, for the tube kernel's mixed instance alone.  Outside these guards stays
+// TRM_MIX_TU: the instance files (trm_kernels.h lists them) include this file again, for the tube kernel alone.  Outside these guards stays
 // ONLY what that kernel needs (constants, types, __device__ functions); every other __global__ kernel, __device__/__constant__
 // variable and host function goes inside them, or the second translation unit builds (and exports) another copy of it.
 #ifndef TRM_MIX_TU
@@ -1153,23 +1139,24 @@ hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream)
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         return hipGetLastError();
+    const int mode = tube_mode(a);
     TubeArgs s = a;
     for (uint32_t base = 0; base < grid;) {
         const uint32_t n = slice == 0 ? grid - base : (grid - base < slice ? grid - base : slice);
         s.wg_base = base;
         s.coef_hold = n <= 2u * (uint32_t)cus;        // one round: two workgroups per CU
-        if (a.seg_periods && a.mix_map) {
-            const hipError_t e = launch_mix_seg(c, s, n, stream);
-            if (e != hipSuccess) return e;
+        hipError_t e = hipSuccess;                    // (of the instance files' launchers; this file's launches: read at the end)
+        switch (mode) {
+        case kModeMixedSegments: e = launch_mix_seg(c, s, n, stream); break;
+        case kModeSegments: hipLaunchKernelGGL(trm_tube_kernel<kModeSegments>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s); break;
+        // (a grouped stream's step: n of the entries that run, from wg_base in their list)
+        case kModeGroupStream: e = launch_grp_wide(c, s, n, stream); break;
+        case kModeMixedStream:
+        case kModeMixed: e = launch_mix_wide(c, s, n, stream, mode); break;
+        case kModeStream: hipLaunchKernelGGL(trm_tube_kernel<kModeStream>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s); break;
+        default: hipLaunchKernelGGL(trm_tube_kernel<kModeOneShot>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s); break;
         }
-        else if (a.seg_periods) hipLaunchKernelGGL(trm_tube_kernel<kModeSegments>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s);
-        else if (a.mix_map) {
-            // (a grouped stream's step: n of the entries that run, from wg_base in their list)
-            const hipError_t e = a.grp_clock ? launch_grp_wide(c, s, n, stream) : launch_mix_wide(c, s, n, stream);
-            if (e != hipSuccess) return e;
-        }
-        else if (a.stream_state) hipLaunchKernelGGL(trm_tube_kernel<kModeStream>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s);
-        else hipLaunchKernelGGL(trm_tube_kernel<kModeOneShot>, dim3(n), dim3(kWave * kRoles), 0, stream, c, s);
+        if (e != hipSuccess) return e;
         base += n;
     }
     return hipGetLastError();

@@ -7,9 +7,9 @@
 
 namespace trm {
 
-hipError_t launch_mix_wide(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream)
+hipError_t launch_mix_wide(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream, int mode)
 {
-    if (a.stream_state) hipLaunchKernelGGL(trm_mix_kernel<kModeMixedStream>, dim3(grid), dim3(kWave * kRoles), 0, stream, c, a);
+    if (mode == kModeMixedStream) hipLaunchKernelGGL(trm_mix_kernel<kModeMixedStream>, dim3(grid), dim3(kWave * kRoles), 0, stream, c, a);
     else hipLaunchKernelGGL(trm_mix_kernel<kModeMixed>, dim3(grid), dim3(kWave * kRoles), 0, stream, c, a);
     return hipGetLastError();
 }

@@ -9,11 +9,7 @@ namespace trm {
 
 hipError_t launch_mix_oct(const Const &c, const TubeArgs &a, hipStream_t stream)
 {
-    static DynamicLdsAllowance lds;
-    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_mix_kernel_o<true>), (int)OctLds::kBytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(trm_mix_kernel_o<true>, dim3(a.mix_grid), dim3(kWave * kORoles), OctLds::kBytes, stream, c, a);
-    return hipGetLastError();
+    return launch_oct<true>(c, a, stream, a.mix_grid);
 }
 
 }  // namespace trm

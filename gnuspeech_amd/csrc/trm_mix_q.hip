@@ -8,31 +8,12 @@
 
 namespace trm {
 
-template <int kSub>
-static hipError_t launch_mix_instance(const Const &c, const TubeArgs &a, hipStream_t stream)
+// sub = blocks per pipeline step, chosen as for a one-shot batch (launch_tube_quad); a chunk of a mixed stream always runs with
+// two, as the uniform streaming instance
+hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int mode, int sub)
 {
-    static DynamicLdsAllowance lds;
-    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_mix_kernel_q<false, kSub, false, true>), (int)QuadLds<kSub>::kBytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((trm_mix_kernel_q<false, kSub, false, true>), dim3(a.mix_grid), dim3(kWave * kQRoles), QuadLds<kSub>::kBytes, stream, c, a);
-    return hipGetLastError();
-}
-
-// a chunk of a mixed stream (TubeArgs::stream_state): two blocks per pipeline step, as the uniform streaming instance
-static hipError_t launch_mix_stream(const Const &c, const TubeArgs &a, hipStream_t stream)
-{
-    static DynamicLdsAllowance lds;
-    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_mix_kernel_q<true, 2, false, true>), (int)QuadLds<2>::kBytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((trm_mix_kernel_q<true, 2, false, true>), dim3(a.mix_grid), dim3(kWave * kQRoles), QuadLds<2>::kBytes, stream, c, a);
-    return hipGetLastError();
-}
-
-// sub = blocks per pipeline step, chosen as for a one-shot batch (launch_tube_quad); stream chunks always run with two
-hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int sub)
-{
-    if (a.stream_state) return launch_mix_stream(c, a, stream);
-    return sub == 1 ? launch_mix_instance<1>(c, a, stream) : launch_mix_instance<2>(c, a, stream);
+    if (mode == kModeMixedStream) return launch_quad<true, 2, false, true>(c, a, stream, a.mix_grid);
+    return sub == 1 ? launch_quad<false, 1, false, true>(c, a, stream, a.mix_grid) : launch_quad<false, 2, false, true>(c, a, stream, a.mix_grid);
 }
 
 }  // namespace trm

@@ -11,11 +11,7 @@ namespace trm {
 // two blocks per pipeline step and QuadLds<2>, one workgroup per CU: as the uniform segment instance (launch_tube_quad)
 hipError_t launch_mix_seg_quad(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream)
 {
-    static DynamicLdsAllowance lds;
-    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_mixqseg_kernel<true, 2, true, true>), (int)QuadLds<2>::kBytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((trm_mixqseg_kernel<true, 2, true, true>), dim3(grid), dim3(kWave * kQRoles), QuadLds<2>::kBytes, stream, c, a);
-    return hipGetLastError();
+    return launch_quad<true, 2, true, true>(c, a, stream, grid);
 }
 
 }  // namespace trm

@@ -817,7 +817,14 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     }
 }
 
-// TRM_MIX_TU: trm_mix*.hip include this file again, for the tube kernel's mixed instance alone.  Outside these guards stays
+// The launch of one instance of the kernel as the including file names it (the instance files' launchers are calls of this).
+template <bool kMix, bool kSeg = false>
+static hipError_t launch_oct(const Const &c, const TubeArgs &a, hipStream_t stream, uint32_t grid)
+{
+    return launch_lds<trm_tube_kernel_o<kMix, kSeg>>(dim3(grid), dim3(kWave * kORoles), OctLds::kBytes, stream, c, a);
+}
+
+// TRM_MIX_TU: the instance files (trm_kernels.h lists them) include this file again, for the tube kernel alone.  Outside these guards stays
 // ONLY what that kernel needs (constants, types, __device__ functions); every other __global__ kernel, __device__/__constant__
 // variable and host function goes inside them, or the second translation unit builds (and exports) another copy of it.
 #ifndef TRM_MIX_TU
@@ -825,17 +832,14 @@ hipError_t launch_tube_oct(const Const &c, const TubeArgs &a, hipStream_t stream
 {
     if (a.nvoices == 0) return hipSuccess;
     if (a.stream_state || c.controlPeriod < 2 * kOB) return hipErrorInvalidValue;     // (the caller picks trm_quad.hip's kernel for these)
+    switch (tube_mode(a)) {
     // time split: 8 voices x one segment per workgroup (trm_oct_seg.hip); a uniform up-sampling launch's alone
-    if (a.seg_periods) return a.mix_map || a.tube_out ? hipErrorInvalidValue : a.seg_grid ? launch_seg_oct(c, a, stream) : hipSuccess;
-    if (a.mix_map) {      // (a mixed launch: every set's control period; the host demotes the launch otherwise)
-        return a.mix_grid == 0 ? hipSuccess : launch_mix_oct(c, a, stream);
+    case kModeSegments: return a.tube_out ? hipErrorInvalidValue : a.seg_grid ? launch_seg_oct(c, a, stream) : hipSuccess;
+    // (a mixed launch: every set's control period; the host demotes the launch otherwise)
+    case kModeMixed: return a.mix_grid == 0 ? hipSuccess : launch_mix_oct(c, a, stream);
+    case kModeOneShot: return launch_oct<false>(c, a, stream, (a.nvoices + kOV - 1) / kOV);
+    default: return hipErrorInvalidValue;     // mixed segments (the stream modes: refused above)
     }
-    static DynamicLdsAllowance lds;
-    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_tube_kernel_o<false>), (int)OctLds::kBytes);
-    if (e != hipSuccess) return e;
-    const uint32_t grid = (a.nvoices + kOV - 1) / kOV;
-    hipLaunchKernelGGL(trm_tube_kernel_o<false>, dim3(grid), dim3(kWave * kORoles), OctLds::kBytes, stream, c, a);
-    return hipGetLastError();
 }
 
 int tube_oct_kernel_blocks_per_cu()

@@ -12,11 +12,7 @@ namespace trm {
 // atomic max, so the caller zeroes it in front (trm_kernels.h).
 hipError_t launch_seg_oct(const Const &c, const TubeArgs &a, hipStream_t stream)
 {
-    static DynamicLdsAllowance lds;
-    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_octseg_kernel<false, true>), (int)OctLds::kBytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((trm_octseg_kernel<false, true>), dim3(a.seg_grid), dim3(kWave * kORoles), OctLds::kBytes, stream, c, a);
-    return hipGetLastError();
+    return launch_oct<false, true>(c, a, stream, a.seg_grid);
 }
 
 }  // namespace trm

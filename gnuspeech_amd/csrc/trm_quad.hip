@@ -924,44 +924,45 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     }
 }
 
-// TRM_MIX_TU: trm_mix*.hip include this file again, for the tube kernel's mixed instance alone.  Outside these guards stays
+// The launch of one instance of the kernel as the including file names it (the instance files' launchers are calls of this): its
+// LDS is QuadLds<kSub>'s.
+template <bool kStream, int kSub, bool kSeg = false, bool kMix = false>
+static hipError_t launch_quad(const Const &c, const TubeArgs &a, hipStream_t stream, uint32_t grid)
+{
+    return launch_lds<trm_tube_kernel_q<kStream, kSub, kSeg, kMix>>(dim3(grid), dim3(kWave * kQRoles), QuadLds<kSub>::kBytes, stream, c, a);
+}
+
+// TRM_MIX_TU: the instance files (trm_kernels.h lists them) include this file again, for the tube kernel alone.  Outside these guards stays
 // ONLY what that kernel needs (constants, types, __device__ functions); every other __global__ kernel, __device__/__constant__
 // variable and host function goes inside them, or the second translation unit builds (and exports) another copy of it.
 #ifndef TRM_MIX_TU
 
 // `cus`: the device's compute units.  A batch of more workgroups than that runs the instance that fits two of them on
 // a CU (kSub = 1); up to one workgroup per CU the instance with two independent blocks per step (kSub = 2).
-template <bool kStream, int kSub, bool kSeg = false>
-static hipError_t launch_instance(const Const &c, const TubeArgs &a, hipStream_t stream, uint32_t grid)
-{
-    static DynamicLdsAllowance lds;
-    hipError_t e = lds.ensure(reinterpret_cast<const void *>(trm_tube_kernel_q<kStream, kSub, kSeg>), (int)QuadLds<kSub>::kBytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((trm_tube_kernel_q<kStream, kSub, kSeg>), dim3(grid), dim3(kWave * kQRoles), QuadLds<kSub>::kBytes, stream, c, a);
-    return hipGetLastError();
-}
-
-
 hipError_t launch_tube_quad(const Const &c, const TubeArgs &a, hipStream_t stream, int cus)
 {
     if (a.nvoices == 0) return hipSuccess;
-    uint32_t grid = (a.nvoices + kQV - 1) / kQV;
-    if (a.seg_periods && a.mix_map) return a.seg_grid ? launch_mix_seg_quad(c, a, a.seg_grid, stream) : hipSuccess;     // ... of one map entry
-    if (a.seg_periods) return launch_instance<true, 2, true>(c, a, stream, a.seg_grid);      // time split: 16 voices x one segment per workgroup
-    if (a.stream_state && a.mix_map && a.grp_clock) return a.mix_grid ? launch_grp_quad(c, a, stream) : hipSuccess;     // a grouped stream's step
-    if (a.stream_state && a.mix_map) return a.mix_grid ? launch_mix_quad(c, a, stream, 2) : hipSuccess;     // (streams: kSub = 2 only)
-    if (a.stream_state) return launch_instance<true, 2>(c, a, stream, grid);
+    const uint32_t grid = (a.nvoices + kQV - 1) / kQV;
+    const int mode = tube_mode(a);
+    switch (mode) {
+    case kModeMixedSegments: return a.seg_grid ? launch_mix_seg_quad(c, a, a.seg_grid, stream) : hipSuccess;     // ... of one map entry
+    case kModeSegments: return launch_quad<true, 2, true>(c, a, stream, a.seg_grid);      // time split: 16 voices x one segment per workgroup
+    case kModeGroupStream: return a.mix_grid ? launch_grp_quad(c, a, stream) : hipSuccess;     // a grouped stream's step
+    case kModeMixedStream: return a.mix_grid ? launch_mix_quad(c, a, stream, mode, 2) : hipSuccess;     // (streams: kSub = 2 only)
+    case kModeStream: return launch_quad<true, 2>(c, a, stream, grid);
+    default: break;
+    }
     // one-shot instances stage the control frames in a ring of four: frame p+3 replaces frame p-1 one step into period p,
     // and the coefficient waves' last lanes read frame p-1 three steps into period p-1 -- a period must hold three steps
     // of up to 8 samples (the caller runs trm_kernels.hip's kernel otherwise)
     // (a mixed launch: every set's control period; the host demotes the launch otherwise)
     if (c.controlPeriod < 24) return hipErrorInvalidValue;
-    if (a.mix_map) {
+    if (mode == kModeMixed) {
         if (a.mix_grid == 0) return hipSuccess;
-        return launch_mix_quad(c, a, stream, cus > 0 && a.mix_grid > (uint32_t)cus ? 1 : 2);
+        return launch_mix_quad(c, a, stream, mode, cus > 0 && a.mix_grid > (uint32_t)cus ? 1 : 2);
     }
-    if (cus > 0 && grid > (uint32_t)cus) return launch_instance<false, 1>(c, a, stream, grid);
-    return launch_instance<false, 2>(c, a, stream, grid);
+    if (cus > 0 && grid > (uint32_t)cus) return launch_quad<false, 1>(c, a, stream, grid);
+    return launch_quad<false, 2>(c, a, stream, grid);
 }
 
 int tube_quad_kernel_blocks_per_cu(int sub)
