@@ -71,7 +71,7 @@ EXPORTS = [
     "trm_events_count_frames", "trm_drift_seed_after", "trm_batch_generate_frames_device", "trm_batch_generate_frames_host",
     "trm_batch_set_kernel", "trm_batch_last_kernel", "trm_batch_last_downsample", "trm_batch_set_time_split", "trm_batch_last_time_split", "trm_batch_hint_frames",
     "trm_batch_set_split_warmup", "trm_batch_split_warmup", "trm_split_warm_periods", "trm_tube_set_split_warmup",
-    "trm_mixed_set_split_warmup", "trm_mixed_split_warmup",
+    "trm_mixed_set_split_warmup", "trm_mixed_split_warmup", "trm_mixed_set_split_form", "trm_mixed_split_form",
     "trm_batch_set_split_form", "trm_batch_split_form", "trm_tube_set_split_form",
     "trm_batch_kernel_time_ms", "trm_batch_set_timing", "trm_batch_noise_table", "trm_device_count", "trm_build_info", "trm_kernel_blocks_per_cu", "trm_kernel_blocks_per_cu_form",
     "trm_mixed_create", "trm_mixed_destroy", "trm_mixed_derived", "trm_mixed_samples_for_frames", "trm_mixed_synthesize_device",
@@ -201,6 +201,8 @@ def lib():
     L.trm_tube_set_split_form.argtypes = [vp, C.c_int]
     L.trm_mixed_set_split_warmup.argtypes = [vp, C.c_int]
     L.trm_mixed_split_warmup.argtypes = [vp]
+    L.trm_mixed_set_split_form.argtypes = [vp, C.c_int]
+    L.trm_mixed_split_form.argtypes = [vp]
     L.trm_batch_noise_table.argtypes = [vp, vp, C.c_size_t]
     L.trm_mixed_create.argtypes = [C.POINTER(TrmInputParams), C.c_size_t, C.c_int, C.POINTER(vp)]
     L.trm_mixed_destroy.argtypes = [vp]

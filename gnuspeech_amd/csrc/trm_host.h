@@ -186,8 +186,9 @@ struct SplitAsk {
     bool quadOk;                              // the four-lane segment form is admissible (the caller's policy)
     // the 64-voice and the 16-voice cut block by block where a hint told the lengths; null: every block of SplitSet's counts is P long
     const std::vector<SplitBlock> *cut64, *cut16;
-    // the eight-lane segment form was asked for (trm_batch_set_split_form) and is admissible: a named S runs in it; AUTO, where no
-    // form is named, prices every candidate in it too.  cut8: the 8-voice cut, as the other two.  (A mixed batch: false, null.)
+    // the eight-lane segment form was asked for (trm_batch_set_split_form, trm_mixed_set_split_form) and is admissible -- in a mixed
+    // batch for every set with voices --: a named S runs in it; AUTO, where no form is named, prices every candidate in it too.
+    // cut8: the 8-voice cut, as the other two.
     bool octOk = false;
     const std::vector<SplitBlock> *cut8 = nullptr;
 };
@@ -272,7 +273,8 @@ struct SetBatches {
 int check_set_begin(size_t nsets, const size_t *set_begin);
 
 // {set, first voice, end voice, 0} per workgroup of perWg voices (TubeArgs::mix_map; a split launch's caller writes the set's
-// warm-up into the fourth component: the 64-voice map's entries, or the 16-voice map's for four-lane segments)
+// warm-up into the fourth component: the 64-voice map's entries, the 16-voice map's for four-lane segments, the 8-voice map's
+// for eight-lane ones)
 void build_block_map(const size_t *set_begin, size_t nsets, size_t perWg, std::vector<uint4> &map);
 
 #pragma GCC visibility pop

@@ -86,7 +86,8 @@ struct TubeArgs {
     // map entry seg_map[w].y with the entry's own warm-up (its fourth component; seg_warm and seg_first are unused), so that
     // every voice's segments are those of its set's own batch; seg_phase rows are indexed by map entry * 64 + lane (pitch
     // 64 * seg_wg_per_seg, seg_wg_per_seg = the map's entries).  The four-lane form's (trm_mixqseg_kernel) is the same over
-    // the 16-voice map: 16 in place of 64.
+    // the 16-voice map: 16 in place of 64; the eight-lane form's (trm_octseg_kernel, the uniform segment instance itself) over the
+    // 8-voice map: 8.
     const uint4 *mix_map = nullptr;       // {set, first voice, end voice, the set's warm-up in control periods (time split; else 0)}
     ConstTable set_const = nullptr;
     uint32_t mix_grid = 0;                // workgroups of the launch = entries of mix_map
@@ -176,8 +177,9 @@ hipError_t launch_tube(const Const &c, const TubeArgs &a, hipStream_t stream);
 // three launchers above decide the mode (tube_mode), keep the early returns and refusals, and call these; none of them looks at
 // the TubeArgs' tables again.
 //   kModeMixed, kModeMixedStream    trm_mix.hip trm_mix_kernel, trm_mix_q.hip trm_mix_kernel_q; kModeMixed also trm_mix_o.hip trm_mix_kernel_o
-//   kModeMixedSegments              trm_mix_seg.hip trm_mixseg_kernel, trm_mix_seg_q.hip trm_mixqseg_kernel
-//   kModeSegments, eight lanes      trm_oct_seg.hip trm_octseg_kernel
+//   kModeMixedSegments              trm_mix_seg.hip trm_mixseg_kernel, trm_mix_seg_q.hip trm_mixqseg_kernel; eight lanes: the line below
+//   kModeSegments, eight lanes      trm_oct_seg.hip trm_octseg_kernel -- and kModeMixedSegments in that form: the SAME instance, which
+//                                   reads "mixed" from the launch (a.mix_map set) in its prologue (trm_oct.hip says why)
 //   kModeGroupStream                trm_grp_stream.hip trm_grpstream_kernel, trm_grp_stream_q.hip trm_grpstream_kernel_q
 // `mode`: kModeMixed or kModeMixedStream, the caller's tube_mode.  `grid` workgroups from a.wg_base.
 hipError_t launch_mix_wide(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream, int mode);
@@ -191,8 +193,10 @@ hipError_t launch_mix_quad(const Const &c, const TubeArgs &a, hipStream_t stream
 // indexed by map entry * 16 + the voice within the entry)
 hipError_t launch_mix_seg_quad(const Const &c, const TubeArgs &a, uint32_t grid, hipStream_t stream);
 hipError_t launch_mix_oct(const Const &c, const TubeArgs &a, hipStream_t stream);
-// The eight-lane form's time-split instance (trm_oct_seg.hip: trm_octseg_kernel; a.seg_periods set, no mix_map, an up-sampling
-// set): a.seg_grid workgroups of 8 voices x one segment, seg_phase rows of 8 * seg_wg_per_seg entries.  launch_tube_oct calls it.
+// The eight-lane form's time-split instance (trm_oct_seg.hip: trm_octseg_kernel; a.seg_periods set, up-sampling sets, no
+// tube_out): a.seg_grid workgroups of 8 voices x one segment, seg_phase rows of 8 * seg_wg_per_seg entries.  With a.mix_map set, a
+// mixed batch's: mix_map is then the 8-voice map, seg_map lists (segment, entry), seg_wg_per_seg = the map's entries, seg_phase rows
+// are indexed by map entry * 8 + the voice within the entry, and the warm-up is the entry's own.  launch_tube_oct calls it.
 hipError_t launch_seg_oct(const Const &c, const TubeArgs &a, hipStream_t stream);
 // Grouped streams (TubeArgs::grp_*): trm_grp_stream.hip and trm_grp_stream_q.hip compile the two streaming forms' mixed instances
 // once more with a clock per map entry (trm_grpstream_kernel, trm_grpstream_kernel_q); launch_tube / launch_tube_quad call these

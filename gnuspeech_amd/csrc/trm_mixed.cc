@@ -72,13 +72,15 @@ extern "C" {
 // so that every voice gets bit for bit what a trm_batch of its set computes with trm_batch_set_time_split(S) in the
 // form of the plan (trm_mixed_last_kernel) -- the boundaries depend on S and W alone, a voice's lane neighbours do not enter
 // its arithmetic.  The form is the one-voice-per-lane one (64-voice map entries) unless the caller NAMED the four-lane form
-// and every set with voices admits its segment instance (mixed_split_quad_ok): then the entries are the 16-voice map's.
+// and every set with voices admits its segment instance (mixed_split_quad_ok): then the entries are the 16-voice map's.  Or the
+// caller asked for eight-lane segments (trm_mixed_set_split_form) and every set with voices admits them (mixed_split_oct_ok):
+// then they are the 8-voice map's, wherever a trm_batch with the same two settings would run that form.
 struct trm_mixed {
     SetBatches sets;                         // (first: destroyed after the device buffers below)
     int kernel = TRM_KERNEL_AUTO;            // trm_mixed_set_kernel
     int lastKernel = TRM_KERNEL_AUTO;
     DevBuf<uint4> dMap;                      // {set, first voice, end voice, the set's warm-up (split launches; else 0)} per workgroup
-    DevBuf<uint4> dMap64;                    // a four-lane split launch: the 64-voice map of its whole-utterance fallback
+    DevBuf<uint4> dMap64;                    // a four- or eight-lane split launch: the 64-voice map of its whole-utterance fallback
     DevBuf<uint64_t> dTubeOff;               // down-sampling sets' voices: their tube-rate rows in dTube
     DevBuf<float> dTube;
     // the shape the three arrays above were built for (rebuilt when it changes: the device entry is pure stream work otherwise)
@@ -89,6 +91,7 @@ struct trm_mixed {
     // time split (trm_mixed_set_time_split): OFF unless asked for; TRM_TIME_SPLIT in the environment is not read here
     int splitSetting = TRM_TIME_SPLIT_OFF;
     int splitWarmup = TRM_SPLIT_WARMUP_DEFAULT;   // trm_mixed_set_split_warmup: the rule every set's warm-up is taken from (trm_warm.h)
+    int splitForm = TRM_KERNEL_AUTO;              // trm_mixed_set_split_form: AUTO, or OCT = eight-lane segments where every set with voices admits them
     uint32_t lastSplitPeriods = 0;          // what the last launch did (0: whole utterances)
     std::vector<uint32_t> lastWarm;          // ... and every set's warm-up in control periods then
     std::vector<uint32_t> hintFrames;        // trm_mixed_hint_frames / the host entries: every voice's length, for the launch that follows
@@ -210,6 +213,16 @@ int trm_mixed_set_split_warmup(trm_mixed *m, int rule)
 
 int trm_mixed_split_warmup(const trm_mixed *m) { return m ? m->splitWarmup : TRM_SPLIT_WARMUP_DEFAULT; }
 
+int trm_mixed_set_split_form(trm_mixed *m, int form)
+{
+    if (!m) return fail(TRM_EINVAL, "null handle");
+    if (form != TRM_KERNEL_AUTO && form != TRM_KERNEL_OCT) return fail(TRM_EINVAL, "split form: %d is neither TRM_KERNEL_AUTO nor TRM_KERNEL_OCT", form);
+    m->splitForm = form;
+    return TRM_OK;
+}
+
+int trm_mixed_split_form(const trm_mixed *m) { return m ? m->splitForm : TRM_KERNEL_AUTO; }
+
 int trm_mixed_last_time_split(const trm_mixed *m, uint32_t *periods, uint32_t *warm_periods, size_t nsets)
 {
     if (!m) return fail(TRM_EINVAL, "null handle");
@@ -264,10 +277,24 @@ static bool mixed_split_quad_ok(const trm_mixed *m, const size_t *set_begin, int
     return true;
 }
 
+// Whether a split launch may run in eight-lane segments: the caller asked for them (trm_mixed_set_split_form) and every set with
+// voices admits them by trm_batch's own rule (trm_batch_synthesize_device) -- it up-samples, within the lane forms' converter
+// ratio, with a control period of at least two of the kernel's steps.  One set that does not, and the launch is planned as if
+// the form had never been asked for.
+static bool mixed_split_oct_ok(const trm_mixed *m, const size_t *set_begin)
+{
+    if (m->splitForm != TRM_KERNEL_OCT) return false;
+    for (size_t s = 0; s < m->sets.size(); s++) {
+        const trm::Const &c = m->sets[s]->c;
+        if (set_begin[s + 1] > set_begin[s] && !(c.upsample && !quad_ratio_too_high(c) && c.controlPeriod >= 16)) return false;
+    }
+    return true;
+}
+
 // trm_mixed_synthesize_device in three parts: the plan, the shape, the launches.  The plan of the time split: one segment length
 // S (control periods) for all sets, every set's own warm-up by the batch's rule, planned (plan_split) over the 64-voice cut (the
 // one-voice-per-lane segments', and every split launch's whole-utterance fallback) and, where the four-lane segment form is
-// admissible, the 16-voice cut; block by block where a hint told the lengths.  `which`: the whole-utterance launch's form.
+// admissible, the 16-voice cut, where the eight-lane one is, the 8-voice cut; block by block where a hint told the lengths.  `which`: the whole-utterance launch's form.
 struct MixedPlan {
     uint32_t split = 0;                   // S; 0: whole utterances
     int segForm = TRM_KERNEL_WIDE;        // the segments' form
@@ -287,7 +314,7 @@ static int mixed_plan(const trm_mixed *m, const size_t *set_begin, uint32_t max_
     for (size_t s = 0; s < S; s++) {
         const size_t n = set_begin[s + 1] - set_begin[s];
         pl.warm[s] = trm::split_warm_periods(m->sets[s]->c, m->splitWarmup);
-        sets[s] = {(uint32_t)m->sets[s]->c.controlPeriod, pl.warm[s], (n + 63) / 64, (n + 15) / 16};
+        sets[s] = {(uint32_t)m->sets[s]->c.controlPeriod, pl.warm[s], (n + 63) / 64, (n + 15) / 16, (n + 7) / 8};
         if (n == 0 || pl.warm[s] != 0) continue;
         if (m->splitSetting > 0)
             return fail(TRM_ERANGE, "time split: the tube of parameter set %zu never forgets (loss factor %g %%)", s, m->sets[s]->params.lossFactor);
@@ -295,7 +322,8 @@ static int mixed_plan(const trm_mixed *m, const size_t *set_begin, uint32_t max_
     }
     if (!forgets) return TRM_OK;
     SplitAsk ask = {sets.data(), S, nvoices, max_nframes - 1, m->splitSetting, which, m->kernel, mixed_split_quad_ok(m, set_begin, which), nullptr, nullptr};
-    std::vector<SplitBlock> blocks16;
+    ask.octOk = mixed_split_oct_ok(m, set_begin);
+    std::vector<SplitBlock> blocks16, blocks8;
     if (pl.hinted) {
         hinted_blocks(set_begin, S, 64, m->hintFrames, max_nframes, pl.blocks);
         ask.cut64 = &pl.blocks;
@@ -303,11 +331,16 @@ static int mixed_plan(const trm_mixed *m, const size_t *set_begin, uint32_t max_
             hinted_blocks(set_begin, S, 16, m->hintFrames, max_nframes, blocks16);
             ask.cut16 = &blocks16;
         }
+        if (ask.octOk) {
+            hinted_blocks(set_begin, S, 8, m->hintFrames, max_nframes, blocks8);
+            ask.cut8 = &blocks8;
+        }
     }
     const SplitPlan sp = plan_split(m->sets[0], ask);
     pl.split = sp.periods;
     pl.segForm = sp.form;
     if (pl.split && pl.segForm == TRM_KERNEL_QUAD) pl.blocks.swap(blocks16);       // (the launch order: per entry of the segments' map)
+    if (pl.split && pl.segForm == TRM_KERNEL_OCT) pl.blocks.swap(blocks8);
     return TRM_OK;
 }
 
@@ -362,7 +395,7 @@ static int mixed_shape(trm_mixed *m, const size_t *set_begin, uint32_t max_nfram
     }
     if (map.size() > 0x7FFFFFFFull) return fail(TRM_ERANGE, "too many workgroups");
     m->hMap64.clear();
-    if (split && pl.segForm == TRM_KERNEL_QUAD) {
+    if (split && pl.segForm != TRM_KERNEL_WIDE) {       // (four- or eight-lane segments: the whole-utterance fallback's own map)
         build_block_map(set_begin, S, 64, m->hMap64);
         if ((rc = m->dMap64.reserve(m->hMap64.size()))) return rc;
         HIP_TRY(hipMemcpyAsync(m->dMap64.p, m->hMap64.data(), m->hMap64.size() * sizeof(uint4), hipMemcpyHostToDevice, stream));
@@ -399,7 +432,7 @@ static int mixed_launches(trm_mixed *m, const size_t *set_begin, trm::TubeArgs a
         // The pre-pass, set by set over its voice range (the oscillator's advance per period and the guard's floor are the
         // set's): its rows of seg_phase start at the set's first map entry, every set ORs into one gate word.  Then both
         // launches, of which the device runs one (TubeArgs::gate): the segments, or -- a frame of any voice below its set's
-        // floor -- whole utterances, over the same map or (four-lane segments) over the 64-voice one.
+        // floor -- whole utterances, over the same map or (four- and eight-lane segments) over the 64-voice one.
         uint32_t *gate = b0->dGate;
         HIP_TRY(trm::launch_split_clear(a.max_sample, (uint32_t)nvoices, gate, stream));
         size_t entry = 0;
@@ -417,8 +450,9 @@ static int mixed_launches(trm_mixed *m, const size_t *set_begin, trm::TubeArgs a
         sa.seg_phase = m->dSegPhase.p;
         sa.seg_map = m->dSegMap.p;
         sa.gate = gate; sa.gate_want = 0;
+        if (pl.segForm == TRM_KERNEL_OCT) sa.tube_out = nullptr;      // (every set with voices up-samples: mixed_split_oct_ok; the launcher refuses rows)
         HIP_TRY(launch_form(pl.segForm, b0, cb->c, sa, stream));
-        if (pl.segForm == TRM_KERNEL_QUAD) {
+        if (pl.segForm != TRM_KERNEL_WIDE) {
             a.mix_map = m->dMap64.p;
             a.mix_grid = m->map64Entries;
         }

@@ -13,7 +13,8 @@
 //   convert                lane = output time (rows of 32 outputs x 2 voices), two row pairs per block
 // One barrier per step of 8 tube samples.  At step i osc works on block i, mix on i-1, the coefficient waves and the two
 // scans on i-2, tube on i-4, convert on whatever is complete, metered.  No streaming instance (trm_quad.hip carries streams);
-// trm_oct_seg.hip builds the time-split instance (kSeg below).
+// trm_oct_seg.hip builds the time-split instance (kSeg below), which serves uniform and mixed batches alike: a mixed split is a
+// run-time property of that instance's launch, read in its prologue.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -119,10 +120,19 @@ __device__ __forceinline__ uint32_t seg_out_phase(uint32_t inc, uint32_t kBase, 
 // kSeg (trm_oct_seg.hip: trm_octseg_kernel): a TIME-SPLIT launch (trm_kernels.h, TubeArgs::seg_*) -- workgroup w runs one
 // segment of 8 voices from rest, a warm-up ahead, with the time bases of trm_quad.hip's segment instance: tube samples count
 // from the warm-up's first (nBase), converter outputs from the segment's first (kBase).  Up-sampling sets only (no tube_out).
+// The segment instance also runs the time split of a MIXED batch (trm_kernels.h, kModeMixedSegments: seg_periods with mix_map) --
+// as a property of the launch read at run time, A.mix_map != nullptr, not as an instance of its own: the library's kernel names
+// are a fixed list, and what a mixed launch changes is the prologue alone.  The workgroup then runs segment seg_map[w].x of map
+// entry seg_map[w].y: the constants of the entry's set (set_const), the entry's voice range, the set's own warm-up (the entry's
+// fourth component) and first segment length seg_first(seg_periods, warm-up).  All of it is wave-uniform and settled before the
+// first step: the step loops read C, vFirst / vEnd and the stretch's values and never ask which kind of launch gave them, so a
+// voice's arithmetic is that of a uniform segment launch of its own set.  A uniform launch is the special case entry == block
+// of voices, entry * 8 + vq == the voice (which is how both kinds index seg_phase).
 template <bool kMix = false, bool kSeg = false>
 __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Const Carg, const TubeArgs A)
 {
-    static_assert(!kSeg || !kMix, "the segment instance is a uniform launch's");
+    // (kMix is the one-shot mixed instance, trm_mix_kernel_o; a mixed time split is the segment instance with a mix_map: above)
+    static_assert(!kSeg || !kMix, "a mixed segment launch is the segment instance's run-time case, not an instance");
     if constexpr (kSeg) {
         if (A.gate && ((*A.gate != 0u) ? 1u : 0u) != A.gate_want) return;      // (two launches, the device runs one: TubeArgs::gate)
     }
@@ -164,13 +174,10 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     const int part = (lane >> 2) & 3;                                    // slot within the block
     const int slot = (upperHalf ? 4 : 0) + part;                         // slot within the step
     const int vq = role == 4 ? lane >> 3 : ((lane >> 4) & 1) * 4 + (lane & 3);      // voice within the workgroup
-    // mixed launch: the workgroup's parameter set (C read in place: a reference into the table) and voice range
-    const uint4 mix = kMix ? A.mix_map[blockIdx.x] : make_uint4(0u, 0u, 0u, 0u);
-    const Const &C = kMix ? *(const Const *)(A.set_const + mix.x) : Carg;
-    // time split: workgroup -> (segment, block of 8 voices)
+    // time split: workgroup -> (segment, block of 8 voices; a mixed launch: entry of the 8-voice map)
     uint32_t seg = 0, vblock = blockIdx.x;
     if constexpr (kSeg) {
-        if (A.seg_map) {                     // (the pairs with work first: trm_kernels.hip, trm_seg_map_kernel)
+        if (A.seg_map) {                     // (the pairs with work first: trm_kernels.hip, trm_seg_map_kernel; a mixed split always has the list)
             const uint2 m = A.seg_map[blockIdx.x];
             seg = m.x;
             vblock = m.y;
@@ -179,7 +186,18 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
             vblock = blockIdx.x - seg * A.seg_wg_per_seg;
         }
     }
-    const uint32_t vFirst = kMix ? mix.y : vblock * kOV, vEnd = kMix ? mix.z : A.nvoices;
+    // mixed launch: the workgroup's parameter set (C read in place: a reference into the table) and voice range.  The segment
+    // instance decides it here, once, from the launch's arguments (see above): everything below reads the values, not the kind.
+    const bool mixed = kMix || (kSeg && A.mix_map != nullptr);
+    uint4 mix = kMix ? A.mix_map[blockIdx.x] : make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (kSeg) {
+        if (mixed) mix = A.mix_map[vblock];
+    }
+    const Const &C = mixed ? *(const Const *)(A.set_const + mix.x) : Carg;
+    // (a mixed split: the set's own warm-up and with it the first segment's length; the boundaries are seg_begin's either way)
+    const uint32_t segWarm = (kSeg && mixed) ? mix.w : A.seg_warm;
+    const uint32_t segFirst = (kSeg && mixed) ? seg_first(A.seg_periods, mix.w) : A.seg_first;
+    const uint32_t vFirst = mixed ? mix.y : vblock * kOV, vEnd = mixed ? mix.z : A.nvoices;
     const uint32_t vRaw = vFirst + vq;
     const bool laneValid = vRaw < vEnd;
     const uint32_t v = laneValid ? vRaw : vEnd - 1;
@@ -192,12 +210,12 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     auto outputs_with_flush = [&](uint64_t ntube) { return (uint32_t)trm::outputs_with_flush(ntube, (uint32_t)C.padSize, inc); };      // (trm_span.h)
     uint32_t nfr = nfrAll, nfrMax = nfrMaxAll, segFrame0 = 0, nBase = 0, kBase = 0, noutSeg = 0;
     if constexpr (kSeg) {     // (trm_span.h; as trm_quad.hip's segment instance has them)
-        const SegStretch st = seg_stretch(nfrAll, seg, A.seg_first, A.seg_periods, A.seg_warm, CP, inc);
+        const SegStretch st = seg_stretch(nfrAll, seg, segFirst, A.seg_periods, segWarm, CP, inc);
         nfr = st.nfr;
         nfrMax = wave_max_u32(nfr);
         segFrame0 = st.segFrame0;                                                                            // (uniform)
         nBase = segFrame0 * CP;
-        kBase = (uint32_t)outputs_before((uint64_t)seg_begin(seg, A.seg_first, A.seg_periods) * CP, inc);   // (uniform)
+        kBase = (uint32_t)outputs_before((uint64_t)seg_begin(seg, segFirst, A.seg_periods) * CP, inc);   // (uniform)
         // outputs of this launch for this lane's voice: its own stretch; the voice's last segment runs to the utterance's end
         const uint32_t noutAll = nfrAll > 0 ? outputs_with_flush((uint64_t)(nfrAll - 1) * CP) : 0u;
         noutSeg = (nfr > 0 && laneValid) ? (st.segLast ? noutAll : st.segOutEnd) - kBase : 0u;
@@ -227,7 +245,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         const uint32_t sv = min(vFirst + ((uint32_t)lane >> 2 & 7u), vEnd - 1);
         stageNfr = min(A.nframes[sv], A.max_nframes);
         // (the segment instance: its own voice's stretch of the segment, from the warm-up's first frame)
-        if constexpr (kSeg) stageNfr = seg_stretch(stageNfr, seg, A.seg_first, A.seg_periods, A.seg_warm, CP, inc).nfr;
+        if constexpr (kSeg) stageNfr = seg_stretch(stageNfr, seg, segFirst, A.seg_periods, segWarm, CP, inc).nfr;
         if constexpr (kSeg) stageSrc = A.frames + (stageNfr > 0 ? (A.frame_offset[sv] + segFrame0) * 16 : 0) + (lane & 3) * 4;
         else stageSrc = A.frames + (stageNfr > 0 ? A.frame_offset[sv] * 16 : 0) + (lane & 3) * 4;
     }
@@ -340,9 +358,11 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         double P = 0.0;                                 // oscillator position at the start of the step
         if constexpr (kSeg) {
             // the position at the warm-up start: the advances between the warm-up starts of the segments so far
-            // (trm_phase_segment_kernel: written for the batch's voices only), summed and wrapped in order -- exact
+            // (trm_phase_segment_kernel: written for the batch's voices only), summed and wrapped in order -- exact.  Rows of 8
+            // entries per block of voices -- in a mixed launch per map entry, a set's voices are not block-aligned; in a uniform one
+            // this is the voice's index --, read by valid lanes alone
             if (laneValid) {
-                const double *ph = A.seg_phase + vRaw;
+                const double *ph = A.seg_phase + (size_t)vblock * kOV + vq;
                 const size_t pitch = (size_t)A.seg_wg_per_seg * kOV;
                 for (uint32_t q = 1; q <= seg; q++) P = osc_wrap(P + ph[q * pitch]);
             }
@@ -834,11 +854,14 @@ hipError_t launch_tube_oct(const Const &c, const TubeArgs &a, hipStream_t stream
     if (a.stream_state || c.controlPeriod < 2 * kOB) return hipErrorInvalidValue;     // (the caller picks trm_quad.hip's kernel for these)
     switch (tube_mode(a)) {
     // time split: 8 voices x one segment per workgroup (trm_oct_seg.hip); a uniform up-sampling launch's alone
-    case kModeSegments: return a.tube_out ? hipErrorInvalidValue : a.seg_grid ? launch_seg_oct(c, a, stream) : hipSuccess;
+    // ... and a mixed batch's, the same instance with a mix_map (one segment of one entry of the 8-voice map per workgroup; `c` is
+    // then the set with the shortest control period: the check above sees it)
+    case kModeSegments:
+    case kModeMixedSegments: return a.tube_out ? hipErrorInvalidValue : a.seg_grid ? launch_seg_oct(c, a, stream) : hipSuccess;
     // (a mixed launch: every set's control period; the host demotes the launch otherwise)
     case kModeMixed: return a.mix_grid == 0 ? hipSuccess : launch_mix_oct(c, a, stream);
     case kModeOneShot: return launch_oct<false>(c, a, stream, (a.nvoices + kOV - 1) / kOV);
-    default: return hipErrorInvalidValue;     // mixed segments (the stream modes: refused above)
+    default: return hipErrorInvalidValue;     // (the stream modes: refused above)
     }
 }
 

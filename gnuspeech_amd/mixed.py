@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import device as dv, layout
-from ._capi import KERNEL_NAMES, KERNELS, TIME_SPLITS, Handle, TrmInputParams, TrmIntonation, check, derived, lib, split_warmup_code, split_warmup_name
+from ._capi import KERNEL_NAMES, KERNELS, TIME_SPLITS, Handle, TrmInputParams, TrmIntonation, check, derived, lib, split_form_code, split_form_name, split_warmup_code, split_warmup_name
 from .layout import group_voices, group_voices_by_group  # noqa: F401
 from .mixed_stream import TRMGroupedStream, TRMMixedStream  # noqa: F401
 
@@ -280,3 +280,16 @@ class TRMMixedBatch(Handle):
     @property
     def split_warmup(self):
         return split_warmup_name(lib().trm_mixed_split_warmup(self._h))
+
+    def set_split_form(self, form):
+        """'auto' | 'oct': the form of a time split's segments (include/trm_c_api.h: trm_mixed_set_split_form).  'oct' runs
+        eight-lane segments (8 voices of a set per workgroup) where EVERY set with voices admits them -- up-sampling, at most four
+        outputs per tube sample, a control period of at least 16 tube samples -- and leaves the launch exactly as it is where one
+        does not.  Every voice then gets what a TRMBatch of its set computes with the same set_time_split and set_split_form;
+        last_kernel reports "oct"."""
+        check(lib().trm_mixed_set_split_form(self._h, split_form_code(form)))
+
+    @property
+    def split_form(self):
+        """'auto' | 'oct' (set_split_form)"""
+        return split_form_name(lib().trm_mixed_split_form(self._h))

@@ -478,7 +478,7 @@ uint32_t trm_split_warm_periods(const trm_input_params *params, int rule);
  * guard on narrow frication bands (whole utterances in the one-voice-per-lane form then), the hint and trm_batch_last_time_split
  * apply unchanged; trm_batch_last_kernel reports TRM_KERNEL_OCT for such a launch.
  * trm_batch_set_kernel(TRM_KERNEL_OCT) is unchanged: it names the form of WHOLE utterances, and with a segment length by name
- * it still runs one-voice-per-lane segments.  Mixed batches and streams have no such setting. */
+ * it still runs one-voice-per-lane segments.  Mixed batches: trm_mixed_set_split_form, below.  Streams have no such setting. */
 int  trm_batch_set_split_form(trm_batch *batch, int form);
 int  trm_batch_split_form(const trm_batch *batch);
 /* A ragged batch through the device-buffer entry: the library sees the lengths (d_nframes) only on the device, and AUTO then
@@ -569,8 +569,8 @@ int    trm_mixed_synthesize_host_int16(trm_mixed *m, const size_t *set_begin, co
  * time split on, TRM_KERNEL_QUAD also asks for four-lane segments (above); every other value leaves split launches in the
  * one-voice-per-lane form. */
 int    trm_mixed_set_kernel(trm_mixed *m, int kernel);
-/* The form the last launch was set up in: of its segments when it was split (TRM_KERNEL_WIDE or TRM_KERNEL_QUAD), else of its
- * whole utterances. */
+/* The form the last launch was set up in: of its segments when it was split (TRM_KERNEL_WIDE, TRM_KERNEL_QUAD or, with
+ * trm_mixed_set_split_form, TRM_KERNEL_OCT), else of its whole utterances. */
 int    trm_mixed_last_kernel(const trm_mixed *m);
 /* Time split of a mixed batch (see trm_batch_set_time_split): TRM_TIME_SPLIT_OFF (the default), TRM_TIME_SPLIT_AUTO (one
  * segment length for all sets, priced with trm_batch's launch-time model; whole utterances when that does not win by a tenth or
@@ -594,6 +594,25 @@ int    trm_mixed_last_time_split(const trm_mixed *m, uint32_t *periods, uint32_t
  * shape: the next launch uploads its block map again. */
 int    trm_mixed_set_split_warmup(trm_mixed *m, int rule);
 int    trm_mixed_split_warmup(const trm_mixed *m);
+/* The form of a mixed batch's time-split segments, opt-in (no default changes; no environment variable), as
+ * trm_batch_set_split_form:
+ *   TRM_KERNEL_AUTO (default)  today's rule, exactly: one voice per lane, or four lanes per voice where TRM_KERNEL_QUAD is named;
+ *   TRM_KERNEL_OCT             eight lanes per voice where admissible: a workgroup is one segment of 8 voices of one set, two
+ *                              workgroups share a CU (a few sentences per voice type).
+ * Anything else: TRM_EINVAL, the setting stays.  Eight-lane segments are ADMISSIBLE when EVERY set with voices admits them by
+ * trm_batch_set_split_form's rule: it up-samples, makes at most four outputs per tube sample, and its control period holds
+ * at least 16 tube samples (a 1 kHz control rate on Monet's tube qualifies, which the four-lane segments do not run).  One set
+ * with voices that does not, and the whole launch is planned and enqueued exactly as if this setter had never been called (the
+ * demotion rule; trm_mixed_set_kernel(TRM_KERNEL_QUAD) is then honoured as ever); an empty set does not count.  Where they are
+ * admissible: a segment length set by name (trm_mixed_set_time_split(periods)) runs eight-lane segments of that length,
+ * whatever trm_mixed_set_kernel says; TRM_TIME_SPLIT_AUTO with no form named (trm_mixed_set_kernel) prices every candidate
+ * length in the eight-lane form too, while its workgroups with work are at most two per CU, and takes the shortest predicted
+ * launch.  Every voice gets bit for bit what a trm_batch of its own set computes with trm_batch_set_time_split(S) and
+ * trm_batch_set_split_form(TRM_KERNEL_OCT), S as trm_mixed_last_time_split reports it; the warm-up rules, the guard on narrow
+ * frication bands (whole utterances in the one-voice-per-lane form then) and the hint apply unchanged;
+ * trm_mixed_last_kernel reports TRM_KERNEL_OCT for such a launch.  With the time split off (the default) the setting does nothing. */
+int    trm_mixed_set_split_form(trm_mixed *m, int form);
+int    trm_mixed_split_form(const trm_mixed *m);
 /* A host copy of every voice's length for the next trm_mixed_synthesize_device call, as trm_batch_hint_frames: the plan under
  * AUTO and the launch order of a split use it, the samples never depend on it; consumed by that call whether it succeeds or
  * fails.  The host-buffer entries pass it themselves. */
