@@ -495,10 +495,8 @@ __global__ __launch_bounds__(kWave *kRoles, 4) void trm_tube_kernel(const Const 
             Coefs K;
             K.td[0] = k0.x; K.td[1] = k0.y; K.td[2] = k0.z; K.td[3] = k0.w;
             K.td[4] = k1.x; K.td[5] = k1.y; K.td[6] = k1.z; K.onePlusK8 = k1.w;
-            K.k8a = fma_f(K.onePlusK8, mA10v, negMA10v); // C8 a10 = (1 + C8) a10 - a10 in one operation (C8 is near -1 when the mouth closes: no cancellation here)
             K.alphaU = k2.x; K.ntd1 = k2.y; K.bpBeta = k2.z; K.bpGamma = k2.w;
-            K.alphaLR = fma_f(-0.5f, K.alphaU, 1.0f);    // the three alphas sum to 2 (TRMTubeModel.m:733-736)
-            K.bpAlpha = fma_f(-0.5f, K.bpBeta, 0.25f);   // (1/2 - beta) / 2, TRMFilters.m:16 (the halving is exact: the same bits in one operation)
+            coefs_rebuild_packed(K, mA10v, negMA10v);    // k8a, alphaLR, bpAlpha (trm_lane.h)
             K.tap[0] = t0.x; K.tap[1] = t0.y; K.tap[2] = t0.z; K.tap[3] = t0.w;
             K.tap[4] = t1.x; K.tap[5] = t1.y; K.tap[6] = t1.z; K.tap[7] = t1.w;
             K.pad_ = 0.0f;

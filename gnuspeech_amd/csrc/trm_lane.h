@@ -500,6 +500,16 @@ TRM_HD Coefs coef_sample(const CoefTrack &T, const CT &C, int j)
     return K;
 }
 
+// The one-voice-per-lane kernel hands its tube wave onePlusK8, alphaU and bpBeta and not the three fields they determine:
+// those are rebuilt here, one operation each (mA10 / negMA10: the mouth filter's a10 and its negative, in the caller's
+// registers).  Not the bits coef_sample forms -- tests/_probe (probe 10) holds this form to the oracle by itself.
+TRM_HD void coefs_rebuild_packed(Coefs &K, float mA10, float negMA10)
+{
+    K.k8a = fma_f(K.onePlusK8, mA10, negMA10);   // C8 a10 = (1 + C8) a10 - a10 in one operation (C8 is near -1 when the mouth closes: no cancellation here)
+    K.alphaLR = fma_f(-0.5f, K.alphaU, 1.0f);    // the three alphas sum to 2 (TRMTubeModel.m:733-736)
+    K.bpAlpha = fma_f(-0.5f, K.bpBeta, 0.25f);   // (1/2 - beta) / 2, TRMFilters.m:16 (the halving is exact: the same bits in one operation)
+}
+
 // ================================================================ stage 3: the tube recurrences
 // Travelling-wave values of one sample (TRMTubeModel.m:161-165).  The reference double-buffers them
 // ([section][top|bottom][ping|pong]); here a step reads one Waves and writes another, so two

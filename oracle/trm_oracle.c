@@ -185,6 +185,7 @@ typedef struct {
     double wavetable[WT_LEN];
     int32_t tableDiv1, tableDiv2;
     double tnLength, tnDelta, basicIncrement, currentPosition;
+    double readPosition[2], readValue[2];       /* the sample's two table reads (what the state tap shows) */
     /* oscillator FIR (TRMFIRFilter.m) */
     double firData[2 * FIR_LIMIT + 1], firCoef[2 * FIR_LIMIT + 1];
     int32_t firPtr, numberTaps;
@@ -520,15 +521,23 @@ static double fir_filter(tube_t *t, double in, int need)
     return 0.0;
 }
 
+/* the interpolated table read of -oscillator: (TRMWavetable.m:183-190) at table position `position` */
+static double table_read(const tube_t *t, double position)
+{
+    int32_t lo = (int32_t)position;
+    int32_t up = (int32_t)mod0(lo + 1);
+    return t->wavetable[lo] + ((position - lo) * (t->wavetable[up] - t->wavetable[lo]));
+}
+
 /* TRMWavetable -oscillator: (TRMWavetable.m:174-195), OVERSAMPLING_OSCILLATOR 1 */
 static double oscillator(tube_t *t, double f)
 {
     double out = 0.0;
     for (int k = 0; k < 2; k++) {
         t->currentPosition = mod0(t->currentPosition + ((f / 2.0) * t->basicIncrement));
-        int32_t lo = (int32_t)t->currentPosition;
-        int32_t up = (int32_t)mod0(lo + 1);
-        double v = t->wavetable[lo] + ((t->currentPosition - lo) * (t->wavetable[up] - t->wavetable[lo]));
+        double v = table_read(t, t->currentPosition);
+        t->readPosition[k] = t->currentPosition;
+        t->readValue[k] = v;
         out = fir_filter(t, v, k == 1);
     }
     return out;
@@ -605,6 +614,72 @@ static double vocal_tract(tube_t *t, double input, double fric)
     return output;
 }
 
+/* source mixing (TRMTubeModel.m:315-341): from the amplitudes, the FIR's output and the low-passed noise to the tract's
+ * input, the noise signal the frication band-pass filters and the throat's input */
+static void source_mix(const tube_t *t, double ax, double ah1, double pulse, double lp_noise, double *gin, double *sig, double *thr)
+{
+    double pulsed_noise = lp_noise * pulse;                                     /* :315 */
+    pulse = ax * ((pulse * (1.0 - t->breathinessFactor)) + (pulsed_noise * t->breathinessFactor)); /* :318 */
+    double signal;
+    if (t->p->usesModulation) {                                                 /* :323-333 */
+        double crossmix = ax * t->crossmixFactor;
+        crossmix = (crossmix < 1.0) ? crossmix : 1.0;
+        signal = (pulsed_noise * crossmix) + (lp_noise * (1.0 - crossmix));
+    } else
+        signal = lp_noise;
+    *gin = (pulse + (ah1 * signal)) * VT_SCALE;                                 /* :336 */
+    *sig = signal;
+    *thr = pulse * VT_SCALE;                                                    /* :341 */
+}
+
+/* frication band-pass (TRMFilters.m:19-29) */
+static double bandpass_filter(tube_t *t, double signal)
+{
+    double bp = 2.0 * ((t->bpAlpha * (signal - t->xn2)) + (t->bpGamma * t->yn1) - (t->bpBeta * t->yn2));
+    t->xn2 = t->xn1; t->xn1 = signal; t->yn2 = t->yn1; t->yn1 = bp;
+    return bp;
+}
+
+/* throat low-pass (:341, TRMFilters.m:72-77) */
+static double throat_filter(tube_t *t, double in)
+{
+    double y = (t->ta0 * in) + (t->tb1 * t->throatY);
+    t->throatY = y;
+    return y;
+}
+
+/* one tube-rate sample from the excitation (:336-341): band-pass, tract, throat, their sum */
+static double tube_sample(tube_t *t, double gin, double sig, double thr, double *bp_out, double *throat_out)
+{
+    double bp = bandpass_filter(t, sig);
+    double signal = vocal_tract(t, gin, bp);                                    /* :336-337 */
+    double y = throat_filter(t, thr);
+    signal += y * t->throatGain;
+    if (bp_out) *bp_out = bp;
+    if (throat_out) *throat_out = y;
+    return signal;
+}
+
+/* The tube's recurrent state in the kernels' order (trm_oracle.h TRM_ORACLE_STATE): the travelling waves the NEXT step
+ * reads -- oropharynx top 1..10, bottom 1..10, nasal top 1..6, bottom 1..6 -- and the 11 filter memories. */
+static void state_get(const tube_t *t, double *s)
+{
+    const int c = t->cur;
+    for (int i = 0; i < N_SECTIONS; i++) { s[i] = t->oro[i][0][c]; s[10 + i] = t->oro[i][1][c]; }
+    for (int i = 0; i < N_NASAL; i++) { s[20 + i] = t->nas[i][0][c]; s[26 + i] = t->nas[i][1][c]; }
+    const double f[11] = {t->m_reflY, t->m_radX, t->m_radY, t->n_reflY, t->n_radX, t->n_radY, t->throatY, t->xn1, t->xn2, t->yn1, t->yn2};
+    for (int i = 0; i < 11; i++) s[32 + i] = f[i];
+}
+
+static void state_set(tube_t *t, const double *s)
+{
+    const int c = t->cur;
+    for (int i = 0; i < N_SECTIONS; i++) { t->oro[i][0][c] = s[i]; t->oro[i][1][c] = s[10 + i]; }
+    for (int i = 0; i < N_NASAL; i++) { t->nas[i][0][c] = s[20 + i]; t->nas[i][1][c] = s[26 + i]; }
+    t->m_reflY = s[32]; t->m_radX = s[33]; t->m_radY = s[34]; t->n_reflY = s[35]; t->n_radX = s[36]; t->n_radY = s[37];
+    t->throatY = s[38]; t->xn1 = s[39]; t->xn2 = s[40]; t->yn1 = s[41]; t->yn2 = s[42];
+}
+
 static void tube_push(tube_t *t, double v)
 {
     if (!t->keep_tube) return;
@@ -636,7 +711,11 @@ static void stage_copy(const tube_t *t, double *o)
     o[25] = t->bpAlpha; o[26] = t->bpBeta; o[27] = t->bpGamma;
 }
 
-typedef struct { int32_t sample; int seen; double *coefs, *table; } stage_tap;
+typedef struct {
+    int32_t sample; int seen; double *coefs, *table;
+    /* the state tap (trm_oracle_synthesize_states): ascending sample indices, one TRM_ORACLE_TAP record each */
+    const int32_t *samples; size_t nsamples, next; double *records;
+} stage_tap;
 
 static int synthesize_impl(const trm_input_params *p, const double *frames, size_t nframes,
                            int keep_tube_samples, trm_oracle_result *out, int tract, int32_t slice, stage_tap *tap)
@@ -675,26 +754,25 @@ static int synthesize_impl(const trm_input_params *p, const double *frames, size
                     tap->seen = 1;
                 }
                 t->ntube_run++;
-                double pulse = oscillator(t, f0);                               /* :312 */
-                double pulsed_noise = lp_noise * pulse;                         /* :315 */
-                pulse = ax * ((pulse * (1.0 - t->breathinessFactor)) + (pulsed_noise * t->breathinessFactor)); /* :318 */
-                double signal;
-                if (p->usesModulation) {                                        /* :323-333 */
-                    double crossmix = ax * t->crossmixFactor;
-                    crossmix = (crossmix < 1.0) ? crossmix : 1.0;
-                    signal = (pulsed_noise * crossmix) + (lp_noise * (1.0 - crossmix));
-                } else
-                    signal = lp_noise;
-                double bp;                                                      /* TRMFilters.m:19-29 */
-                {
-                    bp = 2.0 * ((t->bpAlpha * (signal - t->xn2)) + (t->bpGamma * t->yn1) - (t->bpBeta * t->yn2));
-                    t->xn2 = t->xn1; t->xn1 = signal; t->yn2 = t->yn1; t->yn1 = bp;
+                double *rec = NULL;                                             /* (the state tap: trm_oracle.h) */
+                if (tap && tap->records && tap->next < tap->nsamples && tap->samples[tap->next] == t->ntube_run - 1)
+                    rec = tap->records + TRM_ORACLE_TAP * tap->next++;
+                if (rec) {
+                    state_get(t, rec);
+                    memcpy(rec + 43, t->current, sizeof t->current);
+                    stage_copy(t, rec + 117);
                 }
-                signal = vocal_tract(t, (pulse + (ah1 * signal)) * VT_SCALE, bp); /* :336-337 */
-                {                                                               /* :341, TRMFilters.m:72-77 */
-                    double y = (t->ta0 * (pulse * VT_SCALE)) + (t->tb1 * t->throatY);
-                    t->throatY = y;
-                    signal += y * t->throatGain;
+                double pulse = oscillator(t, f0);                               /* :312 */
+                double gin, sig, thr, bp, ty;
+                source_mix(t, ax, ah1, pulse, lp_noise, &gin, &sig, &thr);      /* :315-333 */
+                double signal = tube_sample(t, gin, sig, thr, &bp, &ty);        /* :336-341 */
+                if (rec) {
+                    const double v[13] = {lp_noise, t->readPosition[0], t->readPosition[1], t->readValue[0], t->readValue[1], ax, ah1,
+                                          pulse, gin, sig, thr, bp, ty};
+                    memcpy(rec + 59, v, sizeof v);
+                    state_get(t, rec + 72);
+                    rec[115] = signal;
+                    rec[116] = f0;
                 }
                 if (tract) signal = signal * 100;                               /* tube.c:1177 */
                 tube_push(t, signal);
@@ -784,9 +862,90 @@ int trm_oracle_synthesize_tapped(const trm_input_params *p, const double *frames
                                  double *coefs, double *table, trm_oracle_result *out)
 {
     if (!coefs || !table || sample < 0) return TRM_EINVAL;
-    stage_tap tap = {sample, 0, coefs, table};
+    stage_tap tap = {sample, 0, coefs, table, NULL, 0, 0, NULL};
     int rc = synthesize_impl(p, frames, nframes, 1, out, 0, 0, &tap);
     if (!rc && !tap.seen) { trm_oracle_result_free(out); return TRM_EINVAL; }
+    return rc;
+}
+
+int trm_oracle_synthesize_states(const trm_input_params *p, const double *frames, size_t nframes, const int32_t *samples,
+                                 size_t nsamples, double *records, trm_oracle_result *out)
+{
+    if (!samples || !records || nsamples == 0) return TRM_EINVAL;
+    for (size_t i = 0; i < nsamples; i++)
+        if (samples[i] < 0 || (i && samples[i] <= samples[i - 1])) return TRM_EINVAL;
+    stage_tap tap = {-1, 1, NULL, NULL, samples, nsamples, 0, records};
+    int rc = synthesize_impl(p, frames, nframes, 1, out, 0, 0, &tap);
+    if (!rc && tap.next != nsamples) { trm_oracle_result_free(out); return TRM_EINVAL; }
+    return rc;
+}
+
+int trm_oracle_stage_constants(const trm_input_params *p, double *out)
+{
+    if (!p || !out) return TRM_EINVAL;
+    tube_t *t = (tube_t *)malloc(sizeof *t);
+    if (!t) return TRM_ENOMEM;
+    trm_derived d;
+    int rc = tube_init(t, p, &d);
+    if (!rc) {
+        const double v[TRM_ORACLE_STAGE_CONSTS] = {
+            t->dampingFactor, t->crossmixFactor, t->breathinessFactor, t->m_a10, t->m_b11, t->m_a20, t->m_a21, t->m_b21,
+            t->n_a10, t->n_b11, t->n_a20, t->n_a21, t->n_b21, t->ta0, t->tb1, t->throatGain,
+            t->nas_k[1], t->nas_k[2], t->nas_k[3], t->nas_k[4], t->nas_k[5], (double)t->sampleRate};
+        memcpy(out, v, sizeof v);
+    }
+    free(t);
+    return rc;
+}
+
+int trm_oracle_stage_steps(const trm_input_params *p, const double *states, const double *controls, const double *excitations,
+                           size_t n, double *out)
+{
+    if (!p || (n && (!states || !controls || !excitations || !out))) return TRM_EINVAL;
+    tube_t *t = (tube_t *)malloc(sizeof *t);
+    if (!t) return TRM_ENOMEM;
+    trm_derived d;
+    int rc = tube_init(t, p, &d);
+    for (size_t i = 0; i < n && !rc; i++) {
+        const double *e = excitations + 3 * i;
+        double *o = out + TRM_ORACLE_STEP_OUT * i;
+        set_control_rate(t, controls + 16 * i, controls + 16 * i);  /* current = the control values, delta 0 */
+        tube_coefficients(t);
+        frication_taps(t, 0);
+        bandpass_coefficients(t);
+        state_set(t, states + TRM_ORACLE_STATE * i);
+        o[TRM_ORACLE_STATE + 2] = tube_sample(t, e[0], e[1], e[2], o + TRM_ORACLE_STATE, o + TRM_ORACLE_STATE + 1);
+        state_get(t, o);
+    }
+    free(t);
+    return rc;
+}
+
+int trm_oracle_stage_mix(const trm_input_params *p, const double *in, size_t n, double *out)
+{
+    if (!p || (n && (!in || !out))) return TRM_EINVAL;
+    tube_t *t = (tube_t *)malloc(sizeof *t);
+    if (!t) return TRM_ENOMEM;
+    trm_derived d;
+    int rc = tube_init(t, p, &d);
+    for (size_t i = 0; i < n && !rc; i++)
+        source_mix(t, in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3], out + 3 * i, out + 3 * i + 1, out + 3 * i + 2);
+    free(t);
+    return rc;
+}
+
+int trm_oracle_stage_osc_reads(const trm_input_params *p, double amplitude, const double *positions, size_t n, double *out)
+{
+    if (!p || (n && (!positions || !out))) return TRM_EINVAL;
+    for (size_t i = 0; i < n; i++)
+        if (!(positions[i] > -1.0 && positions[i] <= (double)(WT_LEN - 1))) return TRM_EINVAL;     /* mod0()'s range */
+    tube_t *t = (tube_t *)malloc(sizeof *t);
+    if (!t) return TRM_ENOMEM;
+    trm_derived d;
+    int rc = tube_init(t, p, &d);
+    if (!rc && p->waveform == TRM_WAVEFORM_PULSE) wavetable_update(t, amplitude);
+    for (size_t i = 0; i < n && !rc; i++) out[i] = table_read(t, positions[i]);
+    free(t);
     return rc;
 }
 

@@ -85,6 +85,38 @@ int trm_oracle_stage_coefficients_n(const trm_input_params *params, const double
 int trm_oracle_synthesize_tapped(const trm_input_params *params, const double *frames, size_t nframes, int32_t sample,
                                  double *coefs, double *table, trm_oracle_result *out);
 
+/* Stage exports of the second half of the sample loop: source mixing, band-pass, tract, throat.  Like the ones above they
+ * fill a tube and call the statics the sample loop calls.
+ *   constants   what -initWithInputData: derives (TRMTubeModel.m:210-239, TRMFilters.m:34-45, :64-68, :692-707):
+ *               damping, crossmix, breathiness factors | mouth a10 b11 a20 a21 b21 | nose a10 b11 a20 a21 b21 |
+ *               ta0, tb1, throatGain | NC2..NC6 | the tube's sample rate
+ *   state       TRM_ORACLE_STATE doubles: the 32 travelling waves a step reads, in the kernels' order (oropharynx top 1..10,
+ *               bottom 1..10, nasal top 1..6, bottom 1..6), then the 11 filter memories: mouth reflection y, radiation x, y |
+ *               the nose's three | throat y | band-pass x1, x2, y1, y2
+ *   steps       item i: state, 16 control values (a frame's columns: the coefficients are formed from them as the loop forms
+ *               them) and the excitation (tract input, noise signal, throat input) -> TRM_ORACLE_STEP_OUT doubles:
+ *               the state after | band-pass output | throat output | the tube sample
+ *   mix         item i: (ax, ah1, the FIR's output, low-passed noise) -> (tract input, noise signal, throat input)
+ *   osc_reads   the interpolated table read of -oscillator: at table positions in (-1, 511], on the table -update: makes for
+ *               `amplitude` (the sine table for the sine waveform) */
+#define TRM_ORACLE_STAGE_CONSTS 22
+#define TRM_ORACLE_STATE 43
+#define TRM_ORACLE_STEP_OUT (TRM_ORACLE_STATE + 3)
+int trm_oracle_stage_constants(const trm_input_params *params, double *out);
+int trm_oracle_stage_steps(const trm_input_params *params, const double *states, const double *controls,
+                           const double *excitations, size_t n, double *out);
+int trm_oracle_stage_mix(const trm_input_params *params, const double *in, size_t n, double *out);
+int trm_oracle_stage_osc_reads(const trm_input_params *params, double amplitude, const double *positions, size_t n, double *out);
+/* trm_oracle_synthesize keeping the tube samples, which also records tube samples samples[0] < samples[1] < ...: one record
+ * of TRM_ORACLE_TAP doubles each,
+ *   [0, 43) state before the step | [43, 59) the 16 current control values | 59 low-passed noise | 60, 61 the oscillator's
+ *   two table positions | 62, 63 its two reads | 64 ax | 65 ah1 | 66 the FIR's output | 67..69 tract input, noise signal,
+ *   throat input | 70 band-pass output | 71 throat output | [72, 115) state after the step | 115 the tube sample |
+ *   116 the oscillator's frequency | [117, 145) the stage values (TRM_ORACLE_STAGE_COEFS, as above) */
+#define TRM_ORACLE_TAP 145
+int trm_oracle_synthesize_states(const trm_input_params *params, const double *frames, size_t nframes, const int32_t *samples,
+                                 size_t nsamples, double *records, trm_oracle_result *out);
+
 /* Output scaling (TRMTubeModel.m:370-389 file path, :515-533 WAV-data path):
  * interleaved int16 (host byte order) for `channels` channels. */
 void trm_oracle_scale_int16(const trm_input_params *params, const double *samples, int32_t n,

@@ -338,6 +338,123 @@ TRM_HD void probe_phase(int v, const Const &C, const float *frames, double *out)
     }
 }
 
+// ---------------------------------------------------------------- 9: the tube constants of build_const
+// out: every field of Const that tube_step, throat_filter and mix_tail read (the Const the kernels receive)
+constexpr int kTubeConstOut = 22;
+TRM_HD void probe_tube_const(const Const &C, float *o)
+{
+    o[0] = C.damping; o[1] = C.mCoeff; o[2] = C.nCoeff; o[3] = C.mA10; o[4] = C.nA10;
+    for (int k = 0; k < 4; k++) o[5 + k] = C.nasalTd[k];
+    o[9] = C.nasalK6a; o[10] = C.onePlusNK6; o[11] = C.ta0; o[12] = C.tb1; o[13] = C.throatGain;
+    o[14] = C.crossmixFactor; o[15] = C.breath;
+    for (int k = 0; k < 5; k++) o[16 + k] = C.nasalK[k];
+    o[21] = (float)C.sampleRate;
+}
+
+// ---------------------------------------------------------------- 10: one tube step
+// item: state[43] (the oracle's order, oracle/trm_oracle.h TRM_ORACLE_STATE: oT, oB, nT, nB | mReflY mRadX mRadY | the
+// nose's three | throatY | bpX1 bpX2 bpY1 bpY2), 16 control values (frame columns; 3..15 are read), excitation[3].
+// out: the state after in the same order, then the tube sample.
+//   variant 0   Coefs from coef_sample, tube_step<Const>                      (the four- and eight-lane kernels' reference form)
+//   variant 1   the one-voice-per-lane kernel's path: coefficients from a CoefConst, the throat section run outside
+//               (throat_filter, its mix wave), tube_step<TubeConst, true>
+//   variant 2   variant 1 with k8a, alphaLR, bpAlpha rebuilt from onePlusK8, alphaU, bpBeta (coefs_rebuild_packed: what that
+//               kernel's tube wave runs)
+constexpr int kStepState = 43, kStepCtl = 16, kStepOut = 44;
+template <int kVariant>
+TRM_HD void probe_step(int i, const Const &C, const float *state, const float *ctl, const float *exc, float *out)
+{
+    const float *s = state + (size_t)i * kStepState, *c = ctl + (size_t)i * kStepCtl, *e = exc + (size_t)i * 3;
+    Waves o, nw;
+    TubeFilters F;
+    for (int k = 0; k < 10; k++) { o.oT[k] = s[k]; o.oB[k] = s[10 + k]; }
+    for (int k = 0; k < 6; k++) { o.nT[k] = s[20 + k]; o.nB[k] = s[26 + k]; }
+    F.mReflY = s[32]; F.mRadX = s[33]; F.mRadY = s[34]; F.nReflY = s[35]; F.nRadX = s[36]; F.nRadY = s[37];
+    F.throatY = s[38]; F.bpX1 = s[39]; F.bpX2 = s[40]; F.bpY1 = s[41]; F.bpY2 = s[42];
+    CoefTrack T;
+    track_zero(T);
+    T.base[0] = c[3]; T.fricPos0 = c[4]; T.base[1] = c[5]; T.base[2] = c[6];
+    for (int k = 0; k < 9; k++) T.base[3 + k] = c[7 + k];
+    Excitation E;
+    E.gin = e[0]; E.sig = e[1]; E.thr = e[2];
+    float y;
+    if (kVariant == 0) {
+        const Coefs K = coef_sample(T, C, 0);
+        y = tube_step<Const>(o, nw, F, C, E, K);
+    } else {
+        CoefConst CC;
+        CC.damping = C.damping; CC.apScaleSq = C.apScaleSq; CC.mA10 = C.mA10; CC.noseR1sq = C.noseR1sq;
+        CC.invSampleRate = C.invSampleRate; CC.fricGain = C.fricGain;
+        Coefs K = coef_sample<false, CoefConst>(T, CC, 0);
+        if (kVariant == 2) coefs_rebuild_packed(K, C.mA10, -C.mA10);
+        TubeConst TC;
+        TC.damping = C.damping; TC.mCoeff = C.mCoeff; TC.nCoeff = C.nCoeff;
+        for (int k = 0; k < 4; k++) TC.nasalTd[k] = C.nasalTd[k];
+        TC.nasalK6a = C.nasalK6a; TC.onePlusNK6 = C.onePlusNK6; TC.ta0 = TC.tb1 = 0.0f; TC.throatGain = C.throatGain;
+        F.throatY = throat_filter(F.throatY, C.ta0, C.tb1, E.thr);
+        E.thr = F.throatY;
+        y = tube_step<TubeConst, true>(o, nw, F, TC, E, K);
+    }
+    float *q = out + (size_t)i * kStepOut;
+    for (int k = 0; k < 10; k++) { q[k] = nw.oT[k]; q[10 + k] = nw.oB[k]; }
+    for (int k = 0; k < 6; k++) { q[20 + k] = nw.nT[k]; q[26 + k] = nw.nB[k]; }
+    q[32] = F.mReflY; q[33] = F.mRadX; q[34] = F.mRadY; q[35] = F.nReflY; q[36] = F.nRadX; q[37] = F.nRadY;
+    q[38] = F.throatY; q[39] = F.bpX1; q[40] = F.bpX2; q[41] = F.bpY1; q[42] = F.bpY2;
+    q[43] = y;
+}
+
+// ---------------------------------------------------------------- 11: the source mix
+// FIR: item = one sequence of `steps` (wa, wb) pairs run through mix_sample from zero state.  out[step] = the FIR's output:
+// with ax = 1, ah1 = 0, no noise and a Const whose breathiness is 0 (the entry refuses another) mix_tail hands the FIR's
+// output on as thr = pulse / 8 exactly, whatever else it does; the probe undoes the power of two.
+TRM_HD void probe_fir(int i, const Const &C, const float *seq, int steps, float *out)
+{
+    FirState S;
+    for (int k = 0; k < 24; k++) S.fir[k] = 0.0f;
+    for (int n = 0; n < steps; n++) {
+        OscOut O;
+        O.wa = seq[((size_t)i * steps + n) * 2]; O.wb = seq[((size_t)i * steps + n) * 2 + 1];
+        O.ax = 1.0f; O.ah1 = 0.0f;
+        const Excitation E = mix_sample(S, C, C.fir, O, 0.0f);
+        out[(size_t)i * steps + n] = E.thr * 8.0f;
+    }
+}
+// mix_tail: item = (ax, ah1, pulse, lpNoise) -> (gin, sig, thr)
+TRM_HD void probe_mix_tail(int i, const Const &C, const float *in, float *out)
+{
+    const float *x = in + (size_t)i * 4;
+    const Excitation E = mix_tail(C, x[0], x[1], x[2], x[3]);
+    out[(size_t)i * 3] = E.gin; out[(size_t)i * 3 + 1] = E.sig; out[(size_t)i * 3 + 2] = E.thr;
+}
+
+// ---------------------------------------------------------------- 12: osc_read between entries
+// item = (amplitude a, position p): both of osc_read's reads at that position (they are the same statement: out[1] == out[0])
+TRM_HD void probe_osc_read(int i, const Const &C, const double *amp, const double *pos, int npos, float *out)
+{
+    const int a = i / npos, p = i % npos;
+    float wa, wb;
+    osc_read(C, amp[a], pos[p], pos[p], [](int k) { return sine_table(k); }, wa, wb);
+    out[(size_t)i * 2] = wa; out[(size_t)i * 2 + 1] = wb;
+}
+
+// ---------------------------------------------------------------- 13: the up-sampling converter
+// item = a 32-sample window and a 32-coefficient row: out[0] = src_dot over the first 26 of each, out[1] = src_dot32 over all
+TRM_HD void probe_src_dot(int i, const float *w, const float *c, float *out)
+{
+    out[(size_t)i * 2] = src_dot(w + (size_t)i * 32, c + (size_t)i * 32);
+    out[(size_t)i * 2 + 1] = src_dot32(w + (size_t)i * 32, c + (size_t)i * 32);
+}
+// item = (k, inc): src_phase, src_position;  item = (ntube, pad, inc): src_count_outputs
+TRM_HD void probe_src_clock(int i, const uint32_t *in, uint32_t *out)
+{
+    out[(size_t)i * 2] = src_phase(in[(size_t)i * 2], in[(size_t)i * 2 + 1]);
+    out[(size_t)i * 2 + 1] = src_position(in[(size_t)i * 2], in[(size_t)i * 2 + 1]);
+}
+TRM_HD void probe_src_count(int i, const uint64_t *in, uint64_t *out)
+{
+    out[i] = src_count_outputs(in[(size_t)i * 3], (uint32_t)in[(size_t)i * 3 + 1], (uint32_t)in[(size_t)i * 3 + 2]);
+}
+
 }  // namespace trm_probe
 
 // ---------------------------------------------------------------- the exported entries (both builds)
@@ -354,4 +471,18 @@ int trm_probe_held(const trm_input_params *p, int period, const float *prev, con
 int trm_probe_quad(const trm_input_params *p, int nwaves, unsigned seed, int poison_odd, int32_t *bad);
 int trm_probe_oct(const trm_input_params *p, int nwaves, unsigned seed, int poison_odd, int32_t *bad);
 int trm_probe_phase(const trm_input_params *p, const float *frames, int nvoices, double *out);
+int trm_probe_tube_const(const trm_input_params *p, int nsets, float *out);
+// exact != 0: the object built without the compiler's own a * b + c fusion (what the bit-for-bit claims hold in)
+int trm_probe_step(const trm_input_params *p, int variant, int exact, const float *state, const float *ctl, const float *exc, int n, float *out);
+int trm_probe_fir(const trm_input_params *p, const float *seq, int nseq, int steps, float *out);
+int trm_probe_mix_tail(const trm_input_params *p, const float *in, int n, float *out);
+int trm_probe_osc_read(const trm_input_params *p, const double *amp, int namp, const double *pos, int npos, float *out);
+int trm_probe_src_dot(const float *w, const float *c, int n, float *out);
+int trm_probe_src_clock(const uint32_t *in, int n, uint32_t *out);
+int trm_probe_src_count(const uint64_t *in, int n, uint64_t *out);
+// host build only: build_src_h's tables [3328] each, build_src_rows [65536 x 32], build_src_fine [3328 x 256]
+int trm_probe_src_tables(double *h, double *dh, float *rows, float *fine);
+// host build only: the reference's serial 16.16 time register and its ring protocol as integer loops (probe 13's references)
+int trm_probe_ref_clock(uint32_t inc, int n, uint32_t *phase, uint32_t *position);
+int trm_probe_ref_count(uint64_t ntube, uint32_t pad, uint32_t inc, uint64_t *count);
 }

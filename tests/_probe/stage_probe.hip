@@ -192,3 +192,157 @@ extern "C" int trm_probe_phase(const trm_input_params *p, const float *frames, i
     }
     return result(e, B);
 }
+
+// ---------------------------------------------------------------- probes 9 - 13
+__global__ void k_tube_const(Const C, float *out)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) probe_tube_const(C, out);
+}
+__global__ void k_fir(Const C, const float *seq, int n, int steps, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_fir(i, C, seq, steps, out);
+}
+__global__ void k_mix_tail(Const C, const float *in, int n, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_mix_tail(i, C, in, out);
+}
+__global__ void k_osc_read(Const C, const double *amp, const double *pos, int npos, int n, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_osc_read(i, C, amp, pos, npos, out);
+}
+__global__ void k_src_dot(const float *w, const float *c, int n, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_src_dot(i, w, c, out);
+}
+__global__ void k_src_clock(const uint32_t *in, int n, uint32_t *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_src_clock(i, in, out);
+}
+__global__ void k_src_count(const uint64_t *in, int n, uint64_t *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_src_count(i, in, out);
+}
+
+// one launch per parameter set: the set's Const arrives as the kernels' Const does, a kernel argument
+extern "C" int trm_probe_tube_const(const trm_input_params *p, int nsets, float *out)
+{
+    if (!p || nsets <= 0 || nsets > 4096) return (int)hipErrorInvalidValue;
+    DevBufs B;
+    float *dOut;
+    hipError_t e = B.get(&dOut, (size_t)nsets * kTubeConstOut);
+    for (int i = 0; i < nsets && e == hipSuccess; i++) {
+        Const C;
+        if (make_const(p + i, C)) e = hipErrorInvalidValue;
+        else {
+            k_tube_const<<<1, 64>>>(C, dOut + (size_t)i * kTubeConstOut);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = finish(out, dOut, (size_t)nsets * kTubeConstOut);
+    return result(e, B);
+}
+
+extern "C" int trm_probe_step_exact(const trm_input_params *p, int variant, const float *state, const float *ctl, const float *exc, int n, float *out);
+extern "C" int trm_probe_step(const trm_input_params *p, int variant, int exact, const float *state, const float *ctl, const float *exc, int n, float *out)
+{
+    return exact ? trm_probe_step_exact(p, variant, state, ctl, exc, n, out) : launch_step<0>(p, variant, state, ctl, exc, n, out);
+}
+
+extern "C" int trm_probe_fir(const trm_input_params *p, const float *seq, int nseq, int steps, float *out)
+{
+    Const C;
+    if (make_const(p, C) || C.breath != 0.0f || nseq <= 0 || steps <= 0 || nseq > kMaxItems / steps) return (int)hipErrorInvalidValue;
+    DevBufs B;
+    float *dIn, *dOut;
+    hipError_t e = B.put(&dIn, seq, (size_t)nseq * steps * 2);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)nseq * steps);
+    if (e == hipSuccess) {
+        k_fir<<<blocks_for(nseq), kBlock>>>(C, dIn, nseq, steps, dOut);
+        e = finish(out, dOut, (size_t)nseq * steps);
+    }
+    return result(e, B);
+}
+
+extern "C" int trm_probe_mix_tail(const trm_input_params *p, const float *in, int n, float *out)
+{
+    Const C;
+    if (make_const(p, C) || n <= 0 || n > kMaxItems) return (int)hipErrorInvalidValue;
+    DevBufs B;
+    float *dIn, *dOut;
+    hipError_t e = B.put(&dIn, in, (size_t)n * 4);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)n * 3);
+    if (e == hipSuccess) {
+        k_mix_tail<<<blocks_for(n), kBlock>>>(C, dIn, n, dOut);
+        e = finish(out, dOut, (size_t)n * 3);
+    }
+    return result(e, B);
+}
+
+extern "C" int trm_probe_osc_read(const trm_input_params *p, const double *amp, int namp, const double *pos, int npos, float *out)
+{
+    Const C;
+    if (make_const(p, C) || namp <= 0 || npos <= 0 || namp > kMaxItems / npos) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < npos; i++)
+        if (!(pos[i] > -1.0 && pos[i] <= 511.0)) return (int)hipErrorInvalidValue;      // osc_read's domain: what osc_wrap hands it
+    const int n = namp * npos;
+    DevBufs B;
+    double *dAmp, *dPos;
+    float *dOut;
+    hipError_t e = B.put(&dAmp, amp, (size_t)namp);
+    if (e == hipSuccess) e = B.put(&dPos, pos, (size_t)npos);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)n * 2);
+    if (e == hipSuccess) {
+        k_osc_read<<<blocks_for(n), kBlock>>>(C, dAmp, dPos, npos, n, dOut);
+        e = finish(out, dOut, (size_t)n * 2);
+    }
+    return result(e, B);
+}
+
+extern "C" int trm_probe_src_dot(const float *w, const float *c, int n, float *out)
+{
+    if (n <= 0 || n > kMaxItems) return (int)hipErrorInvalidValue;
+    DevBufs B;
+    float *dW, *dC, *dOut;
+    hipError_t e = B.put(&dW, w, (size_t)n * 32);
+    if (e == hipSuccess) e = B.put(&dC, c, (size_t)n * 32);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)n * 2);
+    if (e == hipSuccess) {
+        k_src_dot<<<blocks_for(n), kBlock>>>(dW, dC, n, dOut);
+        e = finish(out, dOut, (size_t)n * 2);
+    }
+    return result(e, B);
+}
+
+extern "C" int trm_probe_src_clock(const uint32_t *in, int n, uint32_t *out)
+{
+    if (n <= 0 || n > kMaxItems) return (int)hipErrorInvalidValue;
+    DevBufs B;
+    uint32_t *dIn, *dOut;
+    hipError_t e = B.put(&dIn, in, (size_t)n * 2);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)n * 2);
+    if (e == hipSuccess) {
+        k_src_clock<<<blocks_for(n), kBlock>>>(dIn, n, dOut);
+        e = finish(out, dOut, (size_t)n * 2);
+    }
+    return result(e, B);
+}
+
+extern "C" int trm_probe_src_count(const uint64_t *in, int n, uint64_t *out)
+{
+    if (n <= 0 || n > kMaxItems) return (int)hipErrorInvalidValue;
+    DevBufs B;
+    uint64_t *dIn, *dOut;
+    hipError_t e = B.put(&dIn, in, (size_t)n * 3);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)n);
+    if (e == hipSuccess) {
+        k_src_count<<<blocks_for(n), kBlock>>>(dIn, n, dOut);
+        e = finish(out, dOut, (size_t)n);
+    }
+    return result(e, B);
+}

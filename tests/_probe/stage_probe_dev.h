@@ -61,4 +61,35 @@ inline int result(hipError_t e, DevBufs &B)
 constexpr int kBlock = 256;
 inline unsigned blocks_for(int n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
+// Probe 10's kernel and launcher, instantiated once per object that builds them (kBuild: 0 stage_probe.hip, the product's
+// flags; 1 stage_probe_exact.hip, without the compiler's own fusion): distinct instances, so neither object's code stands in
+// for the other's.
+template <int kBuild, int kVariant>
+__global__ void k_step(Const C, const float *state, const float *ctl, const float *exc, int n, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_step<kVariant>(i, C, state, ctl, exc, out);
+}
+
+template <int kBuild>
+inline int launch_step(const trm_input_params *p, int variant, const float *state, const float *ctl, const float *exc, int n, float *out)
+{
+    Const C;
+    trm_derived d;
+    if (!p || build_const(*p, C, d) || n <= 0 || n > kMaxItems || variant < 0 || variant > 2) return (int)hipErrorInvalidValue;
+    DevBufs B;
+    float *dS, *dC, *dE, *dOut;
+    hipError_t e = B.put(&dS, state, (size_t)n * kStepState);
+    if (e == hipSuccess) e = B.put(&dC, ctl, (size_t)n * kStepCtl);
+    if (e == hipSuccess) e = B.put(&dE, exc, (size_t)n * 3);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)n * kStepOut);
+    if (e == hipSuccess) {
+        if (variant == 0) k_step<kBuild, 0><<<blocks_for(n), kBlock>>>(C, dS, dC, dE, n, dOut);
+        else if (variant == 1) k_step<kBuild, 1><<<blocks_for(n), kBlock>>>(C, dS, dC, dE, n, dOut);
+        else k_step<kBuild, 2><<<blocks_for(n), kBlock>>>(C, dS, dC, dE, n, dOut);
+        e = finish(out, dOut, (size_t)n * kStepOut);
+    }
+    return result(e, B);
+}
+
 }  // namespace trm_probe

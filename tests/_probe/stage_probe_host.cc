@@ -2,6 +2,8 @@
 // stand-ins (1.0f / x, exp2f, compare/select, fmaf; DPP as tests/_emul/trm_emul.cc emulates it: Q4 / O8), behind the
 // entries the device library exports.  Built with g++ -ffp-contract=off, as trm_emul.cc is; tests/test_stage_probe_model.py
 // runs it over the same grids against the same references, the stand-alone sanitizer sweep links it too.
+#include <string.h>
+
 #include "stage_probe.h"
 
 using namespace trm_probe;
@@ -107,5 +109,140 @@ extern "C" int trm_probe_phase(const trm_input_params *p, const float *frames, i
     if (make_const(p, C) || nvoices <= 0 || nvoices > 4096 || C.controlPeriod * kPhasePeriods < kPhaseSamples) return 1;
     C.waveform = 1;
     for (int v = 0; v < nvoices; v++) probe_phase(v, C, frames, out);
+    return 0;
+}
+
+extern "C" int trm_probe_tube_const(const trm_input_params *p, int nsets, float *out)
+{
+    if (!p || nsets <= 0 || nsets > kMaxItems) return 1;
+    for (int i = 0; i < nsets; i++) {
+        Const C;
+        if (make_const(p + i, C)) return 2 + i;         // (which set build_const refused)
+        probe_tube_const(C, out + (size_t)i * kTubeConstOut);
+    }
+    return 0;
+}
+
+// (one object, built without the compiler's own fusion: `exact` selects nothing here)
+extern "C" int trm_probe_step(const trm_input_params *p, int variant, int, const float *state, const float *ctl, const float *exc, int n, float *out)
+{
+    Const C;
+    if (make_const(p, C) || n <= 0 || n > kMaxItems || variant < 0 || variant > 2) return 1;
+    for (int i = 0; i < n; i++) {
+        if (variant == 0) probe_step<0>(i, C, state, ctl, exc, out);
+        else if (variant == 1) probe_step<1>(i, C, state, ctl, exc, out);
+        else probe_step<2>(i, C, state, ctl, exc, out);
+    }
+    return 0;
+}
+
+extern "C" int trm_probe_fir(const trm_input_params *p, const float *seq, int nseq, int steps, float *out)
+{
+    Const C;
+    if (make_const(p, C) || C.breath != 0.0f || nseq <= 0 || steps <= 0 || nseq > kMaxItems / steps) return 1;
+    for (int i = 0; i < nseq; i++) probe_fir(i, C, seq, steps, out);
+    return 0;
+}
+
+extern "C" int trm_probe_mix_tail(const trm_input_params *p, const float *in, int n, float *out)
+{
+    Const C;
+    if (make_const(p, C) || n <= 0 || n > kMaxItems) return 1;
+    for (int i = 0; i < n; i++) probe_mix_tail(i, C, in, out);
+    return 0;
+}
+
+extern "C" int trm_probe_osc_read(const trm_input_params *p, const double *amp, int namp, const double *pos, int npos, float *out)
+{
+    Const C;
+    if (make_const(p, C) || namp <= 0 || npos <= 0 || namp > kMaxItems / npos) return 1;
+    for (int i = 0; i < npos; i++)
+        if (!(pos[i] > -1.0 && pos[i] <= 511.0)) return 1;      // osc_read's domain: what osc_wrap hands it
+    for (int i = 0; i < namp * npos; i++) probe_osc_read(i, C, amp, pos, npos, out);
+    return 0;
+}
+
+extern "C" int trm_probe_src_dot(const float *w, const float *c, int n, float *out)
+{
+    if (n <= 0 || n > kMaxItems) return 1;
+    for (int i = 0; i < n; i++) probe_src_dot(i, w, c, out);
+    return 0;
+}
+
+extern "C" int trm_probe_src_clock(const uint32_t *in, int n, uint32_t *out)
+{
+    if (n <= 0 || n > kMaxItems) return 1;
+    for (int i = 0; i < n; i++) probe_src_clock(i, in, out);
+    return 0;
+}
+
+extern "C" int trm_probe_src_count(const uint64_t *in, int n, uint64_t *out)
+{
+    if (n <= 0 || n > kMaxItems) return 1;
+    for (int i = 0; i < n; i++) probe_src_count(i, in, out);
+    return 0;
+}
+
+extern "C" int trm_probe_src_tables(double *h, double *dh, float *rows, float *fine)
+{
+    std::vector<double> vh, vdh;
+    std::vector<float> vr, vf;
+    build_src_h(vh, vdh);
+    build_src_rows(vr);
+    build_src_fine(vf);
+    if (vh.size() != 3328 || vdh.size() != 3328 || vr.size() != (size_t)65536 * kSrcRowC || vf.size() != (size_t)kSrcFineLen) return 1;
+    memcpy(h, vh.data(), vh.size() * sizeof(double));
+    memcpy(dh, vdh.data(), vdh.size() * sizeof(double));
+    memcpy(rows, vr.data(), vr.size() * sizeof(float));
+    memcpy(fine, vf.data(), vf.size() * sizeof(float));
+    return 0;
+}
+
+// ---------------------------------------------------------------- probe 13's integer references (host build only)
+// The reference's converter bookkeeping ALONE, as it runs it: a 16.16 time register that is advanced by the increment,
+// hands its integer part to the read pointer and keeps its fraction (TRMSampleRateConverter.m:221-232, :290-293), inside
+// the ring's fill / empty / flush protocol (TRMRingBuffer.m:47-105).  Integers only, no closed form: what src_phase,
+// src_position and src_count_outputs (trm_lane.h) are held to.
+extern "C" int trm_probe_ref_clock(uint32_t inc, int n, uint32_t *phase, uint32_t *position)
+{
+    if (n <= 0) return 1;
+    uint32_t reg = 0, pos = 0;
+    for (int k = 0; k < n; k++) {
+        phase[k] = reg & 0xFFFFu;
+        position[k] = pos;
+        reg += inc;
+        pos += reg >> 16;
+        reg &= 0xFFFFu;
+    }
+    return 0;
+}
+
+extern "C" int trm_probe_ref_count(uint64_t ntube, uint32_t pad, uint32_t inc, uint64_t *count)
+{
+    const int32_t ring = 1024, fillSize = ring - 2 * (int32_t)pad;
+    if (fillSize < 1 || inc == 0) return 1;
+    int32_t fillPtr = (int32_t)pad, emptyPtr = 0, fillCounter = 0;
+    uint32_t reg = 0;
+    uint64_t nout = 0;
+    auto empty = [&]() {                                         // -processDataFromRingBuffer: without the arithmetic
+        int32_t endPtr = fillPtr - (int32_t)pad;
+        if (endPtr < 0) endPtr += ring;
+        if (endPtr < emptyPtr) endPtr += ring;
+        while (emptyPtr < endPtr) {
+            nout++;
+            reg += inc;
+            emptyPtr += (int32_t)(reg >> 16);
+            if (emptyPtr >= ring) { emptyPtr -= ring; endPtr -= ring; }
+            reg &= 0xFFFFu;
+        }
+    };
+    auto fill = [&]() {                                          // -dataFill:
+        if (++fillPtr >= ring) fillPtr -= ring;
+        if (++fillCounter >= fillSize) { empty(); fillCounter = 0; }
+    };
+    for (uint64_t i = 0; i < ntube; i++) fill();
+    for (uint32_t i = 0; i < 2 * pad; i++) fill();               // -flush
+    empty();
+    *count = nout;
     return 0;
 }

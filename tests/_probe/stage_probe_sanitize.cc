@@ -101,6 +101,91 @@ int main()
         std::vector<double> out((size_t)nv * kPhaseSamples * kPhaseOut);
         CHECK(trm_probe_phase(&p, fr.data(), nv, out.data()));
     }
+    // ---- probes 9 - 13
+    {
+        trm_input_params sets[3] = {p, p, p};
+        sets[1].mouthCoef = 400.0; sets[1].noseCoef = 9875.0; sets[1].breathiness = 100.0;
+        sets[2].lossFactor = 0.0; sets[2].throatCutoff = 9875.0; sets[2].mixOffset = 60.0;
+        std::vector<float> out(3 * kTubeConstOut);
+        CHECK(trm_probe_tube_const(sets, 3, out.data()));
+    }
+    for (int variant = 0; variant < 3; variant++) {
+        const int n = 9;
+        std::vector<float> state((size_t)n * kStepState), ctl((size_t)n * kStepCtl), exc((size_t)n * 3), out((size_t)n * kStepOut);
+        ProbeRng R{77u + (uint32_t)variant};
+        for (float &v : state) v = R.next();
+        for (float &v : exc) v = R.next();
+        for (int i = 0; i < n; i++) {
+            float *c = &ctl[(size_t)i * kStepCtl];
+            c[0] = -12.0f; c[1] = 60.0f; c[2] = 10.0f; c[3] = 7.5f * (float)i; c[4] = (float)i * 0.875f; c[5] = 500.0f + 1100.0f * (float)i;
+            c[6] = 20.0f + 1200.0f * (float)i;
+            for (int k = 0; k < 8; k++) c[7 + k] = (i + k) % 3 == 0 ? 0.001f : (i + k) % 3 == 1 ? 2.5f : 0.8f;
+            c[15] = i % 2 ? 0.0f : 0.3f * (float)i;
+        }
+        CHECK(trm_probe_step(&p, variant, 1, state.data(), ctl.data(), exc.data(), n, out.data()));
+        for (float v : out)
+            if (!(v == v)) { fprintf(stderr, "stage_probe_sanitize: step variant %d gives NaN\n", variant); return 1; }
+    }
+    {
+        trm_input_params q = p;
+        q.breathiness = 0.0;
+        const int nseq = 3, steps = 30;
+        std::vector<float> seq((size_t)nseq * steps * 2, 0.0f), out((size_t)nseq * steps);
+        seq[0] = 1.0f; seq[(size_t)steps * 2 + 1] = 1.0f;
+        for (int k = 0; k < steps * 2; k++) seq[(size_t)2 * steps * 2 + k] = (float)(k % 7) - 3.0f;
+        CHECK(trm_probe_fir(&q, seq.data(), nseq, steps, out.data()));
+        if (out[24] != 0.0f || out[0] == 0.0f || out[(size_t)steps + 24] == 0.0f || out[(size_t)steps + 25] != 0.0f) { fprintf(stderr, "stage_probe_sanitize: fir\n"); return 1; }
+        if (trm_probe_fir(&p, seq.data(), nseq, steps, out.data()) == 0) { fprintf(stderr, "stage_probe_sanitize: fir took a breathy set\n"); return 1; }
+    }
+    for (int mod = 0; mod < 2; mod++) {
+        trm_input_params q = p;
+        q.usesModulation = mod;
+        std::vector<float> in, out;
+        for (int a = 0; a < 5; a++)
+            for (int b = -2; b <= 2; b++) { in.push_back(0.25f * (float)a); in.push_back(0.1f * (float)a); in.push_back(0.5f * (float)b); in.push_back(-0.4f * (float)b); }
+        out.resize(in.size() / 4 * 3);
+        CHECK(trm_probe_mix_tail(&q, in.data(), (int)(in.size() / 4), out.data()));
+    }
+    for (int wf = 0; wf < 2; wf++) {
+        trm_input_params q = p;
+        q.waveform = wf;
+        std::vector<double> amp = {0.0, 0.37, 1.0};
+        std::vector<double> pos = {-0.999999999, -0.5, -9.3e-10, 0.0, 9.3e-10, 0.5, 204.25, 286.999999999, 510.999999999999, 511.0};
+        std::vector<float> out(amp.size() * pos.size() * 2);
+        CHECK(trm_probe_osc_read(&q, amp.data(), (int)amp.size(), pos.data(), (int)pos.size(), out.data()));
+        std::vector<double> outside = {511.5};
+        if (trm_probe_osc_read(&q, amp.data(), 1, outside.data(), 1, out.data()) == 0) { fprintf(stderr, "stage_probe_sanitize: osc_read took 511.5\n"); return 1; }
+    }
+    {
+        std::vector<double> h(3328), dh(3328);
+        std::vector<float> rows((size_t)65536 * 32), fine((size_t)3328 * 256);
+        CHECK(trm_probe_src_tables(h.data(), dh.data(), rows.data(), fine.data()));
+        const int n = 5;
+        const uint32_t phases[n] = {0u, 1u, 0x7FFFu, 0x8000u, 0xFFFFu};
+        std::vector<float> w((size_t)n * 32), c((size_t)n * 32, 0.0f), out((size_t)n * 2);
+        ProbeRng R{5u};
+        for (float &v : w) v = R.next();
+        for (int i = 0; i < n; i++)
+            for (int k = 0; k < 26; k++) c[(size_t)i * 32 + (i % 4) + k] = rows[(size_t)phases[i] * 32 + k];
+        CHECK(trm_probe_src_dot(w.data(), c.data(), n, out.data()));
+    }
+    {
+        const uint32_t incs[4] = {29350u, 65535u, 65536u, 1284874u};
+        std::vector<uint32_t> in, out;
+        for (uint32_t inc : incs)
+            for (uint32_t k : {0u, 1u, 65535u, 146336u, 4194303u}) { in.push_back(k); in.push_back(inc); }
+        out.resize(in.size());
+        CHECK(trm_probe_src_clock(in.data(), (int)(in.size() / 2), out.data()));
+        std::vector<uint64_t> cin = {0, 13, 29350, 79, 13, 29350, 2999, 490, 2467288, 1048577, 17, 80847}, cout(4);
+        CHECK(trm_probe_src_count(cin.data(), 4, cout.data()));
+        for (int i = 0; i < 4; i++) {
+            uint64_t want = 0;
+            CHECK(trm_probe_ref_count(cin[3 * i], (uint32_t)cin[3 * i + 1], (uint32_t)cin[3 * i + 2], &want));
+            if (want != cout[i]) { fprintf(stderr, "stage_probe_sanitize: count %d\n", i); return 1; }
+        }
+        std::vector<uint32_t> ph(4096), ps(4096);
+        CHECK(trm_probe_ref_clock(80847u, 4096, ph.data(), ps.data()));
+    }
     printf("stage_probe_sanitize: ok (instrumented)\n");
     return 0;
 }

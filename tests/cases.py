@@ -182,7 +182,8 @@ def isolated_path_cases():
     itself and not to a vowel 20-40 dB above it: frication alone at a tap, between taps, at the last tap and past it;
     aspiration alone; the nasal branch with the mouth closed; the throat alone; the pitch extremes (an oscillator increment
     below one table entry, and 4x the default); voicing from 0.5 dB; a glottal pulse that fills its table and a short one;
-    and a closure point that steps through every tie of rint(amplitude * tnDelta).  41 frames each, closure_sweep 81."""
+    a closure point that steps through every tie of rint(amplitude * tnDelta); and a voice whose mouth and nose filters differ
+    widely.  41 frames each, closure_sweep 81."""
     out = {}
     monet = monet_default_params(44100.0)
 
@@ -225,12 +226,18 @@ def isolated_path_cases():
     fr = tract(81)
     fr[:, 1] = np.linspace(30.0, 60.0, 81)
     out["closure_sweep"] = (tract_default_params(), fr)
+    # the two end filters far apart (the defaults have mouthCoef == noseCoef, where a swapped coefficient is invisible), both
+    # ends radiating: mouth open, velum 0.5
+    p = monet_default_params(44100.0); p["mouthCoef"] = 400.0; p["noseCoef"] = 9000.0
+    fr = base()
+    fr[:, 14] = 1.0; fr[:, 15] = 0.5
+    out["end_filters_apart"] = (p, fr)
     return out
 
 
 ISOLATED_PATH_NAMES = ["fric_only_pos%g" % p for p in FRIC_ONLY_POSITIONS] + [
     "fric_only_sweep", "asp_only", "nasal_only", "throat_only", "pitch_-24", "pitch_24", "quiet_voicing", "pulse_full_table",
-    "pulse_short", "closure_sweep"]
+    "pulse_short", "closure_sweep", "end_filters_apart"]
 
 
 # ---------------------------------------------------------------- TRAcT's own loop

@@ -113,8 +113,15 @@ def lib():
         L.trm_oracle_stage_coefficients.argtypes = [C.POINTER(InputParams), dp, C.c_int, dp]
         L.trm_oracle_stage_coefficients_n.argtypes = [C.POINTER(InputParams), dp, C.c_size_t, C.c_int, dp]
         L.trm_oracle_synthesize_tapped.argtypes = [C.POINTER(InputParams), dp, C.c_size_t, C.c_int32, dp, dp, C.POINTER(_Result)]
+        L.trm_oracle_stage_constants.argtypes = [C.POINTER(InputParams), dp]
+        L.trm_oracle_stage_steps.argtypes = [C.POINTER(InputParams), dp, dp, dp, C.c_size_t, dp]
+        L.trm_oracle_stage_mix.argtypes = [C.POINTER(InputParams), dp, C.c_size_t, dp]
+        L.trm_oracle_stage_osc_reads.argtypes = [C.POINTER(InputParams), C.c_double, dp, C.c_size_t, dp]
+        L.trm_oracle_synthesize_states.argtypes = [C.POINTER(InputParams), dp, C.c_size_t, C.POINTER(C.c_int32), C.c_size_t, dp,
+                                                   C.POINTER(_Result)]
         for f in (L.trm_oracle_stage_wavetable, L.trm_oracle_stage_wavetables, L.trm_oracle_stage_coefficients,
-                  L.trm_oracle_stage_coefficients_n, L.trm_oracle_synthesize_tapped):
+                  L.trm_oracle_stage_coefficients_n, L.trm_oracle_synthesize_tapped, L.trm_oracle_stage_constants,
+                  L.trm_oracle_stage_steps, L.trm_oracle_stage_mix, L.trm_oracle_stage_osc_reads, L.trm_oracle_synthesize_states):
             f.restype = C.c_int
         _lib = L
     return _lib
@@ -200,6 +207,72 @@ def synthesize_tapped(params, frames, sample):
     tube = np.ctypeslib.as_array(res.tubeSamples, shape=(nt,)).copy()
     lib().trm_oracle_result_free(C.byref(res))
     return coefs, table, tube
+
+
+STAGE_CONSTS = ("damping", "crossmix", "breath", "m_a10", "m_b11", "m_a20", "m_a21", "m_b21", "n_a10", "n_b11", "n_a20", "n_a21",
+                "n_b21", "ta0", "tb1", "throatGain", "nk2", "nk3", "nk4", "nk5", "nk6", "sampleRate")
+STATE, STEP_OUT, TAP = 43, 46, 145      # TRM_ORACLE_STATE, TRM_ORACLE_STEP_OUT, TRM_ORACLE_TAP (oracle/trm_oracle.h)
+# a tap record's parts
+T_BEFORE, T_CONTROLS, T_AFTER, T_COEFS = slice(0, 43), slice(43, 59), slice(72, 115), slice(117, 145)
+T_LPNOISE, T_POS, T_READS, T_AX, T_AH1, T_FIR, T_EXC, T_BP, T_THROAT, T_SAMPLE, T_F0 = 59, slice(60, 62), slice(62, 64), 64, 65, 66, slice(67, 70), 70, 71, 115, 116
+
+
+def stage_constants(params):
+    """What -initWithInputData: derives for a parameter set (oracle/trm_oracle.h): {name: value}."""
+    out = np.zeros(len(STAGE_CONSTS))
+    rc = lib().trm_oracle_stage_constants(C.byref(params), _dptr(out))
+    if rc != 0:
+        raise RuntimeError("trm_oracle_stage_constants rc=%d" % rc)
+    return dict(zip(STAGE_CONSTS, out))
+
+
+def stage_steps(params, states, controls, excitations):
+    """One tube step per item: states [n,43], control values [n,16], excitations [n,3] -> [n,46] (state after | band-pass
+    output | throat output | tube sample)."""
+    s = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, STATE)
+    c = np.ascontiguousarray(controls, dtype=np.float64).reshape(-1, 16)
+    e = np.ascontiguousarray(excitations, dtype=np.float64).reshape(-1, 3)
+    assert len(s) == len(c) == len(e)
+    out = np.zeros((len(s), STEP_OUT))
+    rc = lib().trm_oracle_stage_steps(C.byref(params), _dptr(s), _dptr(c), _dptr(e), len(s), _dptr(out))
+    if rc != 0:
+        raise RuntimeError("trm_oracle_stage_steps rc=%d" % rc)
+    return out
+
+
+def stage_mix(params, x):
+    """Source mixing per item: (ax, ah1, FIR output, low-passed noise) [n,4] -> (tract input, noise signal, throat input) [n,3]."""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 4)
+    out = np.zeros((len(x), 3))
+    rc = lib().trm_oracle_stage_mix(C.byref(params), _dptr(x), len(x), _dptr(out))
+    if rc != 0:
+        raise RuntimeError("trm_oracle_stage_mix rc=%d" % rc)
+    return out
+
+
+def stage_osc_reads(params, amplitude, positions):
+    """The oscillator's interpolated table read at every position in (-1, 511], on the table made for `amplitude`."""
+    pos = np.ascontiguousarray(np.atleast_1d(positions), dtype=np.float64)
+    out = np.zeros(len(pos))
+    rc = lib().trm_oracle_stage_osc_reads(C.byref(params), float(amplitude), _dptr(pos), len(pos), _dptr(out))
+    if rc != 0:
+        raise RuntimeError("trm_oracle_stage_osc_reads rc=%d" % rc)
+    return out
+
+
+def synthesize_states(params, frames, samples):
+    """synthesize(keep_tube=True) plus one tap record [TAP] per tube sample index of `samples` (ascending): (records, tube)."""
+    frames = np.ascontiguousarray(frames, dtype=np.float64).reshape(-1, 16)
+    idx = np.ascontiguousarray(samples, dtype=np.int32)
+    rec = np.zeros((len(idx), TAP))
+    res = _Result()
+    rc = lib().trm_oracle_synthesize_states(C.byref(params), _dptr(frames), frames.shape[0], idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            len(idx), _dptr(rec), C.byref(res))
+    if rc != 0:
+        raise RuntimeError("trm_oracle_synthesize_states rc=%d" % rc)
+    tube = np.ctypeslib.as_array(res.tubeSamples, shape=(res.numberTubeSamples,)).copy()
+    lib().trm_oracle_result_free(C.byref(res))
+    return rec, tube
 
 
 def derive(params):

@@ -55,6 +55,11 @@ def _sources(names):
                                                                                           "trm_setup.h", "trm_setup.cc")]
 
 
+# probe 9's fields, in probe_tube_const's order (stage_probe.h)
+TUBE_CONST = ("damping", "mCoeff", "nCoeff", "mA10", "nA10", "nasalTd0", "nasalTd1", "nasalTd2", "nasalTd3", "nasalK6a", "onePlusNK6",
+              "ta0", "tb1", "throatGain", "crossmixFactor", "breath", "nasalK0", "nasalK1", "nasalK2", "nasalK3", "nasalK4", "sampleRate")
+
+
 class Probe:
     """One build of the probe entries (stage_probe.h: the same names in both libraries)."""
 
@@ -73,6 +78,19 @@ class Probe:
         L.trm_probe_quad.argtypes = [pp, C.c_int, C.c_uint, C.c_int, ip]
         L.trm_probe_oct.argtypes = [pp, C.c_int, C.c_uint, C.c_int, ip]
         L.trm_probe_phase.argtypes = [pp, fp, C.c_int, dp]
+        up, qp = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        L.trm_probe_tube_const.argtypes = [pp, C.c_int, fp]
+        L.trm_probe_step.argtypes = [pp, C.c_int, C.c_int, fp, fp, fp, C.c_int, fp]
+        L.trm_probe_fir.argtypes = [pp, fp, C.c_int, C.c_int, fp]
+        L.trm_probe_mix_tail.argtypes = [pp, fp, C.c_int, fp]
+        L.trm_probe_osc_read.argtypes = [pp, dp, C.c_int, dp, C.c_int, fp]
+        L.trm_probe_src_dot.argtypes = [fp, fp, C.c_int, fp]
+        L.trm_probe_src_clock.argtypes = [up, C.c_int, up]
+        L.trm_probe_src_count.argtypes = [qp, C.c_int, qp]
+        if hasattr(L, "trm_probe_src_tables"):              # the host build's own: the tables and the integer references
+            L.trm_probe_src_tables.argtypes = [dp, dp, fp, fp]
+            L.trm_probe_ref_clock.argtypes = [C.c_uint32, C.c_int, up, up]
+            L.trm_probe_ref_count.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, qp]
 
     @staticmethod
     def _p(a, t):
@@ -142,6 +160,78 @@ class Probe:
         out = np.zeros((len(fr), 4096, 4))
         self._ok(self.L.trm_probe_phase(C.byref(O.InputParams.from_dict(pd)), self._p(fr, C.c_float), len(fr), self._p(out, C.c_double)), "phase")
         return out
+
+    def tube_const(self, pds):
+        arr = (O.InputParams * len(pds))(*[O.InputParams.from_dict(pd) for pd in pds])
+        out = np.zeros((len(pds), len(TUBE_CONST)), dtype=f32)
+        self._ok(self.L.trm_probe_tube_const(arr, len(pds), self._p(out, C.c_float)), "tube_const")
+        return out
+
+    def step(self, pd, variant, state, ctl, exc, exact=False):
+        state = np.ascontiguousarray(state, dtype=f32).reshape(-1, 43)
+        ctl = np.ascontiguousarray(ctl, dtype=f32).reshape(-1, 16)
+        exc = np.ascontiguousarray(exc, dtype=f32).reshape(-1, 3)
+        assert len(state) == len(ctl) == len(exc)
+        out = np.zeros((len(state), 44), dtype=f32)
+        self._ok(self.L.trm_probe_step(C.byref(O.InputParams.from_dict(pd)), variant, int(exact), self._p(state, C.c_float), self._p(ctl, C.c_float),
+                                       self._p(exc, C.c_float), len(state), self._p(out, C.c_float)), "step")
+        return out
+
+    def fir(self, pd, seq):
+        seq = np.ascontiguousarray(seq, dtype=f32)
+        assert seq.ndim == 3 and seq.shape[2] == 2
+        out = np.zeros(seq.shape[:2], dtype=f32)
+        self._ok(self.L.trm_probe_fir(C.byref(O.InputParams.from_dict(pd)), self._p(seq, C.c_float), seq.shape[0], seq.shape[1], self._p(out, C.c_float)), "fir")
+        return out
+
+    def mix_tail(self, pd, x):
+        x = np.ascontiguousarray(x, dtype=f32).reshape(-1, 4)
+        out = np.zeros((len(x), 3), dtype=f32)
+        self._ok(self.L.trm_probe_mix_tail(C.byref(O.InputParams.from_dict(pd)), self._p(x, C.c_float), len(x), self._p(out, C.c_float)), "mix_tail")
+        return out
+
+    def osc_read(self, pd, amps, pos):
+        amps, pos = np.ascontiguousarray(amps, dtype=np.float64), np.ascontiguousarray(pos, dtype=np.float64)
+        out = np.zeros((len(amps), len(pos), 2), dtype=f32)
+        self._ok(self.L.trm_probe_osc_read(C.byref(O.InputParams.from_dict(pd)), self._p(amps, C.c_double), len(amps), self._p(pos, C.c_double), len(pos),
+                                           self._p(out, C.c_float)), "osc_read")
+        return out
+
+    def src_dot(self, w, c):
+        w, c = np.ascontiguousarray(w, dtype=f32).reshape(-1, 32), np.ascontiguousarray(c, dtype=f32).reshape(-1, 32)
+        assert len(w) == len(c)
+        out = np.zeros((len(w), 2), dtype=f32)
+        self._ok(self.L.trm_probe_src_dot(self._p(w, C.c_float), self._p(c, C.c_float), len(w), self._p(out, C.c_float)), "src_dot")
+        return out
+
+    def src_clock(self, k, inc):
+        x = np.ascontiguousarray(np.stack([k, inc], axis=1), dtype=np.uint32)
+        out = np.zeros((len(x), 2), dtype=np.uint32)
+        self._ok(self.L.trm_probe_src_clock(self._p(x, C.c_uint32), len(x), self._p(out, C.c_uint32)), "src_clock")
+        return out
+
+    def src_count(self, ntube, pad, inc):
+        x = np.ascontiguousarray(np.stack([ntube, pad, inc], axis=1), dtype=np.uint64)
+        out = np.zeros(len(x), dtype=np.uint64)
+        self._ok(self.L.trm_probe_src_count(self._p(x, C.c_uint64), len(x), self._p(out, C.c_uint64)), "src_count")
+        return out
+
+    # ---- the host build's own
+    def src_tables(self):
+        h, dh = np.zeros(3328), np.zeros(3328)
+        rows, fine = np.zeros((65536, 32), dtype=f32), np.zeros(3328 * 256, dtype=f32)
+        self._ok(self.L.trm_probe_src_tables(self._p(h, C.c_double), self._p(dh, C.c_double), self._p(rows, C.c_float), self._p(fine, C.c_float)), "src_tables")
+        return h, dh, rows, fine
+
+    def ref_clock(self, inc, n):
+        ph, pos = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        self._ok(self.L.trm_probe_ref_clock(int(inc), n, self._p(ph, C.c_uint32), self._p(pos, C.c_uint32)), "ref_clock")
+        return ph, pos
+
+    def ref_count(self, ntube, pad, inc):
+        c = C.c_uint64()
+        self._ok(self.L.trm_probe_ref_count(int(ntube), int(pad), int(inc), C.byref(c)), "ref_count")
+        return c.value
 
 
 def host_probe():
@@ -672,3 +762,592 @@ def check_phase(P):
     assert np.all(e_cum <= n * (2 * PHASE_STEP + slack)), float((e_cum / n).max())
     return show(P, "phase", {"advance per sample": (float(e_adv.max()), 2 * PHASE_STEP), "first read": (float(e_half.max()), PHASE_STEP),
                              "position, sample 4096": (float(e_cum[:, -1].max()), 4096 * 2 * PHASE_STEP)})
+
+
+# ================================================================ 9: the tube constants of build_const
+EPS64 = 2.0 ** -53                 # fp64: relative half-ulp (the oracle's and build_const's own arithmetic)
+TINY = 2.0 ** -120                 # below the smallest normal float (2^-126) a result carries an ABSOLUTE error of that size
+                                   # (gradual underflow, or a flush to 0): the floor under every pointwise bar of probes 10 - 13
+
+
+def tube_const_sets(seed=23):
+    """(name, params): the defaults, the ranges of tests/test_gpu_parity.py test_random_voices_and_tracks, and each tube constant's
+    own parameter swept over its range with the others at Monet's defaults."""
+    sets = [("Monet", MONET), ("TRAcT", TRACT)]
+    rng = np.random.default_rng(seed)
+    for k in range(48):
+        pd = dict(cases.monet_default_params(float(rng.choice([22050.0, 44100.0]))))
+        pd.update(controlRate=float(rng.choice([100.0, 250.0, 500.0, 1000.0])), breathiness=float(rng.uniform(0, 10)),
+                  length=float(rng.uniform(11.0, 24.0)), temperature=float(rng.uniform(25, 40)), lossFactor=float(rng.uniform(0.1, 3.0)),
+                  apScale=float(rng.uniform(1.5, 5.0)), mouthCoef=float(rng.uniform(2000, 6000)), noseCoef=float(rng.uniform(2000, 6000)),
+                  noseRadius=[0.0] + [float(x) for x in rng.uniform(0.5, 2.5, 5)], throatCutoff=float(rng.uniform(500, 3000)),
+                  throatVol=float(rng.uniform(0, 24)), mixOffset=float(rng.uniform(30, 60)))
+        sets.append(("random %d" % k, pd))
+    nyq = 19750.0 / 2.0
+    for m, n in zip(np.linspace(100.0, nyq, 13), np.linspace(nyq, 100.0, 13)):
+        sets.append(("mouthCoef %g noseCoef %g" % (m, n), dict(MONET, mouthCoef=float(m), noseCoef=float(n))))
+    sets += [("throatCutoff %g" % t, dict(MONET, throatCutoff=float(t))) for t in np.geomspace(50.0, nyq, 9)]
+    sets += [("throatVol %g" % t, dict(MONET, throatVol=float(t))) for t in (0.0, 0.5, 24.0, 48.0, 60.0, 70.0)]
+    sets += [("lossFactor %g" % x, dict(MONET, lossFactor=float(x))) for x in (0.0, 0.01, 0.8, 2.5, 5.0)]
+    sets += [("mixOffset %g" % x, dict(MONET, mixOffset=float(x))) for x in (30.0, 41.5, 48.0, 54.0, 60.0)]
+    sets += [("breathiness %g" % x, dict(MONET, breathiness=float(x))) for x in (0.0, 0.5, 100.0)]
+    sets += [("length %g" % x, dict(MONET, length=float(x))) for x in (10.0, 12.5, 15.0, 20.0, 25.0, 30.0)]
+    return sets
+
+
+def tube_const_reference(pd):
+    """name -> (the oracle's double value, relative bar).  A field that is one double rounded to float: U.  A field that COMBINES
+    the oracle's values -- (1 + k) d, 1 + k, k a10 -- is formed by build_const in double without the cancellation of 1 + k, so
+    its bar is U plus the double roundings of the oracle's own 1 + k, 4 EPS64 / (1 + k), and of the product."""
+    c = O.stage_constants(O.InputParams.from_dict(pd))
+    # the reference's two end filters have ONE coefficient each (TRMFilters.m:34-45): what tube_step's form rests on
+    for e in "mn":
+        assert c[e + "_b11"] == -c[e + "_a20"] and c[e + "_a21"] == -c[e + "_a20"] and c[e + "_b21"] == -c[e + "_a20"]
+        assert c[e + "_a10"] == 1.0 - abs(c[e + "_a20"])
+    nk = [c["nk%d" % i] for i in range(2, 7)]
+    ref = {"damping": (c["damping"], U), "mCoeff": (c["m_a20"], U), "nCoeff": (c["n_a20"], U), "mA10": (c["m_a10"], U), "nA10": (c["n_a10"], U),
+           "ta0": (c["ta0"], U), "tb1": (c["tb1"], U), "throatGain": (c["throatGain"], U), "crossmixFactor": (c["crossmix"], U),
+           "breath": (c["breath"], U), "sampleRate": (c["sampleRate"], 0.0)}
+    for i in range(4):
+        ref["nasalTd%d" % i] = ((1.0 + nk[i]) * c["damping"], U + (4.0 / (1.0 + nk[i]) + 2.0) * EPS64)
+    for i in range(5):
+        ref["nasalK%d" % i] = (nk[i], U)
+    ref["onePlusNK6"] = (1.0 + nk[4], U + 4.0 / (1.0 + nk[4]) * EPS64)
+    ref["nasalK6a"] = (nk[4] * c["n_a10"], U + 2.0 * EPS64)
+    return ref
+
+
+def check_tube_const(P):
+    sets = tube_const_sets()
+    got = P.tube_const([pd for _, pd in sets]).astype(np.float64)
+    rep = {}
+    for (name, pd), row in zip(sets, got):
+        ref = tube_const_reference(pd)
+        for k, field in enumerate(TUBE_CONST):
+            want, bar = ref[field]
+            r = float(_rel(row[k], want))
+            assert r <= bar, "build_const %s (%s, %s): %r against %r, relative %.3e > %.3e" % (field, name, P.label, row[k], want, r, bar)
+            key = field.rstrip("0123456789") + ", relative"
+            rep[key] = (max(r, rep.get(key, (0.0, bar))[0]), max(bar, rep.get(key, (0.0, bar))[1]))
+    # the sweep reaches the ends it names: a coefficient of 0 (cut-off at Nyquist), a throat that passes everything, no loss
+    flat = {f: got[:, k] for k, f in enumerate(TUBE_CONST)}
+    assert np.any(flat["mCoeff"] == 0.0) and np.any(flat["nCoeff"] == 0.0) and np.any(flat["tb1"] == 0.0) and np.any(flat["damping"] == 1.0)
+    assert np.any(flat["breath"] == 1.0) and np.any(flat["breath"] == 0.0) and np.any(flat["crossmixFactor"] == 1.0) and np.any(flat["throatGain"] == 1.0)
+    assert np.any(np.abs(flat["mCoeff"] - flat["nCoeff"]) > 0.9)
+    worst = max(w for w, _ in rep.values())
+    return show(P, "tube const", dict(rep, **{"all fields, relative": (worst, max(b for _, b in rep.values()))}))
+
+
+# ================================================================ 10: one tube step
+# state order (oracle/trm_oracle.h TRM_ORACLE_STATE, stage_probe.h probe_step)
+S_OT, S_OB, S_NT, S_NB = 0, 10, 20, 26
+S_MREFL, S_MRADX, S_MRADY, S_NREFL, S_NRADX, S_NRADY, S_THROAT, S_BPX1, S_BPX2, S_BPY1, S_BPY2, S_OUT = range(32, 44)
+STEP_VARIANTS = ((0, "tube_step<Const>"), (1, "<TubeConst,true> + throat_filter"), (2, "... with rebuilt k8a, alphaLR, bpAlpha"))
+SECOND_ORDER = 1.0 + 2.0 ** -10    # the bars below are first-order in U: products of two errors are 2^-24 of a bar
+
+
+def _lin(roundings, *terms):
+    """The bar of a short sum of products sum(c_i x_i) evaluated in fp32, counted UNFUSED (the compiler may fuse a * b + c
+    either way; the unfused count bounds both): `roundings` rounded operations, each at most U of sum |c_i x_i|; a coefficient
+    known to dc_i (absolute) moves its term by |x_i| dc_i, an operand known to dx_i by |c_i| dx_i.  terms: (c, dc, x, dx)."""
+    s = sum(np.abs(c * x) for c, _, x, _ in terms)
+    return roundings * U * s + sum(np.abs(x) * dc + np.abs(c) * dx for c, dc, x, dx in terms)
+
+
+def step_voices():
+    """(name, params, frames): the voices whose states the step is probed at -- every golden case, four path-isolating voices,
+    three seeds of the random generator: onsets, steady vowels, frication, aspiration, the nasal branch, both waveforms."""
+    out = [(n, pd, fr) for n, (pd, fr) in cases.golden_cases().items()]
+    iso = cases.isolated_path_cases()
+    out += [(n,) + tuple(iso[n]) for n in ("nasal_only", "fric_only_pos0.5", "asp_only", "throat_only")]
+    out += [(n, pd, fr) for n, (pd, fr) in cases.random_track_cases().items()]
+    return out
+
+
+STEP_SAMPLES_PER_VOICE = 64
+_step_items = {}
+
+
+def step_items():
+    """[(name, params, state f32 [n,43], controls f32 [n,16], excitation f32 [n,3])]: 16 voices x 64 samples from the oracle's
+    state tap (the first 16 samples of the utterance -- the onset --, then spread over all of it), and 4096 synthetic states for
+    a parameter set whose two end filters differ widely.  Everything is rounded to fp32 here; the oracle step gets these values."""
+    if "v" in _step_items:
+        return _step_items["v"]
+    items = []
+    for name, pd, fr in step_voices():
+        ip = O.InputParams.from_dict(pd)
+        _, d = O.derive(ip)
+        nt = (len(fr) - 1) * d["controlPeriod"]
+        idx = np.unique(np.concatenate([np.arange(16), np.linspace(16, nt - 1, STEP_SAMPLES_PER_VOICE - 16).astype(int)])).astype(np.int32)
+        rec, _ = O.synthesize_states(ip, np.asarray(fr, dtype=f32).astype(np.float64), idx)
+        items.append((name, pd, rec[:, O.T_BEFORE].astype(f32), rec[:, O.T_CONTROLS].astype(f32), rec[:, O.T_EXC].astype(f32)))
+    assert len(items) == 16
+    items.append(("synthetic",) + step_synthetic())
+    _step_items["v"] = items
+    return items
+
+
+STEP_PARAMS = dict(MONET, mouthCoef=400.0, noseCoef=9000.0, lossFactor=1.5, throatVol=18.0, throatCutoff=900.0)
+
+
+def step_synthetic(n=4096, seed=29):
+    """Random waves and memories in [-1, 1], random legal control values: radii log-uniform in [0.001, 2.5] with, in a quarter of
+    the items, a radius of 0.001 beside one of 2.5 (k -> -1 and +1), a closed velum in a quarter, frication at integer positions in
+    a quarter and at fractional ones elsewhere, any centre frequency and any bandwidth the band-pass is stable at."""
+    rng = np.random.default_rng(seed)
+    state = rng.uniform(-1.0, 1.0, size=(n, 43))
+    ctl = np.zeros((n, 16))
+    ctl[:, 0] = rng.uniform(-10, 6, n)
+    ctl[:, 1] = rng.uniform(0, 60, n)
+    ctl[:, 2] = rng.uniform(0, 20, n)
+    ctl[:, 3] = rng.choice([0.0, 12.0, 30.0, 47.5, 60.0], n) + rng.uniform(0, 1, n) * (rng.random(n) < 0.5)
+    ctl[:, 4] = np.where(rng.random(n) < 0.25, rng.integers(0, 8, n).astype(np.float64), rng.uniform(0.0, 8.0, n))
+    ctl[:, 5] = rng.uniform(100.0, 9875.0, n)
+    ctl[:, 6] = np.exp(rng.uniform(np.log(20.0), np.log(9800.0), n))
+    ctl[:, 7:15] = np.exp(rng.uniform(np.log(1e-3), np.log(2.5), size=(n, 8)))
+    for i in np.nonzero(rng.random(n) < 0.25)[0]:
+        j = int(rng.integers(0, 7))
+        ctl[i, 7 + j], ctl[i, 8 + j] = (1e-3, 2.5) if rng.random() < 0.5 else (2.5, 1e-3)
+    ctl[:, 15] = np.where(rng.random(n) < 0.25, 0.0, rng.uniform(0.0, 1.5, n))
+    exc = rng.uniform(-1.0, 1.0, size=(n, 3))
+    return STEP_PARAMS, state.astype(f32), ctl.astype(f32), exc.astype(f32)
+
+
+def step_bars(pd, variant, state, ctl, exc, ref):
+    """Pointwise bars [n,44] of probe_step's outputs, derived from the expressions of tube_step (trm_lane.h) as written:
+    every output is a short sum of products and gets _lin's bar -- its own rounded operations, the derived bar of every
+    coefficient it multiplies by (probes 4, 5 and 9: AREA_*_BAR, AMP_REL, bandpass_bars, U for a constant), and the bars of the
+    values of this step it is formed from (the band-pass output under every tap, the junction's top wave under its bottom wave,
+    the reflection under oB[9], ...).  Magnitudes are the oracle's: its coefficients for the item's control values, the item's
+    state, its outputs `ref`.  variant 2: k8a, alphaLR and bpAlpha by coefs_rebuild_packed's one operation each."""
+    ip = O.InputParams.from_dict(pd)
+    c = O.stage_constants(ip)
+    s, x, e = state.astype(np.float64), ctl.astype(np.float64), exc.astype(np.float64)
+    co = O.stage_coefficients(ip, x)
+    assert np.all(np.isfinite(co))
+    k, nk, al, fc, bp = co[:, O.ST_C], co[:, O.ST_NC], co[:, O.ST_ALPHA], co[:, O.ST_FC], co[:, O.ST_BP]
+    d, a10 = c["damping"], c["m_a10"]
+    dd = U * d
+    # ---- the coefficients and what the earlier probes allow them (absolute)
+    td = (1.0 + k[:, :7]) * d
+    dtd = (AREA_TD_BAR + U) * td                       # AREA_TD_BAR is relative to (1 + k) times the FLOAT damping: its U
+    ntd = (1.0 + nk[:, :5]) * d
+    dntd = np.concatenate([(AREA_TD_BAR + U) * ntd[:, :1], (U + (4.0 / (1.0 + nk[:, 1:5]) + 2.0) * EPS64) * ntd[:, 1:]], axis=1)
+    one8, k8 = 1.0 + k[:, 7], k[:, 7]
+    done8 = AREA_ONE_BAR * one8
+    k8a = k8 * a10
+    aLR, aU = al[:, 0], al[:, 2]
+    daU = AREA_ALPHA_BAR * aU
+    fbx = np.stack([x[:, 3], x[:, 4], x[:, 5], x[:, 6]], axis=1).astype(f32)
+    dbeta, dalpha, dgamma = bandpass_bars(fbx, c["sampleRate"])
+    alpha, beta, gamma = bp[:, 0], bp[:, 1], bp[:, 2]
+    if variant == 2:
+        # fma(1 + C8, a10, -a10): (1 + C8)'s error times a10, a10's own rounding in both terms, one rounding
+        dk8a = a10 * (one8 * AREA_ONE_BAR + 2 * U * np.abs(k8)) + U * np.abs(k8a)
+        dLR = 0.5 * daU + U * aLR                      # fma(-1/2, alphaU, 1)
+        dalpha = 0.5 * dbeta + U * np.abs(alpha)       # fma(-1/2, beta, 1/4)
+    else:
+        dk8a = (AREA_K8A_BAR + U * np.abs(k8)) * a10
+        dLR = AREA_ALPHA_BAR * aLR
+    dtap = (AMP_REL + U) * np.abs(fc)                  # check_fric's tap bar (no gain: the amplitude's, the tap's one FMA)
+    mC, nC, nk6a, one6 = c["m_a20"], c["n_a20"], nk[:, 5] * c["n_a10"], 1.0 + nk[:, 5]
+    dnk6a, done6 = (U + 2 * EPS64) * np.abs(nk6a), (U + 4.0 / one6 * EPS64) * one6
+    oT, oB, nT, nB = s[:, 0:10], s[:, 10:20], s[:, 20:26], s[:, 26:32]
+    bar = np.zeros((len(s), 44))
+    zero = np.zeros(len(s))
+    # ---- frication band-pass: 2 (alpha (x - x2) + gamma y1 - beta y2): a difference, three products, two sums; the doubling is exact
+    sig = e[:, 1]
+    dfr = 2.0 * _lin(6, (alpha, dalpha, sig - s[:, S_BPX2], zero), (gamma, dgamma, s[:, S_BPY1], zero), (beta, dbeta, s[:, S_BPY2], zero))
+    fr = ref[:, S_BPY1]
+    bar[:, S_BPY1] = dfr                               # (bpX1, bpX2, bpY2: shifted values, bar 0)
+
+    def junction(t, dt, a, b, iT, iB, tap=None, dtp=None):
+        # T = t (a - b) + d b: the difference, two products, the sum; B = T - d (a - b): one more product and sum; the tap's
+        # injection tap fr onto T afterwards: a product and a sum
+        df = a - b
+        tpre = t * df + d * b
+        dtpre = _lin(4, (t, dt, df, zero), (d, dd, b, zero))
+        bar[:, iB] = _lin(3, (1.0 + zero, zero, tpre, dtpre), (d + zero, dd, df, zero))
+        bar[:, iT] = dtpre if tap is None else _lin(2, (1.0 + zero, zero, tpre, dtpre), (tap, dtp, fr, dfr))
+
+    bar[:, S_OT + 0] = _lin(2, (d + zero, dd, oB[:, 0], zero), (1.0 + zero, zero, e[:, 0], zero))
+    junction(td[:, 0], dtd[:, 0], oT[:, 0], oB[:, 1], S_OT + 1, S_OB + 0)
+    for i in (1, 2):
+        junction(td[:, i], dtd[:, i], oT[:, i], oB[:, i + 1], S_OT + i + 1, S_OB + i, fc[:, i - 1], dtap[:, i - 1])
+    # three-way junction: three products, two sums; then (jp - w) d: a difference and a product
+    jp = aLR * oT[:, 3] + aLR * oB[:, 4] + aU * nB[:, 0]
+    djp = _lin(5, (aLR, dLR, oT[:, 3], zero), (aLR, dLR, oB[:, 4], zero), (aU, daU, nB[:, 0], zero))
+    bar[:, S_OB + 3] = _lin(2, (d + zero, dd, jp - oT[:, 3], djp))
+    bar[:, S_OT + 4] = _lin(4, (d + zero, dd, jp - oB[:, 4], djp), (fc[:, 2], dtap[:, 2], fr, dfr))
+    bar[:, S_NT + 0] = _lin(2, (d + zero, dd, jp - nB[:, 0], djp))
+    junction(td[:, 3], dtd[:, 3], oT[:, 4], oB[:, 5], S_OT + 5, S_OB + 4, fc[:, 3], dtap[:, 3])
+    junction(d + zero, dd + zero, oT[:, 5], oB[:, 6], S_OT + 6, S_OB + 5, fc[:, 4], dtap[:, 4])          # S6|S7: t = d
+    for i in (6, 7, 8):
+        junction(td[:, i - 2], dtd[:, i - 2], oT[:, i], oB[:, i + 1], S_OT + i + 1, S_OB + i, fc[:, i - 1], dtap[:, i - 1])
+    for i in range(5):
+        junction(ntd[:, i], dntd[:, i], nT[:, i], nB[:, i + 1], S_NT + i + 1, S_NB + i)
+
+    def end(ka, dka, onep, donep, cf, top, iRefl, iRadX, iRadY, iBottom):
+        # reflection ka x + cf y1: two products, a sum; the bottom wave d refl; the radiation's input (1 + k) x;
+        # radiation cf (rin - x1 + y1): two sums, a product
+        dcf = U * abs(cf)
+        refl, rin = ref[:, iRefl], ref[:, iRadX]
+        bar[:, iRefl] = _lin(3, (ka, dka, top, zero), (cf + zero, dcf, s[:, iRefl], zero))
+        bar[:, iBottom] = _lin(1, (d + zero, dd, refl, bar[:, iRefl]))
+        bar[:, iRadX] = _lin(1, (onep, donep, top, zero))
+        bar[:, iRadY] = _lin(3, (cf + zero, dcf, rin, bar[:, iRadX]), (cf + zero, dcf, s[:, iRadX], zero), (cf + zero, dcf, s[:, iRadY], zero))
+
+    end(k8a, dk8a, one8, done8, mC, oT[:, 9], S_MREFL, S_MRADX, S_MRADY, S_OB + 9)
+    end(nk6a, dnk6a, one6, done6, nC, nT[:, 5], S_NREFL, S_NRADX, S_NRADY, S_NB + 5)
+    # throat ta0 x + tb1 y1: two products, a sum; output ty gain + (mouth + nose): a sum, a product, a sum
+    bar[:, S_THROAT] = _lin(3, (c["ta0"] + zero, U * c["ta0"], e[:, 2], zero), (c["tb1"] + zero, U * c["tb1"], s[:, S_THROAT], zero))
+    bar[:, S_OUT] = _lin(3, (c["throatGain"] + zero, U * c["throatGain"], ref[:, S_THROAT], bar[:, S_THROAT]),
+                         (1.0 + zero, zero, ref[:, S_MRADY], bar[:, S_MRADY]), (1.0 + zero, zero, ref[:, S_NRADY], bar[:, S_NRADY]))
+    return bar * SECOND_ORDER + TINY
+
+
+def step_reference(pd, state, ctl, exc):
+    """The oracle's step for the fp32 items as doubles, in probe_step's output order [n,44]."""
+    r = O.stage_steps(O.InputParams.from_dict(pd), state.astype(np.float64), ctl.astype(np.float64), exc.astype(np.float64))
+    return np.concatenate([r[:, :43], r[:, 45:46]], axis=1)
+
+
+def check_step(P, exact_builds=(False,)):
+    """Every variant within its bars at every item; `exact_builds`: which of the device library's two objects run (the host build
+    has one)."""
+    rep = {}
+    for name, pd, state, ctl, exc in step_items():
+        ref = step_reference(pd, state, ctl, exc)
+        for variant, vname in STEP_VARIANTS:
+            bars = step_bars(pd, variant, state, ctl, exc, ref)
+            for exact in exact_builds:
+                got = P.step(pd, variant, state, ctl, exc, exact=exact).astype(np.float64)
+                assert np.all(np.isfinite(got)), (name, vname)
+                ratio = np.abs(got - ref) / bars
+                i, j = np.unravel_index(np.argmax(ratio), ratio.shape)
+                assert ratio[i, j] <= 1.0, "tube step %s, %s (%s%s): output %d of item %d is %r, the oracle's %r: error %.3e, bar %.3e" % (
+                    vname, name, P.label, ", unfused object" if exact else "", j, i, got[i, j], ref[i, j], abs(got[i, j] - ref[i, j]), bars[i, j])
+                # the shifted band-pass memories are the old ones and the input, bit for bit
+                assert np.array_equal(got[:, S_BPX2], state[:, S_BPX1]) and np.array_equal(got[:, S_BPX1], exc[:, 1]) and np.array_equal(got[:, S_BPY2], state[:, S_BPY1])
+                for key, cols in (("waves", slice(0, 32)), ("filter memories", slice(32, 43)), ("tube sample", slice(43, 44))):
+                    key = "v%d %s, of its bar" % (variant, key)
+                    rep[key] = (max(float(ratio[:, cols].max()), rep.get(key, (0.0, 1.0))[0]), 1.0)
+    return show(P, "step", rep)
+
+
+def check_step_exact(P, exact=True):
+    """The header's exact promises, bit for bit, in the object built without the compiler's own fusion."""
+    pd, state, ctl, exc = step_synthetic(1024, seed=31)
+    # 1: an all-zero state with zero excitation stays zero, whatever the control values
+    for variant, vname in STEP_VARIANTS:
+        got = P.step(pd, variant, np.zeros_like(state), ctl, np.zeros_like(exc), exact=exact)
+        assert np.all(got == 0.0), "tube step %s (%s): a silent tube does not stay silent" % (vname, P.label)
+    # 2: the throat section run outside (kThroatDone) is the plain instantiation, on the synthetic items and on the voices'
+    for name, vpd, s, c, e in step_items():
+        a, b = P.step(vpd, 0, s, c, e, exact=exact), P.step(vpd, 1, s, c, e, exact=exact)
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), "tube_step<TubeConst, true> + throat_filter != tube_step<Const> at %d values (%s, %s)" % (
+            np.count_nonzero(a.view(np.uint32) != b.view(np.uint32)), name, P.label)
+    # 3: every tap lands on its own section and no other: zero state, frication input 1, a one-hot tap (60 dB at an integer
+    #    position: amplitude exactly 1) -- tap i injects into oT[i + 2] (FC1 -> S3 ... FC8 -> S10, TRMTubeModel.m:783-816)
+    ctl8 = np.tile(np.asarray(cases.MONET_VOWEL_FRAME, dtype=f32), (8, 1))
+    ctl8[:, 3], ctl8[:, 4] = 60.0, np.arange(8)
+    exc8 = np.tile(f32([0.0, 1.0, 0.0]), (8, 1))
+    for variant, vname in STEP_VARIANTS:
+        got = P.step(pd, variant, np.zeros((8, 43), dtype=f32), ctl8, exc8, exact=exact)
+        for i in range(8):
+            fr = got[i, S_BPY1]
+            assert fr != 0.0 and got[i, S_OT + i + 2] == fr, "tap %d (%s, %s): oT[%d] is %r, the band-pass output %r" % (i, vname, P.label, i + 2, got[i, S_OT + i + 2], fr)
+            others = np.delete(got[i, :32], S_OT + i + 2)
+            assert np.all(others == 0.0), "tap %d (%s, %s) reaches waves %r" % (i, vname, P.label, np.nonzero(got[i, :32])[0].tolist())
+    return {}
+
+
+# ================================================================ 11: the source mix
+FIR_PARAMS = dict(MONET, breathiness=0.0)      # probe_fir reads the FIR's output through mix_tail: exact with breathiness 0
+FIR_IMPULSE_STEPS, FIR_STEPS = 26, 256
+
+
+def fir_reference(taps, seq):
+    """float64 direct convolution of fp32 sequences [n, steps, (wa, wb)] with the 49 taps: y[m] = sum c[2k] wb[m-k] + c[2k+1] wa[m-k]
+    (TRMFIRFilter.m:116-146, the 2x decimation: an output after every second input), and sum |c x| with each term weighted by
+    the rounded operations it passes through in mix_sample's transposed form: tap i enters partial sum (i - 2) / 2 and is added
+    to at most i + 1 times on its way to the output (two sums a stage), after its own product and the tap's rounding to
+    float: i + 3, and 50 for the last tap (its partial sum starts as the bare product) -- at most chain length 49, + 1."""
+    x = seq.astype(np.float64)
+    wa, wb = x[:, :, 0], x[:, :, 1]
+    n, steps = wa.shape
+    y, weighted = np.zeros((n, steps)), np.zeros((n, steps))
+    for i in range(49):
+        src = wb if i % 2 == 0 else wa
+        k = i // 2
+        term = np.zeros((n, steps))
+        term[:, k:] = taps[i] * src[:, :steps - k]
+        y += term
+        weighted += np.abs(term) * min(i + 3, 50)
+    return y, weighted
+
+
+def fir_sequences(seed=37):
+    rng = np.random.default_rng(seed)
+    seqs = [rng.uniform(-1.0, 1.0, size=(FIR_STEPS, 2)) for _ in range(13)]
+    # the oracle's own table reads: the first 256 samples of three voices (pulse with a moving closure point, sine, frication sweep)
+    gc = cases.golden_cases()
+    for name in ("gnuspeech_window_44k", "sine_nomod", "frication_sweep"):
+        pd, fr = gc[name]
+        rec, _ = O.synthesize_states(O.InputParams.from_dict(pd), np.asarray(fr, dtype=f32).astype(np.float64), np.arange(FIR_STEPS, dtype=np.int32))
+        assert np.any(rec[:, O.T_READS] != 0.0) or name == "frication_sweep"
+        seqs.append(rec[:, O.T_READS])
+    return np.stack(seqs).astype(f32)
+
+
+def check_fir(P):
+    taps = O.fir_taps()
+    assert len(taps) == 49
+    # exact: a unit impulse in wa and one in wb at step 0, from zero state -- the outputs ARE the taps rounded to float, the
+    # odd-indexed ones from wa and the even-indexed ones from wb, in order; then nothing
+    imp = np.zeros((2, FIR_IMPULSE_STEPS, 2), dtype=f32)
+    imp[0, 0, 0] = imp[1, 0, 1] = 1.0
+    got = P.fir(FIR_PARAMS, imp)
+    want = np.zeros((2, FIR_IMPULSE_STEPS), dtype=f32)
+    want[0, :24], want[1, :25] = taps[1::2].astype(f32), taps[0::2].astype(f32)
+    assert np.array_equal(got, want), "mix_sample's impulse response (%s) is not the oracle's taps: wa at steps %r, wb at steps %r" % (
+        P.label, np.nonzero(got[0] != want[0])[0].tolist(), np.nonzero(got[1] != want[1])[0].tolist())
+    seq = fir_sequences()
+    got = P.fir(FIR_PARAMS, seq).astype(np.float64)
+    ref, weighted = fir_reference(taps, seq)
+    bar = U * weighted * SECOND_ORDER + TINY
+    ratio = np.abs(got - ref) / bar
+    assert ratio.max() <= 1.0, "mix_sample FIR (%s): error %.3e of sequence %d, step %d; bar %.3e" % (
+        (P.label, np.abs(got - ref).max()) + np.unravel_index(np.argmax(ratio), ratio.shape) + (bar.flat[np.argmax(ratio)],))
+    flat = U * 50 * np.abs(ref).max()
+    return show(P, "fir", {"output, of its bar": (float(ratio.max()), 1.0), "output, absolute": (float(np.abs(got - ref).max()), float(bar.max())),
+                           "output, against 50 U max|y|": (float(np.abs(got - ref).max()), float(flat))})
+
+
+MIX_AX = [0.0] + [2.0 ** -k for k in range(10, -1, -1)] + [0.3, 0.77]
+MIX_AH1 = [0.0, 2.0 ** -10, 2.0 ** -5, 0.1, 0.5, 1.0]
+
+
+def mix_sets():
+    return [(b, m, mod, dict(MONET, breathiness=b, mixOffset=m, usesModulation=mod))
+            for b in (0.0, 1.0, 10.0, 100.0) for m in (30.0, 48.0, 54.0, 60.0) for mod in (1, 0)]
+
+
+def mix_grid(crossmix, seed=41):
+    """[n,4] fp32 (ax, ah1, pulse, lpNoise); among the ax: the float where ax crossmixFactor is 1 and its two neighbours either side."""
+    rng = np.random.default_rng(seed)
+    edge = f32(1.0) / f32(crossmix)
+    ax = list(MIX_AX)
+    for step in range(-2, 3):
+        v = edge
+        for _ in range(abs(step)):
+            v = np.nextafter(v, f32(2.0 if step > 0 else 0.0))
+        if v <= 1.0:
+            ax.append(float(v))
+    pulse = np.concatenate([np.linspace(-1.0, 1.0, 9), rng.uniform(-1.0, 1.0, 4)])
+    noise = np.concatenate([np.linspace(-1.0, 1.0, 9), rng.uniform(-1.0, 1.0, 4)])
+    g = np.stack(np.meshgrid(ax, MIX_AH1, pulse, noise, indexing="ij"), axis=-1).reshape(-1, 4)
+    return g.astype(f32)
+
+
+def mix_bars(c, mod, x, ref):
+    """mix_tail as written (trm_lane.h), inputs exact: pn = lp pulse (one rounding); pulse' = ax (pn b + pulse (1 - b)): b is a
+    float constant (U), 1 - b one rounded difference below 1 (so 1 - b is known to U b + U (1 - b) = U); two products, a sum,
+    the product with ax.  cm = min(ax cf, 1): cf's U and the product's; 1 - cm one more rounding.  sig = pn cm + lp (1 - cm):
+    two products, a sum.  gin = (ah1 sig + pulse') / 8: a product, a sum; the eighth is exact."""
+    ax, ah1, pulse, lp = (x[:, k].astype(np.float64) for k in range(4))
+    zero = np.zeros(len(x))
+    b, cf = c["breath"], c["crossmix"]
+    pn = lp * pulse
+    dpn = U * np.abs(pn)
+    inner = pn * b + pulse * (1.0 - b)
+    dinner = _lin(3, (b + zero, U * b, pn, dpn), (1.0 - b + zero, U + zero, pulse, zero))
+    p2 = ax * inner
+    dp2 = _lin(1, (ax, zero, inner, dinner))
+    if mod:
+        cm = np.minimum(ax * cf, 1.0)
+        dcm = 2 * U * cm * SECOND_ORDER
+        dsig = _lin(3, (cm, dcm, pn, dpn), (1.0 - cm, dcm + U * (1.0 - cm), lp, zero))
+    else:
+        dsig = zero
+    sig = ref[:, 1]
+    dgin = 0.125 * _lin(2, (ah1, zero, sig, dsig), (1.0 + zero, zero, p2, dp2))
+    return np.stack([dgin, dsig, 0.125 * dp2], axis=1) * SECOND_ORDER + TINY
+
+
+def check_mix_tail(P):
+    rep = {}
+    for b, m, mod, pd in mix_sets():
+        ip = O.InputParams.from_dict(pd)
+        c = O.stage_constants(ip)
+        x = mix_grid(c["crossmix"])
+        got = P.mix_tail(pd, x).astype(np.float64)
+        ref = O.stage_mix(ip, x.astype(np.float64))
+        what = "mix_tail (breathiness %g, mixOffset %g, modulation %d, %s)" % (b, m, mod, P.label)
+        edge = x[:, 0].astype(np.float64) * c["crossmix"]
+        if mod:
+            # both sides of the clamp (mixOffset 60: the factor is 1 and no amplitude lies above it)
+            assert (np.any(edge > 1.0) or c["crossmix"] == 1.0) and np.any(edge < 1.0) and np.any(np.abs(edge - 1.0) < 4 * U), what
+        # exact: no modulation -> the noise itself; no voicing -> no throat input and the noise itself
+        if not mod:
+            assert np.array_equal(got[:, 1], x[:, 3]), what + ": sig != lpNoise without modulation"
+        silent = x[:, 0] == 0.0
+        assert silent.any() and np.all(got[silent, 2] == 0.0) and np.array_equal(got[silent, 1], x[silent, 3].astype(np.float64)), what + ": ax == 0"
+        bars = mix_bars(c, mod, x, ref)
+        ratio = np.abs(got - ref) / bars
+        i, j = np.unravel_index(np.argmax(ratio), ratio.shape)
+        assert ratio[i, j] <= 1.0, what + ": %s at (ax, ah1, pulse, lpNoise) = %r is %r, the oracle's %r: error %.3e, bar %.3e" % (
+            ("gin", "sig", "thr")[j], x[i].tolist(), got[i, j], ref[i, j], abs(got[i, j] - ref[i, j]), bars[i, j])
+        for j, key in enumerate(("gin", "sig", "thr")):
+            key += ", of its bar"
+            rep[key] = (max(float(ratio[:, j].max()), rep.get(key, (0.0, 1.0))[0]), 1.0)
+    return show(P, "mix_tail", rep)
+
+
+# ================================================================ 12: osc_read between entries
+OSC_SHAPES = [("pulse 40/16/32", dict(MONET)), ("pulse 25/5/35", dict(TRACT, tp=25.0, tnMin=5.0, tnMax=35.0)),
+              ("pulse 0/5/35 (no rise)", dict(TRACT, tp=0.0, tnMin=5.0, tnMax=35.0)), ("sine", dict(MONET, waveform=1))]
+OSC_AMPS = [0.0, 1e-3, 0.1, 0.25, 0.5, 0.7071, 0.9, 1.0]
+
+
+def osc_positions():
+    """Every entry + fractions {2^-30, 1/4, 1/2, 1 - 2^-30}; positions in (-1, 0), where the cast truncates to entry 0 and the
+    fraction is negative (the reference extrapolates); the last double below 511, and 511 exactly -- the only position whose upper
+    entry is the wrapped one (weight 0).  All in osc_wrap's range (-1, 511]."""
+    e = np.arange(511, dtype=np.float64)[:, None]
+    pos = (e + np.array([0.0, 2.0 ** -30, 0.25, 0.5, 1.0 - 2.0 ** -30])[None, :]).ravel()
+    extra = [-2.0 ** -30, -0.5, -1.0 + 2.0 ** -30, float(np.nextafter(511.0, 0.0)), 511.0]
+    return np.concatenate([pos, extra])
+
+
+def check_osc_read(P):
+    pos = osc_positions()
+    lo = pos.astype(np.int64)                       # truncation, as the cast
+    assert lo.min() == 0 and lo.max() == 511 and np.any(pos < 0)
+    frac = pos - lo
+    sens = np.abs(1.0 - frac) + np.abs(frac)
+    rep = {}
+    for name, pd in OSC_SHAPES:
+        ip = O.InputParams.from_dict(pd)
+        # the entries' own bars (probes 2 and 3) on both entries, the interpolation's two roundings (the difference and the FMA's:
+        # values below 1, U each), times what the read weighs its entries by
+        entry = SINE_BAR if pd["waveform"] == 1 else max(PULSE_RISE_BAR, PULSE_FALL_BAR)
+        bar = (entry + 2 * U) * sens
+        got = P.osc_read(pd, OSC_AMPS, pos)
+        assert np.array_equal(got[:, :, 0], got[:, :, 1]), name
+        worst = 0.0
+        for a, amp in enumerate(OSC_AMPS):
+            ref = O.stage_osc_reads(ip, amp, pos)
+            err = np.abs(got[a, :, 0].astype(np.float64) - ref)
+            i = int(np.argmax(err / bar))
+            assert err[i] <= bar[i], "osc_read %s (%s): amplitude %g, position %r: %r against %r, error %.3e, bar %.3e" % (
+                name, P.label, amp, pos[i], got[a, i, 0], ref[i], err[i], bar[i])
+            worst = max(worst, float((err / bar).max()))
+        rep[name + ", of its bar"] = (worst, 1.0)
+    return show(P, "osc_read", rep)
+
+
+# ================================================================ 13: the up-sampling converter
+def check_src_rows(H):
+    """Host only.  Every coefficient of build_src_rows and build_src_fine against the oracle's h / deltaH (pinned to the
+    reference's by tests/test_oracle_golden.py): (float)(h[l + 256 i] + deltaH[l + 256 i] m / 256), the left wing at phase f in
+    columns 12 - i, the right wing at 0xFFFF - f in columns 13 + i, columns 26 .. 31 zero."""
+    h, dh = O.src_tables()
+    ph, pdh, rows, fine = H.src_tables()
+    same = np.array_equal(ph, h) and np.array_equal(pdh, dh)
+    print("build_src_h against the oracle's tables: %s (h differs at %d entries, deltaH at %d)" % (
+        "bit for bit" if same else "NOT bit for bit", np.count_nonzero(ph != h), np.count_nonzero(pdh != dh)))
+    assert same, "build_src_h is not the oracle's h / deltaH bit for bit"
+    f = np.arange(65536)
+
+    def wing(g, i):
+        fi = (g >> 8) + 256 * i
+        return (h[fi] + dh[fi] * ((g & 255).astype(np.float64) / 256.0)).astype(f32)
+    want = np.zeros((65536, 32), dtype=f32)
+    for i in range(13):
+        want[:, 12 - i] = wing(f, i)
+        want[:, 13 + i] = wing(0xFFFF - f, i)
+    bad = np.count_nonzero(rows != want)
+    assert bad == 0, "build_src_rows: %d of %d coefficients differ from the oracle's tables, first at (phase, column) %r" % (
+        bad, rows.size, tuple(np.argwhere(rows != want)[0]))
+    assert np.all(rows[:, 26:] == 0.0)
+    q = np.arange(3328 * 256)
+    wantf = (h[q >> 8] + dh[q >> 8] * ((q & 255).astype(np.float64) / 256.0)).astype(f32)
+    assert np.array_equal(fine, wantf), "build_src_fine: %d entries differ" % np.count_nonzero(fine != wantf)
+    return rows
+
+
+SRC_PHASES = [0, 1, 0x7FFF, 0x8000, 0xFFFF]
+SRC_DOT_BAR, SRC_DOT32_BAR = 13 + 1, 9 + 1     # the longest chain of sums (12 in an accumulator + 1; 7 + 2) and the term's own product
+
+
+def src_dot_items(rows, seed=43):
+    """(w32, c32, o): 32-sample windows -- random, and cut from the oracle's tube samples of a vowel -- against rows at random
+    phases and at SRC_PHASES, each shifted right by o = 0 .. 3 with zeros around it."""
+    rng = np.random.default_rng(seed)
+    pd, fr = cases.golden_cases()["gnuspeech_window_44k"]
+    tube = O.synthesize(O.InputParams.from_dict(pd), fr, keep_tube=True)["tubeSamples"]
+    starts = rng.integers(2000, len(tube) - 32, 64)
+    wins = np.concatenate([rng.uniform(-1.0, 1.0, size=(64, 32)), np.stack([tube[s:s + 32] for s in starts])]).astype(f32)
+    phases = np.concatenate([SRC_PHASES, rng.integers(0, 65536, len(wins) - len(SRC_PHASES))])
+    w, c, o = [], [], []
+    for win, f in zip(wins, phases):
+        for sh in range(4):
+            row = np.zeros(32, dtype=f32)
+            row[sh:sh + 26] = rows[f, :26]
+            w.append(win); c.append(row); o.append(sh)
+    return np.stack(w), np.stack(c), np.array(o)
+
+
+def check_src_dot(P, rows):
+    w, c, o = src_dot_items(rows)
+    # src_dot32 over the window and the shifted row; src_dot over the 26 samples from the output's first tap on and the row itself
+    w26 = np.zeros_like(w)
+    c26 = np.zeros_like(c)
+    for i, sh in enumerate(o):
+        w26[i, :26], c26[i, :26] = w[i, sh:sh + 26], c[i, sh:sh + 26]
+    d32 = P.src_dot(w, c)[:, 1].astype(np.float64)
+    d26 = P.src_dot(w26, c26)[:, 0].astype(np.float64)
+    prod = w26.astype(np.float64) * c26.astype(np.float64)
+    ref, mag = prod.sum(axis=1), np.abs(prod).sum(axis=1)
+    b26, b32 = U * SRC_DOT_BAR * mag + TINY, U * SRC_DOT32_BAR * mag + TINY
+    r26, r32, rx = np.abs(d26 - ref) / b26, np.abs(d32 - ref) / b32, np.abs(d32 - d26) / (b26 + b32)
+    assert r26.max() <= 1.0 and r32.max() <= 1.0 and rx.max() <= 1.0, "src_dot / src_dot32 (%s): %.3f, %.3f, %.3f of their bars" % (P.label, r26.max(), r32.max(), rx.max())
+    return show(P, "src_dot", {"src_dot, of its bar": (float(r26.max()), 1.0), "src_dot32, of its bar": (float(r32.max()), 1.0),
+                               "src_dot32 - src_dot, of its bar": (float(rx.max()), 1.0)})
+
+
+def src_increments():
+    import downsample_paths_common as DP
+    incs = []
+    for name in DP.PATH_SETS:
+        rc, d = O.derive(O.InputParams.from_dict(DP.params_of(name)))
+        assert rc == 0
+        incs.append((d["timeRegisterIncrement"], d["padSize"]))
+    rc, d = O.derive(O.InputParams.from_dict(MONET))
+    incs.append((d["timeRegisterIncrement"], d["padSize"]))                  # the flagship's up-sampling ratio
+    return incs + [(17000, 13), (65011, 13), (65535, 13), (65536, 13)]
+
+
+SRC_KMAX = 1 << 22
+
+
+def check_src_clock(P, H):
+    """src_phase, src_position and src_count_outputs against the reference's serial 16.16 register (the host build's integer loops,
+    stage_probe_host.cc): every output k of the first 2^16, a stride over 2^22 outputs, and the outputs around k inc = 2^32."""
+    for inc, pad in src_increments():
+        ph, pos = H.ref_clock(inc, SRC_KMAX)
+        cross = (1 << 32) // inc
+        k = np.unique(np.concatenate([np.arange(1 << 16), np.arange(0, SRC_KMAX, 61), np.arange(SRC_KMAX - 4096, SRC_KMAX),
+                                      np.clip(np.arange(cross - 64, cross + 64), 0, SRC_KMAX - 1)]))
+        assert inc * (SRC_KMAX - 1) > (1 << 32)
+        got = P.src_clock(k, np.full(len(k), inc))
+        assert np.array_equal(got[:, 0], ph[k]), "src_phase (%s, increment %d): first at k = %d" % (P.label, inc, k[np.argmax(got[:, 0] != ph[k])])
+        assert np.array_equal(got[:, 1], pos[k]), "src_position (%s, increment %d): first at k = %d" % (P.label, inc, k[np.argmax(got[:, 1] != pos[k])])
+        nt = np.concatenate([np.arange(3001), np.arange((1 << 20) - 4, (1 << 20) + 5)])
+        want = np.array([H.ref_count(n, pad, inc) for n in nt], dtype=np.uint64)
+        cnt = P.src_count(nt, np.full(len(nt), pad), np.full(len(nt), inc))
+        assert np.array_equal(cnt, want), "src_count_outputs (%s, increment %d, pad %d): ntube %d gives %d, the serial register %d" % (
+            (P.label, inc, pad) + tuple(int(a[np.argmax(cnt != want)]) for a in (nt, cnt, want)))
+    return {}

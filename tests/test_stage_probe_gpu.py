@@ -66,3 +66,40 @@ def test_lane_forms_equal_tube_step(P, which):
 
 def test_oscillator_phase(P):
     S.check_phase(P)
+
+
+# ---- probes 9 - 13: the second half of the sample loop
+def test_tube_constants(P):
+    """build_const's tube constants as the kernels receive them: a Const passed as a kernel argument, read on the device."""
+    S.check_tube_const(P)
+
+
+def test_tube_step(P):
+    """tube_step by itself against the oracle's one-step export: the plain instantiation, the one-voice-per-lane kernel's path
+    (throat outside, TubeConst) and that path with k8a / alphaLR / bpAlpha rebuilt as its tube wave rebuilds them; in the object
+    built with the product's flags and in the one built without the compiler's own fusion."""
+    S.check_step(P, exact_builds=(False, True))
+
+
+def test_tube_step_exact_claims(P):
+    S.check_step_exact(P, exact=True)
+
+
+def test_fir(P):
+    S.check_fir(P)
+
+
+def test_mix_tail(P):
+    S.check_mix_tail(P)
+
+
+def test_osc_read_between_entries(P):
+    S.check_osc_read(P)
+
+
+def test_src_dot(P, H):
+    S.check_src_dot(P, H.src_tables()[2])
+
+
+def test_src_clock_and_counts(P, H):
+    S.check_src_clock(P, H)

@@ -55,3 +55,46 @@ def test_lane_forms_equal_tube_step(P, which):
 
 def test_oscillator_phase(P):
     S.check_phase(P)
+
+
+# ---- probes 9 - 13: the second half of the sample loop (tube constants, one tube step, the source mix, osc_read, the converter)
+def test_tube_constants(P):
+    S.check_tube_const(P)
+
+
+def test_tube_step(P):
+    S.check_step(P)
+
+
+def test_tube_step_exact_claims(P):
+    S.check_step_exact(P)
+
+
+def test_fir(P):
+    S.check_fir(P)
+
+
+def test_mix_tail(P):
+    S.check_mix_tail(P)
+
+
+def test_osc_read_between_entries(P):
+    S.check_osc_read(P)
+
+
+def test_src_rows_are_the_oracles_tables(P):
+    """build_src_h, build_src_rows and build_src_fine against the oracle's h / deltaH, bit for bit (host only)."""
+    assert S.check_src_rows(P).shape == (65536, 32)
+
+
+@pytest.fixture(scope="module")
+def src_rows(P):
+    return P.src_tables()[2]
+
+
+def test_src_dot(P, src_rows):
+    S.check_src_dot(P, src_rows)
+
+
+def test_src_clock_and_counts(P):
+    S.check_src_clock(P, P)
