@@ -292,12 +292,25 @@ TRM_HD double osc_increment(double f0, const Const &C)
 // (TRMWavetable.m:28-34,165-168).  (Also right for x in (-2, -1], the sum of two representatives.)
 TRM_HD double osc_wrap(double x) { return x - 512.0 * __builtin_ceil((x - 511.0) * (1.0 / 512.0)); }
 
+// amplitude()'s two clamps (TRMUtility.m:26-41) decided the way the reference decides them: on db - 60 in double, "<= -60 -> 0"
+// and ">= 0 -> 1".  The difference absorbs a level of 0 < db <= 2^-48, which is silence to the reference: compared on db
+// itself, such a level -- a ramp through 0 dB whose running sum lands a rounding error above it, at control periods 20, 24 and
+// 200 for -1 -> 1 dB -- gave 10^-3 for one sample where the reference gives 0 (tests/_probe, probe 15).  `geo` = 10^((db-60)/20).
+TRM_HD double clamp_amplitude_d(double db, double geo)
+{
+    const double x = db - 60.0;
+    double a = x >= 0.0 ? 1.0 : geo;
+    a = x <= -60.0 ? 0.0 : a;
+    return a;
+}
+
+// The amplitude of voicing of the track's current sample (TRMTubeModel.m:294-296), in fp64: it feeds osc_read's rint().
+TRM_HD double excite_track_ax(const ExciteTrack &T) { return clamp_amplitude_d(T.glotDb, T.axGeo); }
+
 template <class SineLookup>
 TRM_HD OscOut osc_sample(OscState &S, ExciteTrack &T, const Const &C, int j, SineLookup sineTab)
 {
-    // amplitude of voicing with its clamps (:294-296), in fp64: it feeds rint() below
-    double axd = T.glotDb >= 60.0 ? 1.0 : T.axGeo;
-    axd = T.glotDb <= 0.0 ? 0.0 : axd;
+    const double axd = excite_track_ax(T);
     OscOut O;
     O.ax = (float)axd;
     O.ah1 = amplitude_f(fma_f((float)j, T.aspDelta, T.aspBase));
@@ -405,6 +418,11 @@ TRM_HD bool coef_track_held(const CoefTrack &T)
     return h;
 }
 
+// The control-rate interpolation (TRMTubeModel.m:676-688 evaluated as base + j * delta): column i of the track at sample
+// fj of its control period, and the frication position there.  The only way j enters coef_sample.
+TRM_HD float coef_track_at(const CoefTrack &T, int i, float fj) { return fma_f(fj, T.delta[i], T.base[i]); }
+TRM_HD float coef_track_fric_pos(const CoefTrack &T, float fj) { return fma_f(fj, T.fricPosDelta, T.fricPos0); }
+
 // Stateless in the sample index: any wave may compute any sample j of the current control period.
 // Two halves that touch disjoint fields of Coefs (they may run in different waves):
 //   coef_sample_area   radii, velum -> scattering coefficients, three-way junction, NC1
@@ -420,13 +438,13 @@ template <class CT>
 TRM_HD void coef_sample_area(Coefs &K, const CoefTrack &T, const CT &C, int j)
 {
     const float fj = (float)j;
-    // control-rate interpolation (:676-688 evaluated as base + j*delta)
+    // control-rate interpolation (coef_track_at)
     float r2[8];
     for (int i = 0; i < 8; i++) {
-        float r = fma_f(fj, T.delta[3 + i], T.base[3 + i]);
+        float r = coef_track_at(T, 3 + i, fj);
         r2[i] = r * r;
     }
-    float velum = fma_f(fj, T.delta[11], T.base[11]);
+    float velum = coef_track_at(T, 11, fj);
 
     // scattering coefficients (:712-744) as transmission factors (1 + k) d = 2 a^2 d / (a^2 + b^2): no
     // cancellation when a junction nearly closes (k -> -1), see tube_step
@@ -451,9 +469,9 @@ template <bool kFricGain = false, bool kSatTaps = false, class CT = Const>
 TRM_HD void coef_sample_fric(Coefs &K, const CoefTrack &T, const CT &C, int j)
 {
     const float fj = (float)j;
-    float fricDb = fma_f(fj, T.delta[0], T.base[0]);
-    float fricCF = fma_f(fj, T.delta[1], T.base[1]);
-    float fricBW = fma_f(fj, T.delta[2], T.base[2]);
+    float fricDb = coef_track_at(T, 0, fj);
+    float fricCF = coef_track_at(T, 1, fj);
+    float fricBW = coef_track_at(T, 2, fj);
     // frication taps (:748-773).  The reference splits the position into (int) and fraction and gives the two taps
     // around it (1 - frac) amp and frac amp: the values of ONE continuous function, tap[i] = amp max(0, 1 - |pos - i|)
     // (linear interpolation between the taps; position 7.x: the second tap would be FC9, which does not exist, :761).
@@ -462,7 +480,7 @@ TRM_HD void coef_sample_fric(Coefs &K, const CoefTrack &T, const CT &C, int j)
     // is meaningless there as well).
     float fricAmp = amplitude_f(fricDb);
     if (kFricGain) fricAmp *= C.fricGain;
-    const float fricPos = fma_f(fj, T.fricPosDelta, T.fricPos0);                 // (:676-688)
+    const float fricPos = coef_track_fric_pos(T, fj);
     for (int i = 0; i < 8; i++) {
         const float dist = fabsf(fricPos - (float)i);
         const float t = fma_f(-fricAmp, dist, fricAmp);

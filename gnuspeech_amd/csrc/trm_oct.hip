@@ -412,9 +412,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
                     j -= CP;
                     T = Tn;
                 }
-                const double db = __builtin_fma((double)j, T.glotDelta, T.glot0);
-                double axd = db >= 60.0 ? 1.0 : T.axGeo;      // amplitude() with its clamps (:294-296)
-                axd = db <= 0.0 ? 0.0 : axd;
+                const double axd = osc_slot_ax(T, j);             // amplitude() with its clamps (:294-296)
                 const float ah1 = amplitude_f(fma_f((float)j, T.aspDelta, T.aspBase));
                 const double oinc = osc_increment(T.f0, C);       // (a multiple of 2^-30: the sums below are exact)
                 // position after this lane's sample = P + the inclusive prefix sum of 2*inc over the step's slots: within
@@ -439,9 +437,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
                 T.f0 *= T.f0Step;
                 T.axGeo *= T.axStep;
                 j += kOB;
-                const uint32_t rs = (step * kOB + (uint32_t)slot) & (kORing - 1);
-                ring[rs] = make_float2(wa, wb);
-                if (rs < (uint32_t)kOMirror) ring[rs + kORing] = make_float2(wa, wb);
+                osc_ring_store(ring, step * kOB + (uint32_t)slot, wa, wb);
                 sA[(step & 1u) * kWave + lane] = make_float2((float)axd, ah1);
             }
             STAMP_MID
@@ -497,7 +493,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
                     rowBlk < lds_flag_consume(&sRowSync[0]) + kRowBufs) {
                     if (rowsInFlight) rows_to_lds();            // (a second block in the same step: its predecessor's loads are waited for here)
                     const uint32_t k = rowBlk * kCvtCols + ((uint32_t)lane >> 1);
-                    const uint32_t off = (seg_out_position<kSeg>(inc, kBase, nBase, k) + (kQLead - (kSrcWindow - 1))) & 3u;
+                    const uint32_t off = cvt_row_shift(seg_out_position<kSeg>(inc, kBase, nBase, k));
                     const float *pc = A.src_rows + (size_t)seg_out_phase<kSeg>(inc, kBase, k) * kSrcRowC - off + (lane & 1) * 16;
                     for (int q = 0; q < 4; q++) rq[q] = make_float4(pc[4 * q], pc[4 * q + 1], pc[4 * q + 2], pc[4 * q + 3]);
                     rowsInFlight = true;
@@ -513,7 +509,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
                 }
                 const uint32_t m = n0 + (uint32_t)slot;
                 // 26-sample window starting at the even index m - 24 - o (zeros before the first sample)
-                const uint32_t s0 = (m + kORing - 24u - (uint32_t)o) & (kORing - 1);
+                const uint32_t s0 = osc_ring_window_start(m, (uint32_t)o);
                 const float4 *wp = reinterpret_cast<const float4 *>(&ring[s0]);
                 const float pulse = fir_window_dot(wp, cab);
                 const float2 a = sA[((step - 1) & 1u) * kWave + lane];
@@ -720,13 +716,12 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
 
         // output k reads tube samples e-25 .. e, e = src_position(k): ring slots e + kRingShift .. + 25
         // (kLane = this lane's output within the launch, ring positions are relative to the launch's first tube sample: seg_out_position)
-        constexpr uint32_t kRingShift = kQLead - (kSrcWindow - 1);
         v2f cc[16];
         uint32_t blk = 0, pr = 0;       // next work item: row pair `pr` (0..1) of block `blk`: voices 4*pr .. 4*pr+3
         uint32_t winBase = 0, kLane = 0, needLast = 0, needNext = 0;
         auto begin_block = [&]() {
             kLane = blk * kCvtCols + col;
-            winBase = (seg_out_position<kSeg>(inc, kBase, nBase, kLane) + kRingShift) & (kYRing - 1) & ~3u;
+            winBase = cvt_window_base(seg_out_position<kSeg>(inc, kBase, nBase, kLane));
             needLast = seg_out_position<kSeg>(inc, kBase, nBase, blk * kCvtCols + (kCvtCols - 1));
             needLast = needLast < nTotal - 1 ? needLast : nTotal - 1;
             needNext = seg_out_position<kSeg>(inc, kBase, nBase, (blk + 1) * kCvtCols + (kCvtCols - 1));   // (past the end: never "behind")
@@ -739,9 +734,9 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         };
         auto begin_block_from_global = [&]() {
             kLane = blk * kCvtCols + col;
-            winBase = (seg_out_position<kSeg>(inc, kBase, nBase, kLane) + kRingShift) & (kYRing - 1) & ~3u;
+            winBase = cvt_window_base(seg_out_position<kSeg>(inc, kBase, nBase, kLane));
             needLast = nTotal - 1;
-            const uint32_t off = (seg_out_position<kSeg>(inc, kBase, nBase, kLane) + kRingShift) & 3u;
+            const uint32_t off = cvt_row_shift(seg_out_position<kSeg>(inc, kBase, nBase, kLane));
             const float *pc = A.src_rows + (size_t)seg_out_phase<kSeg>(inc, kBase, kLane) * kSrcRowC - off;
             for (int q = 0; q < 16; q++) cc[q] = v2f{pc[2 * q], pc[2 * q + 1]};
         };

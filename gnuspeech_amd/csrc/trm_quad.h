@@ -326,6 +326,16 @@ TRM_HD void osc_slot_setup(OscSlotTrack &T, const Const &C, const float *prev, c
     osc_slot_setup_pow2<2>(T, C, prev, cur, j);
 }
 
+// The amplitude of voicing of the lane's sample `j` of its control period, in fp64 (it feeds osc_read's rint()): the
+// geometric sequence with amplitude()'s two clamps (TRMTubeModel.m:294-296) decided as the reference decides them
+// (clamp_amplitude_d, trm_lane.h) on the dB value in closed form, glot0 + j glotDelta in one rounding.  (The reference's dB is a
+// running sum; the two differ by rounding errors far below 2^-48, which the comparison on db - 60 absorbs at 0 dB, and at
+// 60 dB the sequence is within 1e-15 of 1 on either side: the float is 1.)
+TRM_HD double osc_slot_ax(const OscSlotTrack &T, uint32_t j)
+{
+    return clamp_amplitude_d(__builtin_fma((double)j, T.glotDelta, T.glot0), T.axGeo);
+}
+
 // ================================================================ 49-tap FIR, direct form over a window
 // y[m] = sum_{k=0..24} c[2k] b[m-k] + sum_{k=0..23} c[2k+1] a[m-k] (TRMFIRFilter.m:116-146, decimating by 2:
 // a, b = the two oversampled oscillator reads of a tube sample).  The window holds 26 samples starting at

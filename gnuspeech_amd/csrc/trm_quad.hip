@@ -438,9 +438,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
                         osc_slot_setup(T, C, prev, cur, (int)j);
                     }
                 }
-                const double db = __builtin_fma((double)j, T.glotDelta, T.glot0);
-                double axd = db >= 60.0 ? 1.0 : T.axGeo;      // amplitude() with its clamps (:294-296)
-                axd = db <= 0.0 ? 0.0 : axd;
+                const double axd = osc_slot_ax(T, j);             // amplitude() with its clamps (:294-296)
                 const float ah1 = amplitude_f(fma_f((float)j, T.aspDelta, T.aspBase));
                 const double oinc = osc_increment(T.f0, C);       // (a multiple of 2^-30: the sums below are exact)
                 // position after this lane's sample = P + the inclusive prefix sum of 2*inc over the slots
@@ -460,9 +458,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
                 T.f0 *= T.f0Step;
                 T.axGeo *= T.axStep;
                 j += kQB;
-                const uint32_t slot = (oblk * kQB + (uint32_t)part) & (kORing - 1);
-                ring[slot] = make_float2(wa, wb);
-                if (slot < (uint32_t)kOMirror) ring[slot + kORing] = make_float2(wa, wb);
+                osc_ring_store(ring, oblk * kQB + (uint32_t)part, wa, wb);
                 sA[(oblk % kABufs) * kWave + lane] = make_float2((float)axd, ah1);
               }
             }
@@ -531,7 +527,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
                     rowBlk < lds_flag_consume(&sRowSync[0]) + kRowBufs) {
                     if (rowsInFlight) rows_to_lds();            // (a second block in the same step: its predecessor's loads are waited for here)
                     const uint32_t k = kBase + rowBlk * kCvtCols + ((uint32_t)lane >> 1);
-                    const uint32_t off = (src_position(k, inc) - nBase + (kQLead - (kSrcWindow - 1))) & 3u;
+                    const uint32_t off = cvt_row_shift(src_position(k, inc) - nBase);
                     const float *pc = A.src_rows + (size_t)src_phase(k, inc) * kSrcRowC - off + (lane & 1) * 16;
                     for (int q = 0; q < 4; q++) rq[q] = make_float4(pc[4 * q], pc[4 * q + 1], pc[4 * q + 2], pc[4 * q + 3]);
                     rowsInFlight = true;
@@ -551,7 +547,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
                 }
                 const uint32_t m = n0 + (uint32_t)part;
                 // 26-sample window starting at the even index m - 24 - o (zeros before the first sample)
-                const uint32_t s0 = (m + kORing - 24u - (uint32_t)o) & (kORing - 1);
+                const uint32_t s0 = osc_ring_window_start(m, (uint32_t)o);
                 const float4 *wp = reinterpret_cast<const float4 *>(&ring[s0]);
                 const float pulse = fir_window_dot(wp, cab);
                 const float2 a = sA[buf * kWave + lane];
@@ -785,7 +781,6 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         for (int r = 0; r < 8; r++) sMx[r * kWave + lane] = 0.0f;
 
         // output k reads tube samples e-25 .. e, e = src_position(k): ring slots e + kRingShift .. + 25
-        constexpr uint32_t kRingShift = kQLead - (kSrcWindow - 1);
         // Coefficient rows: the mix wave stages every block's 32 rows in LDS several steps ahead (the latency of
         // global memory would otherwise sit in front of each block's first row pair: this wave's vector-memory
         // counter also counts its PCM stores); a block begins by copying this lane's row into registers.
@@ -796,7 +791,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         // relative to the launch's first tube sample (nBase)
         auto begin_block = [&]() {
             kLane = blk * kCvtCols + col;
-            winBase = (src_position(kBase + kLane, inc) - nBase + kRingShift) & (kYRing - 1) & ~3u;
+            winBase = cvt_window_base(src_position(kBase + kLane, inc) - nBase);
             needLast = src_position(kBase + blk * kCvtCols + (kCvtCols - 1), inc) - nBase;
             needLast = needLast < nTotal - 1 ? needLast : nTotal - 1;
             needNext = src_position(kBase + (blk + 1) * kCvtCols + (kCvtCols - 1), inc) - nBase;   // (past the end: never "behind")
@@ -809,9 +804,9 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         };
         auto begin_block_from_global = [&]() {
             kLane = blk * kCvtCols + col;
-            winBase = (src_position(kBase + kLane, inc) - nBase + kRingShift) & (kYRing - 1) & ~3u;
+            winBase = cvt_window_base(src_position(kBase + kLane, inc) - nBase);
             needLast = nTotal - 1;
-            const uint32_t off = (src_position(kBase + kLane, inc) - nBase + kRingShift) & 3u;
+            const uint32_t off = cvt_row_shift(src_position(kBase + kLane, inc) - nBase);
             const float *pc = A.src_rows + (size_t)src_phase(kBase + kLane, inc) * kSrcRowC - off;
             for (int q = 0; q < 16; q++) cc[q] = v2f{pc[2 * q], pc[2 * q + 1]};
         };

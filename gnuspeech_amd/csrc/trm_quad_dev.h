@@ -40,6 +40,28 @@ constexpr int kRowPitch = kSrcRowC + 4;  // staged coefficient rows: 144 bytes a
 constexpr int kQLead = 28;           // tube sample n sits at converter-ring slot (n + 28) & 127: the converter's 25 zeros of
                                      // pre-roll (TRMSampleRateConverter.m:138-150) + 3, so that a block of 4 is 16-byte aligned
 
+// The osc -> mix ring of one voice (kOStride float2): tube sample n's two reads stand in slot n & (kORing - 1), and once more
+// kORing slots on where that slot is below kOMirror.
+__device__ __forceinline__ void osc_ring_store(float2 *ring, uint32_t n, float wa, float wb)
+{
+    const uint32_t slot = n & (kORing - 1);
+    ring[slot] = make_float2(wa, wb);
+    if (slot < (uint32_t)kOMirror) ring[slot + kORing] = make_float2(wa, wb);
+}
+// ... and where tube sample m's 26-sample window (fir_direct, trm_quad.h) starts in it: the slot of the even sample
+// m - 24 - o, o = m & 1 (the window runs on into the mirror and never wraps; zeros before the first sample)
+__device__ __forceinline__ uint32_t osc_ring_window_start(uint32_t m, uint32_t o) { return (m + kORing - 24u - o) & (kORing - 1); }
+
+// The converter's read of the tube-rate ring (kYStride floats a voice; tube sample n of the launch in slot (n + kQLead) &
+// (kYRing - 1)).  An output whose newest tube sample is `pos` (src_position, relative to the launch's first sample) reads
+// samples pos - 25 .. pos: ring slots pos + kRingShift .. + 25.  Its window is read from the 16-byte aligned slot below
+// (cvt_window_base) and its coefficient row is fetched that many floats early (cvt_row_shift: row - shift), so that the
+// coefficients meet their samples; the floats in front of a row are the previous row's zero columns, in front of row 0 the
+// table's own four zeros (trm_capi.cc).
+constexpr uint32_t kRingShift = kQLead - (kSrcWindow - 1);
+__device__ __forceinline__ uint32_t cvt_window_base(uint32_t pos) { return (pos + kRingShift) & (kYRing - 1) & ~3u; }
+__device__ __forceinline__ uint32_t cvt_row_shift(uint32_t pos) { return (pos + kRingShift) & 3u; }
+
 // The oscillator FIR of one tube sample in direct form (fir_direct, trm_quad.h) over the LDS ring of oscillator reads: the
 // 26-sample window as 13 aligned 16-byte reads of (a, b) pairs, fir_direct's four partial sums as two packed ones
 // (even / odd window slots x (a, b)); `cab` = the window taps of the sample's parity as (a, b) pairs.

@@ -239,9 +239,7 @@ extern "C" int trm_emul_synthesize_quad(const trm_input_params *p, const float *
                 osc_slot_setup(OT[s], C, frame(per[s]), frame(per[s] + 1), jj[s]);
                 coef_track_setup(CT[s], C, frame(per[s]), frame(per[s] + 1));
             }
-            double db = __builtin_fma((double)jj[s], OT[s].glotDelta, OT[s].glot0);
-            double a = db >= 60.0 ? 1.0 : OT[s].axGeo;
-            axd[s] = db <= 0.0 ? 0.0 : a;
+            axd[s] = osc_slot_ax(OT[s], (uint32_t)jj[s]);
             ax[s] = (float)axd[s];
             ah1[s] = amplitude_f(fma_f((float)jj[s], OT[s].aspDelta, OT[s].aspBase));
             incs[s] = osc_increment(OT[s].f0, C);

@@ -14,6 +14,9 @@
 #include "../../gnuspeech_amd/csrc/trm_oct.h"
 #include "../../gnuspeech_amd/csrc/trm_quad.h"
 #include "../../gnuspeech_amd/csrc/trm_setup.h"
+#if defined(__HIP__)
+#include "../../gnuspeech_amd/csrc/trm_quad_dev.h"      // probes 16 and 17: what only the kernels run
+#endif
 
 namespace trm_probe {
 using namespace trm;
@@ -455,6 +458,152 @@ TRM_HD void probe_src_count(int i, const uint64_t *in, uint64_t *out)
     out[i] = src_count_outputs(in[(size_t)i * 3], (uint32_t)in[(size_t)i * 3 + 1], (uint32_t)in[(size_t)i * 3 + 2]);
 }
 
+// ---------------------------------------------------------------- 14: the coefficient tracks at every sample of a period
+// item = (track t, sample j) of a period of `period` samples (the parameter set's own: its invControlPeriod is build_const's).
+//   out[13]   the interpolated values in frame-column order 3 .. 15: fricVol, fricPos, fricCF, fricBW, r1 .. r8, velum
+//   differ[2] bytes of coef_sample(T, C, j) that differ from coef_sample at sample 0 of a HELD track whose bases are those
+//             values -- "the only way j enters coef_sample" -- for coef_sample<false> and coef_sample<true>
+constexpr int kTrackOut = 13;
+TRM_HD void probe_track(int i, const Const &C, const float *prev, const float *cur, int period, float *out, int32_t *differ)
+{
+    const int t = i / period, j = i % period;
+    CoefTrack T, H;
+    coef_track_setup(T, C, prev + 16 * (size_t)t, cur + 16 * (size_t)t);
+    const float fj = (float)j;
+    float *o = out + (size_t)i * kTrackOut;
+    track_zero(H);
+    o[0] = H.base[0] = coef_track_at(T, 0, fj);
+    o[1] = H.fricPos0 = coef_track_fric_pos(T, fj);
+    for (int k = 1; k < 12; k++) o[1 + k] = H.base[k] = coef_track_at(T, k, fj);
+    const Coefs K = coef_sample(T, C, j), K0 = coef_sample(H, C, 0);
+    const Coefs G = coef_sample<true>(T, C, j), G0 = coef_sample<true>(H, C, 0);
+    differ[2 * (size_t)i] = coefs_differ(K, K0);
+    differ[2 * (size_t)i + 1] = coefs_differ(G, G0);
+}
+
+// ---------------------------------------------------------------- 15: ax, ah1, f0 per sample, three forms
+// item = one voice: a frame pair (pitch, glotVol, aspVol are read), every sample j of one control period.  Per (voice, j),
+// kExciteOut doubles: {ax in fp64, ah1, f0} of
+//   form 0   excite_track_setup + osc_sample advanced from j = 0 (ax: excite_track_ax before the call; o[9] = osc_sample's own
+//            float ax, which must be its rounding)
+//   form 1   osc_slot_setup_pow2<2> set up at each j0 < 4 and stepped 4 samples at a time, as trm_quad.hip's oscillator wave
+//   form 2   osc_slot_setup_pow2<3>, 8 at a time, as trm_oct.hip's
+// (the slot forms' ah1 and their tracks' advance are the kernels' statements; ax is osc_slot_ax)
+constexpr int kExciteOut = 10;
+template <int kLog2Slots>
+TRM_HD void probe_excite_slots(const Const &C, const float *prev, const float *cur, double *o, int form)
+{
+    const int CP = C.controlPeriod;
+    for (int j0 = 0; j0 < (1 << kLog2Slots) && j0 < CP; j0++) {
+        OscSlotTrack T;
+        osc_slot_setup_pow2<kLog2Slots>(T, C, prev, cur, j0);
+        for (uint32_t j = (uint32_t)j0; j < (uint32_t)CP; j += 1u << kLog2Slots) {
+            double *q = o + (size_t)j * kExciteOut + 3 * form;
+            q[0] = osc_slot_ax(T, j);
+            q[1] = (double)amplitude_f(fma_f((float)j, T.aspDelta, T.aspBase));
+            q[2] = T.f0;
+            T.f0 *= T.f0Step;
+            T.axGeo *= T.axStep;
+        }
+    }
+}
+TRM_HD void probe_excite(int v, const Const &C, const float *prev, const float *cur, double *out)
+{
+    const int CP = C.controlPeriod;
+    const float *a = prev + 16 * (size_t)v, *b = cur + 16 * (size_t)v;
+    double *o = out + (size_t)v * CP * kExciteOut;
+    OscState S; S.oscPos = 0.0;
+    ExciteTrack T;
+    excite_track_setup(T, C, a, b);
+    for (int j = 0; j < CP; j++) {
+        double *q = o + (size_t)j * kExciteOut;
+        q[0] = excite_track_ax(T);
+        q[2] = T.f0;
+        const OscOut O = osc_sample(S, T, C, j, [](int k) { return sine_table(k); });
+        q[1] = (double)O.ah1;
+        q[9] = (double)O.ax;
+    }
+    probe_excite_slots<2>(C, a, b, o, 1);
+    probe_excite_slots<3>(C, a, b, o, 2);
+}
+
+// ---------------------------------------------------------------- 16: the lane forms' FIR (fir_direct; the device: fir_window_dot)
+// item = one sequence of `steps` oscillator reads (a, b).  out[(item, m)] = {the packed form, fir_direct} of tube sample m.
+// Host: fir_direct over the sequence itself with 26 zero pairs in front (tests/_emul/trm_emul.cc's unrolled ring) in both.
+constexpr int kLaneFirOut = 2;
+TRM_HD void lane_fir_taps(const Const &C, float ca[2][kFirWin], float cb[2][kFirWin])
+{
+    for (int o = 0; o < 2; o++)
+        for (int k = 0; k < kFirWin; k++) { ca[o][k] = fir_window_tap_a(C.fir, o, k); cb[o][k] = fir_window_tap_b(C.fir, o, k); }
+}
+inline void probe_lane_fir_host(int i, const Const &C, const float *seq, int steps, float *out)
+{
+    float ca[2][kFirWin], cb[2][kFirWin];
+    lane_fir_taps(C, ca, cb);
+    std::vector<float> ab(2 * ((size_t)26 + steps), 0.0f);
+    for (int n = 0; n < 2 * steps; n++) ab[52 + n] = seq[(size_t)i * steps * 2 + n];
+    for (int m = 0; m < steps; m++) {
+        const int o = m & 1;
+        const float y = fir_direct(&ab[2 * (size_t)(26 + m - 24 - o)], ca[o], cb[o]);
+        out[((size_t)i * steps + m) * kLaneFirOut] = out[((size_t)i * steps + m) * kLaneFirOut + 1] = y;
+    }
+}
+#if defined(__HIP__)
+// Device: every read is written through osc_ring_store into a zeroed ring of one voice, mirror included, `ahead` samples
+// before sample m is read at osc_ring_window_start (the kernels' oscillator wave runs one step ahead of the mix wave: up to
+// 15 samples in trm_oct.hip); a ring of kORing slots holds a 26-sample window up to kORing - 26 samples back.
+constexpr int kLaneFirMaxAhead = kORing - kFirWin;
+__device__ inline void probe_lane_fir(int i, const Const &C, const float *seq, int steps, int ahead, float *out)
+{
+    __attribute__((aligned(16))) float2 ring[kOStride];
+    for (int k = 0; k < kOStride; k++) ring[k] = make_float2(0.0f, 0.0f);
+    float ca[2][kFirWin], cb[2][kFirWin];
+    lane_fir_taps(C, ca, cb);
+    v2f cab[2][kFirWin];
+    for (int o = 0; o < 2; o++)
+        for (int k = 0; k < kFirWin; k++) cab[o][k] = v2f{ca[o][k], cb[o][k]};
+    for (int n = 0; n < steps + ahead; n++) {
+        if (n < steps) osc_ring_store(ring, (uint32_t)n, seq[((size_t)i * steps + n) * 2], seq[((size_t)i * steps + n) * 2 + 1]);
+        const int m = n - ahead;
+        if (m < 0) continue;
+        const uint32_t o = (uint32_t)m & 1u, s0 = osc_ring_window_start((uint32_t)m, o);
+        float *q = out + ((size_t)i * steps + m) * kLaneFirOut;
+        q[0] = fir_window_dot(reinterpret_cast<const float4 *>(&ring[s0]), cab[o]);
+        q[1] = fir_direct(reinterpret_cast<const float *>(&ring[s0]), ca[o], cb[o]);
+    }
+}
+
+// ---------------------------------------------------------------- 17: the lane forms' converter fetch (device only)
+// item = (ring r, output k, increment, nBase): output k of a launch whose first tube sample is nBase reads the launch's samples
+// pos - 25 .. pos, pos = src_position(k, inc) - nBase, from ring r [kYStride], which the caller filled the kernels' way (sample n
+// of the launch in slot (n + kQLead) & (kYRing - 1), slots below kYMirror once more after the ring).  `rows` is the table as
+// trm_capi.cc allocates it: its row 0 stands four zeros into the allocation.
+//   o[0]  cvt_window_base / cvt_row_shift + cvt_window_dot: the kernels' fetch       o[1]  src_dot32 on the same aligned window and shifted row
+//   o[2]  src_dot on the unaligned window (winBase + off) and the row itself
+//   o[3]  the terms of the aligned product outside the output's 26 (below off, from 26 + off on), summed in magnitude
+constexpr int kCvtOut = 4;
+__device__ inline void probe_cvt(int i, const float *rings, const float *rows, const uint32_t *items, float *out)
+{
+    const uint32_t *it = items + (size_t)i * 4;
+    const uint32_t k = it[1], inc = it[2], nBase = it[3];
+    const float *ring = rings + (size_t)it[0] * kYStride;
+    const uint32_t pos = src_position(k, inc) - nBase;
+    const uint32_t winBase = cvt_window_base(pos), off = cvt_row_shift(pos);
+    const float *pc = rows + (size_t)src_phase(k, inc) * kSrcRowC - off;
+    v2f cc[16];
+    float c32[32];
+    for (int q = 0; q < 16; q++) { cc[q] = v2f{pc[2 * q], pc[2 * q + 1]}; c32[2 * q] = pc[2 * q]; c32[2 * q + 1] = pc[2 * q + 1]; }
+    float *o = out + (size_t)i * kCvtOut;
+    o[0] = cvt_window_dot(reinterpret_cast<const float4 *>(ring + winBase), cc);
+    o[1] = src_dot32(ring + winBase, c32);
+    o[2] = src_dot(ring + winBase + off, rows + (size_t)src_phase(k, inc) * kSrcRowC);
+    float tail = 0.0f;
+    for (uint32_t q = 0; q < 32; q++)
+        if (q < off || q >= 26 + off) tail += fabsf(ring[winBase + q] * c32[q]);
+    o[3] = tail;
+}
+#endif
+
 }  // namespace trm_probe
 
 // ---------------------------------------------------------------- the exported entries (both builds)
@@ -480,6 +629,14 @@ int trm_probe_osc_read(const trm_input_params *p, const double *amp, int namp, c
 int trm_probe_src_dot(const float *w, const float *c, int n, float *out);
 int trm_probe_src_clock(const uint32_t *in, int n, uint32_t *out);
 int trm_probe_src_count(const uint64_t *in, int n, uint64_t *out);
+// probes 14, 15: `period` is the parameter set's own control period (the entry refuses another: the tracks are set up with
+// build_const's invControlPeriod)
+int trm_probe_track(const trm_input_params *p, int period, const float *prev, const float *cur, int ntracks, float *out, int32_t *differ);
+int trm_probe_excite(const trm_input_params *p, int period, const float *prev, const float *cur, int nvoices, double *out);
+// probe 16.  Device: `ahead` samples between the ring's store and its read, 0 .. 38.  Host: fir_direct alone, `exact` and `ahead` unused
+int trm_probe_lane_fir(const trm_input_params *p, int exact, int ahead, const float *seq, int nseq, int steps, float *out);
+// probe 17, device build only: rings [nrings][kYStride], rows [65536 x 32] (the entry puts the four zeros in front), items [n][4]
+int trm_probe_cvt(int exact, const float *rings, int nrings, const float *rows, const uint32_t *items, int n, float *out);
 // host build only: build_src_h's tables [3328] each, build_src_rows [65536 x 32], build_src_fine [3328 x 256]
 int trm_probe_src_tables(double *h, double *dh, float *rows, float *fine);
 // host build only: the reference's serial 16.16 time register and its ring protocol as integer loops (probe 13's references)

@@ -346,3 +346,67 @@ extern "C" int trm_probe_src_count(const uint64_t *in, int n, uint64_t *out)
     }
     return result(e, B);
 }
+
+// ---------------------------------------------------------------- probes 14 - 17
+__global__ void k_track(Const C, const float *prev, const float *cur, int period, int n, float *out, int32_t *differ)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_track(i, C, prev, cur, period, out, differ);
+}
+__global__ void k_excite(Const C, const float *prev, const float *cur, int n, double *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_excite(i, C, prev, cur, out);
+}
+
+// out and differ come back in one buffer each; `period` must be the set's own (see stage_probe.h)
+extern "C" int trm_probe_track(const trm_input_params *p, int period, const float *prev, const float *cur, int ntracks, float *out, int32_t *differ)
+{
+    Const C;
+    if (make_const(p, C) || period <= 0 || period != C.controlPeriod || ntracks <= 0 || ntracks > kMaxItems / period) return (int)hipErrorInvalidValue;
+    const int n = ntracks * period;
+    DevBufs B;
+    float *dPrev, *dCur, *dOut;
+    int32_t *dDiffer;
+    hipError_t e = B.put(&dPrev, prev, (size_t)ntracks * 16);
+    if (e == hipSuccess) e = B.put(&dCur, cur, (size_t)ntracks * 16);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)n * kTrackOut);
+    if (e == hipSuccess) e = B.get(&dDiffer, (size_t)n * 2);
+    if (e == hipSuccess) {
+        k_track<<<blocks_for(n), kBlock>>>(C, dPrev, dCur, period, n, dOut, dDiffer);
+        e = finish(out, dOut, (size_t)n * kTrackOut);
+        if (e == hipSuccess) e = hipMemcpy(differ, dDiffer, (size_t)n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost);
+    }
+    return result(e, B);
+}
+
+extern "C" int trm_probe_excite(const trm_input_params *p, int period, const float *prev, const float *cur, int nvoices, double *out)
+{
+    Const C;
+    if (make_const(p, C) || period <= 0 || period != C.controlPeriod || nvoices <= 0 || nvoices > kMaxItems / period) return (int)hipErrorInvalidValue;
+    C.waveform = 1;         // (the reads are not looked at)
+    DevBufs B;
+    float *dPrev, *dCur;
+    double *dOut;
+    const size_t nout = (size_t)nvoices * period * kExciteOut;
+    hipError_t e = B.put(&dPrev, prev, (size_t)nvoices * 16);
+    if (e == hipSuccess) e = B.put(&dCur, cur, (size_t)nvoices * 16);
+    if (e == hipSuccess) e = B.get(&dOut, nout);
+    if (e == hipSuccess) {
+        k_excite<<<blocks_for(nvoices), kBlock>>>(C, dPrev, dCur, nvoices, dOut);
+        e = finish(out, dOut, nout);
+    }
+    return result(e, B);
+}
+
+extern "C" int trm_probe_lane_fir_exact(const trm_input_params *p, int ahead, const float *seq, int nseq, int steps, float *out);
+extern "C" int trm_probe_lane_fir(const trm_input_params *p, int exact, int ahead, const float *seq, int nseq, int steps, float *out)
+{
+    return exact ? trm_probe_lane_fir_exact(p, ahead, seq, nseq, steps, out) : launch_lane_fir<0>(p, ahead, seq, nseq, steps, out);
+}
+
+extern "C" int trm_probe_cvt_exact(const float *rings, int nrings, const float *rows, const uint32_t *items, int n, float *out);
+extern "C" int trm_probe_cvt(int exact, const float *rings, int nrings, const float *rows, const uint32_t *items, int n, float *out)
+{
+    return exact ? trm_probe_cvt_exact(rings, nrings, rows, items, n, out) : launch_cvt<0>(rings, nrings, rows, items, n, out);
+}

@@ -92,4 +92,59 @@ inline int launch_step(const trm_input_params *p, int variant, const float *stat
     return result(e, B);
 }
 
+// Probes 16 and 17 likewise: the packed dot products are held to the written-out forms bit for bit in both objects.
+template <int kBuild>
+__global__ void k_lane_fir(Const C, const float *seq, int n, int steps, int ahead, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_lane_fir(i, C, seq, steps, ahead, out);
+}
+
+template <int kBuild>
+inline int launch_lane_fir(const trm_input_params *p, int ahead, const float *seq, int nseq, int steps, float *out)
+{
+    Const C;
+    trm_derived d;
+    if (!p || build_const(*p, C, d) || nseq <= 0 || steps <= 0 || nseq > kMaxItems / steps || ahead < 0 || ahead > kLaneFirMaxAhead) return (int)hipErrorInvalidValue;
+    DevBufs B;
+    float *dIn, *dOut;
+    hipError_t e = B.put(&dIn, seq, (size_t)nseq * steps * 2);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)nseq * steps * kLaneFirOut);
+    if (e == hipSuccess) {
+        k_lane_fir<kBuild><<<blocks_for(nseq), kBlock>>>(C, dIn, nseq, steps, ahead, dOut);
+        e = finish(out, dOut, (size_t)nseq * steps * kLaneFirOut);
+    }
+    return result(e, B);
+}
+
+template <int kBuild>
+__global__ void k_cvt(const float *rings, const float *rows, const uint32_t *items, int n, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) probe_cvt(i, rings, rows, items, out);
+}
+
+template <int kBuild>
+inline int launch_cvt(const float *rings, int nrings, const float *rows, const uint32_t *items, int n, float *out)
+{
+    if (!rings || !rows || !items || nrings <= 0 || nrings > 4096 || n <= 0 || n > kMaxItems) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n; i++)
+        if (items[(size_t)i * 4] >= (uint32_t)nrings || items[(size_t)i * 4 + 2] == 0u) return (int)hipErrorInvalidValue;
+    const size_t nrows = (size_t)65536 * kSrcRowC;
+    DevBufs B;
+    float *dRings, *dRows, *dOut;
+    uint32_t *dItems;
+    hipError_t e = B.put(&dRings, rings, (size_t)nrings * kYStride);
+    if (e == hipSuccess) e = B.get(&dRows, nrows + 4);          // [4 zeros][rows], as trm_capi.cc allocates the table
+    if (e == hipSuccess) e = hipMemset(dRows, 0, 4 * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(dRows + 4, rows, nrows * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = B.put(&dItems, items, (size_t)n * 4);
+    if (e == hipSuccess) e = B.get(&dOut, (size_t)n * kCvtOut);
+    if (e == hipSuccess) {
+        k_cvt<kBuild><<<blocks_for(n), kBlock>>>(dRings, dRows + 4, dItems, n, dOut);
+        e = finish(out, dOut, (size_t)n * kCvtOut);
+    }
+    return result(e, B);
+}
+
 }  // namespace trm_probe

@@ -183,6 +183,32 @@ extern "C" int trm_probe_src_count(const uint64_t *in, int n, uint64_t *out)
     return 0;
 }
 
+// ---------------------------------------------------------------- probes 14 - 16 (17 is the device's alone)
+extern "C" int trm_probe_track(const trm_input_params *p, int period, const float *prev, const float *cur, int ntracks, float *out, int32_t *differ)
+{
+    Const C;
+    if (make_const(p, C) || period <= 0 || period != C.controlPeriod || ntracks <= 0 || ntracks > kMaxItems / period) return 1;
+    for (int i = 0; i < ntracks * period; i++) probe_track(i, C, prev, cur, period, out, differ);
+    return 0;
+}
+
+extern "C" int trm_probe_excite(const trm_input_params *p, int period, const float *prev, const float *cur, int nvoices, double *out)
+{
+    Const C;
+    if (make_const(p, C) || period <= 0 || period != C.controlPeriod || nvoices <= 0 || nvoices > kMaxItems / period) return 1;
+    C.waveform = 1;         // (the reads are not looked at)
+    for (int v = 0; v < nvoices; v++) probe_excite(v, C, prev, cur, out);
+    return 0;
+}
+
+extern "C" int trm_probe_lane_fir(const trm_input_params *p, int, int, const float *seq, int nseq, int steps, float *out)
+{
+    Const C;
+    if (make_const(p, C) || nseq <= 0 || steps <= 0 || nseq > kMaxItems / steps) return 1;
+    for (int i = 0; i < nseq; i++) probe_lane_fir_host(i, C, seq, steps, out);
+    return 0;
+}
+
 extern "C" int trm_probe_src_tables(double *h, double *dh, float *rows, float *fine)
 {
     std::vector<double> vh, vdh;

@@ -186,6 +186,34 @@ int main()
         std::vector<uint32_t> ph(4096), ps(4096);
         CHECK(trm_probe_ref_clock(80847u, 4096, ph.data(), ps.data()));
     }
+    // ---- probes 14 - 16 (17 has no host body)
+    {
+        const int ntracks = 3, period = (int)c[0];
+        std::vector<float> prev(ntracks * 16, 0.5f), cur(ntracks * 16, 1.25f);
+        prev[1] = -1.0f; cur[1] = 1.0f; prev[2] = 61.0f; cur[2] = 59.0f; prev[0] = -24.0f; cur[0] = 24.0f;
+        prev[16 + 4] = 0.0f; cur[16 + 4] = 7.5f; prev[16 + 1] = 0.0f; cur[16 + 1] = 1e-45f;
+        prev[32 + 9] = cur[32 + 9] = __builtin_nanf("");
+        std::vector<float> out((size_t)ntracks * period * kTrackOut);
+        std::vector<int32_t> differ((size_t)ntracks * period * 2);
+        CHECK(trm_probe_track(&p, period, prev.data(), cur.data(), ntracks, out.data(), differ.data()));
+        for (int32_t d : differ)
+            if (d) { fprintf(stderr, "stage_probe_sanitize: track\n"); return 1; }
+        if (trm_probe_track(&p, period + 1, prev.data(), cur.data(), ntracks, out.data(), differ.data()) == 0) { fprintf(stderr, "stage_probe_sanitize: track took a foreign period\n"); return 1; }
+        std::vector<double> ex((size_t)ntracks * period * kExciteOut);
+        CHECK(trm_probe_excite(&p, period, prev.data(), cur.data(), ntracks, ex.data()));
+        trm_input_params q = p;
+        q.controlRate = 19794.0f;       // a control period of one sample: fewer samples than slots
+        std::vector<double> ex1((size_t)ntracks * kExciteOut);
+        CHECK(trm_probe_excite(&q, 1, prev.data(), cur.data(), ntracks, ex1.data()));
+    }
+    {
+        const int nseq = 2, steps = 70;
+        std::vector<float> seq((size_t)nseq * steps * 2, 0.0f), out((size_t)nseq * steps * kLaneFirOut);
+        seq[2 * 3] = 1.0f;
+        for (int k = 0; k < steps * 2; k++) seq[(size_t)steps * 2 + k] = (float)(k % 5) - 2.0f;
+        CHECK(trm_probe_lane_fir(&p, 0, 0, seq.data(), nseq, steps, out.data()));
+        if (out[2 * 2] != 0.0f || out[2 * 3] == 0.0f || out[2 * 28] != 0.0f) { fprintf(stderr, "stage_probe_sanitize: lane fir\n"); return 1; }
+    }
     printf("stage_probe_sanitize: ok (instrumented)\n");
     return 0;
 }

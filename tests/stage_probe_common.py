@@ -87,6 +87,11 @@ class Probe:
         L.trm_probe_src_dot.argtypes = [fp, fp, C.c_int, fp]
         L.trm_probe_src_clock.argtypes = [up, C.c_int, up]
         L.trm_probe_src_count.argtypes = [qp, C.c_int, qp]
+        L.trm_probe_track.argtypes = [pp, C.c_int, fp, fp, C.c_int, fp, ip]
+        L.trm_probe_excite.argtypes = [pp, C.c_int, fp, fp, C.c_int, dp]
+        L.trm_probe_lane_fir.argtypes = [pp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp]
+        if hasattr(L, "trm_probe_cvt"):                     # the device build's own: what only the kernels run
+            L.trm_probe_cvt.argtypes = [C.c_int, fp, C.c_int, fp, up, C.c_int, fp]
         if hasattr(L, "trm_probe_src_tables"):              # the host build's own: the tables and the integer references
             L.trm_probe_src_tables.argtypes = [dp, dp, fp, fp]
             L.trm_probe_ref_clock.argtypes = [C.c_uint32, C.c_int, up, up]
@@ -214,6 +219,40 @@ class Probe:
         x = np.ascontiguousarray(np.stack([ntube, pad, inc], axis=1), dtype=np.uint64)
         out = np.zeros(len(x), dtype=np.uint64)
         self._ok(self.L.trm_probe_src_count(self._p(x, C.c_uint64), len(x), self._p(out, C.c_uint64)), "src_count")
+        return out
+
+    def track(self, pd, period, prev, cur):
+        prev = np.ascontiguousarray(prev, dtype=f32).reshape(-1, 16)
+        cur = np.ascontiguousarray(cur, dtype=f32).reshape(-1, 16)
+        out, differ = np.zeros((len(prev), period, 13), dtype=f32), np.zeros((len(prev), period, 2), dtype=np.int32)
+        self._ok(self.L.trm_probe_track(C.byref(O.InputParams.from_dict(pd)), period, self._p(prev, C.c_float), self._p(cur, C.c_float),
+                                        len(prev), self._p(out, C.c_float), self._p(differ, C.c_int32)), "track")
+        return out, differ
+
+    def excite(self, pd, period, prev, cur):
+        prev = np.ascontiguousarray(prev, dtype=f32).reshape(-1, 16)
+        cur = np.ascontiguousarray(cur, dtype=f32).reshape(-1, 16)
+        out = np.zeros((len(prev), period, 10))
+        self._ok(self.L.trm_probe_excite(C.byref(O.InputParams.from_dict(pd)), period, self._p(prev, C.c_float), self._p(cur, C.c_float),
+                                         len(prev), self._p(out, C.c_double)), "excite")
+        return out
+
+    def lane_fir(self, pd, seq, exact=False, ahead=0):
+        seq = np.ascontiguousarray(seq, dtype=f32)
+        assert seq.ndim == 3 and seq.shape[2] == 2
+        out = np.zeros(seq.shape[:2] + (2,), dtype=f32)
+        self._ok(self.L.trm_probe_lane_fir(C.byref(O.InputParams.from_dict(pd)), int(exact), int(ahead), self._p(seq, C.c_float), seq.shape[0],
+                                           seq.shape[1], self._p(out, C.c_float)), "lane_fir")
+        return out
+
+    def cvt(self, rings, rows, items, exact=False):
+        rings = np.ascontiguousarray(rings, dtype=f32)
+        rows = np.ascontiguousarray(rows, dtype=f32)
+        items = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1, 4)
+        assert rings.ndim == 2 and rows.shape == (65536, 32)
+        out = np.zeros((len(items), 4), dtype=f32)
+        self._ok(self.L.trm_probe_cvt(int(exact), self._p(rings, C.c_float), len(rings), self._p(rows, C.c_float), self._p(items, C.c_uint32),
+                                      len(items), self._p(out, C.c_float)), "cvt")
         return out
 
     # ---- the host build's own
@@ -1351,3 +1390,433 @@ def check_src_clock(P, H):
         assert np.array_equal(cnt, want), "src_count_outputs (%s, increment %d, pad %d): ntube %d gives %d, the serial register %d" % (
             (P.label, inc, pad) + tuple(int(a[np.argmax(cnt != want)]) for a in (nt, cnt, want)))
     return {}
+
+
+# ================================================================ 14, 15: the tracks at every sample of a control period
+TRACK_PERIODS = (1, 5, 16, 20, 24, 79, 139, 200, 395)          # 1: the smallest build_const admits
+EXP2_D = 6 * EPS64                 # exp2 in double: 3 ulp is what an OpenCL-conformant device library promises; glibc's is below 1
+FLUSH = 2.0 ** -126                # a product below the smallest normal float may come back as 0
+
+
+def period_params(cp):
+    """Monet's defaults at the control rate that gives a control period of `cp` samples (TRMTubeModel.m:200; the tube runs at
+    19 794 Hz for every one of them)."""
+    speed = 331.4 + 0.6 * MONET["temperature"]
+    pd = dict(MONET, controlRate=float(f32(speed * 1000.0 / (MONET["length"] * cp))))
+    rc, d = O.derive(O.InputParams.from_dict(pd))
+    assert rc == 0 and d["controlPeriod"] == cp, (cp, d)
+    return pd
+
+
+def _ramp(a, b):
+    return (float(a), float(b))
+
+
+def _near(x, toward):
+    return float(np.nextafter(f32(x), f32(toward)))
+
+
+# (glottal volume | aspiration volume) ramps, dB: inside (0, 60); across 0 and across 60 both ways; the ties found on the CPU -- at
+# control periods 20 and 24 the running sum and the closed form land on different sides of a clamp --; held at 0, at 60 and at the
+# floats beside each
+LEVEL_RAMPS = [_ramp(20, 45), _ramp(45, 20), _ramp(-5, 7), _ramp(7, -5), _ramp(50, 70), _ramp(70, 50),
+               _ramp(-1, 1), _ramp(-0.3, 0.3), _ramp(61, 59), _ramp(66, 58), _ramp(59.3, 60.7),
+               _ramp(0, 0), _ramp(60, 60), _ramp(_near(0, 1), _near(0, 1)), _ramp(_near(0, -1), _near(0, -1)),
+               _ramp(_near(60, 0), _near(60, 0)), _ramp(_near(60, 100), _near(60, 100))]
+PITCH_RAMPS = [_ramp(-24, 24), _ramp(24, -24), _ramp(-24, -24), _ramp(24, 24), _ramp(0, 0), _ramp(3.3, 3.3), _ramp(-12, -5.5)]
+
+
+def track_pairs(seed=47):
+    """(prev, cur, nan) fp32 [n,16] frame pairs and the columns that carry NaN [n,16].  Columns 0 - 2 (probe 15) cycle through
+    PITCH_RAMPS and LEVEL_RAMPS (the aspiration's list runs 5 entries ahead of the voicing's); columns 3 - 15 (probe 14):
+    neighbouring rows of the gnuspeech utterance that differ, radii 0 -> 4 and 4 -> 0, a radius through 0, the velum 0 <-> 1.5,
+    the frication position 0 -> 7.5 and back (every integer position is passed), the frication volume through 0 and through
+    60 dB, centre frequency and bandwidth across SR / 2 (9 897 Hz), every column rising, every column falling, one column NaN."""
+    rng = np.random.default_rng(seed)
+    rows = cases.load_gnuspeech_rows().astype(f32)
+    moving = [i for i in range(len(rows) - 1) if np.any(rows[i, 3:] != rows[i + 1, 3:])]
+    pick = [moving[i] for i in np.linspace(0, len(moving) - 1, 12).astype(int)]
+    base = np.asarray(cases.MONET_VOWEL_FRAME, dtype=np.float64)
+    prev, cur = [rows[i].astype(np.float64) for i in pick], [rows[i + 1].astype(np.float64) for i in pick]
+
+    def special(**cols):
+        a, b = base.copy(), base.copy()
+        for c, (x, y) in cols.items():
+            a[int(c[1:])], b[int(c[1:])] = x, y
+        prev.append(a)
+        cur.append(b)
+
+    special(**{"c%d" % c: ((0.0, 4.0) if c % 2 else (4.0, 0.0)) for c in range(7, 15)})
+    special(**{"c%d" % c: ((4.0, 0.0) if c % 2 else (0.0, 4.0)) for c in range(7, 15)})
+    special(c9=(-0.3, 0.5), c12=(0.25, -0.25))
+    special(c15=(0.0, 1.5))
+    special(c15=(1.5, 0.0))
+    special(c4=(0.0, 7.5), c3=(-3.0, 5.0))
+    special(c4=(7.5, 0.0), c3=(5.0, -3.0))
+    special(c3=(55.0, 66.0), c5=(8000.0, 12000.0), c6=(6000.0, 11000.0))
+    special(c3=(66.0, 55.0), c5=(12000.0, 8000.0), c6=(11000.0, 6000.0))
+    lo = np.array([0, 0, 0, 0.0, 0.0, 100.0, 50.0] + [0.05] * 8 + [0.0])
+    hi = np.array([0, 0, 0, 60.0, 7.0, 9000.0, 5000.0] + [3.0] * 8 + [1.5])
+    for _ in range(2):
+        a, b = rng.uniform(lo, lo + 0.45 * (hi - lo)), rng.uniform(lo + 0.55 * (hi - lo), hi)
+        prev += [a, b]                  # every column rising, then every column falling
+        cur += [b, a]
+    n_plain = len(prev)
+    nan_cols = (3, 5, 9, 15)
+    for c in nan_cols:
+        special(**{"c%d" % c: (np.nan, np.nan), "c8": (0.4, 1.7)})
+    prev, cur = np.array(prev), np.array(cur)
+    n = max(len(prev), len(LEVEL_RAMPS))
+    i = np.arange(n)
+    prev, cur = prev[i % len(prev)].copy(), cur[i % len(cur)].copy()
+    for k in range(n):
+        for col, ramps, shift in ((0, PITCH_RAMPS, 0), (1, LEVEL_RAMPS, 0), (2, LEVEL_RAMPS, 5)):
+            prev[k, col], cur[k, col] = ramps[(k + shift) % len(ramps)]
+    prev, cur = prev.astype(f32), cur.astype(f32)
+    nan = np.isnan(prev)
+    assert nan.any(axis=1).sum() >= len(nan_cols) and np.array_equal(nan, np.isnan(cur)) and n_plain >= 24
+    return prev, cur, nan
+
+
+_track_ref = {}
+
+
+def track_reference(cp):
+    """(params, prev, cur, nan, records [n, cp, TAP]): the oracle's tap record of every sample of the first of two control periods,
+    per frame pair (frames prev, cur, cur as doubles of the fp32 values; a NaN column is handed over as 0 -- the columns are
+    interpolated independently -- and never compared)."""
+    if cp not in _track_ref:
+        pd = period_params(cp)
+        ip = O.InputParams.from_dict(pd)
+        prev, cur, nan = track_pairs()
+        rec = np.zeros((len(prev), cp, O.TAP))
+        idx = np.arange(cp, dtype=np.int32)
+        for t in range(len(prev)):
+            a, b = np.where(nan[t], 0.0, prev[t].astype(np.float64)), np.where(nan[t], 0.0, cur[t].astype(np.float64))
+            with np.errstate(all="ignore"):
+                rec[t], _ = O.synthesize_states(ip, np.stack([a, b, b]), idx)
+        _track_ref[cp] = (pd, prev, cur, nan, rec)
+    return _track_ref[cp]
+
+
+def track_bar(prev, cur, cp, ref):
+    """The bar of fma(j, delta, base), delta = fl(fl(cur - prev) fl(1 / cp)), against the reference's prev + j additions of
+    (cur - prev) / cp in double, absolute, [n, cp, columns]; prev, cur [n, columns] fp32, ref [n, cp, columns] the oracle's values.
+      delta    the fp32 difference (U |cur - prev|), invControlPeriod's rounding and the product's: 3 U |cur - prev| / cp; a
+               product below the smallest normal float may be flushed: 2^-126
+      j delta  j times that (the product inside the FMA is not rounded)
+      the FMA  half an ulp of the value: U |value|
+      oracle   its delta carries one double rounding and each of its j additions another, of values no larger than the frames':
+               (j + 1) 2 EPS64 max(|prev|, |cur|) -- at most 396 x 2.2e-16 of the value, 1.5e-6 of U: negligible, and counted."""
+    a, b = prev.astype(np.float64)[:, None, :], cur.astype(np.float64)[:, None, :]
+    j = np.arange(cp, dtype=np.float64)[None, :, None]
+    d = np.abs(b - a)
+    return (3 * U * d * j / cp + U * np.abs(ref)) * SECOND_ORDER + j * FLUSH + (j + 1) * 2 * EPS64 * np.maximum(np.abs(a), np.abs(b)) + TINY
+
+
+def check_tracks(P):
+    """Probe 14: coef_track_setup and the interpolated values of coef_sample_area / coef_sample_fric at every j of nine control
+    periods against the reference's current control values."""
+    rep = {}
+    for cp in TRACK_PERIODS:
+        pd, prev, cur, nan, rec = track_reference(cp)
+        got, differ = P.track(pd, cp, prev, cur)
+        what = "tracks, control period %d (%s)" % (cp, P.label)
+        ref = rec[:, :, 43 + 3:43 + 16]
+        nanc = np.broadcast_to(nan[:, None, 3:], got.shape)
+        # exact: j = 0 hands back prev's columns; a NaN column is NaN at every j and no other column is
+        assert np.array_equal(got[:, 0, :][~nan[:, 3:]].view(np.uint32), prev[:, 3:][~nan[:, 3:]].view(np.uint32)), what + ": sample 0 is not the previous frame"
+        assert np.array_equal(np.isnan(got), nanc), what + ": NaN where no column carries one, or none where one does"
+        # exact: the only way j enters coef_sample -- both instances equal coef_sample at sample 0 of a held track of these values
+        assert not differ.any(), what + ": coef_sample(T, C, j) differs from coef_sample of the held values at %d (track, j), first %r" % (
+            np.count_nonzero(differ.any(axis=2)), tuple(np.argwhere(differ.any(axis=2))[0]))
+        bar = track_bar(prev[:, 3:], cur[:, 3:], cp, ref)
+        ratio = np.where(nanc, 0.0, np.abs(np.where(nanc, 0.0, got.astype(np.float64)) - ref) / bar)
+        t, j, c = np.unravel_index(np.argmax(ratio), ratio.shape)
+        assert ratio[t, j, c] <= 1.0, what + ": column %d of pair %d at j = %d is %r, the reference's %r: error %.3e, bar %.3e" % (
+            c + 3, t, j, got[t, j, c], ref[t, j, c], abs(got[t, j, c] - ref[t, j, c]), bar[t, j, c])
+        rep["interpolated value, of its bar"] = (max(float(ratio.max()), rep.get("interpolated value, of its bar", (0.0, 1.0))[0]), 1.0)
+        # (the same in plain units: the error and the bar over the larger of the two frames' values, 4 U + at the most)
+        scale = np.maximum(np.abs(prev[:, None, 3:]), np.abs(cur[:, None, 3:])).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            e = np.where(nanc | (scale == 0.0), 0.0, np.abs(np.where(nanc, 0.0, got.astype(np.float64)) - ref) / scale)
+            b = np.where(nanc | (scale == 0.0), 0.0, bar / scale)
+        key = "error / max(|prev|, |cur|)"
+        rep[key] = (max(float(e.max()), rep.get(key, (0.0, 0.0))[0]), max(float(b.max()), rep.get(key, (0.0, 0.0))[1]))
+    return show(P, "tracks", rep)
+
+
+def _amp_ref(db):
+    return np.array([O.lib().trm_oracle_amplitude(float(x)) for x in np.ravel(db)]).reshape(np.shape(db))
+
+
+def check_excite(P):
+    """Probe 15: the amplitude of voicing, the aspiration amplitude and f0 at every sample of a control period, as osc_sample
+    forms them (running sums and products from j = 0) and as the four- and eight-lane oscillator waves do (set up at the lane's
+    own j, stepped 4 / 8 samples at a time), against the reference's ax, ah1 and frequency."""
+    rep = {}
+    k_db = np.log(10.0) / 20.0
+    forms = ("osc_sample", "slots of 4", "slots of 8")
+    excluded_total = 0
+    for cp in TRACK_PERIODS:
+        pd, prev, cur, nan, rec = track_reference(cp)
+        got = P.excite(pd, cp, prev, cur)
+        tnd = P.const(pd)["tnDelta"]
+        assert tnd > 0
+        what = "excitation tracks, control period %d (%s)" % (cp, P.label)
+        j = np.arange(cp, dtype=np.float64)[None, :]
+        r_ax, r_ah1, r_f0 = rec[:, :, O.T_AX], rec[:, :, O.T_AH1], rec[:, :, O.T_F0]
+        r_glot, r_asp = rec[:, :, 43 + 1], rec[:, :, 43 + 2]
+        a64, b64 = prev.astype(np.float64), cur.astype(np.float64)
+        # ---- ax.  Relative: the float's rounding (U), and the geometric sequences' growth in double, per sample: the ratio's
+        # exp2 (EXP2_D) and the product, two roundings a sample at most in the bits-of-j form (EXP2_D + 2 EPS64); the reference's
+        # dB value carries j additions' roundings of values up to M = max(|prev|, |cur|), which its pow() turns into
+        # ln(10)/20 M j EPS64.  Once: the first exp2 and its argument's three roundings ((v0 - 60) k: 3 EPS64 ln 2 |x| <= 21 EPS64),
+        # the ratio's argument over the period (3 EPS64 ln 2 k |cur - prev| j / cp), the reference's pow() and its argument (16 EPS64)
+        m_glot = np.maximum(np.abs(a64[:, 1]), np.abs(b64[:, 1]))[:, None]
+        d_glot = np.abs(b64[:, 1] - a64[:, 1])[:, None]
+        ax_bar = U + (j * (EXP2_D + 2 * EPS64 + k_db * m_glot * EPS64) + EXP2_D + 21 * EPS64 + 3 * EPS64 * np.log(2.0) * LOG2_10_20 * d_glot * j / cp + 16 * EPS64)
+        # ---- f0 = 220 2^((p + 3) / 12), the same construction: |pitch| <= 24, (p0 + 3) / 12 <= 2.25
+        d_pitch = np.abs(b64[:, 0] - a64[:, 0])[:, None]
+        f0_bar = j * (EXP2_D + 2 * EPS64 + np.log(2.0) / 12.0 * 24.0 * EPS64) + EXP2_D + (3 * np.log(2.0) * 2.25 + 1) * EPS64 + 3 * EPS64 * np.log(2.0) / 12.0 * d_pitch * j / cp + 8 * EPS64
+        # ---- ah1 = amplitude_f of the interpolated level: AMP_REL, and the level's own bar (probe 14's) through 10^(dB / 20)
+        asp_bar_db = track_bar(prev[:, 2:3], cur[:, 2:3], cp, r_asp[:, :, None])[:, :, 0]
+        ah1_bar = AMP_REL + k_db * asp_bar_db
+        moves = (prev[:, 2] != cur[:, 2])[:, None]
+        crosses = ((a64[:, 2] < 0) != (b64[:, 2] < 0)) | ((a64[:, 2] <= 0) != (b64[:, 2] <= 0))
+        tiny = ((a64[:, 2] > 0) & (a64[:, 2] < float(T100)) & ~moves[:, 0])          # held inside (0, 2^-100): amplitude_f's documented exclusion
+        # the reference jumps from 0 to 10^-3 at 0+: a sample of a MOVING level whose reference dB lies within the level's bar of 0
+        # is held to "exactly 0, or amplitude_f of the device's own level"; at most one per ramp that crosses 0, none otherwise
+        near0 = moves & (np.abs(r_asp) <= asp_bar_db)
+        per_ramp = near0.sum(axis=1)
+        assert np.all(per_ramp <= np.where(crosses, 1, 0)), what + ": %r samples within the interpolation bar of 0 dB per ramp" % per_ramp.tolist()
+        excluded_total += int(per_ramp.sum())
+        # the device's own level, fp32: base + j delta with delta = fl(fl(cur - prev) fl(1 / cp)) (exact for a held level)
+        delta32 = ((cur[:, 2] - prev[:, 2]).astype(f32) * f32(1.0 / cp)).astype(f32)
+        level32 = (j * delta32.astype(np.float64)[:, None] + a64[:, 2][:, None]).astype(f32)
+        own = P.amplitude(level32.ravel()).reshape(level32.shape).astype(np.float64)
+        for f, fname in enumerate(forms):
+            ax, ah1, f0 = got[:, :, 3 * f], got[:, :, 3 * f + 1], got[:, :, 3 * f + 2]
+            w = "%s, %s" % (what, fname)
+            ax32 = ax.astype(f32).astype(np.float64)
+            if f == 0:
+                assert np.array_equal(ax32, got[:, :, 9]), w + ": osc_sample's ax is not the rounding of excite_track_ax"
+            # exact: the reference's decision at both clamps, its absorption of 0 < dB <= 2^-48 included
+            z, one = r_ax == 0.0, r_ax == 1.0
+            assert np.all(ax[z] == 0.0), w + ": ax is not 0 at %d samples where the reference's is (first: pair %d, j = %d, ax %r, reference dB %r)" % (
+                (np.count_nonzero(ax[z]),) + tuple(np.argwhere(z & (ax != 0.0))[0]) + (ax[z & (ax != 0.0)][0], r_glot[z & (ax != 0.0)][0]))
+            assert np.all(ax32[one] == 1.0), w + ": ax is not 1 at %d samples where the reference's is" % np.count_nonzero(ax32[one] != 1.0)
+            r = _rel(ax32, r_ax)
+            t, jj = np.unravel_index(np.argmax(r / ax_bar), r.shape)
+            assert r[t, jj] <= ax_bar[t, jj], w + ": ax of pair %d at j = %d is %r, the reference's %r (dB %r): relative %.3e, bar %.3e" % (
+                t, jj, ax[t, jj], r_ax[t, jj], r_glot[t, jj], r[t, jj], ax_bar[t, jj])
+            inside = ~z & ~one
+            rd = np.where(inside, np.abs(ax - r_ax) / np.where(inside, r_ax, 1.0), 0.0)
+            geo = ax_bar - U
+            assert np.all(rd <= geo), w + ": ax in double, relative %.3e of a bar of %.3e" % (rd.max(), geo.flat[np.argmax(rd / geo)])
+            rf = np.abs(f0 - r_f0) / r_f0
+            assert np.all(rf <= f0_bar), w + ": f0 relative %.3e, bar %.3e" % (rf.max(), f0_bar.flat[np.argmax(rf / f0_bar)])
+            # ah1
+            ok0 = (ah1 == 0.0) | (np.abs(ah1 - own) <= AMP_REL * own)
+            assert np.all(ok0[near0]), w + ": ah1 beside 0 dB is neither 0 nor amplitude_f of its own level"
+            assert np.array_equal(ah1[tiny], own[tiny]), w + ": ah1 of a level held inside (0, 2^-100)"
+            skip = near0 | tiny[:, None]
+            ra = np.where(skip, 0.0, _rel(ah1, r_ah1))
+            t, jj = np.unravel_index(np.argmax(ra / ah1_bar), ra.shape)
+            assert ra[t, jj] <= ah1_bar[t, jj], w + ": ah1 of pair %d at j = %d is %r, the reference's %r (dB %r): relative %.3e, bar %.3e" % (
+                t, jj, ah1[t, jj], r_ah1[t, jj], r_asp[t, jj], ra[t, jj], ah1_bar[t, jj])
+            for key, worst, bar in (("ax (float), of its bar", (r / ax_bar).max(), 1.0), ("ax (double) growth, of its bar", (rd / geo).max(), 1.0),
+                                    ("f0, of its bar", (rf / f0_bar).max(), 1.0), ("ah1, of its bar", (ra / ah1_bar).max(), 1.0),
+                                    ("ax (double), relative", rd.max(), float(geo.max())), ("f0, relative", rf.max(), float(f0_bar.max())),
+                                    ("ah1, relative", ra.max(), float(ah1_bar.max()))):
+                rep[key] = (max(float(worst), rep.get(key, (0.0, bar))[0]), max(bar, rep.get(key, (0.0, bar))[1]))
+        # the closure point: where the three forms and the reference stand on the same side of both clamps, rint(ax tnDelta) is the
+        # reference's at every sample
+        side = [np.where(got[:, :, 3 * f] == 0.0, 0, np.where(got[:, :, 3 * f] == 1.0, 2, 1)) for f in range(3)]
+        same = (side[0] == side[1]) & (side[1] == side[2])
+        for f, fname in enumerate(forms):
+            cl, rcl = np.rint(got[:, :, 3 * f] * tnd), np.rint(r_ax * tnd)
+            assert np.array_equal(cl[same], rcl[same]), "%s, %s: the closure point differs from the reference's at %d samples" % (what, fname, np.count_nonzero(cl[same] != rcl[same]))
+        print("%s: the three forms stand on different sides of a clamp at %d samples" % (what, np.count_nonzero(~same)))
+    print("excitation tracks (%s): %d samples beside 0 dB taken out of ah1's relative bar" % (P.label, excluded_total))
+    return show(P, "excite", rep)
+
+
+# ================================================================ 16: the lane forms' FIR
+LANE_FIR_STEPS = 200                                  # past two laps of the ring of 64
+LANE_FIR_IMPULSES = (0, 1, 38, 41, 66, 67, 127, 130)  # both parities; windows inside the ring, across its end (the mirror), after a lap
+LANE_FIR_AHEAD = (0, 15, 38)                          # samples between the ring's store and its read: none, trm_oct.hip's most, the ring's most
+
+
+def lane_fir_reference(taps, seq):
+    """float64 convolution of fp32 sequences with the 49 taps (fir_reference's), and sum |c x| with each term weighted by the
+    rounded operations it passes through in fir_direct / fir_window_dot (trm_quad.h): window slot w = 24 + o - k (o = m & 1) is
+    term p = w // 2 of one of four chains of 13; the chain's first term is a rounded product and every later one a rounded FMA,
+    so term p passes through 13 - p roundings (13 for p = 0), then the two final sums, and the tap's own rounding to float."""
+    x = seq.astype(np.float64)
+    n, steps = x.shape[:2]
+    y, weighted = np.zeros((n, steps)), np.zeros((n, steps))
+    m = np.arange(steps)
+    for i in range(49):
+        src = x[:, :, 1] if i % 2 == 0 else x[:, :, 0]
+        k = i // 2
+        term = np.zeros((n, steps))
+        term[:, k:] = taps[i] * src[:, :steps - k]
+        y += term
+        p = (24 + (m & 1) - k) // 2
+        weighted += np.abs(term) * (np.where(p == 0, 13, 13 - p) + 3)[None, :]
+    return y, weighted
+
+
+def check_lane_fir(P, host=None, exact_builds=(False,)):
+    """Probe 16.  `host`: the host build beside a device build (fir_direct of the device's ring == fir_direct of the host's
+    unrolled sequence, bit for bit); with the host build alone the ring is not run and fir_direct is held to the reference."""
+    taps = O.fir_taps()
+    device = host is not None
+    imp = np.zeros((2 * len(LANE_FIR_IMPULSES), LANE_FIR_STEPS, 2), dtype=f32)
+    want = np.zeros(imp.shape[:2], dtype=f32)
+    crossing = set()
+    for q, s in enumerate(LANE_FIR_IMPULSES):
+        imp[2 * q, s, 0] = imp[2 * q + 1, s, 1] = 1.0
+        want[2 * q, s:s + 24], want[2 * q + 1, s:s + 25] = taps[1::2].astype(f32), taps[0::2].astype(f32)
+        for m in range(s, s + 25):
+            first = m - 24 - (m & 1)
+            if first >= 0 and first // 64 != (first + 25) // 64:
+                crossing.add(s & 1)
+    assert crossing == {0, 1}                       # an impulse of each parity is read through a window that runs past the ring's end
+    rnd = fir_sequences()[:, :LANE_FIR_STEPS]
+    ref, weighted = lane_fir_reference(taps, rnd)
+    bar = U * weighted * SECOND_ORDER + TINY
+    mix = P.fir(FIR_PARAMS, rnd).astype(np.float64)
+    _, mix_weighted = fir_reference(taps, rnd)
+    mix_bar = U * mix_weighted * SECOND_ORDER + TINY
+    rep = {}
+    for exact in exact_builds:
+        for ahead in (LANE_FIR_AHEAD if device else (0,)):
+            what = "lane FIR (%s%s, %d ahead)" % (P.label, ", unfused object" if exact else "", ahead)
+            gi = P.lane_fir(MONET, imp, exact=exact, ahead=ahead)
+            gr = P.lane_fir(MONET, rnd, exact=exact, ahead=ahead)
+            for g in (gi, gr):
+                assert np.array_equal(g[:, :, 0].view(np.uint32), g[:, :, 1].view(np.uint32)), what + ": fir_window_dot != fir_direct at %d samples" % (
+                    np.count_nonzero(g[:, :, 0].view(np.uint32) != g[:, :, 1].view(np.uint32)))
+            for col, name in ((0, "fir_window_dot"), (1, "fir_direct")):
+                bad = np.argwhere(gi[:, :, col] != want)
+                assert len(bad) == 0, what + ": %s's response to impulse %d (%s) is not the oracle's taps from sample %d on" % (
+                    name, LANE_FIR_IMPULSES[bad[0][0] // 2], "ab"[bad[0][0] % 2], bad[0][1])
+            if device:
+                for g, x in ((gi, imp), (gr, rnd)):
+                    assert np.array_equal(g[:, :, 1], host.lane_fir(MONET, x)[:, :, 1]), what + ": fir_direct over the ring != fir_direct over the sequence (host build)"
+            got = gr[:, :, 0].astype(np.float64)
+            ratio, cross = np.abs(got - ref) / bar, np.abs(got - mix) / (bar + mix_bar)
+            assert ratio.max() <= 1.0, what + ": error %.3e at sequence %d, sample %d; bar %.3e" % (
+                (np.abs(got - ref).max(),) + np.unravel_index(np.argmax(ratio), ratio.shape) + (bar.flat[np.argmax(ratio)],))
+            assert cross.max() <= 1.0, what + ": differs from mix_sample by %.3f of the two bars' sum" % cross.max()
+            for key, w in (("output, of its bar", ratio.max()), ("against mix_sample, of the bars' sum", cross.max())):
+                rep[key] = (max(float(w), rep.get(key, (0.0, 1.0))[0]), 1.0)
+            rep["output, absolute"] = (float(np.abs(got - ref).max()), float(bar.max()))
+    return show(P, "lane fir", rep)
+
+
+# ================================================================ 17: the lane forms' converter fetch (device only)
+Y_RING, Y_MIRROR, Y_STRIDE, Q_LEAD = 128, 32, 164, 28        # trm_devutil.h, trm_quad_dev.h: the tube-rate ring of one voice
+CVT_INCS = (16384, 17000, 29350, 65011, 65535, 65536)
+CVT_NBASE = (0, 1, 2, 3, 1000003)                            # the launch's first tube sample: 0 .. 3, and a stream chunk's
+CVT_RUN = 48                                                 # consecutive outputs per (increment, nBase)
+
+
+def cvt_ring(sample_of, last):
+    """The ring after the launch's tube samples 0 .. last were stored the kernels' way from a zeroed ring: sample n in slot
+    (n + Q_LEAD) & (Y_RING - 1), and once more Y_RING slots on where that slot is below Y_MIRROR."""
+    ring = np.zeros(Y_STRIDE, dtype=f32)
+    for n in range(max(0, last - Y_RING + 1), last + 1):
+        slot = (n + Q_LEAD) & (Y_RING - 1)
+        ring[slot] = sample_of(n)
+        if slot < Y_MIRROR:
+            ring[slot + Y_RING] = ring[slot]
+    return ring
+
+
+def cvt_items(seed=53):
+    """(rings [r, Y_STRIDE], items [n, 4] = (ring, k, inc, nBase), windows [n, 26] the output's samples pos - 25 .. pos,
+    one_hot [n] = the window index that is 1, or -1): runs of consecutive outputs for every increment and nBase over a random
+    sequence; outputs at phase 0 and at phase 0xFFFF with every shift 0 .. 3; and for one output of each shift and both of those
+    phases, 26 rings that are 1 at one sample of its window and 0 elsewhere."""
+    rng = np.random.default_rng(seed)
+    table = rng.uniform(-1.0, 1.0, 4093).astype(f32)
+    rings, items, wins, hot = [], [], [], []
+
+    def pos_of(k, inc, nbase):
+        return ((k * inc) >> 16) - nbase
+
+    def add(k, inc, nbase, one=None):
+        pos = pos_of(k, inc, nbase)
+        assert pos >= 0
+        f = (lambda n: f32(1.0 if n == pos - 25 + one else 0.0)) if one is not None else (lambda n: table[(n + nbase) % 4093])
+        rings.append(cvt_ring(f, pos + 2))                 # (two samples past the output's newest: the tube wave is ahead)
+        items.append((len(rings) - 1, k, inc, nbase))
+        wins.append([f(n) if n >= 0 else 0.0 for n in range(pos - 25, pos + 1)])
+        hot.append(-1 if one is None else one)
+
+    for inc in CVT_INCS:
+        for nbase in CVT_NBASE:
+            k0 = -((-nbase << 16) // inc)                   # the first output at or after the launch's first sample
+            for k in range(k0, k0 + CVT_RUN):
+                add(k, inc, nbase)
+        k = np.arange(1, 1 << 19, dtype=np.int64)
+        ph, pos = (k * inc) & 0xFFFF, (k * inc) >> 16
+        for phase in (0, 0xFFFF):
+            for nbase in (0, 1):
+                for off in range(4):
+                    hit = k[(ph == phase) & (pos - nbase >= 25) & (((pos - nbase + Q_LEAD - 25) & 3) == off)]
+                    if len(hit):
+                        add(int(hit[0]), inc, nbase)
+                        if nbase == 0 and inc in (65011, 65536):
+                            for one in range(26):
+                                add(int(hit[0]), inc, nbase, one)
+    return np.stack(rings), np.array(items, dtype=np.int64), np.array(wins, dtype=f32), np.array(hot)
+
+
+def check_cvt(P, rows, exact_builds=(False, True)):
+    """Probe 17: cvt_window_base / cvt_row_shift + cvt_window_dot as the four- and eight-lane convert waves use them."""
+    rings, items, wins, hot = cvt_items()
+    k, inc, nbase = items[:, 1], items[:, 2], items[:, 3]
+    phase, pos = (k * inc) & 0xFFFF, ((k * inc) >> 16) - nbase
+    off = (pos + Q_LEAD - 25) & 3
+    wraps = ((pos + Q_LEAD - 25) & (Y_RING - 1) & ~3) + 32 > Y_RING
+    for ph in (0, 0xFFFF):
+        assert set(off[phase == ph]) == {0, 1, 2, 3}, "the items do not reach every shift at phase %#x" % ph
+    assert set(off[wraps]) == {0, 1, 2, 3} and len(rings) <= 4096
+    assert set(zip(off[hot >= 0], hot[hot >= 0])) == {(o, i) for o in range(4) for i in range(26)}
+    h, dh = O.src_tables()
+
+    def wing(g, i):
+        fi = (g >> 8) + 256 * i
+        return h[fi] + dh[fi] * ((g & 255).astype(np.float64) / 256.0)
+    coef = np.zeros((len(items), 26))                       # the reference's coefficients in double (check_src_rows: rows are their floats)
+    for i in range(13):
+        coef[:, 12 - i], coef[:, 13 + i] = wing(phase, i), wing(0xFFFF - phase, i)
+    c32 = rows[phase, :26]
+    prod = wins.astype(np.float64) * c32.astype(np.float64)
+    ref, mag = prod.sum(axis=1), np.abs(prod).sum(axis=1)
+    oracle = (wins.astype(np.float64) * coef).sum(axis=1)
+    b32, b26 = U * SRC_DOT32_BAR * mag + TINY, U * SRC_DOT_BAR * mag + TINY
+    rep = {}
+    for exact in exact_builds:
+        what = "converter fetch (%s%s)" % (P.label, ", unfused object" if exact else "")
+        got = P.cvt(rings, rows, items.astype(np.uint32), exact=exact)
+        dot, dot32, dot26, outside = (got[:, c] for c in range(4))
+        assert np.array_equal(dot.view(np.uint32), dot32.view(np.uint32)), what + ": cvt_window_dot != src_dot32 at %d outputs" % np.count_nonzero(dot.view(np.uint32) != dot32.view(np.uint32))
+        assert np.all(outside == 0.0), what + ": terms outside the output's 26 contribute at %d outputs" % np.count_nonzero(outside)
+        one = hot >= 0
+        want = c32[one, hot[one]]
+        bad = np.nonzero(dot[one] != want)[0]
+        assert len(bad) == 0, what + ": a ring that is 1 at window sample i gives another coefficient than i of the output's row at %d of %d (first: shift %d, i = %d)" % (
+            len(bad), one.sum(), off[one][bad[0]] if len(bad) else -1, hot[one][bad[0]] if len(bad) else -1)
+        r32, r26 = np.abs(dot.astype(np.float64) - ref) / b32, np.abs(dot26.astype(np.float64) - ref) / b26
+        rx = np.abs(dot.astype(np.float64) - dot26) / (b32 + b26)
+        ro = np.abs(dot.astype(np.float64) - oracle) / (b32 + U * mag)          # + the coefficients' own rounding to float
+        assert max(r32.max(), r26.max(), rx.max(), ro.max()) <= 1.0, what + ": %.3f, %.3f, %.3f, %.3f of their bars" % (r32.max(), r26.max(), rx.max(), ro.max())
+        for key, w in (("cvt_window_dot, of src_dot32's bar", r32.max()), ("src_dot on the unaligned window, of its bar", r26.max()),
+                       ("cvt_window_dot - src_dot, of the bars' sum", rx.max()), ("against the oracle's coefficients, of its bar", ro.max())):
+            rep[key] = (max(float(w), rep.get(key, (0.0, 1.0))[0]), 1.0)
+    return show(P, "cvt", rep)

@@ -103,3 +103,25 @@ def test_src_dot(P, H):
 
 def test_src_clock_and_counts(P, H):
     S.check_src_clock(P, H)
+
+
+# ---- probes 14 - 17: per-period tracks and the lane forms' dot products
+def test_coefficient_tracks_at_every_sample(P):
+    """coef_track_setup and coef_track_at at every j of nine control periods against the reference's current control values."""
+    S.check_tracks(P)
+
+
+def test_excitation_tracks_at_every_sample(P):
+    """ax, ah1 and f0 as osc_sample forms them and as the four- and eight-lane oscillator waves do, against the reference's."""
+    S.check_excite(P)
+
+
+def test_lane_fir(P, H):
+    """fir_window_dot over the LDS ring's geometry (osc_ring_store, mirror included; osc_ring_window_start) against fir_direct, bit
+    for bit, in the object with the product's flags and in the one without the compiler's own fusion; against the oracle's taps."""
+    S.check_lane_fir(P, host=H, exact_builds=(False, True))
+
+
+def test_converter_fetch(P, H):
+    """cvt_window_base / cvt_row_shift + cvt_window_dot against src_dot32, bit for bit, and one-hot rings against the row."""
+    S.check_cvt(P, H.src_tables()[2], exact_builds=(False, True))

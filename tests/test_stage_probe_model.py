@@ -98,3 +98,17 @@ def test_src_dot(P, src_rows):
 
 def test_src_clock_and_counts(P):
     S.check_src_clock(P, P)
+
+
+# ---- probes 14 - 16: per-period tracks and the lane forms' FIR (probe 17 runs what only the kernels run: tests/test_stage_probe_gpu.py)
+def test_coefficient_tracks_at_every_sample(P):
+    S.check_tracks(P)
+
+
+def test_excitation_tracks_at_every_sample(P):
+    S.check_excite(P)
+
+
+def test_lane_fir(P):
+    """fir_direct with fir_window_tap_a / _b over the sequence with its zeros in front, as the host model runs it."""
+    S.check_lane_fir(P)
