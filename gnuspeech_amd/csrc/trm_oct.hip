@@ -15,6 +15,9 @@
 // scans on i-2, tube on i-4, convert on whatever is complete, metered.  No streaming instance (trm_quad.hip carries streams);
 // trm_oct_seg.hip builds the time-split instance (kSeg below), which serves uniform and mixed batches alike: a mixed split is a
 // run-time property of that instance's launch, read in its prologue.
+// What the six roles share with trm_quad.hip is stated once, in trm_roles.h (the scans, the frame ring's read, the time base, the
+// noise request, the row stager's store, the convert wave's block begin, row pair and hand-shake); what this file still spells
+// like trm_quad.hip -- the stager's loop, the metering, the drain, the maximum, the tube wave's store -- is listed in DESIGN.md.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,6 +28,7 @@
 #include "trm_quad.h"
 #include "trm_quad_dev.h"
 #include "trm_span.h"
+#include "trm_roles.h"
 
 #ifndef TRM_EXPERIMENTS
 #undef TRM_OCT_ROLE_PERM
@@ -97,22 +101,6 @@ __device__ __forceinline__ HalfPair across_halves(float x)
 {
     const HalfPairU r = across_halves(__builtin_bit_cast(unsigned, x));
     return HalfPair{__builtin_bit_cast(float, r.lo), __builtin_bit_cast(float, r.hi)};
-}
-
-// The launch's output k: the tube sample its window ends at, counted from the launch's first (src_position: trm_lane.h), and its
-// converter phase.  In the segment instance (kSeg, below) the output's index in the utterance is kBase + k and the launch's
-// first tube sample is nBase; otherwise both are 0 and the arguments unused.
-template <bool kSeg>
-__device__ __forceinline__ uint32_t seg_out_position(uint32_t inc, uint32_t kBase, uint32_t nBase, uint32_t k)
-{
-    if constexpr (kSeg) return src_position(kBase + k, inc) - nBase;
-    else return src_position(k, inc);
-}
-template <bool kSeg>
-__device__ __forceinline__ uint32_t seg_out_phase(uint32_t inc, uint32_t kBase, uint32_t k)
-{
-    if constexpr (kSeg) return src_phase(kBase + k, inc);
-    else return src_phase(k, inc);
 }
 
 // kMix: a launch whose workgroups may belong to different parameter sets (trm_kernels.h, TubeArgs::mix_map): the
@@ -231,13 +219,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     auto x_at = [&](int arr, uint32_t blk, int s) -> float & { return sX[arr * kOXArray + ((blk % kXDepth) * kOB + s) * kOV + vq]; };
 
     // this lane's voice's frame f (nominal index: past the voice's last frame the stager repeats it), quarter q
-    auto frame_q = [&](uint32_t f, int q) { return sF[((f % kFrameRing) * kOV + vq) * 4 + q]; };
-    auto frame_to = [&](uint32_t f, float *dst, int quads) {
-        for (int q = 0; q < quads; q++) {
-            const float4 x = frame_q(f, q);
-            dst[4 * q] = x.x; dst[4 * q + 1] = x.y; dst[4 * q + 2] = x.z; dst[4 * q + 3] = x.w;
-        }
-    };
+    auto frame_to = [&](uint32_t f, float *dst, int quads) { trm::frame_to<kFrameRing, kOV>(sF, vq, f, dst, quads); };
     // the stager's lanes (area wave, lanes 0-31): lane -> (voice lane / 4, quarter lane % 4) of the workgroup's 8 frames
     const float *stageSrc = nullptr;
     uint32_t stageNfr = 0;
@@ -272,40 +254,20 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
     }
     __syncthreads();
 
-    // The two recurrences that only FEED the tube (frication band-pass, throat low-pass) run in feed-forward waves,
-    // serially over a voice's slots: slot s's output is slot s+1's y1 and slot s+2's y2.  A pass of four turns settles
-    // the four slots of a block (a lane's evaluation is final from its own turn on); the step's two blocks are two passes:
-    // the first settles lanes 0-31, its end state crosses to lanes 32-63, the second settles those, and their end state
-    // crosses back for the next step.
-    struct ScanState { float by1, by2, ny1, ny2, prevSig, thY, thNext; };
+    // The two scans (trm_roles.h): a pass of four turns settles the four slots of a block; the step's two blocks are two
+    // passes: the first settles lanes 0-31, its end state crosses to lanes 32-63, the second settles those, and their end
+    // state crosses back for the next step.
     auto scans_reset = [&](ScanState &Z) { Z.by1 = Z.by2 = Z.ny1 = Z.ny2 = Z.prevSig = Z.thY = Z.thNext = 0.0f; };
-    // band-pass (TRMFilters.m:19-29) of one block of four: the lane's input `sig`, coefficients bp = {2 alpha, 2 beta, 2 gamma}
-    auto bandpass_pass = [&](ScanState &Z, float sig, const float4 bp) {
-        const float X = q_take<0, kPart2 | kPart3>(sig, Z.prevSig);         // slots 0, 1 look into the previous block
-        const float x2 = q_take<2, kPartAll>(X, X);
-        float f = 0.0f;
-#pragma unroll
-        for (int t = 0; t < kSlots; t++) {
-            f = bandpass_eval<float>(bp.x, bp.y, bp.z, sig, x2, Z.by1, Z.by2);
-            if (t == 0) { Z.by1 = q_take<1, kPart1>(Z.by1, f); Z.by2 = q_take<2, kPart2>(Z.by2, f); }
-            if (t == 1) { Z.by1 = q_take<1, kPart2>(Z.by1, f); Z.by2 = q_take<2, kPart3>(Z.by2, f); }
-            if (t == 2) { Z.by1 = q_take<1, kPart3>(Z.by1, f); Z.ny2 = q_take<2, kPart0>(Z.ny2, f); }
-            if (t == 3) { Z.ny1 = q_take<1, kPart0>(Z.ny1, f); Z.ny2 = q_take<2, kPart1>(Z.ny2, f); }
-        }
-        Z.by1 = q_take<0, kPart0>(Z.by1, Z.ny1);
-        Z.by2 = q_take<0, kPart0 | kPart1>(Z.by2, Z.ny2);
-        Z.prevSig = sig;
-        return f;
-    };
+    // band-pass of the step's two blocks: the lane's input `sig`, coefficients bp = {2 alpha, 2 beta, 2 gamma}
     auto bandpass_scan = [&](ScanState &Z, float sig, const float4 bp) {
-        const float fLo = bandpass_pass(Z, sig, bp);            // final in lanes 0-31
+        const float fLo = bandpass_block(Z, sig, bp);           // final in lanes 0-31
         {   // the first block's end state -> the second block's lanes
             const HalfPair a = across_halves(Z.by1), b = across_halves(Z.by2), c = across_halves(Z.prevSig);
             Z.by1 = upperHalf ? a.lo : Z.by1;
             Z.by2 = upperHalf ? b.lo : Z.by2;
             Z.prevSig = upperHalf ? c.lo : Z.prevSig;
         }
-        const float fHi = bandpass_pass(Z, sig, bp);            // final in lanes 32-63
+        const float fHi = bandpass_block(Z, sig, bp);           // final in lanes 32-63
         {   // the second block's end state -> the first block's lanes, for the next step
             const HalfPair a = across_halves(Z.by1), b = across_halves(Z.by2), c = across_halves(Z.prevSig);
             Z.by1 = upperHalf ? Z.by1 : a.hi;
@@ -314,24 +276,11 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         }
         return upperHalf ? fHi : fLo;
     };
-    // throat low-pass (:341, TRMFilters.m:72-77) over this lane's input `thr`
-    auto throat_pass = [&](ScanState &Z, float thr) {
-        float ty = 0.0f;
-#pragma unroll
-        for (int t = 0; t < kSlots; t++) {
-            ty = throat_eval<float>(C, thr, Z.thY);
-            if (t == 0) Z.thY = q_take<1, kPart1>(Z.thY, ty);
-            if (t == 1) Z.thY = q_take<1, kPart2>(Z.thY, ty);
-            if (t == 2) Z.thY = q_take<1, kPart3>(Z.thY, ty);
-            if (t == 3) Z.thNext = q_take<1, kPart0>(Z.thNext, ty);
-        }
-        Z.thY = q_take<0, kPart0>(Z.thY, Z.thNext);
-        return ty;
-    };
+    // throat low-pass over this lane's input `thr`
     auto throat_scan = [&](ScanState &Z, float thr) {
-        const float tLo = throat_pass(Z, thr);
+        const float tLo = throat_block(C, Z, thr);
         { const HalfPair a = across_halves(Z.thY); Z.thY = upperHalf ? a.lo : Z.thY; }
-        const float tHi = throat_pass(Z, thr);
+        const float tHi = throat_block(C, Z, thr);
         { const HalfPair a = across_halves(Z.thY); Z.thY = upperHalf ? Z.thY : a.hi; }
         return upperHalf ? tHi : tLo;
     };
@@ -450,12 +399,12 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         __builtin_amdgcn_s_setprio(TRM_OCT_PRIO_MIX);
 #endif
         // ------------------------------------------------------------ mix: block i-1 at step i, lane = (voice, slot)
+        // window taps of this lane's parity (m & 1 == slot & 1: steps start on multiples of 8), as (a, b) pairs
         auto fill_noise_half = [&](uint32_t nFirst, int half) {
             // (the noise sequence is addressed by the utterance's sample index)
-            if constexpr (kSeg) dma4(A.lp_noise + nBase + nFirst + lane, &sNoise[half * kNoiseHalf]);
-            else dma4(A.lp_noise + nFirst + lane, &sNoise[half * kNoiseHalf]);
+            if constexpr (kSeg) trm::fill_noise_half(A.lp_noise + nBase, sNoise, lane, nFirst, half);
+            else trm::fill_noise_half(A.lp_noise, sNoise, lane, nFirst, half);
         };
-        // window taps of this lane's parity (m & 1 == slot & 1: steps start on multiples of 8), as (a, b) pairs
         const int o = slot & 1;
         v2f cab[kFirWin];
         for (int i = 0; i < kFirWin; i++)
@@ -467,9 +416,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
             dma_wait_all();
         }
         const float2 *const ring = &sO[vq * kOStride];
-        // Converter coefficient rows, staged for the convert wave (see trm_quad.hip): block B's 32 rows are loaded when the
-        // oscillator's time is within 4 samples of the block's first output, written to LDS one step later and visible
-        // one step after that; sRowSync[1] = blocks staged, sRowSync[0] = the first block the convert wave has not copied yet.
+        // the converter's coefficient rows, staged for the convert wave (trm_roles.h, rows_to_lds)
         uint32_t rowBlk = 0;
         bool rowsInFlight = false;
         float4 rq[4];
@@ -482,19 +429,19 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         for (uint32_t step = 0; step < nSteps; step++) {
             STAMP_BEGIN
             auto rows_to_lds = [&]() {
-                float4 *dst = reinterpret_cast<float4 *>(&sRows[((rowBlk - 1) % kRowBufs) * (kCvtCols * kRowPitch) + (lane >> 1) * kRowPitch + (lane & 1) * 16]);
-                for (int q = 0; q < 4; q++) dst[q] = rq[q];
+                trm::rows_to_lds(sRows, sRowSync, lane, rowBlk, rq);
                 rowsInFlight = false;
-                lds_flag_publish(&sRowSync[1], rowBlk, lane == 0);     // blocks 0 .. rowBlk-1 are in LDS
             };
             if (rowsInFlight) rows_to_lds();
+            // never more than kRowBufs blocks past the first one the convert wave still has to copy (looked up only
+            // when a block is due: about once per block).  Up to two blocks per step (rate ratios above 4).
             for (int r = 0; r < 2; r++) {
-                if (rowBlk < cvtBlocks && seg_out_position<kSeg>(inc, kBase, nBase, rowBlk * kCvtCols) <= step * kOB + 4u &&
+                if (rowBlk < cvtBlocks && out_position<kSeg>(inc, kBase, nBase, rowBlk * kCvtCols) <= step * kOB + 4u &&
                     rowBlk < lds_flag_consume(&sRowSync[0]) + kRowBufs) {
                     if (rowsInFlight) rows_to_lds();            // (a second block in the same step: its predecessor's loads are waited for here)
                     const uint32_t k = rowBlk * kCvtCols + ((uint32_t)lane >> 1);
-                    const uint32_t off = cvt_row_shift(seg_out_position<kSeg>(inc, kBase, nBase, k));
-                    const float *pc = A.src_rows + (size_t)seg_out_phase<kSeg>(inc, kBase, k) * kSrcRowC - off + (lane & 1) * 16;
+                    const uint32_t off = cvt_row_shift(out_position<kSeg>(inc, kBase, nBase, k));
+                    const float *pc = A.src_rows + (size_t)out_phase<kSeg>(inc, kBase, k) * kSrcRowC - off + (lane & 1) * 16;
                     for (int q = 0; q < 4; q++) rq[q] = make_float4(pc[4 * q], pc[4 * q + 1], pc[4 * q + 2], pc[4 * q + 3]);
                     rowsInFlight = true;
                     rowBlk++;
@@ -714,61 +661,21 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
         // running max |y| per (row, lane): row r = voices 2r (lanes 0-31) and 2r+1 (lanes 32-63)
         for (int r = 0; r < 4; r++) sMx[r * kWave + lane] = 0.0f;
 
-        // output k reads tube samples e-25 .. e, e = src_position(k): ring slots e + kRingShift .. + 25
-        // (kLane = this lane's output within the launch, ring positions are relative to the launch's first tube sample: seg_out_position)
+        // the wave's state, and the statements over it (trm_roles.h); the time base is the segment instance's alone
         v2f cc[16];
         uint32_t blk = 0, pr = 0;       // next work item: row pair `pr` (0..1) of block `blk`: voices 4*pr .. 4*pr+3
         uint32_t winBase = 0, kLane = 0, needLast = 0, needNext = 0;
-        auto begin_block = [&]() {
-            kLane = blk * kCvtCols + col;
-            winBase = cvt_window_base(seg_out_position<kSeg>(inc, kBase, nBase, kLane));
-            needLast = seg_out_position<kSeg>(inc, kBase, nBase, blk * kCvtCols + (kCvtCols - 1));
-            needLast = needLast < nTotal - 1 ? needLast : nTotal - 1;
-            needNext = seg_out_position<kSeg>(inc, kBase, nBase, (blk + 1) * kCvtCols + (kCvtCols - 1));   // (past the end: never "behind")
-            const float4 *row = reinterpret_cast<const float4 *>(&sRows[(blk % kRowBufs) * (kCvtCols * kRowPitch) + col * kRowPitch]);
-            for (int q = 0; q < 8; q++) {
-                const float4 x = row[q];
-                cc[2 * q] = v2f{x.x, x.y};
-                cc[2 * q + 1] = v2f{x.z, x.w};
-            }
-        };
-        auto begin_block_from_global = [&]() {
-            kLane = blk * kCvtCols + col;
-            winBase = cvt_window_base(seg_out_position<kSeg>(inc, kBase, nBase, kLane));
-            needLast = nTotal - 1;
-            const uint32_t off = cvt_row_shift(seg_out_position<kSeg>(inc, kBase, nBase, kLane));
-            const float *pc = A.src_rows + (size_t)seg_out_phase<kSeg>(inc, kBase, kLane) * kSrcRowC - off;
-            for (int q = 0; q < 16; q++) cc[q] = v2f{pc[2 * q], pc[2 * q + 1]};
-        };
+        const CvtBeginBlock<kSeg> begin_block{kLane, blk, col, winBase, kBase, inc, nBase, needLast, nTotal, needNext, sRows, cc};
+        const CvtBeginBlockFromGlobal<kSeg> begin_block_from_global{kLane, blk, col, winBase, kBase, inc, nBase, needLast, nTotal, A, cc};
         bool needBegin = nBlocks > 0;
-        typedef __attribute__((address_space(1))) float *GlobalFloatPtr;
-        typedef __attribute__((address_space(3))) float *LdsFloatPtr;
         // metering (16.16 row pairs per step): a step's kOB tube samples turn into kOB * 2^16/inc outputs per voice =
         // that / 32 blocks of 2 row pairs
         const uint32_t earn = (uint32_t)(((uint64_t)kOB << 32) / inc / 16) + 2048;
-        // the cap must leave room to catch up after waiting for a block (see trm_quad.hip)
+        // the cap must leave room to catch up after waiting for a block (trm_quad.hip has the case)
         const uint32_t capPairs = (earn + 0x18000u) >> 16;                  // floor(earn + 1.5)
         const uint32_t creditCap = (capPairs > 2u ? capPairs : 2u) << 16;
         uint32_t credit = 0;
-        auto do_pair = [&]() {
-            const int la = 4 * (int)pr, lb = la + 2;
-            const int ha = upperHalf ? 1 : 0;
-            const float4 *wa = reinterpret_cast<const float4 *>(&sY[(la + ha) * kYStride + winBase]);
-            const float4 *wb = reinterpret_cast<const float4 *>(&sY[(lb + ha) * kYStride + winBase]);
-            const uint4 ia = sInfo[la + ha], ib = sInfo[lb + ha];
-            // (the second row's window is read while the first row's chains run: one row's registers are live at a time)
-            const float ya = cvt_window_dot(wa, cc), yb = cvt_window_dot(wb, cc);
-            const bool okA = kLane < ia.x, okB = kLane < ib.x;
-            if (okA) reinterpret_cast<GlobalFloatPtr>(((uintptr_t)ia.z << 32) | ia.y)[kLane] = ya;
-            if (okB) reinterpret_cast<GlobalFloatPtr>(((uintptr_t)ib.z << 32) | ib.y)[kLane] = yb;
-            __builtin_amdgcn_ds_fmaxf((LdsFloatPtr)&sMx[(2 * pr) * kWave + lane], okA ? fabsf(ya) : 0.0f, 0, 0, false);
-            __builtin_amdgcn_ds_fmaxf((LdsFloatPtr)&sMx[(2 * pr + 1) * kWave + lane], okB ? fabsf(yb) : 0.0f, 0, 0, false);
-            if (++pr == 2) {
-                pr = 0;
-                blk++;
-                needBegin = blk < nBlocks;
-            }
-        };
+        const CvtPair<kOV / 4> do_pair{pr, upperHalf, sY, winBase, sInfo, cc, kLane, sMx, lane, blk, needBegin, nBlocks};
         STAMP_DECL
         for (uint32_t step = 0; step < nSteps; step++) {
             STAMP_BEGIN
@@ -776,13 +683,7 @@ __global__ __launch_bounds__(kWave *kORoles, 4) void trm_tube_kernel_o(const Con
             const uint32_t ready = step >= 4 ? (step - 4) * kOB : 0;
             credit += earn;
             if (credit > creditCap) credit = creditCap;     // a ready block is spread over the next steps, not done in a burst
-            auto try_begin = [&]() {
-                if (blk < lds_flag_consume(&sRowSync[1])) {
-                    begin_block();
-                    needBegin = false;
-                    lds_flag_publish(&sRowSync[0], blk + 1, lane == 0);    // this block's rows are in registers now
-                }
-            };
+            const CvtTryBegin<decltype(begin_block)> try_begin{blk, sRowSync, begin_block, needBegin, lane};
             if (needBegin) try_begin();
             while (blk < nBlocks && !needBegin && needLast < ready && (credit >= (1u << 16) || needNext < ready)) {
                 credit = credit >= (1u << 16) ? credit - (1u << 16) : credit;

@@ -16,6 +16,8 @@
 // on those of step i-1, the two coefficient waves and the band-pass and throat scans (recurrences that only FEED
 // the tube; they live in feed-forward waves) on those of step i-2, tube on those of step i-4, convert on whatever
 // is complete, metered.  trm_tube_kernel_q<true, .> is the streaming instance (state in / out).
+// What the six roles share with the eight-lane kernel (trm_oct.hip) is stated once, in trm_roles.h: the two scans, the frame
+// ring's read, the time base, the noise request, the row stager's store, the convert wave's block begin, row pair and hand-shake.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,10 +27,11 @@
 #include "trm_quad.h"
 #include "trm_quad_dev.h"
 #include "trm_span.h"
+#include "trm_roles.h"
 
 // Timing experiments (tools/bench_variants.sh) live behind ONE switch; the product build defines none of them.
+// (Retired: TRM_ABL_CVT and TRM_THROAT_IN_OSC, DESIGN.md "The roles the lane kernels share".)
 #ifndef TRM_EXPERIMENTS
-#undef TRM_ABL_CVT
 #undef TRM_ABL_SKIP
 #undef TRM_QROLE_PERM
 #undef TRM_QPRIO_TUBE
@@ -37,14 +40,6 @@
 #undef TRM_QPRIO_COEF
 #undef TRM_QPRIO_COEF2
 #undef TRM_QPRIO_CVT
-#undef TRM_THROAT_IN_OSC
-#endif
-#ifndef TRM_ABL_CVT
-#define TRM_ABL_CVT 0
-#endif
-/* where the throat low-pass scan runs: the oscillator wave (1) or the mix wave (0) */
-#ifndef TRM_THROAT_IN_OSC
-#define TRM_THROAT_IN_OSC 1
 #endif
 
 #ifndef TRM_GRP_INSTANCE
@@ -259,12 +254,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     auto frame_index = [&](uint32_t i) { return nfr > 0 ? (i < nfr ? i : nfr - 1) : 0u; };
     // staged frames (kLdsFrames): this lane's voice's frame f (nominal index: past the voice's last frame the stager
     // repeats it), `quads` 16-byte quarters of it
-    auto frame_to = [&](uint32_t f, float *dst, int quads) {
-        for (int q = 0; q < quads; q++) {
-            const float4 x = sF[((f % kQFrameRing) * kQV + vq) * 4 + q];
-            dst[4 * q] = x.x; dst[4 * q + 1] = x.y; dst[4 * q + 2] = x.z; dst[4 * q + 3] = x.w;
-        }
-    };
+    auto frame_to = [&](uint32_t f, float *dst, int quads) { trm::frame_to<kQFrameRing, kQV>(sF, vq, f, dst, quads); };
     // the stager (area wave): lane -> (voice lane / 4, quarter lane % 4) of the workgroup's 16 frames
     const float *stageSrc = nullptr;
     uint32_t stageNfr = 0;
@@ -301,11 +291,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
     }
     __syncthreads();
 
-    // The two recurrences that only FEED the tube (frication band-pass, throat low-pass: nothing of the tube's state
-    // enters them) run in a feed-forward wave, serially over a voice's four slots: slot s's output is slot s+1's y1
-    // and slot s+2's y2; what wraps around belongs to the next block.  A lane's evaluation is final from its own turn
-    // on (its inputs no longer change), so the value of the last turn is everyone's.
-    struct ScanState { float by1, by2, ny1, ny2, prevSig, thY, thNext; };
+    // The two scans (trm_roles.h: bandpass_block, throat_block) with this kernel's LDS reads and stream state around them
     auto scans_restore = [&](ScanState &Z, bool bandpass, bool throat) {
         Z.by1 = Z.by2 = Z.ny1 = Z.ny2 = Z.prevSig = Z.thY = Z.thNext = 0.0f;
         if (streaming && !sFirst) {
@@ -317,24 +303,11 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
             if (throat) Z.thY = st[2];
         }
     };
-    // band-pass (TRMFilters.m:19-29) of block `blk`: input sX.y (mix wave, in LDS), coefficients bp = this lane's
-    // sample's {2 alpha, 2 beta, 2 gamma}; returns the lane's band-pass output
+    // band-pass of block `blk`: input sX.y (mix wave, in LDS), coefficients bp = this lane's sample's {2 alpha, 2 beta,
+    // 2 gamma}; returns the lane's band-pass output
     auto bandpass_scan = [&](ScanState &Z, uint32_t blk, const float4 bp) {
         const float sig = reinterpret_cast<const float *>(&sX[((blk % kXBufs) * kQB + part) * kXPitch + vq])[1];
-        const float X = q_take<0, kPart2 | kPart3>(sig, Z.prevSig);         // slots 0, 1 look into the previous block
-        const float x2 = q_take<2, kPartAll>(X, X);
-        float f = 0.0f;
-#pragma unroll
-        for (int t = 0; t < kQB; t++) {
-            f = bandpass_eval<float>(bp.x, bp.y, bp.z, sig, x2, Z.by1, Z.by2);
-            if (t == 0) { Z.by1 = q_take<1, kPart1>(Z.by1, f); Z.by2 = q_take<2, kPart2>(Z.by2, f); }
-            if (t == 1) { Z.by1 = q_take<1, kPart2>(Z.by1, f); Z.by2 = q_take<2, kPart3>(Z.by2, f); }
-            if (t == 2) { Z.by1 = q_take<1, kPart3>(Z.by1, f); Z.ny2 = q_take<2, kPart0>(Z.ny2, f); }
-            if (t == 3) { Z.ny1 = q_take<1, kPart0>(Z.ny1, f); Z.ny2 = q_take<2, kPart1>(Z.ny2, f); }
-        }
-        Z.by1 = q_take<0, kPart0>(Z.by1, Z.ny1);
-        Z.by2 = q_take<0, kPart0 | kPart1>(Z.by2, Z.ny2);
-        Z.prevSig = sig;
+        const float f = bandpass_block(Z, sig, bp);
         if (saving) {
             const uint32_t n = blk * kQB + (uint32_t)part;
             if (n + 2u == ntubeLane) { st[4] = f; st[6] = sig; }
@@ -342,18 +315,9 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         }
         return f;
     };
-    // throat low-pass (:341, TRMFilters.m:72-77) over this lane's input `thr` of sample m
+    // throat low-pass over this lane's input `thr` of sample m
     auto throat_scan = [&](ScanState &Z, float thr, uint32_t m) {
-        float ty = 0.0f;
-#pragma unroll
-        for (int t = 0; t < kQB; t++) {
-            ty = throat_eval<float>(C, thr, Z.thY);
-            if (t == 0) Z.thY = q_take<1, kPart1>(Z.thY, ty);
-            if (t == 1) Z.thY = q_take<1, kPart2>(Z.thY, ty);
-            if (t == 2) Z.thY = q_take<1, kPart3>(Z.thY, ty);
-            if (t == 3) Z.thNext = q_take<1, kPart0>(Z.thNext, ty);
-        }
-        Z.thY = q_take<0, kPart0>(Z.thY, Z.thNext);
+        const float ty = throat_block(C, Z, thr);
         if (saving && m + 1u == ntubeLane) st[2] = ty;
         return ty;
     };
@@ -406,7 +370,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         }
         float2 *const ring = &sO[vq * kOStride];
         ScanState Z;
-        scans_restore(Z, false, TRM_THROAT_IN_OSC);
+        scans_restore(Z, false, true);
         STAMP_DECL
         for (uint32_t step = 0; step < nSteps; step++) {
             STAMP_BEGIN
@@ -415,7 +379,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
                 // the blocks of step i-2: the mix wave's {sig, thr} were written during step i-1; the tube wave reads
                 // the result from step i+1 on
                 const uint32_t blk = (step - 2) * kSub + u;
-                if (TRM_THROAT_IN_OSC && step >= 2 && blk * kQB < nTotal) {
+                if (step >= 2 && blk * kQB < nTotal) {
                     float *const xr = reinterpret_cast<float *>(&sX[((blk % kXBufs) * kQB + part) * kXPitch + vq]);
                     xr[2] = throat_scan(Z, xr[2], blk * kQB + (uint32_t)part);
                 }
@@ -481,9 +445,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
 #endif
         // ------------------------------------------------------------ mix: block i-1 at step i, lane = (voice, slot)
         const float *const lpNoise = A.lp_noise + ((kSeg || kMixStream) ? nBase : 0u);      // (a uniform stream's pointer arrives advanced)
-        auto fill_noise_half = [&](uint32_t nFirst, int half) {
-            dma4(lpNoise + nFirst + lane, &sNoise[half * kNoiseHalf]);
-        };
+        auto fill_noise_half = [&](uint32_t nFirst, int half) { trm::fill_noise_half(lpNoise, sNoise, lane, nFirst, half); };
         // window taps of this lane's parity (m & 1 == part & 1: blocks start on multiples of 4), as (a, b) pairs
         const int o = part & 1;
         v2f cab[kFirWin];
@@ -496,14 +458,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
             dma_wait_all();
         }
         const float2 *const ring = &sO[vq * kOStride];
-        // Converter coefficient rows, staged for the convert wave: block B's 32 rows (128 bytes each, shifted per
-        // output like the wide kernel's fetch) are loaded when the oscillator's time is within 4 samples of the
-        // block's first output, written to LDS one step later and visible one step after that -- normally several
-        // steps before the convert wave can begin the block.  Two words in LDS make that independent of timing:
-        // sRowSync[1] = blocks staged (the convert wave begins no block beyond it), sRowSync[0] = the first block
-        // whose rows the convert wave has not copied yet (buffer B % 3 is not rewritten before).
-        ScanState Z;
-        scans_restore(Z, false, !TRM_THROAT_IN_OSC);
+        // the converter's coefficient rows, staged for the convert wave (trm_roles.h, rows_to_lds)
         uint32_t rowBlk = 0;
         bool rowsInFlight = false;
         float4 rq[4];
@@ -514,16 +469,14 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         for (uint32_t step = 0; step < nSteps; step++) {
             STAMP_BEGIN
             auto rows_to_lds = [&]() {
-                float4 *dst = reinterpret_cast<float4 *>(&sRows[((rowBlk - 1) % kRowBufs) * (kCvtCols * kRowPitch) + (lane >> 1) * kRowPitch + (lane & 1) * 16]);
-                for (int q = 0; q < 4; q++) dst[q] = rq[q];
+                trm::rows_to_lds(sRows, sRowSync, lane, rowBlk, rq);
                 rowsInFlight = false;
-                lds_flag_publish(&sRowSync[1], rowBlk, lane == 0);     // blocks 0 .. rowBlk-1 are in LDS
             };
             if (rowsInFlight) rows_to_lds();
             // never more than kRowBufs blocks past the first one the convert wave still has to copy (looked up only
             // when a block is due: about once per block).  Up to two blocks per step (rate ratios above 4).
             for (int r = 0; r < 2; r++) {
-                if (TRM_ABL_CVT != 4 && rowBlk < cvtBlocks && src_position(kBase + rowBlk * kCvtCols, inc) - nBase <= step * kStepN + 4u &&
+                if (rowBlk < cvtBlocks && src_position(kBase + rowBlk * kCvtCols, inc) - nBase <= step * kStepN + 4u &&
                     rowBlk < lds_flag_consume(&sRowSync[0]) + kRowBufs) {
                     if (rowsInFlight) rows_to_lds();            // (a second block in the same step: its predecessor's loads are waited for here)
                     const uint32_t k = kBase + rowBlk * kCvtCols + ((uint32_t)lane >> 1);
@@ -552,12 +505,9 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
                 const float pulse = fir_window_dot(wp, cab);
                 const float2 a = sA[buf * kWave + lane];
                 const Excitation E = mix_tail(C, a.x, a.y, pulse, sNoise[m & (kNoiseRing - 1)]);
-#if TRM_THROAT_IN_OSC
-                const float ty = E.thr;         // (raw: the oscillator wave turns it into the throat output two steps on)
-#else
-                const float ty = throat_scan(Z, E.thr, m);
-#endif
-                sX[(xbuf * kQB + part) * kXPitch + vq] = make_float4(E.gin, E.sig, ty, 0.0f);
+                // (the throat input raw: the oscillator wave turns it into the throat output two steps on; in the mix wave
+                // instead the scan measured 2.5 % slower, trm_oct.hip)
+                sX[(xbuf * kQB + part) * kXPitch + vq] = make_float4(E.gin, E.sig, E.thr, 0.0f);
               }
             }
             STAMP_MID
@@ -780,39 +730,13 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         // running max |y| per (row, lane): row r = voices 2r (lanes 0-31) and 2r+1 (lanes 32-63)
         for (int r = 0; r < 8; r++) sMx[r * kWave + lane] = 0.0f;
 
-        // output k reads tube samples e-25 .. e, e = src_position(k): ring slots e + kRingShift .. + 25
-        // Coefficient rows: the mix wave stages every block's 32 rows in LDS several steps ahead (the latency of
-        // global memory would otherwise sit in front of each block's first row pair: this wave's vector-memory
-        // counter also counts its PCM stores); a block begins by copying this lane's row into registers.
+        // the wave's state, and the statements over it (trm_roles.h).  The one-shot instances have no time base: kBase = nBase = 0
         v2f cc[16];
         uint32_t blk = 0, pr = 0;       // next work item: row pair `pr` (0..3) of block `blk`: voices 4*pr .. 4*pr+3
         uint32_t winBase = 0, kLane = 0, needLast = 0, needNext = 0;
-        // kLane = this lane's output within the launch; its global index is kBase + kLane, and ring positions are
-        // relative to the launch's first tube sample (nBase)
-        auto begin_block = [&]() {
-            kLane = blk * kCvtCols + col;
-            winBase = cvt_window_base(src_position(kBase + kLane, inc) - nBase);
-            needLast = src_position(kBase + blk * kCvtCols + (kCvtCols - 1), inc) - nBase;
-            needLast = needLast < nTotal - 1 ? needLast : nTotal - 1;
-            needNext = src_position(kBase + (blk + 1) * kCvtCols + (kCvtCols - 1), inc) - nBase;   // (past the end: never "behind")
-            const float4 *row = reinterpret_cast<const float4 *>(&sRows[(blk % kRowBufs) * (kCvtCols * kRowPitch) + col * kRowPitch]);
-            for (int q = 0; q < 8; q++) {
-                const float4 x = row[q];
-                cc[2 * q] = v2f{x.x, x.y};
-                cc[2 * q + 1] = v2f{x.z, x.w};
-            }
-        };
-        auto begin_block_from_global = [&]() {
-            kLane = blk * kCvtCols + col;
-            winBase = cvt_window_base(src_position(kBase + kLane, inc) - nBase);
-            needLast = nTotal - 1;
-            const uint32_t off = cvt_row_shift(src_position(kBase + kLane, inc) - nBase);
-            const float *pc = A.src_rows + (size_t)src_phase(kBase + kLane, inc) * kSrcRowC - off;
-            for (int q = 0; q < 16; q++) cc[q] = v2f{pc[2 * q], pc[2 * q + 1]};
-        };
+        const CvtBeginBlock<kStream> begin_block{kLane, blk, col, winBase, kBase, inc, nBase, needLast, nTotal, needNext, sRows, cc};
+        const CvtBeginBlockFromGlobal<kStream> begin_block_from_global{kLane, blk, col, winBase, kBase, inc, nBase, needLast, nTotal, A, cc};
         bool needBegin = nBlocks > 0;
-        typedef __attribute__((address_space(1))) float *GlobalFloatPtr;
-        typedef __attribute__((address_space(3))) float *LdsFloatPtr;
         // metering (16.16 row pairs per step): a step's kQB tube samples turn into kQB * 2^16/inc outputs per
         // voice = that / 32 blocks of 4 row pairs
         const uint32_t earn = (uint32_t)(((uint64_t)kStepN << 32) / inc / 8) + 2048;
@@ -821,31 +745,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
         const uint32_t capPairs = (earn + 0x18000u) >> 16;                  // floor(earn + 1.5)
         const uint32_t creditCap = (capPairs > 2u ? capPairs : 2u) << 16;   // two pairs per step at speech rates (earn ~ 1.1)
         uint32_t credit = 0;
-        auto do_pair = [&]() {
-#if TRM_ABL_CVT == 3 || TRM_ABL_CVT == 4     /* (timing experiments: 3 = the converter's control flow only; 4 = and no row staging) */
-            if (++pr == 4) { pr = 0; blk++; needBegin = blk < nBlocks; }
-            return;
-#endif
-            const int la = 4 * (int)pr, lb = la + 2;
-            const int ha = upper ? 1 : 0;
-            const float4 *wa = reinterpret_cast<const float4 *>(&sY[(la + ha) * kYStride + winBase]);
-            const float4 *wb = reinterpret_cast<const float4 *>(&sY[(lb + ha) * kYStride + winBase]);
-            const uint4 ia = sInfo[la + ha], ib = sInfo[lb + ha];
-            // (the second row's window is read while the first row's chains run: one row's registers are live at a time)
-            const float ya = cvt_window_dot(wa, cc), yb = cvt_window_dot(wb, cc);
-            const bool okA = kLane < ia.x, okB = kLane < ib.x;
-#if TRM_ABL_CVT != 1      /* (timing experiments: 1 = no PCM stores) */
-            if (okA) reinterpret_cast<GlobalFloatPtr>(((uintptr_t)ia.z << 32) | ia.y)[kLane] = ya;
-            if (okB) reinterpret_cast<GlobalFloatPtr>(((uintptr_t)ib.z << 32) | ib.y)[kLane] = yb;
-#endif
-            __builtin_amdgcn_ds_fmaxf((LdsFloatPtr)&sMx[(2 * pr) * kWave + lane], okA ? fabsf(ya) : 0.0f, 0, 0, false);
-            __builtin_amdgcn_ds_fmaxf((LdsFloatPtr)&sMx[(2 * pr + 1) * kWave + lane], okB ? fabsf(yb) : 0.0f, 0, 0, false);
-            if (++pr == 4) {
-                pr = 0;
-                blk++;
-                needBegin = blk < nBlocks;
-            }
-        };
+        const CvtPair<kQV / 4> do_pair{pr, upper, sY, winBase, sInfo, cc, kLane, sMx, lane, blk, needBegin, nBlocks};
         STAMP_DECL
         for (uint32_t step = 0; step < nSteps; step++) {
             STAMP_BEGIN
@@ -853,14 +753,7 @@ __global__ __launch_bounds__(kWave *kQRoles, 4) void trm_tube_kernel_q(const Con
             const uint32_t ready = step >= 4 ? (step - 4) * kStepN : 0;
             credit += earn;
             if (credit > creditCap) credit = creditCap;     // a ready block is spread over the next steps, not done in a burst
-            // (the two sync words are touched once per block: when a block has to begin)
-            auto try_begin = [&]() {
-                if (TRM_ABL_CVT == 4 || blk < lds_flag_consume(&sRowSync[1])) {
-                    begin_block();
-                    needBegin = false;
-                    lds_flag_publish(&sRowSync[0], blk + 1, lane == 0);    // this block's rows are in registers now
-                }
-            };
+            const CvtTryBegin<decltype(begin_block)> try_begin{blk, sRowSync, begin_block, needBegin, lane};
             if (needBegin) try_begin();
             // Metered by the credit (smooth: at most creditCap pairs in a step) -- but a wave that is a whole block
             // behind production works through its backlog regardless: the credit alone loses what it earns while it
